@@ -12,6 +12,11 @@ Multi-GPU: `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 ranks (weak scaling); the server keys (KSK, BSK, PFPKSK: 672 MB) and the expanded round key are
 broadcast once from rank 0 over RCCL (torch.distributed "nccl") before timing; no collective on the
 data path.
+
+A plain run does only what the headline line needs: set-up, warm-up, the timed steps, the decrypt-and-
+compare gate on their output, `--dump-outputs`, the JSON line.  `--full` adds every other leg (effective
+clock step, one block alone, host buffers, CPU baseline, the 8-bit model); each leg's own on/off option
+still overrides.
 """
 import argparse
 import ctypes as C
@@ -58,19 +63,27 @@ def main():
     ap.add_argument("--blocks-per-gpu", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--key-schedule", choices=["fhe", "plain"], default="fhe")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the clock-stamped step (effective_clock_ghz), "
+                         "--single-block, --host-buffers, --cpu-baseline and --model8-leg (their `auto` = on with "
+                         "--full at world size 1, off without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float64): a "
+                         "fixed seeded sample of the output ciphertexts' rows, each u64 word as its high and low 32 "
+                         "bits, and the decrypted blocks' bytes")
     ap.add_argument("--cpu-baseline", choices=["auto", "on", "off"], default="auto")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (0: this process's CPU share, capped by OMP_NUM_THREADS)")
     ap.add_argument("--single-block", choices=["auto", "on", "off"], default="auto",
                     help="also time one block alone (BASELINE configs[1]: 16 SBOX x 10 rounds on 1 GPU); "
-                         "auto = on at world size 1")
+                         "auto = on with --full at world size 1")
     ap.add_argument("--model", choices=["1bit", "8bit"], default="1bit",
                     help="1bit: ShortintWoppbs1BitSboxGalMulPbsAesEncrypt (params_sqrd_lvl_64, the metric); "
                          "8bit: ShortintWoppbs8BitSboxPbsAesEncrypt (BASELINE config #5)")
     ap.add_argument("--model8-leg", choices=["auto", "on", "off"], default="auto",
                     help="with --model 1bit: also time BASELINE config #5 (8-bit model) on a bounded batch "
                          "(--model8-blocks blocks, one step) and report it beside the headline line; auto = on "
-                         "at world size 1")
+                         "with --full at world size 1")
     ap.add_argument("--model8-blocks", type=int, default=64)
     ap.add_argument("--force-dist", action="store_true",
                     help="take the torch.distributed branch even at world size 1 (backend nccl = RCCL unless "
@@ -78,7 +91,7 @@ def main():
                          "keys and the round key, device-built contexts, max/min over ranks; launch it under "
                          "torch.distributed.run (MASTER_ADDR / MASTER_PORT)")
     ap.add_argument("--host-buffers", choices=["auto", "on", "off"], default="auto",
-                    help="one extra step with host arrays (PCIe-inclusive rate); auto = on at world 1")
+                    help="one extra step with host arrays (PCIe-inclusive rate); auto = on with --full at world 1")
     args = ap.parse_args()
     PBS_KERNEL = PBS_KERNELS[args.model]
 
@@ -97,6 +110,7 @@ def main():
     torch.cuda.set_device(dev)
     dist = None
     use_dist = world > 1 or args.force_dist
+    want = lambda opt: opt == "on" or (opt == "auto" and args.full and world == 1)
     if use_dist:
         import torch.distributed as dist
         if backend == "gloo":
@@ -192,34 +206,38 @@ def main():
         elapsed = D.max_over_ranks(dist, elapsed, f"cuda:{dev}")
     # the timed steps' own output, copied out before anything else writes a ciphertext buffer
     out = out_dev.cpu().numpy().view(np.uint64)
-    # effective shader clock of the PBS launches: one more step, right after the timed ones (chip warm),
-    # with in-kernel clock stamps (a diagnostic mode: each stamped launch is read back synchronously), into
-    # its own output buffer; its ciphertexts must equal the timed steps' bit for bit
-    clk_out = torch.empty_like(out_dev)
-    ctx.set_timing(True, clock=True)
-    step(clk_out)
-    ctx.synchronize()
-    clk = ctx.last_stage_times()
-    ctx.set_timing(False)
-    clock_ghz = clk.get("pbs_clock_ghz")
-    clock_step_identical = bool(np.array_equal(clk_out.cpu().numpy().view(np.uint64), out))
-    del clk_out
+    # effective shader clock of the PBS launches (--full): one more step, right after the timed ones (chip
+    # warm), with in-kernel clock stamps (a diagnostic mode: each stamped launch is read back synchronously),
+    # into its own output buffer; its ciphertexts must equal the timed steps' bit for bit
+    clock_ghz, clock_step_identical = None, None
+    if args.full:
+        clk_out = torch.empty_like(out_dev)
+        ctx.set_timing(True, clock=True)
+        step(clk_out)
+        ctx.synchronize()
+        clk = ctx.last_stage_times()
+        ctx.set_timing(False)
+        clock_ghz = clk.get("pbs_clock_ghz")
+        clock_step_identical = bool(np.array_equal(clk_out.cpu().numpy().view(np.uint64), out))
+        del clk_out
 
     # ---- correctness gate on the timed steps' output: decrypt and compare with plain AES ----
     got = aes_128.bits_to_blocks(ck.decrypt_bits_raw(out))
     ek_plain = aes_128.key_schedule_plain(README_KEY)
     ok = int(all(g == aes_128.encrypt_block_plain(ek_plain, b, args.rounds) for g, b in zip(got, blocks)))
-    if not clock_step_identical:  # the stamped step must reproduce the timed steps' ciphertexts bit for bit
+    if clock_step_identical is False:  # the stamped step must reproduce the timed steps' ciphertexts bit for bit
         print(f"rank {rank}: the clock-stamped step's ciphertexts differ from the timed steps'", file=sys.stderr)
         ok = 0
     if dist:
         ok = D.min_over_ranks(dist, ok, f"cuda:{dev}")
     if not ok:
         raise SystemExit(f"rank {rank}: decrypted AES output differs from plain AES")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, got)
 
     # ---- BASELINE configs[1]: one block alone (latency; not the headline value) ----
     single = None
-    if args.single_block == "on" or (args.single_block == "auto" and world == 1):
+    if want(args.single_block):
         one_dev = blk_dev[:128].contiguous()
         one_out = torch.empty_like(one_dev)
 
@@ -247,7 +265,7 @@ def main():
     # ---- host buffers: one step through tae_aes_encrypt_blocks_raw with host arrays (PCIe copies of
     # the expanded key, blocks and results included); reported beside `value`, never as it ----
     host_io = None
-    if args.host_buffers == "on" or (args.host_buffers == "auto" and world == 1):
+    if want(args.host_buffers):
         blocks_h = cts.reshape(nb, 128, L)
         t1 = time.time()
         out_h = E.encrypt_blocks_raw(ctx, rk_np, blocks_h, args.rounds)
@@ -323,18 +341,16 @@ def main():
     stage_share = {k: v / args.steps for k, v in stage_ms.items() if k not in ("pbs_launches", "pbs_main_cts")}
 
     cpu = None
-    want_cpu = args.cpu_baseline == "on" or (args.cpu_baseline == "auto" and world == 1)
-    if want_cpu and rank == 0:
+    if want(args.cpu_baseline) and rank == 0:
         cpu = cpu_baseline(raw, ck, args.cpu_threads or cpu_share(), args.model, rk_np)
 
     model8 = None
-    want8 = args.model == "1bit" and (args.model8_leg == "on" or (args.model8_leg == "auto" and world == 1))
-    if want8 and rank == 0:
+    if args.model == "1bit" and want(args.model8_leg) and rank == 0:
         model8 = model8_leg(torch, dev, args.model8_blocks, threads)
 
     if rank == 0:
         rec = {"metric": "FHE AES-128 blocks/sec", "value": value, "unit": "blocks/s", "n_gpus": world,
-               "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+               "steps": args.steps, "warmup": args.warmup, "full": args.full, "ms_per_step": ms_per_step, "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                "config": {"workload": f"{nb} counter-mode blocks per GPU, {args.rounds}-round FHE AES-128 ("
                                       + ("ShortintWoppbs1BitSboxGalMulPbsAesEncrypt, params_sqrd_lvl_64)"
@@ -351,6 +367,25 @@ def main():
         print(json.dumps(rec), flush=True)
     if dist:
         dist.destroy_process_group()
+
+
+DUMP_ROWS = 1024  # ciphertext rows kept by --dump-outputs (1024 x 2049 words x 2 halves x 8 B = 34 MB)
+
+
+def dump_outputs(path, out, blocks):
+    """--dump-outputs: the timed steps' output as float64 .npy files.  `out` is the [bits][lwe_size] u64 array
+    the caller of encrypt_blocks_device receives; a fixed seeded choice of DUMP_ROWS of its rows is written
+    exactly, each word as its high and its low 32 bits (a float64 holds 53), beside the rows' indices and
+    the decrypted blocks' bytes."""
+    os.makedirs(path, exist_ok=True)
+    n = out.shape[0]
+    rows = np.sort(np.random.default_rng(20240607).choice(n, size=min(n, DUMP_ROWS), replace=False))
+    sample = out[rows]
+    np.save(os.path.join(path, "ciphertext_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "ciphertext_hi32.npy"), (sample >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(path, "ciphertext_lo32.npy"), (sample & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(path, "decrypted_blocks.npy"),
+            np.array([list(b) for b in blocks], dtype=np.float64).reshape(len(blocks), -1))
 
 
 def at_clock(tflops, ghz):

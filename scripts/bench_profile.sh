@@ -9,7 +9,7 @@ OUT="$ROOT/gpurun_out"
 mkdir -p "$OUT"
 STEPS=${STEPS:-2}
 BLOCKS=${BLOCKS:-128}
-timeout -k 10 ${BENCH_TIMEOUT:-900} python "$ROOT/bench.py" --steps $STEPS --warmup 1 --blocks-per-gpu $BLOCKS > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed rc=$?"; tail -30 "$OUT/bench.err"; exit 1; }
+timeout -k 10 ${BENCH_TIMEOUT:-900} python "$ROOT/bench.py" --full --steps $STEPS --warmup 1 --blocks-per-gpu $BLOCKS > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed rc=$?"; tail -30 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
 [ "${PROFILE:-1}" = "1" ] || exit 0
 cd /tmp && export TMPDIR=/tmp
