@@ -12,8 +12,9 @@
 // The kernel is bound by VALU issue (scripts/probes/valu_rates.hip: one wave issues a VALU op at
 // most every ~14 cycles, four waves keep the SIMD near its ~6-cycle f64 rate): the permlane
 // transposes cost ~7% of the launch and moving them to LDS costs more (+15%, the MAC, table and
-// pass traffic already keeps LDS about half busy); the torus conversion takes the integer fast path
-// (fft_device.hpp torus_add_fast).
+// pass traffic already keeps LDS about half busy); the torus conversion and the PBS decomposition take
+// integer fast paths that leave their rare cases to wave-uniform fallbacks (fft_device.hpp
+// torus_add_fast2_sh, decompose16p_fast).
 // 16 waves (15 jobs + 1 idle) give the SIMDs four waves each; registers are held under 128 per
 // lane.  The MAC splits the 15 (q, ct) accumulators of a Fourier position 4/4/4/3 over four
 // 256-thread groups (one wave of each group per SIMD).  Lane (u, r) of a job decomposes and
@@ -285,27 +286,32 @@ __global__ void __launch_bounds__(THREADS, 1)
         // digits (shortint_1bit: 7 levels of 2^6) byte pairs, two levels per dword (16 instead of 28 VGPRs)
         constexpr bool DBYTES = PBS && LEV > 3 && BLOG <= 7;
         uint32_t dig[DBYTES ? (LEV + 1) / 2 : LEV][4];
+        // the fast digits are refused for the wave when one of its 128 LEV digits sits on the tie (2^-BLOG each):
+        // 9% of the calls at 3 levels of 2^12, nearly all at 7 of 2^6, which keeps decompose16p (as does vertical
+        // packing, 1 level of 2^13: nothing to gain from one level)
+        constexpr bool FASTDEC = PBS && 128 * LEV * 8 <= (1 << BLOG);
         if (fjob) {
             const uint64_t *poly = acc + jb * ACC_STRIDE;
-            // coefficient j of ACC * X^e is entry t = (j - e) mod 2N of [ACC, -ACC]
-            const int bt = ll - e;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
+                // ACC X^e - ACC at j = lane + 64 i (+ M) (fft_device.hpp rot_diff)
                 const int j = ll + 64 * i;
-                const int t = (bt + 64 * i) & (2 * N - 1);
-                const int ph = t & (N - 1);
-                const uint64_t m0 = (uint64_t)(int64_t)((t << 22) >> 31);
-                const uint64_t m1 = (uint64_t)(int64_t)(((t + M) << 22) >> 31);
-                const uint64_t v0 = poly[ph], v1 = poly[ph ^ M];
-                const uint64_t p0 = poly[j], p1 = poly[j + M];
-                const uint64_t x0 = (v0 ^ m0) - (p0 + m0), x1 = (v1 ^ m1) - (p1 + m1);
-                // both halves at once with 16-bit SIMD ops (fft_device.hpp decompose16p)
+                uint64_t x0, x1;
+                rot_diff<LOGN>(poly, j, e, poly[j], poly[j + M], x0, x1);
+                // both halves at once with 16-bit SIMD ops: the biased-field digits (fft_device.hpp
+                // decompose16p_fast), and decompose16p for the whole wave when a digit sits on the tie
                 uint32_t dp[LEV];
 #ifdef TAE_X4_NODEC  // timing-only bound (garbage results): bit fields instead of the balanced decomposition
 #pragma unroll
                 for (int l = 0; l < LEV; l++) dp[l] = (uint32_t)(x0 >> (20 * l)) ^ (uint32_t)(x1 >> (20 * l + 8));
 #else
-                decompose16p<LEV, BLOG>(x0, x1, dp);
+                if constexpr (FASTDEC) {
+                    bool dok;
+                    decompose16p_fast<LEV, BLOG>(x0, x1, dp, dok);
+                    if (__builtin_amdgcn_ballot_w64(!dok)) decompose16p<LEV, BLOG>(x0, x1, dp);
+                } else {
+                    decompose16p<LEV, BLOG>(x0, x1, dp);
+                }
 #endif
                 if constexpr (DBYTES) {
 #pragma unroll
@@ -485,8 +491,9 @@ __global__ void __launch_bounds__(THREADS, 1)
                     uint64_t a0 = poly[j] + f64_bits(t.re), a1 = poly[j + M] + f64_bits(t.im);
 #else
                     bool o0, o1;
-                    uint64_t a0 = torus_add_fast_sh<8>(t.re, poly[j], o0), a1 = torus_add_fast_sh<8>(t.im, poly[j + M], o1);
-                    if (__builtin_amdgcn_ballot_w64(!(o0 && o1))) {  // zeros, out-of-range magnitudes (rare)
+                    uint64_t a0 = torus_add_fast2_sh<8>(t.re, poly[j], o0), a1 = torus_add_fast2_sh<8>(t.im, poly[j + M], o1);
+                    // zeros, out-of-range magnitudes, a magnitude's high dword 0x80000000 (rare)
+                    if (__builtin_amdgcn_ballot_w64(!(o0 && o1))) {
                         a0 = poly[j] + from_torus_bits(t.re * 0x1p-8);
                         a1 = poly[j + M] + from_torus_bits(t.im * 0x1p-8);
                     }

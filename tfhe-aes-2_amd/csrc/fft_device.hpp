@@ -196,6 +196,63 @@ __host__ __device__ __forceinline__ uint64_t torus_add_fast_sh(double x, uint64_
     return acc + (mag ^ sg) + carry;
 }
 
+// Successor of torus_add_fast_sh: the rare cases are all the caller's fallback's job (from_torus_bits is
+// exact for every finite x, so `ok` may be conservative).  With s = biased exponent - 1011 - SH:
+//   * s in [12, 63] only (|x 2^-SH| in [1, 2^52)): the sign, the exponent and the hidden bit then leave the
+//     64-bit shift by themselves, mag = bits << s, with no masking of the significand.  The inverse-FFT
+//     outputs of a blind rotation are sums of ~10^4 products of digits up to 2^(B-1) with uniform torus
+//     values, thousands of turns; |x 2^-SH| < 1 has a probability of about 2^-16 per value.
+//   * the i64 saturation (mag = 2^63 exactly, x = -(n + 1/2)) is refused with every mag whose high dword is
+//     0x80000000: one 32-bit compare (true once in 2^31 values) instead of the 64-bit compare and the
+//     masked third addend that every value paid for.
+// Whenever `ok` is true the result is acc + from_torus_bits(x 2^-SH):
+//   acc + (mag ^ sg) + neg = acc + mag (x > 0), acc - mag (x < 0)       (sg = 0 or ~0, neg = 0 or 1)
+// and `ok` is false exactly when s is outside [12, 63] or mag >> 32 == 0x80000000.
+template <int SH>
+__host__ __device__ __forceinline__ uint64_t torus_add_fast2_sh(double x, uint64_t acc, bool &ok) {
+    const uint64_t b = f64_bits(x);
+    const uint32_t hi = (uint32_t)(b >> 32);
+#ifdef __HIP_DEVICE_COMPILE__
+    uint32_t s = __builtin_amdgcn_ubfe(hi, 20, 11) - (1011u + SH);
+    asm("" : "+v"(s));  // one s for the shift and the range test (the optimiser derives the two apart)
+#else
+    const uint32_t s = ((hi >> 20) & 0x7ff) - (1011u + SH);
+#endif
+    const uint64_t mag0 = b << (s & 63);
+    uint32_t mh = (uint32_t)(mag0 >> 32);
+#ifdef __HIP_DEVICE_COMPILE__
+    asm("" : "+v"(mh));  // keeps the test below a 32-bit compare (the optimiser widens it to a 64-bit one)
+#endif
+    const uint64_t mag = ((uint64_t)mh << 32) | (uint32_t)mag0;
+    ok = (s - 12u <= 51u) & (mh != 0x80000000u);
+    const uint64_t sg = (uint64_t)(int64_t)((int32_t)hi >> 31);
+    return acc + (mag ^ sg) + (uint64_t)(hi >> 31);
+}
+
+// Rotated difference of a CMux step for N = 2^LOGN, M = N / 2: coefficient j of ACC X^e is entry
+// t = (j - e) mod 2N of [ACC, -ACC].  rot_index gives, for the coefficient pair (j, j + M) with j < M, the
+// source index ph of the first (the second reads ph ^ M) and the negation masks m0 / m1 (0 or ~0) of the
+// two; rot_diff the differences x0 = (ACC X^e - ACC)[j], x1 = ...[j + M], from the lane's own words
+// p0 = poly[j], p1 = poly[j + M] (-v - p = (v ^ ~0) - (p + ~0)).
+template <int LOGN>
+__host__ __device__ __forceinline__ void rot_index(int j, int e, int &ph, uint64_t &m0, uint64_t &m1) {
+    constexpr int N = 1 << LOGN, M = N / 2;
+    const int t = (j - e) & (2 * N - 1);
+    ph = t & (N - 1);
+    m0 = (uint64_t)(int64_t)((int32_t)((uint32_t)t << (31 - LOGN)) >> 31);
+    m1 = (uint64_t)(int64_t)((int32_t)((uint32_t)(t + M) << (31 - LOGN)) >> 31);
+}
+template <int LOGN>
+__host__ __device__ __forceinline__ void rot_diff(const uint64_t *poly, int j, int e, uint64_t p0, uint64_t p1,
+                                                  uint64_t &x0, uint64_t &x1) {
+    int ph;
+    uint64_t m0, m1;
+    rot_index<LOGN>(j, e, ph, m0, m1);
+    const uint64_t v0 = poly[ph], v1 = poly[ph ^ (1 << (LOGN - 1))];
+    x0 = (v0 ^ m0) - (p0 + m0);
+    x1 = (v1 ^ m1) - (p1 + m1);
+}
+
 // tfhe-rs SignedDecomposer (closest_representable + balanced digits, the carry rule of
 // decompose_one_level) for LEV levels of B bits with B * (LEV - 1) < 32: d[l] = the 16-bit two's
 // complement pattern of the digit of level l + 1 (1 = most significant), upper half zero.
@@ -268,19 +325,12 @@ __host__ __device__ __forceinline__ uint32_t alignbit_b32(uint32_t hi, uint32_t 
 #endif
 }
 
-// decompose16 of two coefficients at once, d[l] = digit of x0 | digit of x1 << 16 (the packed
-// layout the FFT passes read), with 16-bit SIMD ops on both halves.  Same digits as decompose16:
-// with F_i the B-bit fields of X = x + 2^(nrb-1) above bit nrb (F_0 lowest), the state at field i
-// is G_i = F_i + k_i (k_0 = 0), res_i = G_i mod 2^B, ovf_i = G_i >> B, and the carry rule reads bit
-// B-1 of the state above, i.e. of F_{i+1} + ovf_i; then k_{i+1} = ovf_i + c_i <= 1 (ovf_i = 1
-// forces res_i = 0, so c_i = 0).  The top state above the last field is ovf <= 1: bit B-1 clear.
+// The packed B-bit fields of X0 / X1 above bit nrb = 64 - B LEV: F[i] = field i of X0 | field i of X1 << 16.
 template <int LEV, int B>
-__host__ __device__ __forceinline__ void decompose16p(uint64_t x0, uint64_t x1, uint32_t *d) {
+__host__ __device__ __forceinline__ void fields16p(uint64_t X0, uint64_t X1, uint32_t *F) {
     static_assert(B <= 15 && B * LEV <= 64 && B >= 2, "decompose16p shape");
     constexpr int nrb = 64 - B * LEV;
-    const uint64_t X0 = x0 + (1ull << (nrb - 1)), X1 = x1 + (1ull << (nrb - 1));
     constexpr uint32_t MASK = ((1u << B) - 1) * 0x10001u;
-    uint32_t F[LEV];
     if constexpr (LEV == 3 && B == 12) {
         // fields at bits 28..39, 40..51, 52..63: F0 straddles the dwords, F1 / F2 are bytes 1-2 / 2-3
         const uint32_t h0 = (uint32_t)(X0 >> 32), h1 = (uint32_t)(X1 >> 32);
@@ -307,6 +357,20 @@ __host__ __device__ __forceinline__ void decompose16p(uint64_t x0, uint64_t x1, 
             F[i] = ((uint32_t)(X0 >> (nrb + B * i)) & ((1u << B) - 1)) |
                    (((uint32_t)(X1 >> (nrb + B * i)) & ((1u << B) - 1)) << 16);
     }
+}
+
+// decompose16 of two coefficients at once, d[l] = digit of x0 | digit of x1 << 16 (the packed
+// layout the FFT passes read), with 16-bit SIMD ops on both halves.  Same digits as decompose16:
+// with F_i the B-bit fields of X = x + 2^(nrb-1) above bit nrb (F_0 lowest), the state at field i
+// is G_i = F_i + k_i (k_0 = 0), res_i = G_i mod 2^B, ovf_i = G_i >> B, and the carry rule reads bit
+// B-1 of the state above, i.e. of F_{i+1} + ovf_i; then k_{i+1} = ovf_i + c_i <= 1 (ovf_i = 1
+// forces res_i = 0, so c_i = 0).  The top state above the last field is ovf <= 1: bit B-1 clear.
+template <int LEV, int B>
+__host__ __device__ __forceinline__ void decompose16p(uint64_t x0, uint64_t x1, uint32_t *d) {
+    constexpr int nrb = 64 - B * LEV;
+    constexpr uint32_t MASK = ((1u << B) - 1) * 0x10001u;
+    uint32_t F[LEV];
+    fields16p<LEV, B>(x0 + (1ull << (nrb - 1)), x1 + (1ull << (nrb - 1)), F);
     const u16x2 one = {1, 1}, sh = {B, B}, shm = {B - 1, B - 1};
     const u16x2 neg = {(unsigned short)(0x10000u - (1u << B)), (unsigned short)(0x10000u - (1u << B))};
     u16x2 k = {0, 0};
@@ -327,6 +391,31 @@ __host__ __device__ __forceinline__ void decompose16p(uint64_t x0, uint64_t x1, 
         d[LEV - 1 - i] = as_u32(res + c * neg);
         if (i == 0) k = c; else k = k + c;
     }
+}
+
+// decompose16p without the per-level carry chain, for all inputs but the ties.  Adding half a base to every
+// field, X + 2^(nrb-1) + sum_i 2^(B-1) 2^(nrb + B i), lets the 64-bit add propagate the carries: the field
+// then reads res_i + 2^(B-1) mod 2^B with res_i = (F_i + k_i) mod 2^B, and a carry leaves it exactly when
+// res_i >= 2^(B-1), so field_i - 2^(B-1) is the digit res_i - 2^B [res_i >= 2^(B-1)].  The SignedDecomposer
+// carries when res_i > 2^(B-1), and at res_i = 2^(B-1) only if bit B-1 of the state above is set: the two
+// differ at most where a biased field is 0 (digit -2^(B-1)).  `ok` is false exactly when one of the 2 LEV
+// biased fields is 0 (2 LEV 2^-B of the inputs; d is then not to be used): the caller runs decompose16p
+// for the whole wave behind one wave-uniform branch.
+template <int LEV, int B>
+__host__ __device__ __forceinline__ void decompose16p_fast(uint64_t x0, uint64_t x1, uint32_t *d, bool &ok) {
+    constexpr int nrb = 64 - B * LEV;
+    uint64_t bias = 1ull << (nrb - 1);
+    for (int i = 0; i < LEV; i++) bias += 1ull << (nrb + B * i + B - 1);
+    uint32_t F[LEV];
+    fields16p<LEV, B>(x0 + bias, x1 + bias, F);
+    const u16x2 half = {1 << (B - 1), 1 << (B - 1)}, one = {1, 1};
+    u16x2 z = as_u16x2(F[0]);
+#pragma unroll
+    for (int i = 0; i < LEV; i++) {
+        d[LEV - 1 - i] = as_u32(as_u16x2(F[i]) - half);
+        if (i > 0) z = __builtin_elementwise_min(z, as_u16x2(F[i]));
+    }
+    ok = (as_u32(z - one) & 0x80008000u) == 0;  // fields are below 2^15: bit 15 of z - 1 means z = 0
 }
 
 // The same digits one level at a time, least significant level first, as signed 32-bit values (what
