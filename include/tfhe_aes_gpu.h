@@ -220,6 +220,31 @@ int tae_aes_encrypt_blocks_raw(const tae_context *ctx, const uint64_t *rk, const
 /* key_schedule on raw fresh key bits [128][L] -> [44*32][L] (either model) */
 int tae_aes_key_schedule_raw(const tae_context *ctx, const uint64_t *key, uint64_t *expanded, int mem);
 
+/* ---- AES-128-CTR with public counters: transciphering (src/bin/main.rs:108-128) -------------------
+ * Counter block i is iv[8] || be64(first_counter + i) (main.rs:108-115 counts from 1); a range that wraps
+ * past 2^64 - 1 is TAE_E_ARG.  The iv and the counters are public, so the server needs no counter
+ * ciphertexts: round 0 is built from rk0 and the public bytes, and round 1 is bootstrapped once per
+ * distinct (byte position, byte value) pair and shared between the blocks, giving the words
+ * tae_aes_encrypt_blocks_raw gives on trivial encryptions of the counter blocks.  Parameter sets:
+ * TAE_PARAMS_SQRD_LVL_* (gal-mul driver) and TAE_PARAMS_WOPPBS_8BIT; TAE_PARAMS_SHORTINT_1BIT is
+ * TAE_E_PARAM.  The noise schedule is validated statically, before any device work. */
+/* number of round-1 SBOX groups of the range (host only, no context): 8 for the iv + the distinct values
+ * of each counter byte; 0 for n_blocks == 0 */
+int tae_aes_ctr_plan(const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, size_t *round1_groups);
+/* keystream blocks: out [n_blocks][128][L]; rk [44*32][L]; rk/out follow `mem`, iv is a host pointer.
+ * n_blocks == 0 is TAE_OK and writes nothing.  Calls above TAE_CTR_CHUNK_BLOCKS (default 1024, read at
+ * context creation) blocks run in consecutive chunks; the result does not depend on the chunk size. */
+int tae_aes_ctr_keystream_raw(const tae_context *ctx, const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter,
+                              size_t n_blocks, int rounds, uint64_t *out, int mem);
+/* data: AES-128-CTR ciphertext bytes (host); out [len][8][L] = FHE encryptions of the plaintext bits, 10 rounds
+ * (keystream bit + data bit << 63 on the body; main.rs:117-128 XORs the decrypted keystream instead).
+ * len need not be a multiple of 16; len == 0 is TAE_OK and writes nothing. */
+int tae_aes_ctr_transcipher_raw(const tae_context *ctx, const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter,
+                                const uint8_t *data, size_t len, uint64_t *out, int mem);
+/* the same on handles: out[len*8] new bits carrying the round function's noise bookkeeping */
+int tae_aes_ctr_transcipher(const tae_context *ctx, const tae_bit *const *expanded_key, const uint8_t iv[8],
+                            uint64_t first_counter, const uint8_t *data, size_t len, tae_bit **out /*[len*8]*/);
+
 /* ---- Aes128Encrypt for the fhe_sbox_pbs driver (src/aes_128/fhe/fhe_sbox_pbs.rs:22-171) ------------
  * ShortintWoppbs1BitSboxPbsAesEncrypt on the 1-bit model (fhe_impls/shortint_woppbs_1bit.rs:47-81:
  * SubBytes = one 8 -> 8 circuit bootstrap per byte, MixColumns = gf_256_mul by BitCt XORs) and

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/tfhe_aes_gpu.h"
+#include "aes.hpp"
 #include "client.hpp"
 #include "engine.hpp"
 #include "cplx.hpp"
@@ -575,6 +576,40 @@ int tae_aes_encrypt_blocks_raw(const tae_context *ctx, const uint64_t *rk, const
     return guarded([&] {
         require(ctx && rk && blocks && out, "null");
         ctx->ctx->aes_encrypt_blocks_raw(rk, blocks, n_blocks, rounds, out, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_aes_ctr_plan(const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, size_t *round1_groups) {
+    return guarded([&] {
+        require(iv && round1_groups, "null");
+        tae::CtrPlan plan;
+        if (!tae::ctr_plan(iv, first_counter, n_blocks, plan))
+            throw tae::ModelError{TAE_E_ARG, "counter range wraps past 2^64 - 1"};
+        *round1_groups = plan.groups.size();
+    });
+}
+
+int tae_aes_ctr_keystream_raw(const tae_context *ctx, const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter,
+                              size_t n_blocks, int rounds, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && rk && iv && (out || !n_blocks), "null");
+        ctx->ctx->aes_ctr_keystream_raw(rk, iv, first_counter, n_blocks, rounds, out, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_aes_ctr_transcipher_raw(const tae_context *ctx, const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter,
+                                const uint8_t *data, size_t len, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && rk && iv && ((data && out) || !len), "null");
+        ctx->ctx->aes_ctr_transcipher_raw(rk, iv, first_counter, data, len, tae::kAesRounds, out, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_aes_ctr_transcipher(const tae_context *ctx, const tae_bit *const *expanded_key, const uint8_t iv[8],
+                            uint64_t first_counter, const uint8_t *data, size_t len, tae_bit **out) {
+    return guarded([&] {
+        require(ctx && expanded_key && iv && ((data && out) || !len), "null");
+        emit(ctx->ctx->aes_ctr_transcipher(unwrap(expanded_key, 44 * 32), iv, first_counter, data, len), out);
     });
 }
 

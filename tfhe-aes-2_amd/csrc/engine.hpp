@@ -15,6 +15,7 @@
 
 #include "client.hpp"
 #include "cplx.hpp"
+#include "ctr_plan.hpp"
 #include "kslots.hpp"
 #include "params.hpp"
 
@@ -102,6 +103,22 @@ class Engine {
     void aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, size_t nb, int rounds,
                             uint64_t *d_out);
 
+    // ---- AES-128-CTR with public counters (main.rs:108-128; ctr_plan.hpp) ----
+    // The keystream blocks of one plan (nb blocks) for the 1-bit model: round 0 builds the plan's U
+    // deduplicated SubBytes inputs from rk0, round 1 bootstraps those U groups only and the linear layer
+    // reads them through the plan's map; rounds 2.. run as in aes_encrypt_blocks.  No input ciphertexts.
+    // Writes the first out_bytes (<= 16 nb) keystream bytes [out_bytes][8][K+1]; with d_data (out_bytes
+    // public bytes on the device) each output is keystream xor data (transciphering).
+    void aes_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
+                        size_t out_bytes, uint64_t *d_out);
+    // the same for the 8-bit model (small-key bits [n+1], bootstrap_bytes8 + the gf_256_mul network)
+    void aes8_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
+                         size_t out_bytes, uint64_t *d_out);
+    // counters first_counter .. first_counter + nb - 1 in consecutive chunks of ctr_chunk_ blocks, each with
+    // its own plan, on the model of the parameter set (1-bit or 8-bit)
+    void aes_ctr(const uint64_t *d_rk, const uint8_t iv[8], uint64_t first_counter, size_t nb, int rounds,
+                 const uint8_t *d_data, size_t out_bytes, uint64_t *d_out);
+
     // ---- shortint_1bit model (src/tfhe/shortint_1bit.rs; param set SHORTINT_1BIT) ----
     // FheContext::bootstrap / bootstrap_assign (:257-291): PBS with test vector d_tvs + (b % lut_mod) (k+1)N, then the keyswitch
     // back to the small key: [B][n+1] -> [B][n+1]
@@ -175,6 +192,14 @@ class Engine {
     uint64_t *d_xbuf_ = nullptr, *d_xsh_ = nullptr, *d_xks_ = nullptr, *d_xpbs_ = nullptr, *d_ints_ = nullptr;
     size_t cap_xbuf_ = 0, cap_xsh_ = 0, cap_xks_ = 0, cap_xpbs_ = 0, cap_ints_ = 0;
     int8_t mix_idx_[32][8] = {};
+    // counter mode: blocks per device pass (TAE_CTR_CHUNK_BLOCKS; 1024 = the largest batch the tests pin),
+    // the plan of the chunk in flight on the device, and the host plans the pending uploads read
+    size_t ctr_chunk_ = 1024;
+    uint16_t *d_ctr_groups_ = nullptr;
+    int32_t *d_ctr_map_ = nullptr;
+    size_t cap_ctr_groups_ = 0, cap_ctr_map_ = 0;
+    std::vector<CtrPlan> ctr_plans_;
+    void upload_ctr_plan(const CtrPlan &plan, size_t nb);
     // shortint_1bit: S-box / identity test vectors and tree-level scratch
     uint64_t *d_s1_sbox_tv_ = nullptr, *d_s1_id_tv_ = nullptr, *d_s1_in_ = nullptr, *d_s1_out_ = nullptr,
              *d_s1_pks_ = nullptr, *d_s1_tv_ = nullptr;

@@ -505,6 +505,69 @@ __global__ void aes_final_kernel(const uint64_t *__restrict__ sb, const uint64_t
     }
 }
 
+// ---- AES-128-CTR with public counters (ctr_plan.hpp): round 1 runs on U deduplicated groups ----
+// Round 0 without input ciphertexts: the SubBytes input of group g = (pos, v) is rk0[pos] + trivial(v),
+// i.e. bit b is rk0[pos*8 + b] with ((v >> (7-b)) & 1) << 63 on the body (what aes_ark0_kernel computes for
+// a trivial counter block).  groups [U] = (pos << 8) | v, state [U][8][L].
+__global__ void aes_ctr_round0_kernel(const uint64_t *__restrict__ rk, const uint16_t *__restrict__ groups,
+                                      uint64_t *__restrict__ state, size_t U, int L) {
+    const size_t total = U * 8 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t coef = t % L;
+        const size_t ct = t / L;  // g*8 + bit
+        const int bit = (int)(ct & 7);
+        const uint16_t g = groups[ct >> 3];
+        const int pos = g >> 8, v = g & 0xff;
+        uint64_t w = rk[(size_t)(pos * 8 + bit) * L + coef];
+        if (coef == (size_t)L - 1) w += (uint64_t)((v >> (7 - bit)) & 1) << 63;
+        state[t] = w;
+    }
+}
+
+// aes_mix_kernel with the SubBytes*{1,2,3} outputs of (blk, byte) at group map[blk*16 + byte]: muls [U][24][L]
+__global__ void aes_mix_idx_kernel(const uint64_t *__restrict__ muls, const int32_t *__restrict__ map,
+                                   const uint64_t *__restrict__ rk_round, uint64_t *__restrict__ state, size_t nb,
+                                   int L) {
+    const size_t total = nb * 128 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t coef = t % L;
+        const size_t ct = t / L;  // blk*128 + pos*8 + bit
+        const int bit = (int)(ct & 7);
+        const int pos = (int)((ct >> 3) & 15);
+        const size_t blk = ct >> 7;
+        const int c = pos >> 2, row = pos & 3;
+        auto src = [&](int rr, int m) {
+            const int byte = 4 * ((c + rr) & 3) + rr;
+            const size_t g = (size_t)map[blk * 16 + byte];
+            return muls[((g * 24) + 8 * m + bit) * (size_t)L + coef];
+        };
+        state[t] = src(row, 1) + src((row + 3) & 3, 0) + src((row + 2) & 3, 0) + src((row + 1) & 3, 2) +
+                   rk_round[(size_t)(pos * 8 + bit) * L + coef];
+    }
+}
+
+// aes_final_kernel for counter mode: the first n_bytes keystream bytes (block order) only, SubBytes output
+// of (blk, byte) at group map[blk*16 + byte] (map == nullptr: at blk*16 + byte), and with data != nullptr
+// the public byte data[i] XORed in: bit b of it << 63 on the body of keystream bit b of byte i
+__global__ void aes_ctr_final_kernel(const uint64_t *__restrict__ sb, const int32_t *__restrict__ map,
+                                     const uint64_t *__restrict__ rk_round, const uint8_t *__restrict__ data,
+                                     uint64_t *__restrict__ out, size_t n_bytes, int L) {
+    const size_t total = n_bytes * 8 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t coef = t % L;
+        const size_t ct = t / L;
+        const int bit = (int)(ct & 7);
+        const int pos = (int)((ct >> 3) & 15);
+        const size_t blk = ct >> 7;
+        const int c = pos >> 2, row = pos & 3;
+        const int byte = 4 * ((c + row) & 3) + row;
+        const size_t g = map ? (size_t)map[blk * 16 + byte] : blk * 16 + byte;
+        uint64_t w = sb[(g * 8 + bit) * (size_t)L + coef] + rk_round[(size_t)(pos * 8 + bit) * L + coef];
+        if (data && coef == (size_t)L - 1) w += (uint64_t)((data[ct >> 3] >> (7 - bit)) & 1) << 63;
+        out[t] = w;
+    }
+}
+
 __global__ void lwe_add_kernel(uint64_t *__restrict__ a, const uint64_t *__restrict__ b, size_t count) {
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (size_t)gridDim.x * blockDim.x)
         a[t] += b[t];
@@ -559,6 +622,32 @@ __global__ void aes8_mix_kernel(const uint64_t *__restrict__ sb, const uint64_t 
             const int ri = i >> 3, bi = i & 7;
             const int byte = 4 * ((c + ri) & 3) + ri;  // ShiftRows: state[ri][c] = sb[ri][(c + ri) % 4]
             acc += sb[((blk * 16 + byte) * 8 + bi) * (size_t)L + coef];
+        }
+        state[t] = acc;
+    }
+}
+
+// aes8_mix_kernel with the SubBytes output of (blk, byte) at group map[blk*16 + byte]: sb [U][8][L]
+__global__ void aes8_mix_idx_kernel(const uint64_t *__restrict__ sb, const int32_t *__restrict__ map,
+                                    const uint64_t *__restrict__ rk_round, uint64_t *__restrict__ state, size_t nb,
+                                    int L, MixTerms T) {
+    const size_t total = nb * 128 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t coef = t % L;
+        const size_t ct = t / L;
+        const int bit = (int)(ct & 7);
+        const int pos = (int)((ct >> 3) & 15);
+        const size_t blk = ct >> 7;
+        const int c = pos >> 2, row = pos & 3, o = 8 * row + bit;
+        uint64_t acc = rk_round[(size_t)(pos * 8 + bit) * L + coef];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int i = T.idx[o][q];
+            if (i < 0) break;
+            const int ri = i >> 3, bi = i & 7;
+            const int byte = 4 * ((c + ri) & 3) + ri;
+            const size_t g = (size_t)map[blk * 16 + byte];
+            acc += sb[(g * 8 + bi) * (size_t)L + coef];
         }
         state[t] = acc;
     }
@@ -812,6 +901,15 @@ void Engine::init_common() {
     }
     const char *blat = getenv("TAE_BR_LAT_MAX");
     lat_max_ = blat ? atol(blat) : 256;
+    // counter mode (aes_ctr): blocks per device pass; the value must be a positive integer
+    if (const char *cc = getenv("TAE_CTR_CHUNK_BLOCKS")) {
+        char *end = nullptr;
+        errno = 0;
+        const long long v = strtoll(cc, &end, 10);
+        if (errno != 0 || end == cc || *end != '\0' || v <= 0)
+            throw std::runtime_error(std::string("TAE_CTR_CHUNK_BLOCKS must be a positive integer, got '") + cc + "'");
+        ctr_chunk_ = (size_t)v;
+    }
     HIPC(hipDeviceGetAttribute(&num_cu_, hipDeviceAttributeMultiprocessorCount, device_));
     if (mask_cus) num_cu_ = mask_cus;
     // the lvl_64 PBS throughput kernel: br512p16 (sixteen points per lane, two ciphertexts per workgroup) or
@@ -1027,7 +1125,8 @@ Engine::~Engine() {
                     (void *)d_ggsw_f_, (void *)d_state_, (void *)d_muls_, (void *)d_pf_bt_, (void *)d_ks_bt_, (void *)d_pf_corr_, (void *)d_pf_bt_kl_,
                     (void *)d_digits_, (void *)d_wlut_sbox_, (void *)d_wlut_id_, (void *)d_lut_x_, (void *)d_xbuf_,
                     (void *)d_xsh_, (void *)d_xks_, (void *)d_xpbs_, (void *)d_ints_, (void *)d_s1_sbox_tv_,
-                    (void *)d_s1_id_tv_, (void *)d_s1_in_, (void *)d_s1_out_, (void *)d_s1_pks_, (void *)d_s1_tv_, (void *)d_pf_flags_, (void *)d_clk_, (void *)d_lf_, (void *)d_acc_w_})
+                    (void *)d_s1_id_tv_, (void *)d_s1_in_, (void *)d_s1_out_, (void *)d_s1_pks_, (void *)d_s1_tv_, (void *)d_pf_flags_, (void *)d_clk_, (void *)d_lf_, (void *)d_acc_w_,
+                    (void *)d_ctr_groups_, (void *)d_ctr_map_})
         if (q) hipFree(q);
     for (auto &e : ev_pool_) hipEventDestroy(e);
     if (caller_ev_) hipEventDestroy(caller_ev_);
@@ -1523,6 +1622,119 @@ void Engine::aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, 
     aes_final_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_rk + (size_t)160 * byte_stride, d_out,
                                                                      nb, L);
     HIPC(hipGetLastError());
+}
+
+// ---- AES-128-CTR with public counters ----
+void Engine::upload_ctr_plan(const CtrPlan &plan, size_t nb) {
+    if (plan.map.size() != nb * 16 || plan.groups.empty()) throw std::runtime_error("counter plan does not match the blocks");
+    for (int32_t g : plan.map)
+        if (g < 0 || (size_t)g >= plan.groups.size()) throw std::runtime_error("counter plan: group index out of range");
+    grow(d_ctr_groups_, cap_ctr_groups_, plan.groups.size());
+    grow(d_ctr_map_, cap_ctr_map_, plan.map.size());
+    HIPC(hipMemcpyAsync(d_ctr_groups_, plan.groups.data(), plan.groups.size() * sizeof(uint16_t), hipMemcpyHostToDevice,
+                        stream_));
+    HIPC(hipMemcpyAsync(d_ctr_map_, plan.map.data(), plan.map.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+}
+
+void Engine::aes_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
+                            size_t out_bytes, uint64_t *d_out) {
+    if (!nb) return;
+    if (p_.model != 1) throw std::runtime_error("aes_ctr_blocks needs the 1-bit model parameters");
+    if (rounds < 1 || rounds > 10) throw std::runtime_error("rounds must be in 1..=10");
+    if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
+    const int L = (int)p_.big_len();
+    const size_t U = plan.groups.size();
+    upload_ctr_plan(plan, nb);
+    // round 1 works on U groups; the per-block state and the 24 SubBytes multiples exist from round 2 on
+    const size_t state_len = nb * 128 * (size_t)L;
+    grow(d_state_, cap_state_, rounds == 1 ? U * 8 * (size_t)L : state_len);
+    grow(d_muls_, cap_muls_, rounds == 1 ? U * 8 * (size_t)L : nb * 16 * 24 * (size_t)L);
+    const size_t byte_stride = 8 * (size_t)L;
+    aes_ctr_round0_kernel<<<grid_for(U * 8 * (size_t)L), kThreads, 0, stream_>>>(d_rk, d_ctr_groups_, d_state_, U, L);
+    HIPC(hipGetLastError());
+    size_t G = U;
+    const int32_t *map = d_ctr_map_;
+    for (int r = 1; r < rounds; r++) {
+        circuit_bootstrap(d_state_, G, 8, d_lut24_, 24, d_muls_);
+        const uint64_t *rk_r = d_rk + (size_t)16 * r * byte_stride;
+        if (map)
+            aes_mix_idx_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, map, rk_r, d_state_, nb, L);
+        else
+            aes_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, rk_r, d_state_, nb, L);
+        HIPC(hipGetLastError());
+        G = nb * 16;
+        map = nullptr;
+    }
+    circuit_bootstrap(d_state_, G, 8, d_lut8_, 8, d_muls_);
+    if (out_bytes) {
+        aes_ctr_final_kernel<<<grid_for(out_bytes * 8 * (size_t)L), kThreads, 0, stream_>>>(
+            d_muls_, map, d_rk + (size_t)160 * byte_stride, d_data, d_out, out_bytes, L);
+        HIPC(hipGetLastError());
+    }
+}
+
+void Engine::aes8_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
+                             size_t out_bytes, uint64_t *d_out) {
+    if (!nb) return;
+    if (p_.model != 8) throw std::runtime_error("aes8_ctr_blocks needs the 8-bit model parameters");
+    if (rounds < 1 || rounds > 10) throw std::runtime_error("rounds must be in 1..=10");
+    if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
+    const int L = (int)p_.small_len();
+    const size_t U = plan.groups.size();
+    upload_ctr_plan(plan, nb);
+    const size_t state_len = nb * 128 * (size_t)L;
+    grow(d_state_, cap_state_, rounds == 1 ? U * 8 * (size_t)L : state_len);
+    grow(d_muls_, cap_muls_, rounds == 1 ? U * 8 * (size_t)L : state_len);
+    const size_t byte_stride = 8 * (size_t)L;
+    MixTerms T;
+    std::memcpy(T.idx, mix_idx_, sizeof(T.idx));
+    aes_ctr_round0_kernel<<<grid_for(U * 8 * (size_t)L), kThreads, 0, stream_>>>(d_rk, d_ctr_groups_, d_state_, U, L);
+    HIPC(hipGetLastError());
+    size_t G = U;
+    const int32_t *map = d_ctr_map_;
+    for (int r = 1; r < rounds; r++) {
+        bootstrap_bytes8(d_state_, G, d_wlut_sbox_, d_muls_);
+        const uint64_t *rk_r = d_rk + (size_t)16 * r * byte_stride;
+        if (map)
+            aes8_mix_idx_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, map, rk_r, d_state_, nb, L, T);
+        else
+            aes8_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, rk_r, d_state_, nb, L, T);
+        HIPC(hipGetLastError());
+        G = nb * 16;
+        map = nullptr;
+    }
+    bootstrap_bytes8(d_state_, G, d_wlut_sbox_, d_muls_);
+    if (out_bytes) {
+        aes_ctr_final_kernel<<<grid_for(out_bytes * 8 * (size_t)L), kThreads, 0, stream_>>>(
+            d_muls_, map, d_rk + (size_t)160 * byte_stride, d_data, d_out, out_bytes, L);
+        HIPC(hipGetLastError());
+    }
+}
+
+void Engine::aes_ctr(const uint64_t *d_rk, const uint8_t iv[8], uint64_t first_counter, size_t nb, int rounds,
+                     const uint8_t *d_data, size_t out_bytes, uint64_t *d_out) {
+    if (!nb) return;
+    if (p_.model != 1 && p_.model != 8) throw std::runtime_error("counter mode runs on the 1-bit and 8-bit models");
+    if (!ctr_range_ok(first_counter, nb)) throw std::runtime_error("counter range wraps past 2^64 - 1");
+    if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
+    times_ = StageTimes{};
+    const size_t L = p_.bit_len();
+    // the uploads of a plan are asynchronous: every chunk's plan lives until the next call
+    ctr_plans_.clear();
+    ctr_plans_.reserve((nb + ctr_chunk_ - 1) / ctr_chunk_);
+    for (size_t b0 = 0; b0 < nb; b0 += ctr_chunk_) {
+        const size_t cn = std::min(ctr_chunk_, nb - b0);
+        const size_t byte0 = b0 * 16;
+        const size_t cbytes = out_bytes > byte0 ? std::min(cn * 16, out_bytes - byte0) : 0;
+        ctr_plans_.emplace_back();
+        ctr_plan(iv, first_counter + b0, cn, ctr_plans_.back());
+        const uint8_t *data = d_data ? d_data + byte0 : nullptr;
+        uint64_t *out = d_out + byte0 * 8 * L;
+        if (p_.model == 8)
+            aes8_ctr_blocks(d_rk, ctr_plans_.back(), cn, rounds, data, cbytes, out);
+        else
+            aes_ctr_blocks(d_rk, ctr_plans_.back(), cn, rounds, data, cbytes, out);
+    }
 }
 
 // ---- shortint_1bit model ----

@@ -529,6 +529,114 @@ std::vector<BitCt> Context::aes_encrypt_blocks(const std::vector<const BitCt *> 
     return res;
 }
 
+// ---------------------------------------------------------------------------------------------
+// AES-128-CTR with public counters (main.rs:108-128)
+// ---------------------------------------------------------------------------------------------
+std::vector<std::vector<NoiseLevel>> aes_ctr_noise_schedule(const std::vector<NoiseLevel> &rk, const CtrPlan &plan,
+                                                            size_t n_blocks, int rounds, uint64_t max) {
+    const std::vector<NoiseLevel> triv(128, NoiseLevel::trivial());
+    std::vector<std::vector<NoiseLevel>> out(n_blocks);
+    if (rounds != 1) {
+        for (auto &o : out) o = aes_noise_schedule(rk, triv, rounds, max);
+        return out;
+    }
+    // one round: ARK(rk0) on trivial bits, SubBytes 8 -> 8 of every group (noise^2 = 8, one id per output
+    // bit of a GROUP), ShiftRows, ARK(rk10)
+    std::vector<NoiseLevel> sb(plan.groups.size() * 8);
+    for (auto &x : sb) x = NoiseLevel::with_noise_level(8, next_ct_id());
+    for (size_t blk = 0; blk < n_blocks; blk++) {
+        out[blk].resize(128);
+        for (int c = 0; c < 4; c++)
+            for (int r = 0; r < 4; r++)
+                for (int b = 0; b < 8; b++) {
+                    NoiseLevel v = sb[(size_t)plan.map[blk * 16 + 4 * ((c + r) % 4) + r] * 8 + b];
+                    v.add_assign(rk[((40 + c) * 4 + r) * 8 + b], max);
+                    out[blk][(4 * c + r) * 8 + b] = std::move(v);
+                }
+    }
+    return out;
+}
+
+// argument checks and the static noise validation, before any device work
+void Context::check_ctr(uint64_t first_counter, size_t n_blocks, int rounds) const {
+    if (params().model == 2)
+        throw ModelError{TAE_E_PARAM, "counter mode is not available for the shortint_1bit parameter set"};
+    if (rounds < 1 || rounds > kAesRounds) throw ModelError{TAE_E_PARAM, "rounds must be in 1..=10"};
+    if (!ctr_range_ok(first_counter, n_blocks)) throw ModelError{TAE_E_ARG, "counter range wraps past 2^64 - 1"};
+    std::vector<NoiseLevel> krk(44 * 32), kbl(128, NoiseLevel::trivial());
+    for (auto &x : krk) x = params().model != 1 ? NoiseLevel{1, {}} : NoiseLevel::with_noise_level(1, next_ct_id());
+    block_noise_schedule(AesDriver::GalMul, krk, kbl, rounds);
+}
+
+void Context::run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
+                          const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem) {
+    const size_t S = bit_len();
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    DevBuf d_data(data ? out_bytes : 0);  // the public bytes are a host array, always
+    if (data)
+        hip_check(hipMemcpyAsync(d_data.p, data, out_bytes, hipMemcpyHostToDevice, engine_->stream()), "upload data");
+    const uint8_t *dd = data ? d_data.as<uint8_t>() : nullptr;
+    if (device_mem) {
+        engine_->order_after_caller();
+        engine_->aes_ctr(rk, iv, first_counter, n_blocks, rounds, dd, out_bytes, out);
+        engine_->synchronize();
+        return;
+    }
+    DevBuf d_rk(44 * 32 * S * 8), d_out(out_bytes * 8 * S * 8);
+    hip_check(hipMemcpyAsync(d_rk.p, rk, 44 * 32 * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload rk");
+    engine_->aes_ctr(d_rk.as<uint64_t>(), iv, first_counter, n_blocks, rounds, dd, out_bytes, d_out.as<uint64_t>());
+    hip_check(hipMemcpyAsync(out, d_out.p, out_bytes * 8 * S * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+void Context::aes_ctr_keystream_raw(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks,
+                                    int rounds, uint64_t *out, bool device_mem) {
+    check_ctr(first_counter, n_blocks, rounds);
+    if (!n_blocks) return;
+    run_aes_ctr(rk, iv, first_counter, n_blocks, rounds, nullptr, n_blocks * 16, out, device_mem);
+}
+
+void Context::aes_ctr_transcipher_raw(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter,
+                                      const uint8_t *data, size_t len, int rounds, uint64_t *out, bool device_mem) {
+    const size_t n_blocks = len / 16 + (len % 16 != 0);
+    check_ctr(first_counter, n_blocks, rounds);
+    if (!len) return;
+    run_aes_ctr(rk, iv, first_counter, n_blocks, rounds, data, len, out, device_mem);
+}
+
+std::vector<BitCt> Context::aes_ctr_transcipher(const std::vector<const BitCt *> &expanded_key, const uint8_t iv[8],
+                                                uint64_t first_counter, const uint8_t *data, size_t len, int rounds) {
+    if (expanded_key.size() != 44 * 32) throw ModelError{TAE_E_ARG, "expanded key must be 44 words (1408 bits)"};
+    const size_t L = bit_len();
+    for (const BitCt *b : expanded_key)
+        if (b->ct.size() != L) throw ModelError{TAE_E_ARG, "ciphertext size mismatch"};
+    const size_t n_blocks = len / 16 + (len % 16 != 0);
+    check_ctr(first_counter, n_blocks, rounds);
+    if (!len) return {};
+    std::vector<NoiseLevel> krk(44 * 32);
+    for (size_t i = 0; i < krk.size(); i++) krk[i] = expanded_key[i]->noise;
+    std::vector<std::vector<NoiseLevel>> out_noise(n_blocks);
+    if (params().model == 1) {
+        CtrPlan plan;
+        ctr_plan(iv, first_counter, n_blocks, plan);
+        out_noise = aes_ctr_noise_schedule(krk, plan, n_blocks, rounds, params().max_noise_sq);
+    } else {
+        const std::vector<NoiseLevel> triv(128, NoiseLevel::trivial());
+        for (auto &o : out_noise) o = block_noise_schedule(AesDriver::GalMul, krk, triv, rounds);
+    }
+    std::vector<uint64_t> rk(44 * 32 * L), out(len * 8 * L);
+    for (size_t i = 0; i < 44 * 32; i++) std::memcpy(&rk[i * L], expanded_key[i]->ct.data(), L * 8);
+    run_aes_ctr(rk.data(), iv, first_counter, n_blocks, rounds, data, len, out.data(), false);
+    std::vector<BitCt> res(len * 8);
+    for (size_t i = 0; i < res.size(); i++) {
+        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
+        res[i].noise = out_noise[i / 128][i % 128];  // xor with a public bit adds no noise
+        res[i].max_noise_sq = params().max_noise_sq;
+    }
+    return res;
+}
+
 // fhe_sbox_gal_mul_pbs::key_schedule (:134-164) with ByteT::{sbox_substitute, bootstrap_assign}
 // (fhe_impls/shortint_woppbs_1bit.rs:18-45): words 0..3 = key; word i>=4 from words i-4, i-1
 // (SubWord(RotWord) + Rcon when i%4 == 0), then every bit of word i is bootstrapped (identity LUT).

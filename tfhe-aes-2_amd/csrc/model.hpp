@@ -90,6 +90,22 @@ class Context {  // FheContext
     void aes_key_schedule_raw(const uint64_t *key, uint64_t *expanded, bool device_mem,
                               AesDriver driver = AesDriver::GalMul);
 
+    // ---- AES-128-CTR with public counters (main.rs:108-128): counter block i = iv || be64(first_counter + i)
+    // is public, so no counter ciphertexts exist and round 1 is bootstrapped once per distinct (position,
+    // byte) pair (ctr_plan.hpp).  Gal-mul driver on the 1-bit sets, fhe_sbox_pbs on the 8-bit set;
+    // SHORTINT_1BIT is TAE_E_PARAM.  The noise schedule is validated statically for trivial blocks. ----
+    // keystream blocks [n_blocks][128][bit_len]; rk / out host or device, iv host
+    void aes_ctr_keystream_raw(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks,
+                               int rounds, uint64_t *out, bool device_mem);
+    // data (host bytes, AES-CTR ciphertext) -> [len][8][bit_len] encryptions of the plaintext bits
+    void aes_ctr_transcipher_raw(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, const uint8_t *data,
+                                 size_t len, int rounds, uint64_t *out, bool device_mem);
+    // BitCt variant, [len*8] bits with the schedule's noise; with rounds == 1 outputs that share a round-1
+    // group share its component id
+    std::vector<BitCt> aes_ctr_transcipher(const std::vector<const BitCt *> &expanded_key, const uint8_t iv[8],
+                                           uint64_t first_counter, const uint8_t *data, size_t len,
+                                           int rounds = 10);
+
     // ---- 8-bit model (src/tfhe/shortint_woppbs_8bit.rs, fhe_impls/shortint_woppbs_8bit.rs) ----
     size_t bit_len() const { return params().bit_len(); }
     // FheContext::bootstrap_from_bits over G bytes: bits [G][8][n+1] -> int ciphertexts [G][K+1]
@@ -117,6 +133,9 @@ class Context {  // FheContext
     std::vector<BitCt> sbox_pbs_key_schedule(const std::vector<const BitCt *> &key);
     std::vector<NoiseLevel> block_noise_schedule(AesDriver driver, const std::vector<NoiseLevel> &rk,
                                                  const std::vector<NoiseLevel> &block, int rounds) const;
+    void check_ctr(uint64_t first_counter, size_t n_blocks, int rounds) const;
+    void run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
+                     const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem);
     void run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint64_t *d_in, size_t n_blocks, int rounds,
                         uint64_t *d_out);
     std::unique_ptr<Engine> engine_;
@@ -134,5 +153,11 @@ std::vector<NoiseLevel> sbox_pbs_noise_schedule(const std::vector<NoiseLevel> &r
 // outputs are NOMINAL = 1).
 std::vector<NoiseLevel> aes8_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &block,
                                             int rounds, uint64_t max_noise_level);
+
+// Counter mode on the 1-bit model: output noise [n_blocks][128] of the gal-mul schedule for trivial counter
+// blocks.  rounds >= 2: aes_noise_schedule per block.  rounds == 1: the final SubBytes runs on the plan's
+// groups, so outputs that read the same group carry the same component id.
+std::vector<std::vector<NoiseLevel>> aes_ctr_noise_schedule(const std::vector<NoiseLevel> &rk, const CtrPlan &plan,
+                                                            size_t n_blocks, int rounds, uint64_t max_noise_sq);
 
 }  // namespace tae

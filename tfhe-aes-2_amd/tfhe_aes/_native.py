@@ -38,6 +38,7 @@ EXPORTED = [
     "tae_aes_sbox_pbs_key_schedule_raw", "tae_aes_noise_schedule_check",
     "tae_s1_test_vector_from_fn", "tae_s1_bootstrap", "tae_s1_packing_keyswitch",
     "tae_s1_test_vectors_from_ciphertexts", "tae_s1_multivariate",
+    "tae_aes_ctr_plan", "tae_aes_ctr_keystream_raw", "tae_aes_ctr_transcipher_raw", "tae_aes_ctr_transcipher",
 ]
 TAE_DRIVER_GAL_MUL, TAE_DRIVER_SBOX_PBS = 0, 1
 TAE_KEYS_CLIENT, TAE_KEYS_SERVER = 1, 2
@@ -118,6 +119,10 @@ def lib() -> C.CDLL:
         "tae_aes_sbox_pbs_encrypt_blocks_raw": ([vp, vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_aes_sbox_pbs_key_schedule_raw": ([vp, vp, vp, C.c_int], C.c_int),
         "tae_aes_noise_schedule_check": ([C.c_int, C.c_int, C.c_int], C.c_int),
+        "tae_aes_ctr_plan": ([C.c_char_p, u64, sz, C.POINTER(sz)], C.c_int),
+        "tae_aes_ctr_keystream_raw": ([vp, vp, C.c_char_p, u64, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aes_ctr_transcipher_raw": ([vp, vp, C.c_char_p, u64, vp, sz, vp, C.c_int], C.c_int),
+        "tae_aes_ctr_transcipher": ([vp, vp, C.c_char_p, u64, vp, sz, vp], C.c_int),
         "tae_stage_keyswitch": ([vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_pbs_shift_boolean": ([vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_stage_bootstrap": ([vp, vp, sz, vp, vp, C.c_int], C.c_int),

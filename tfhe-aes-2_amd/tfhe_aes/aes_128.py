@@ -204,6 +204,50 @@ class ShortintWoppbs1BitSboxGalMulPbsAesEncrypt:
                                           N.TAE_MEM_HOST))
         return out
 
+    # ---- AES-128-CTR with public counters: transciphering (main.rs:108-128) ----
+    # Counter block i is iv || be64(first_counter + i); the iv and the counters are public, so no counter
+    # ciphertexts are made or uploaded, and round 1 is bootstrapped once per distinct (position, byte) pair.
+    # The entry points are the same for every driver class (tae_aes_ctr_*; the C-ABI dispatches on the model).
+    @staticmethod
+    def ctr_keystream_raw(ctx: FheContext, rk: np.ndarray, iv: bytes, first_counter: int, n_blocks: int,
+                          rounds: int = ROUNDS) -> np.ndarray:
+        """Host arrays: rk [1408][L] -> keystream blocks [n_blocks][128][L], equal word for word to
+        encrypt_blocks_raw on trivial encryptions of the counter blocks."""
+        rk = np.ascontiguousarray(rk, dtype=np.uint64)
+        out = np.zeros((n_blocks, 128, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aes_ctr_keystream_raw(ctx._h, rk.ctypes.data_as(C.c_void_p), _iv8(iv), first_counter,
+                                              n_blocks, rounds, out.ctypes.data_as(C.c_void_p), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def ctr_keystream_device(ctx: FheContext, d_rk: int, iv: bytes, first_counter: int, n_blocks: int, rounds: int,
+                             d_out: int):
+        """Device pointers (ints) for rk and the output [n_blocks][128][L]; iv is host bytes."""
+        check(lib().tae_aes_ctr_keystream_raw(ctx._h, C.c_void_p(d_rk), _iv8(iv), first_counter, n_blocks, rounds,
+                                              C.c_void_p(d_out), N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def ctr_transcipher_raw(ctx: FheContext, rk: np.ndarray, iv: bytes, first_counter: int, data: bytes) -> np.ndarray:
+        """data: AES-128-CTR ciphertext bytes -> [len][8][L] FHE encryptions of the plaintext bits (10 rounds)."""
+        rk = np.ascontiguousarray(rk, dtype=np.uint64)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        out = np.zeros((len(buf), 8, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aes_ctr_transcipher_raw(ctx._h, rk.ctypes.data_as(C.c_void_p), _iv8(iv), first_counter,
+                                                buf.ctypes.data_as(C.c_void_p), len(buf),
+                                                out.ctypes.data_as(C.c_void_p), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def ctr_transcipher(ctx: FheContext, expanded_key, iv: bytes, first_counter: int, data: bytes):
+        """expanded_key: [44][4][8] BitCt (nested or flat) -> [len][8] BitCt of the plaintext bits."""
+        ek = _flat_bits(expanded_key)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        outs = (C.c_void_p * (8 * len(buf)))()
+        check(lib().tae_aes_ctr_transcipher(ctx._h, _handles(ek), _iv8(iv), first_counter,
+                                            buf.ctypes.data_as(C.c_void_p), len(buf), outs))
+        bits = [BitCt(h, ctx) for h in outs]
+        return [bits[8 * i:8 * i + 8] for i in range(len(buf))]
+
 
 class ShortintWoppbs1BitSboxPbsAesEncrypt(ShortintWoppbs1BitSboxGalMulPbsAesEncrypt):
     """fhe_impls/shortint_woppbs_1bit.rs:47-81: the generic fhe_sbox_pbs driver (fhe_sbox_pbs.rs:22-171) over
@@ -248,9 +292,35 @@ def noise_schedule_check(param_set: int, driver: int, rounds: int) -> None:
     check(lib().tae_aes_noise_schedule_check(param_set, driver, rounds))
 
 
-def counter_blocks(iv: bytes, count: int) -> List[bytes]:
-    """main.rs:108-115: block = iv (8 bytes) || ctr as u64 big-endian, ctr = 1..=count."""
-    return [bytes(iv) + c.to_bytes(8, "big") for c in range(1, count + 1)]
+def _iv8(iv: bytes) -> bytes:
+    iv = bytes(iv)
+    if len(iv) != 8:
+        raise ValueError("iv must be 8 bytes")
+    return iv
+
+
+def counter_blocks(iv: bytes, count: int, *, first: int = 1) -> List[bytes]:
+    """main.rs:108-115: block = iv (8 bytes) || ctr as u64 big-endian, ctr = first..first + count - 1
+    (the reference counts from 1)."""
+    return [bytes(iv) + c.to_bytes(8, "big") for c in range(first, first + count)]
+
+
+def ctr_plan(iv: bytes, first_counter: int, n_blocks: int) -> int:
+    """Number of round-1 SBOX groups the counter-mode entry points bootstrap for this range: one per
+    distinct (byte position, byte value) of the counter blocks (8 for the iv + the distinct values of
+    each counter byte).  Host only; a range that wraps past 2^64 - 1 raises TaeError (TAE_E_ARG)."""
+    n = C.c_size_t(0)
+    check(lib().tae_aes_ctr_plan(_iv8(iv), first_counter, n_blocks, C.byref(n)))
+    return n.value
+
+
+def ctr_xor_plain(key: bytes, iv: bytes, first_counter: int, data: bytes) -> bytes:
+    """Plain AES-128-CTR (main.rs:117-128): data xor the keystream of counters first_counter.. ; encrypts
+    and decrypts."""
+    ek = key_schedule_plain(key)
+    nb = (len(data) + 15) // 16
+    ks = b"".join(encrypt_block_plain(ek, b) for b in counter_blocks(_iv8(iv), nb, first=first_counter))
+    return bytes(d ^ k for d, k in zip(data, ks))
 
 
 def blocks_to_bits(blocks: Sequence[bytes]) -> np.ndarray:

@@ -9,7 +9,7 @@ xGMI; the same functions run on CPU tensors under "gloo" for the world_size-2 te
 """
 import numpy as np
 
-__all__ = ["shard_counters", "counter_blocks_for_rank", "encrypt_start_index", "broadcast_u64",
+__all__ = ["shard_counters", "shard_counter_range", "counter_blocks_for_rank", "encrypt_start_index", "broadcast_u64",
            "max_over_ranks", "min_over_ranks"]
 
 
@@ -20,6 +20,13 @@ def shard_counters(rank, world, blocks_per_rank, first=1):
         raise ValueError(f"rank {rank} outside world of size {world}")
     start = first + rank * blocks_per_rank
     return range(start, start + blocks_per_rank)
+
+
+def shard_counter_range(rank, world, blocks_per_rank, first=1):
+    """(first_counter, n_blocks) of `rank`'s shard, the arguments of the counter-mode entry points
+    (aes_128 ctr_keystream_* / ctr_transcipher_*): the same counters as shard_counters."""
+    r = shard_counters(rank, world, blocks_per_rank, first)
+    return r.start, len(r)
 
 
 def counter_blocks_for_rank(iv, rank, world, blocks_per_rank):
