@@ -245,6 +245,47 @@ int tae_aes_ctr_transcipher_raw(const tae_context *ctx, const uint64_t *rk, cons
 int tae_aes_ctr_transcipher(const tae_context *ctx, const tae_bit *const *expanded_key, const uint8_t iv[8],
                             uint64_t first_counter, const uint8_t *data, size_t len, tae_bit **out /*[len*8]*/);
 
+/* ---- AES-128 inverse cipher and CBC transciphering (FIPS-197 section 5.3) ---------------------------
+ * The reference has no decryption and no counterpart of these functions; they are FIPS-197 5.3 (in the
+ * order of 5.3.5) in this library's conventions.  InvSubBytes and InvMixColumns' Galois multiples
+ * {14, 11, 13, 9} (true products modulo 0x11b) come from one 8 -> 32 circuit bootstrap per byte and middle
+ * round, the last round from one 8 -> 8: `rounds` bootstraps per block, as encryption.
+ * tae_aes_decrypt_blocks(rounds) inverts tae_aes_encrypt_blocks(rounds) (round keys 10, rounds-1 .. 1, 0).
+ * Parameter sets: TAE_PARAMS_SQRD_LVL_* (gal-mul driver) only; TAE_PARAMS_WOPPBS_8BIT and
+ * TAE_PARAMS_SHORTINT_1BIT are TAE_E_PARAM.  Raw entry points validate the noise schedule statically,
+ * before any device work; handle entry points propagate it per bit. */
+/* FIPS-197 5.3.5 decryption key (no reference counterpart): dk [44*32] laid out like the expanded key; words
+ * 0..3 and 40..43 are copies, words 4r..4r+3 (r = 1..9) = InvMixColumns(rk[r]), derived on the device by one
+ * 8 -> 32 bootstrap of the 144 bytes, the 4-term sums and one identity bootstrap of the 1152 bits
+ * (noise^2 = 1, new ids). */
+int tae_aes_decrypt_key(const tae_context *ctx, const tae_bit *const *expanded_key, tae_bit **dk /*[44*32]*/);
+/* FIPS-197 5.3.5 decryption key on raw arrays (no reference counterpart): rk, dk [44*32][L] follow `mem`;
+ * with TAE_MEM_DEVICE dk must not be rk */
+int tae_aes_decrypt_key_raw(const tae_context *ctx, const uint64_t *rk, uint64_t *dk, int mem);
+/* FIPS-197 5.3 inverse cipher on handles (no reference counterpart): blocks, out [n_blocks*128]; feeding
+ * tae_aes_encrypt_blocks' output back with a key derived from the same expanded key is TAE_E_INDEP (the
+ * output carries round key 10's ids) */
+int tae_aes_decrypt_blocks(const tae_context *ctx, const tae_bit *const *dk, const tae_bit *const *blocks,
+                           size_t n_blocks, int rounds, tae_bit **out);
+/* FIPS-197 5.3 inverse cipher on raw arrays (no reference counterpart): dk [44*32][L], blocks / out
+ * [n_blocks][128][L], all following `mem` */
+int tae_aes_decrypt_blocks_raw(const tae_context *ctx, const uint64_t *dk, const uint64_t *blocks, size_t n_blocks,
+                               int rounds, uint64_t *out, int mem);
+/* CBC decryption of a public ciphertext, FIPS-197 5.3 per block (no reference counterpart): out[len*8] =
+ * encryptions of P_i = Dec(C_i) ^ C_{i-1}, C_{-1} = iv, 10 rounds.  len % 16 != 0 is TAE_E_ARG, len == 0 is
+ * TAE_OK and writes nothing; padding is the client's business.  No input ciphertexts are made: round 0 is
+ * dk[40..43] + the public bits, and the last step adds the public bits of C_{i-1} (no noise). */
+int tae_aes_cbc_transcipher(const tae_context *ctx, const tae_bit *const *dk, const uint8_t iv[16], const uint8_t *data,
+                            size_t len, tae_bit **out /*[len*8]*/);
+/* the same on raw arrays (FIPS-197 5.3, no reference counterpart): dk / out [len][8][L] follow `mem`; iv and
+ * data are host pointers */
+int tae_aes_cbc_transcipher_raw(const tae_context *ctx, const uint64_t *dk, const uint8_t iv[16], const uint8_t *data,
+                                size_t len, uint64_t *out, int mem);
+/* noise bookkeeping of the FIPS-197 5.3 inverse cipher for fresh inputs (no reference counterpart; no GPU):
+ * the decryption-key derivation, then `rounds` rounds with the derived key.  TAE_OK, TAE_E_NOISE or
+ * TAE_E_INDEP; parameter sets other than TAE_PARAMS_SQRD_LVL_* and rounds outside 1..=10 are TAE_E_PARAM */
+int tae_aes_decrypt_noise_schedule_check(int param_set, int rounds);
+
 /* ---- Aes128Encrypt for the fhe_sbox_pbs driver (src/aes_128/fhe/fhe_sbox_pbs.rs:22-171) ------------
  * ShortintWoppbs1BitSboxPbsAesEncrypt on the 1-bit model (fhe_impls/shortint_woppbs_1bit.rs:47-81:
  * SubBytes = one 8 -> 8 circuit bootstrap per byte, MixColumns = gf_256_mul by BitCt XORs) and

@@ -613,6 +613,67 @@ int tae_aes_ctr_transcipher(const tae_context *ctx, const tae_bit *const *expand
     });
 }
 
+/* ---- inverse cipher, FIPS-197 5.3 (no counterpart in the reference) ---- */
+int tae_aes_decrypt_key(const tae_context *ctx, const tae_bit *const *expanded_key, tae_bit **dk) {
+    return guarded([&] {
+        require(ctx && expanded_key && dk, "null");
+        emit(ctx->ctx->aes_decrypt_key(unwrap(expanded_key, 44 * 32)), dk);
+    });
+}
+
+int tae_aes_decrypt_key_raw(const tae_context *ctx, const uint64_t *rk, uint64_t *dk, int mem) {
+    return guarded([&] {
+        require(ctx && rk && dk, "null");
+        ctx->ctx->aes_decrypt_key_raw(rk, dk, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_aes_decrypt_blocks(const tae_context *ctx, const tae_bit *const *dk, const tae_bit *const *blocks,
+                           size_t n_blocks, int rounds, tae_bit **out) {
+    return guarded([&] {
+        require(ctx && dk && (n_blocks == 0 || (blocks && out)), "null");
+        emit(ctx->ctx->aes_decrypt_blocks(unwrap(dk, 44 * 32), unwrap(blocks, 128 * n_blocks), n_blocks, rounds), out);
+    });
+}
+
+int tae_aes_decrypt_blocks_raw(const tae_context *ctx, const uint64_t *dk, const uint64_t *blocks, size_t n_blocks,
+                               int rounds, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && dk && (n_blocks == 0 || (blocks && out)), "null");
+        ctx->ctx->aes_decrypt_blocks_raw(dk, blocks, n_blocks, rounds, out, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_aes_cbc_transcipher(const tae_context *ctx, const tae_bit *const *dk, const uint8_t iv[16], const uint8_t *data,
+                            size_t len, tae_bit **out) {
+    return guarded([&] {
+        require(ctx && dk && iv && ((data && out) || !len), "null");
+        emit(ctx->ctx->aes_cbc_transcipher(unwrap(dk, 44 * 32), iv, data, len), out);
+    });
+}
+
+int tae_aes_cbc_transcipher_raw(const tae_context *ctx, const uint64_t *dk, const uint8_t iv[16], const uint8_t *data,
+                                size_t len, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && dk && iv && ((data && out) || !len), "null");
+        ctx->ctx->aes_cbc_transcipher_raw(dk, iv, data, len, tae::kAesRounds, out, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_aes_decrypt_noise_schedule_check(int param_set, int rounds) {
+    return guarded([&] {
+        const tae::Params p = params_of(param_set);
+        if (p.model != 1)
+            throw tae::ModelError{TAE_E_PARAM, "the inverse cipher runs on the 1-bit WoP-PBS parameter sets only"};
+        if (rounds < 1 || rounds > 10) throw tae::ModelError{TAE_E_PARAM, "rounds must be in 1..=10"};
+        std::vector<tae::NoiseLevel> rk(44 * 32), blk(128);
+        for (auto &x : rk) x = tae::NoiseLevel::with_noise_level(1, tae::next_ct_id());
+        for (auto &x : blk) x = tae::NoiseLevel::with_noise_level(1, tae::next_ct_id());
+        const std::vector<tae::NoiseLevel> dk = tae::aes_decrypt_key_noise_schedule(rk, p.max_noise_sq);
+        tae::aes_decrypt_noise_schedule(dk, blk, rounds, p.max_noise_sq);
+    });
+}
+
 int tae_aes_sbox_pbs_encrypt_blocks(const tae_context *ctx, const tae_bit *const *expanded_key,
                                     const tae_bit *const *blocks, size_t n_blocks, int rounds, tae_bit **out) {
     return guarded([&] {

@@ -119,6 +119,18 @@ class Engine {
     void aes_ctr(const uint64_t *d_rk, const uint8_t iv[8], uint64_t first_counter, size_t nb, int rounds,
                  const uint8_t *d_data, size_t out_bytes, uint64_t *d_out);
 
+    // ---- AES-128 inverse cipher on the 1-bit model (FIPS-197 5.3; the reference has no decryption).  The
+    // algorithm is in aes_inv.hpp: InvSubBytes and InvMixColumns' multiples {14,11,13,9} in one 8 -> 32 circuit
+    // bootstrap per byte and middle round, one 8 -> 8 for the last: `rounds` bootstraps per block, as encryption ----
+    // dk [44*32][K+1] (aes_decrypt_key), blocks / out [nb][128][K+1]; inverts aes_encrypt_blocks(rounds)
+    void aes_decrypt_blocks(const uint64_t *d_dk, const uint64_t *d_blocks, size_t nb, int rounds, uint64_t *d_out);
+    // decryption key: words 0..3 and 40..43 copied, words 4r..4r+3 = InvMixColumns(rk[r]) by one 8 -> 32 bootstrap
+    // of the 144 bytes (multiples only), the 4-term sums and one identity bootstrap of the 1152 bits.  d_dk != d_rk
+    void aes_decrypt_key(const uint64_t *d_rk, uint64_t *d_dk);
+    // CBC with a public ciphertext: d_iv_data = iv[16] || nb blocks of ciphertext bytes on the device; out
+    // [nb][128][K+1] = Dec(C_i) ^ C_{i-1}.  Round 0 and the last XOR come from the public bytes: no input ciphertexts
+    void aes_cbc_transcipher(const uint64_t *d_dk, const uint8_t *d_iv_data, size_t nb, int rounds, uint64_t *d_out);
+
     // ---- shortint_1bit model (src/tfhe/shortint_1bit.rs; param set SHORTINT_1BIT) ----
     // FheContext::bootstrap / bootstrap_assign (:257-291): PBS with test vector d_tvs + (b % lut_mod) (k+1)N, then the keyswitch
     // back to the small key: [B][n+1] -> [B][n+1]
@@ -186,6 +198,10 @@ class Engine {
     cplx *d_twist_ = nullptr, *d_untwist_ = nullptr, *d_w_ = nullptr;
     uint64_t *d_lut_shift_ = nullptr;  // per cbs level: trivial GLWE with body = -alpha
     uint64_t *d_lut24_ = nullptr, *d_lut8_ = nullptr;
+    // inverse cipher (1-bit model): InvSbox * {14,11,13,9}, InvSbox, the multiples alone, the 1 -> 1 identity
+    uint64_t *d_lut_inv32_ = nullptr, *d_lut_inv8_ = nullptr, *d_lut_mul32_ = nullptr, *d_lut_id1_ = nullptr;
+    void require_inverse(int rounds) const;
+    void aes_decrypt_rounds(const uint64_t *d_dk, size_t nb, int rounds, const uint8_t *d_xor, uint64_t *d_out);
     uint64_t *d_wlut_sbox_ = nullptr, *d_wlut_id_ = nullptr;  // 8-bit model
     uint64_t *d_lut_x_ = nullptr;                             // extract_bits accumulators [nbits][glwe]
     int lut_x_delta_ = -1, lut_x_bits_ = 0;

@@ -20,6 +20,7 @@
 #include <stdexcept>
 
 #include "aes.hpp"
+#include "aes_inv.hpp"
 #include "br512.hpp"
 #include "br512x4.hpp"
 #include "br512p16.hpp"
@@ -568,6 +569,66 @@ __global__ void aes_ctr_final_kernel(const uint64_t *__restrict__ sb, const int3
     }
 }
 
+// ---- AES-128 inverse cipher (FIPS-197 5.3; aes_inv.hpp has the algorithm and the source-byte indices) ----
+// InvShiftRows (shift_rows != 0), InvMixColumns and AddRoundKey on the four InvSubBytes*{14,11,13,9} states:
+// muls [nb*16][32][L], multiple m at ciphertexts 8m..8m+7 of a byte.  rk_round == nullptr adds no key and
+// shift_rows == 0 skips InvShiftRows: InvMixColumns alone, which derives the decryption key from nb round
+// keys.  Consecutive threads walk the coefficients of one ciphertext, so every read and the write coalesce.
+__global__ void aes_inv_mix_kernel(const uint64_t *__restrict__ muls, const uint64_t *__restrict__ rk_round,
+                                   uint64_t *__restrict__ state, size_t nb, int L, int shift_rows) {
+    const size_t total = nb * 128 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t coef = t % L;
+        const size_t ct = t / L;  // blk*128 + pos*8 + bit
+        const int bit = (int)(ct & 7);
+        const int pos = (int)((ct >> 3) & 15);
+        const size_t blk = ct >> 7;
+        const int c = pos >> 2, row = pos & 3;
+        uint64_t acc = rk_round ? rk_round[(size_t)(pos * 8 + bit) * L + coef] : 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int byte = inv_mix_src_byte(row, c, j, shift_rows != 0);
+            acc += muls[(((blk * 16 + byte) * 32) + 8 * j + bit) * (size_t)L + coef];
+        }
+        state[t] = acc;
+    }
+}
+
+// last round of the inverse cipher: InvSubBytes (8 -> 8), InvShiftRows, AddRoundKey(dk[0..3]); with
+// xor_bytes != nullptr (nb*16 public bytes) bit b of byte blk*16 + pos is XORed in as well, << 63 on the
+// body (CBC: the previous ciphertext block)
+__global__ void aes_inv_final_kernel(const uint64_t *__restrict__ sb, const uint64_t *__restrict__ rk_round,
+                                     const uint8_t *__restrict__ xor_bytes, uint64_t *__restrict__ out, size_t nb,
+                                     int L) {
+    const size_t total = nb * 128 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t coef = t % L;
+        const size_t ct = t / L;
+        const int bit = (int)(ct & 7);
+        const int pos = (int)((ct >> 3) & 15);
+        const size_t blk = ct >> 7;
+        const int byte = inv_final_src_byte(pos & 3, pos >> 2);
+        uint64_t w = sb[((blk * 16 + byte) * 8 + bit) * (size_t)L + coef] + rk_round[(size_t)(pos * 8 + bit) * L + coef];
+        if (xor_bytes && coef == (size_t)L - 1) w += (uint64_t)((xor_bytes[ct >> 3] >> (7 - bit)) & 1) << 63;
+        out[t] = w;
+    }
+}
+
+// round 0 of the inverse cipher on public blocks (nb*16 bytes): rk_last (dk words 40..43) + trivial(byte),
+// what aes_ark0_kernel computes for trivial encryptions of the blocks
+__global__ void aes_inv_round0_public_kernel(const uint64_t *__restrict__ rk_last, const uint8_t *__restrict__ bytes,
+                                             uint64_t *__restrict__ state, size_t nb, int L) {
+    const size_t total = nb * 128 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t coef = t % L;
+        const size_t ct = t / L;
+        const int bit = (int)(ct & 7);
+        uint64_t w = rk_last[(ct & 127) * (size_t)L + coef];
+        if (coef == (size_t)L - 1) w += (uint64_t)((bytes[ct >> 3] >> (7 - bit)) & 1) << 63;
+        state[t] = w;
+    }
+}
+
 __global__ void lwe_add_kernel(uint64_t *__restrict__ a, const uint64_t *__restrict__ b, size_t count) {
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (size_t)gridDim.x * blockDim.x)
         a[t] += b[t];
@@ -836,6 +897,27 @@ void Engine::init_common() {
     d_lut8_ = static_cast<uint64_t *>(alloc(l8.size() * 8));
     HIPC(hipMemcpy(d_lut24_, l24.data(), l24.size() * 8, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(d_lut8_, l8.data(), l8.size() * 8, hipMemcpyHostToDevice));
+    if (p_.model == 1) {
+        // inverse cipher (aes_inv.hpp): InvSbox * {14,11,13,9} (8 -> 32), InvSbox (8 -> 8), the multiples alone
+        // (8 -> 32, decryption-key derivation) and the identity (1 -> 1, key_schedule's boot_word)
+        std::vector<uint64_t> fi32(256), fi8(256), fm32(256), fid = {0, 1};
+        for (int x = 0; x < 256; x++) {
+            fi32[x] = inv_sbox_mul_lut((uint8_t)x);
+            fi8[x] = inv_sbox_lut((uint8_t)x);
+            fm32[x] = inv_mul_lut((uint8_t)x);
+        }
+        auto upload = [&](int n_in, int n_out, const std::vector<uint64_t> &f) {
+            std::vector<uint64_t> l((size_t)n_out * lut_small_len(p_.N, n_in));
+            generate_lut(p_.N, n_in, n_out, f.data(), l.data());
+            uint64_t *d = static_cast<uint64_t *>(alloc(l.size() * 8));
+            HIPC(hipMemcpy(d, l.data(), l.size() * 8, hipMemcpyHostToDevice));
+            return d;
+        };
+        d_lut_inv32_ = upload(8, 32, fi32);
+        d_lut_inv8_ = upload(8, 8, fi8);
+        d_lut_mul32_ = upload(8, 32, fm32);
+        d_lut_id1_ = upload(1, 1, fid);
+    }
     if (p_.model == 2) {
         // shortint_1bit ByteT (fhe_impls/shortint_1bit.rs:17-50): bootstrap_assign's identity test vector
         // and sbox_substitute's 8 multivariate test vectors (one per output bit, MSB first), each the
@@ -1126,7 +1208,8 @@ Engine::~Engine() {
                     (void *)d_digits_, (void *)d_wlut_sbox_, (void *)d_wlut_id_, (void *)d_lut_x_, (void *)d_xbuf_,
                     (void *)d_xsh_, (void *)d_xks_, (void *)d_xpbs_, (void *)d_ints_, (void *)d_s1_sbox_tv_,
                     (void *)d_s1_id_tv_, (void *)d_s1_in_, (void *)d_s1_out_, (void *)d_s1_pks_, (void *)d_s1_tv_, (void *)d_pf_flags_, (void *)d_clk_, (void *)d_lf_, (void *)d_acc_w_,
-                    (void *)d_ctr_groups_, (void *)d_ctr_map_})
+                    (void *)d_ctr_groups_, (void *)d_ctr_map_,
+                    (void *)d_lut_inv32_, (void *)d_lut_inv8_, (void *)d_lut_mul32_, (void *)d_lut_id1_})
         if (q) hipFree(q);
     for (auto &e : ev_pool_) hipEventDestroy(e);
     if (caller_ev_) hipEventDestroy(caller_ev_);
@@ -1735,6 +1818,86 @@ void Engine::aes_ctr(const uint64_t *d_rk, const uint8_t iv[8], uint64_t first_c
         else
             aes_ctr_blocks(d_rk, ctr_plans_.back(), cn, rounds, data, cbytes, out);
     }
+}
+
+// ---- AES-128 inverse cipher (FIPS-197 5.3; aes_inv.hpp) ----
+// rounds R-1 .. 1 and the last round on d_state_ = block ^ dk[40..43]: R circuit bootstraps per block
+void Engine::aes_decrypt_rounds(const uint64_t *d_dk, size_t nb, int rounds, const uint8_t *d_xor, uint64_t *d_out) {
+    const int L = (int)p_.big_len();
+    const size_t state_len = nb * 128 * (size_t)L, byte_stride = 8 * (size_t)L;
+    for (int r = rounds - 1; r >= 1; r--) {
+        circuit_bootstrap(d_state_, nb * 16, 8, d_lut_inv32_, 32, d_muls_);
+        timed(ST_LINEAR, [&] {
+            aes_inv_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_dk + (size_t)16 * r * byte_stride,
+                                                                               d_state_, nb, L, 1);
+            HIPC(hipGetLastError());
+        });
+    }
+    circuit_bootstrap(d_state_, nb * 16, 8, d_lut_inv8_, 8, d_muls_);
+    timed(ST_LINEAR, [&] {
+        aes_inv_final_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_dk, d_xor, d_out, nb, L);
+        HIPC(hipGetLastError());
+    });
+    collect_times();
+}
+
+void Engine::require_inverse(int rounds) const {
+    if (p_.model != 1 || !d_lut_inv32_) throw std::runtime_error("the inverse cipher needs the 1-bit model parameters");
+    if (rounds < 1 || rounds > 10) throw std::runtime_error("rounds must be in 1..=10");
+}
+
+void Engine::aes_decrypt_blocks(const uint64_t *d_dk, const uint64_t *d_blocks, size_t nb, int rounds,
+                                uint64_t *d_out) {
+    if (!nb) return;
+    require_inverse(rounds);
+    const int L = (int)p_.big_len();
+    const size_t state_len = nb * 128 * (size_t)L;
+    times_ = StageTimes{};
+    grow(d_state_, cap_state_, state_len);
+    grow(d_muls_, cap_muls_, nb * 16 * (size_t)(rounds > 1 ? 32 : 8) * L);
+    timed(ST_LINEAR, [&] {
+        aes_ark0_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_blocks, d_dk + (size_t)160 * 8 * L, d_state_,
+                                                                        nb, L);
+        HIPC(hipGetLastError());
+    });
+    aes_decrypt_rounds(d_dk, nb, rounds, nullptr, d_out);
+}
+
+void Engine::aes_cbc_transcipher(const uint64_t *d_dk, const uint8_t *d_iv_data, size_t nb, int rounds,
+                                 uint64_t *d_out) {
+    if (!nb) return;
+    require_inverse(rounds);
+    const int L = (int)p_.big_len();
+    const size_t state_len = nb * 128 * (size_t)L;
+    times_ = StageTimes{};
+    grow(d_state_, cap_state_, state_len);
+    grow(d_muls_, cap_muls_, nb * 16 * (size_t)(rounds > 1 ? 32 : 8) * L);
+    // d_iv_data = iv || C_0 .. C_{nb-1}: block i is decrypted from bytes 16 (i + 1) .. and XORed with bytes 16 i ..
+    timed(ST_LINEAR, [&] {
+        aes_inv_round0_public_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_dk + (size_t)160 * 8 * L,
+                                                                                     d_iv_data + 16, d_state_, nb, L);
+        HIPC(hipGetLastError());
+    });
+    aes_decrypt_rounds(d_dk, nb, rounds, d_iv_data, d_out);
+}
+
+void Engine::aes_decrypt_key(const uint64_t *d_rk, uint64_t *d_dk) {
+    require_inverse(10);
+    if (d_rk == d_dk) throw std::runtime_error("the decryption key cannot be derived in place");
+    const int L = (int)p_.big_len();
+    const size_t word = 32 * (size_t)L, mid = 36 * word;  // words 4..39: 144 bytes = 9 round keys
+    times_ = StageTimes{};
+    grow(d_state_, cap_state_, mid);
+    grow(d_muls_, cap_muls_, 144 * 32 * (size_t)L);
+    HIPC(hipMemcpyAsync(d_dk, d_rk, 4 * word * 8, hipMemcpyDeviceToDevice, stream_));
+    HIPC(hipMemcpyAsync(d_dk + 40 * word, d_rk + 40 * word, 4 * word * 8, hipMemcpyDeviceToDevice, stream_));
+    circuit_bootstrap(d_rk + 4 * word, 144, 8, d_lut_mul32_, 32, d_muls_);
+    timed(ST_LINEAR, [&] {
+        aes_inv_mix_kernel<<<grid_for(mid), kThreads, 0, stream_>>>(d_muls_, nullptr, d_state_, 9, L, 0);
+        HIPC(hipGetLastError());
+    });
+    circuit_bootstrap(d_state_, 36 * 32, 1, d_lut_id1_, 1, d_dk + 4 * word);
+    collect_times();
 }
 
 // ---- shortint_1bit model ----

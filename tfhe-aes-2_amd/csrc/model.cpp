@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "aes.hpp"
+#include "aes_inv.hpp"
 #include "cplx.hpp"
 #include "../../include/tfhe_aes_gpu.h"
 
@@ -628,6 +629,229 @@ std::vector<BitCt> Context::aes_ctr_transcipher(const std::vector<const BitCt *>
     std::vector<uint64_t> rk(44 * 32 * L), out(len * 8 * L);
     for (size_t i = 0; i < 44 * 32; i++) std::memcpy(&rk[i * L], expanded_key[i]->ct.data(), L * 8);
     run_aes_ctr(rk.data(), iv, first_counter, n_blocks, rounds, data, len, out.data(), false);
+    std::vector<BitCt> res(len * 8);
+    for (size_t i = 0; i < res.size(); i++) {
+        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
+        res[i].noise = out_noise[i / 128][i % 128];  // xor with a public bit adds no noise
+        res[i].max_noise_sq = params().max_noise_sq;
+    }
+    return res;
+}
+
+// ---------------------------------------------------------------------------------------------
+// AES-128 inverse cipher (FIPS-197 5.3; aes_inv.hpp).  The reference has no decryption.
+// ---------------------------------------------------------------------------------------------
+// Metadata-only replay of decrypt_block_for_rounds for ONE block: dk [44*32], block [128].
+std::vector<NoiseLevel> aes_decrypt_noise_schedule(const std::vector<NoiseLevel> &dk, const std::vector<NoiseLevel> &block,
+                                                   int rounds, uint64_t max) {
+    auto key_bit = [&](int word, int byte, int bit) -> const NoiseLevel & { return dk[(word * 4 + byte) * 8 + bit]; };
+    std::vector<NoiseLevel> st = block;  // index (4*col + row)*8 + bit
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 4; r++)
+            for (int b = 0; b < 8; b++) st[(4 * c + r) * 8 + b].add_assign(key_bit(40 + c, r, b), max);
+    auto cbs_outputs = [&](int n_out) {
+        std::vector<NoiseLevel> o((size_t)16 * n_out);
+        for (auto &x : o) x = NoiseLevel::with_noise_level(8, next_ct_id());
+        return o;
+    };
+    for (int round = rounds - 1; round >= 1; round--) {
+        const std::vector<NoiseLevel> muls = cbs_outputs(32);  // [byte][32]
+        for (int c = 0; c < 4; c++)
+            for (int r = 0; r < 4; r++)
+                for (int b = 0; b < 8; b++) {
+                    NoiseLevel v = muls[inv_mix_src_byte(r, c, 0, true) * 32 + b];
+                    for (int j = 1; j < 4; j++) v.add_assign(muls[inv_mix_src_byte(r, c, j, true) * 32 + 8 * j + b], max);
+                    v.add_assign(key_bit(4 * round + c, r, b), max);
+                    st[(4 * c + r) * 8 + b] = std::move(v);
+                }
+    }
+    const std::vector<NoiseLevel> sb = cbs_outputs(8);
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 4; r++)
+            for (int b = 0; b < 8; b++) {
+                NoiseLevel v = sb[inv_final_src_byte(r, c) * 8 + b];
+                v.add_assign(key_bit(c, r, b), max);
+                st[(4 * c + r) * 8 + b] = std::move(v);
+            }
+    return st;
+}
+
+// The decryption-key derivation on metadata: words 0..3 and 40..43 keep the expanded key's levels; every bit
+// of words 4..39 is a 4-term sum of fresh 8 -> 32 outputs (noise^2 = 32, validated), then bootstrapped.
+std::vector<NoiseLevel> aes_decrypt_key_noise_schedule(const std::vector<NoiseLevel> &rk, uint64_t max) {
+    std::vector<NoiseLevel> dk = rk;
+    std::vector<NoiseLevel> muls((size_t)144 * 32);
+    for (auto &x : muls) x = NoiseLevel::with_noise_level(8, next_ct_id());
+    for (int w = 4; w < 40; w++)
+        for (int r = 0; r < 4; r++)
+            for (int b = 0; b < 8; b++) {
+                const int blk = w / 4 - 1, c = w % 4;
+                NoiseLevel v = muls[(size_t)(blk * 16 + inv_mix_src_byte(r, c, 0, false)) * 32 + b];
+                for (int j = 1; j < 4; j++)
+                    v.add_assign(muls[(size_t)(blk * 16 + inv_mix_src_byte(r, c, j, false)) * 32 + 8 * j + b], max);
+                dk[(w * 4 + r) * 8 + b] = NoiseLevel::with_noise_level(1, next_ct_id());  // identity bootstrap
+            }
+    return dk;
+}
+
+void Context::require_inverse(int rounds) const {
+    if (params().model != 1)
+        throw ModelError{TAE_E_PARAM, "the inverse cipher runs on the 1-bit WoP-PBS parameter sets (gal-mul driver) only"};
+    if (rounds < 1 || rounds > kAesRounds) throw ModelError{TAE_E_PARAM, "rounds must be in 1..=10"};
+}
+
+static std::vector<NoiseLevel> fresh_levels(size_t n) {
+    std::vector<NoiseLevel> v(n);
+    for (auto &x : v) x = NoiseLevel::with_noise_level(1, next_ct_id());
+    return v;
+}
+
+static std::vector<uint64_t> gather_bits(const std::vector<const BitCt *> &bits, size_t L) {
+    std::vector<uint64_t> a(bits.size() * L);
+    for (size_t i = 0; i < bits.size(); i++) {
+        if (bits[i]->ct.size() != L) throw ModelError{TAE_E_ARG, "ciphertext size mismatch"};
+        std::memcpy(&a[i * L], bits[i]->ct.data(), L * 8);
+    }
+    return a;
+}
+
+// host or device arrays through the engine: in (in_len words, may be null), fixed (1408 key words), out
+void Context::run_inverse(const uint64_t *key, const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes,
+                          uint64_t *out, size_t out_len, bool device_mem,
+                          const std::function<void(const uint64_t *, const uint64_t *, const uint8_t *, uint64_t *)> &fn) {
+    const size_t S = bit_len();
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    DevBuf d_bytes(n_bytes);  // the public bytes are a host array, always
+    if (n_bytes)
+        hip_check(hipMemcpyAsync(d_bytes.p, bytes, n_bytes, hipMemcpyHostToDevice, engine_->stream()), "upload data");
+    if (device_mem) {
+        engine_->order_after_caller();
+        fn(key, in, d_bytes.as<uint8_t>(), out);
+        engine_->synchronize();
+        return;
+    }
+    DevBuf d_key(44 * 32 * S * 8), d_in(in_len * 8), d_out(out_len * 8);
+    hip_check(hipMemcpyAsync(d_key.p, key, 44 * 32 * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
+    if (in_len) hip_check(hipMemcpyAsync(d_in.p, in, in_len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload");
+    fn(d_key.as<uint64_t>(), d_in.as<uint64_t>(), d_bytes.as<uint8_t>(), d_out.as<uint64_t>());
+    hip_check(hipMemcpyAsync(out, d_out.p, out_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+void Context::aes_decrypt_key_raw(const uint64_t *rk, uint64_t *dk, bool device_mem) {
+    require_inverse(kAesRounds);
+    aes_decrypt_key_noise_schedule(fresh_levels(44 * 32), params().max_noise_sq);
+    if (device_mem && rk == dk) throw ModelError{TAE_E_ARG, "the decryption key cannot be derived in place"};
+    run_inverse(rk, nullptr, 0, nullptr, 0, dk, 44 * 32 * bit_len(), device_mem,
+                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) { engine_->aes_decrypt_key(k, o); });
+}
+
+std::vector<BitCt> Context::aes_decrypt_key(const std::vector<const BitCt *> &expanded_key) {
+    require_inverse(kAesRounds);
+    if (expanded_key.size() != 44 * 32) throw ModelError{TAE_E_ARG, "expanded key must be 44 words (1408 bits)"};
+    const size_t L = bit_len();
+    const std::vector<uint64_t> rk = gather_bits(expanded_key, L);
+    std::vector<NoiseLevel> krk(44 * 32);
+    for (size_t i = 0; i < krk.size(); i++) krk[i] = expanded_key[i]->noise;
+    const std::vector<NoiseLevel> kdk = aes_decrypt_key_noise_schedule(krk, params().max_noise_sq);
+    std::vector<uint64_t> dk(rk.size());
+    run_inverse(rk.data(), nullptr, 0, nullptr, 0, dk.data(), dk.size(), false,
+                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) { engine_->aes_decrypt_key(k, o); });
+    std::vector<BitCt> res(44 * 32);
+    for (size_t i = 0; i < res.size(); i++) {
+        res[i].ct.assign(dk.begin() + i * L, dk.begin() + (i + 1) * L);
+        res[i].noise = kdk[i];
+        res[i].max_noise_sq = params().max_noise_sq;
+    }
+    return res;
+}
+
+void Context::aes_decrypt_blocks_raw(const uint64_t *dk, const uint64_t *blocks, size_t n_blocks, int rounds,
+                                     uint64_t *out, bool device_mem) {
+    require_inverse(rounds);
+    // static validation of the fixed schedule for a derived key and fresh blocks (noise^2 = 1, own ids)
+    aes_decrypt_noise_schedule(fresh_levels(44 * 32), fresh_levels(128), rounds, params().max_noise_sq);
+    if (!n_blocks) return;
+    const size_t len = n_blocks * 128 * bit_len();
+    run_inverse(dk, blocks, len, nullptr, 0, out, len, device_mem,
+                [&](const uint64_t *k, const uint64_t *i, const uint8_t *, uint64_t *o) {
+                    engine_->aes_decrypt_blocks(k, i, n_blocks, rounds, o);
+                });
+}
+
+std::vector<BitCt> Context::aes_decrypt_blocks(const std::vector<const BitCt *> &dk,
+                                               const std::vector<const BitCt *> &blocks, size_t n_blocks, int rounds) {
+    require_inverse(rounds);
+    if (dk.size() != 44 * 32) throw ModelError{TAE_E_ARG, "decryption key must be 44 words (1408 bits)"};
+    if (blocks.size() != n_blocks * 128) throw ModelError{TAE_E_ARG, "blocks must be 128 bits each"};
+    const size_t L = bit_len();
+    const std::vector<uint64_t> key = gather_bits(dk, L), in = gather_bits(blocks, L);
+    std::vector<NoiseLevel> kdk(44 * 32);
+    for (size_t i = 0; i < kdk.size(); i++) kdk[i] = dk[i]->noise;
+    std::vector<std::vector<NoiseLevel>> out_noise(n_blocks);
+    for (size_t blk = 0; blk < n_blocks; blk++) {
+        std::vector<NoiseLevel> kb(128);
+        for (int i = 0; i < 128; i++) kb[i] = blocks[blk * 128 + i]->noise;
+        out_noise[blk] = aes_decrypt_noise_schedule(kdk, kb, rounds, params().max_noise_sq);
+    }
+    std::vector<uint64_t> out(in.size());
+    if (n_blocks)
+        run_inverse(key.data(), in.data(), in.size(), nullptr, 0, out.data(), out.size(), false,
+                    [&](const uint64_t *k, const uint64_t *i, const uint8_t *, uint64_t *o) {
+                        engine_->aes_decrypt_blocks(k, i, n_blocks, rounds, o);
+                    });
+    std::vector<BitCt> res(n_blocks * 128);
+    for (size_t i = 0; i < res.size(); i++) {
+        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
+        res[i].noise = out_noise[i / 128][i % 128];
+        res[i].max_noise_sq = params().max_noise_sq;
+    }
+    return res;
+}
+
+// iv || data, the public bytes both ends of the CBC pass read
+static std::vector<uint8_t> cbc_public_bytes(const uint8_t iv[16], const uint8_t *data, size_t len) {
+    if (len % 16 != 0) throw ModelError{TAE_E_ARG, "CBC data must be whole 16-byte blocks"};
+    std::vector<uint8_t> pub(16 + len);
+    std::memcpy(pub.data(), iv, 16);
+    if (len) std::memcpy(pub.data() + 16, data, len);
+    return pub;
+}
+
+void Context::aes_cbc_transcipher_raw(const uint64_t *dk, const uint8_t iv[16], const uint8_t *data, size_t len,
+                                      int rounds, uint64_t *out, bool device_mem) {
+    require_inverse(rounds);
+    const std::vector<uint8_t> pub = cbc_public_bytes(iv, data, len);
+    aes_decrypt_noise_schedule(fresh_levels(44 * 32), std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds,
+                               params().max_noise_sq);
+    if (!len) return;
+    const size_t n_blocks = len / 16;
+    run_inverse(dk, nullptr, 0, pub.data(), pub.size(), out, len * 8 * bit_len(), device_mem,
+                [&](const uint64_t *k, const uint64_t *, const uint8_t *b, uint64_t *o) {
+                    engine_->aes_cbc_transcipher(k, b, n_blocks, rounds, o);
+                });
+}
+
+std::vector<BitCt> Context::aes_cbc_transcipher(const std::vector<const BitCt *> &dk, const uint8_t iv[16],
+                                                const uint8_t *data, size_t len, int rounds) {
+    require_inverse(rounds);
+    if (dk.size() != 44 * 32) throw ModelError{TAE_E_ARG, "decryption key must be 44 words (1408 bits)"};
+    const size_t L = bit_len();
+    const std::vector<uint64_t> key = gather_bits(dk, L);
+    const std::vector<uint8_t> pub = cbc_public_bytes(iv, data, len);
+    std::vector<NoiseLevel> kdk(44 * 32);
+    for (size_t i = 0; i < kdk.size(); i++) kdk[i] = dk[i]->noise;
+    const size_t n_blocks = len / 16;
+    const std::vector<NoiseLevel> triv(128, NoiseLevel::trivial());
+    std::vector<std::vector<NoiseLevel>> out_noise(n_blocks);
+    for (auto &o : out_noise) o = aes_decrypt_noise_schedule(kdk, triv, rounds, params().max_noise_sq);
+    if (!len) return {};
+    std::vector<uint64_t> out(len * 8 * L);
+    run_inverse(key.data(), nullptr, 0, pub.data(), pub.size(), out.data(), out.size(), false,
+                [&](const uint64_t *k, const uint64_t *, const uint8_t *b, uint64_t *o) {
+                    engine_->aes_cbc_transcipher(k, b, n_blocks, rounds, o);
+                });
     std::vector<BitCt> res(len * 8);
     for (size_t i = 0; i < res.size(); i++) {
         res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);

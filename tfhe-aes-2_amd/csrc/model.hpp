@@ -14,6 +14,7 @@
 #pragma once
 #include <atomic>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -106,6 +107,26 @@ class Context {  // FheContext
                                            uint64_t first_counter, const uint8_t *data, size_t len,
                                            int rounds = 10);
 
+    // ---- AES-128 inverse cipher, FIPS-197 5.3 (the reference has no decryption; aes_inv.hpp): InvSubBytes and
+    // InvMixColumns' multiples {14,11,13,9} in one 8 -> 32 circuit bootstrap per byte, `rounds` bootstraps per
+    // block.  1-bit WoP-PBS sets (gal-mul driver) only: every other model is TAE_E_PARAM. ----
+    // decryption key [44*32]: words 0..3 / 40..43 unchanged, words 4r..4r+3 = InvMixColumns(rk[r]) with fresh
+    // noise (noise^2 = 1, new ids)
+    std::vector<BitCt> aes_decrypt_key(const std::vector<const BitCt *> &expanded_key);
+    void aes_decrypt_key_raw(const uint64_t *rk, uint64_t *dk, bool device_mem);
+    // inverts aes_encrypt_blocks(rounds): round keys 10, rounds-1 .. 1, 0.  Noise bookkeeping per bit
+    std::vector<BitCt> aes_decrypt_blocks(const std::vector<const BitCt *> &dk, const std::vector<const BitCt *> &blocks,
+                                          size_t n_blocks, int rounds);
+    // raw arrays; the schedule is validated statically for a derived key and fresh blocks
+    void aes_decrypt_blocks_raw(const uint64_t *dk, const uint64_t *blocks, size_t n_blocks, int rounds, uint64_t *out,
+                                bool device_mem);
+    // CBC with a public ciphertext: data (host bytes, len % 16 == 0 or TAE_E_ARG) -> [len][8][bit_len]
+    // encryptions of P_i = Dec(C_i) ^ C_{i-1}, C_{-1} = iv; no input ciphertexts are made
+    void aes_cbc_transcipher_raw(const uint64_t *dk, const uint8_t iv[16], const uint8_t *data, size_t len, int rounds,
+                                 uint64_t *out, bool device_mem);
+    std::vector<BitCt> aes_cbc_transcipher(const std::vector<const BitCt *> &dk, const uint8_t iv[16],
+                                           const uint8_t *data, size_t len, int rounds = 10);
+
     // ---- 8-bit model (src/tfhe/shortint_woppbs_8bit.rs, fhe_impls/shortint_woppbs_8bit.rs) ----
     size_t bit_len() const { return params().bit_len(); }
     // FheContext::bootstrap_from_bits over G bytes: bits [G][8][n+1] -> int ciphertexts [G][K+1]
@@ -134,6 +155,10 @@ class Context {  // FheContext
     std::vector<NoiseLevel> block_noise_schedule(AesDriver driver, const std::vector<NoiseLevel> &rk,
                                                  const std::vector<NoiseLevel> &block, int rounds) const;
     void check_ctr(uint64_t first_counter, size_t n_blocks, int rounds) const;
+    void require_inverse(int rounds) const;
+    void run_inverse(const uint64_t *key, const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes,
+                     uint64_t *out, size_t out_len, bool device_mem,
+                     const std::function<void(const uint64_t *, const uint64_t *, const uint8_t *, uint64_t *)> &fn);
     void run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
                      const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem);
     void run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint64_t *d_in, size_t n_blocks, int rounds,
@@ -153,6 +178,14 @@ std::vector<NoiseLevel> sbox_pbs_noise_schedule(const std::vector<NoiseLevel> &r
 // outputs are NOMINAL = 1).
 std::vector<NoiseLevel> aes8_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &block,
                                             int rounds, uint64_t max_noise_level);
+
+// The inverse cipher (aes_inv.hpp) on metadata, ONE block: dk [44*32], block [128] -> output levels [128].
+// CBS outputs are noise^2 = 8 with fresh ids: a middle round is 4 * 8 + the key bit, the output 8 + the key bit.
+std::vector<NoiseLevel> aes_decrypt_noise_schedule(const std::vector<NoiseLevel> &dk, const std::vector<NoiseLevel> &block,
+                                                   int rounds, uint64_t max_noise_sq);
+// The decryption-key derivation on metadata: rk [44*32] -> dk [44*32]; the 4-term sums (noise^2 = 32) are
+// validated, words 4..39 come out of the identity bootstrap at noise^2 = 1 with fresh ids.
+std::vector<NoiseLevel> aes_decrypt_key_noise_schedule(const std::vector<NoiseLevel> &rk, uint64_t max_noise_sq);
 
 // Counter mode on the 1-bit model: output noise [n_blocks][128] of the gal-mul schedule for trivial counter
 // blocks.  rounds >= 2: aes_noise_schedule per block.  rounds == 1: the final SubBytes runs on the plan's

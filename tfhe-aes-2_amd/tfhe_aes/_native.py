@@ -39,6 +39,8 @@ EXPORTED = [
     "tae_s1_test_vector_from_fn", "tae_s1_bootstrap", "tae_s1_packing_keyswitch",
     "tae_s1_test_vectors_from_ciphertexts", "tae_s1_multivariate",
     "tae_aes_ctr_plan", "tae_aes_ctr_keystream_raw", "tae_aes_ctr_transcipher_raw", "tae_aes_ctr_transcipher",
+    "tae_aes_decrypt_key", "tae_aes_decrypt_key_raw", "tae_aes_decrypt_blocks", "tae_aes_decrypt_blocks_raw",
+    "tae_aes_cbc_transcipher", "tae_aes_cbc_transcipher_raw", "tae_aes_decrypt_noise_schedule_check",
 ]
 TAE_DRIVER_GAL_MUL, TAE_DRIVER_SBOX_PBS = 0, 1
 TAE_KEYS_CLIENT, TAE_KEYS_SERVER = 1, 2
@@ -123,6 +125,13 @@ def lib() -> C.CDLL:
         "tae_aes_ctr_keystream_raw": ([vp, vp, C.c_char_p, u64, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_aes_ctr_transcipher_raw": ([vp, vp, C.c_char_p, u64, vp, sz, vp, C.c_int], C.c_int),
         "tae_aes_ctr_transcipher": ([vp, vp, C.c_char_p, u64, vp, sz, vp], C.c_int),
+        "tae_aes_decrypt_key": ([vp, vp, vp], C.c_int),
+        "tae_aes_decrypt_key_raw": ([vp, vp, vp, C.c_int], C.c_int),
+        "tae_aes_decrypt_blocks": ([vp, vp, vp, sz, C.c_int, vp], C.c_int),
+        "tae_aes_decrypt_blocks_raw": ([vp, vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aes_cbc_transcipher": ([vp, vp, C.c_char_p, vp, sz, vp], C.c_int),
+        "tae_aes_cbc_transcipher_raw": ([vp, vp, C.c_char_p, vp, sz, vp, C.c_int], C.c_int),
+        "tae_aes_decrypt_noise_schedule_check": ([C.c_int, C.c_int], C.c_int),
         "tae_stage_keyswitch": ([vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_pbs_shift_boolean": ([vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_stage_bootstrap": ([vp, vp, sz, vp, vp, C.c_int], C.c_int),

@@ -103,6 +103,79 @@ def expand_key_and_encrypt_blocks(key: bytes, blocks: Sequence[bytes], rounds: i
     return [encrypt_block_plain(ek, b, rounds) for b in blocks]
 
 
+# ---------------------------------------------------------------- FIPS-197 5.3 (no reference counterpart) ----
+def gf_mul(a: int, b: int) -> int:
+    """The true product in GF(2^8) modulo 0x11b (gf_256_mul above carries the reference's quirk, which
+    cancels only inside the forward MixColumns)."""
+    res = 0
+    for _ in range(8):
+        if b & 1:
+            res ^= a
+        a <<= 1
+        if a & 0x100:
+            a ^= 0x11B
+        b >>= 1
+    return res
+
+
+INV_SBOX = [0] * 256
+for _x, _y in enumerate(SBOX):
+    INV_SBOX[_y] = _x
+INV_MIX = (14, 11, 13, 9)  # InvMixColumns: out(row) = 14 s(row) ^ 11 s(row+1) ^ 13 s(row+2) ^ 9 s(row+3)
+
+
+def _inv_mix_columns(t: Sequence[int]) -> List[int]:
+    return [gf_mul(t[4 * c + row], 14) ^ gf_mul(t[4 * c + (row + 1) % 4], 11) ^ gf_mul(t[4 * c + (row + 2) % 4], 13)
+            ^ gf_mul(t[4 * c + (row + 3) % 4], 9) for c in range(4) for row in range(4)]
+
+
+def decrypt_key_plain(expanded_key: Sequence[bytes]) -> List[bytes]:
+    """The decryption key of FIPS-197 5.3.5, 44 words: words 0..3 and 40..43 are the expanded key's, words
+    4r..4r+3 (r = 1..9) are InvMixColumns(rk[r])."""
+    rk = b"".join(expanded_key)
+    dk = bytearray(rk)
+    for r in range(1, 10):
+        dk[16 * r:16 * r + 16] = bytes(_inv_mix_columns(rk[16 * r:16 * r + 16]))
+    return [bytes(dk[4 * i:4 * i + 4]) for i in range(44)]
+
+
+def decrypt_block_plain(expanded_key: Sequence[bytes], block: bytes, rounds: int = ROUNDS) -> bytes:
+    """The straightforward inverse cipher (FIPS-197 5.3, figure 12) with the ENCRYPTION key: inverts
+    encrypt_block_plain(expanded_key, ., rounds), which uses round keys 0, 1..rounds-1 and 10."""
+    rk = b"".join(expanded_key)
+    s = [block[i] ^ rk[160 + i] for i in range(16)]
+    for r in range(rounds - 1, -1, -1):
+        s = [s[4 * ((c - row) % 4) + row] for c in range(4) for row in range(4)]  # InvShiftRows
+        s = [INV_SBOX[x] for x in s]
+        s = [s[i] ^ rk[16 * r + i] for i in range(16)]
+        if r:
+            s = _inv_mix_columns(s)
+    return bytes(s)
+
+
+def cbc_encrypt_plain(key: bytes, iv: bytes, data: bytes) -> bytes:
+    """Plain AES-128-CBC of whole blocks (no padding)."""
+    if len(iv) != 16 or len(data) % 16:
+        raise ValueError("iv must be 16 bytes and data whole 16-byte blocks")
+    ek, prev, out = key_schedule_plain(key), bytes(iv), []
+    for i in range(0, len(data), 16):
+        prev = encrypt_block_plain(ek, bytes(a ^ b for a, b in zip(data[i:i + 16], prev)))
+        out.append(prev)
+    return b"".join(out)
+
+
+def cbc_decrypt_plain(key: bytes, iv: bytes, data: bytes) -> bytes:
+    """P_i = Dec(C_i) ^ C_{i-1}, C_{-1} = iv."""
+    if len(iv) != 16 or len(data) % 16:
+        raise ValueError("iv must be 16 bytes and data whole 16-byte blocks")
+    ek, prev, out = key_schedule_plain(key), bytes(iv), []
+    for i in range(0, len(data), 16):
+        c = bytes(data[i:i + 16])
+        out.append(bytes(a ^ b for a, b in zip(decrypt_block_plain(ek, c), prev)))
+        prev = c
+    return b"".join(out)
+
+
 # ---------------------------------------------------------------- fhe_encryption.rs ----
 def encrypt_byte(client_key: ClientKey, byte: int) -> List[BitCt]:
     return [client_key.encrypt(Cleartext(b)) for b in u8_to_bits(byte)]
@@ -248,6 +321,109 @@ class ShortintWoppbs1BitSboxGalMulPbsAesEncrypt:
         bits = [BitCt(h, ctx) for h in outs]
         return [bits[8 * i:8 * i + 8] for i in range(len(buf))]
 
+    # ---- inverse cipher and CBC transciphering (FIPS-197 5.3; the reference has no decryption) ----
+    # InvSubBytes and InvMixColumns' multiples {14, 11, 13, 9} in one 8 -> 32 WoP-PBS per byte and middle round,
+    # 8 -> 8 for the last: `rounds` circuit bootstraps per block, as encryption.  This driver on the 1-bit
+    # model only: the other driver classes raise TaeError (TAE_E_PARAM), as the C-ABI does for their models.
+    _INVERSE = True
+
+    @classmethod
+    def _require_inverse(cls):
+        if not cls._INVERSE:
+            raise N.TaeError(N.TAE_E_PARAM, "the inverse cipher belongs to the gal-mul driver on the 1-bit model")
+
+    @classmethod
+    def decrypt_key(cls, ctx: FheContext, expanded_key):
+        """[44][4][8] BitCt -> the decryption key [44][4][8]: words 4..39 = InvMixColumns of the round keys,
+        derived on the device with fresh noise; words 0..3 and 40..43 are the expanded key's."""
+        cls._require_inverse()
+        ek = _flat_bits(expanded_key)
+        outs = (C.c_void_p * (44 * 32))()
+        check(lib().tae_aes_decrypt_key(ctx._h, _handles(ek), outs))
+        bits = [BitCt(h, ctx) for h in outs]
+        return [[bits[w * 32 + 8 * b:w * 32 + 8 * b + 8] for b in range(4)] for w in range(44)]
+
+    @classmethod
+    def decrypt_block(cls, ctx: FheContext, dk, block):
+        return cls.decrypt_block_for_rounds(ctx, dk, block, ROUNDS)
+
+    @classmethod
+    def decrypt_block_for_rounds(cls, ctx: FheContext, dk, block, rounds: int):
+        """dk: decrypt_key's output; block [16][8] BitCt -> [16][8]; inverts encrypt_block_for_rounds(rounds)."""
+        return cls.decrypt_blocks(ctx, dk, [block], rounds)[0]
+
+    @classmethod
+    def decrypt_blocks(cls, ctx: FheContext, dk, blocks, rounds: int = ROUNDS):
+        cls._require_inverse()
+        key = _flat_bits(dk)
+        flat = _flat_bits(blocks)
+        nb = len(flat) // 128
+        outs = (C.c_void_p * (128 * nb))()
+        check(lib().tae_aes_decrypt_blocks(ctx._h, _handles(key), _handles(flat), nb, rounds, outs))
+        bits = [BitCt(h, ctx) for h in outs]
+        return [[bits[b * 128 + 8 * i:b * 128 + 8 * i + 8] for i in range(16)] for b in range(nb)]
+
+    @classmethod
+    def decrypt_key_raw(cls, ctx: FheContext, rk: np.ndarray) -> np.ndarray:
+        """Host arrays: expanded key [1408][L] -> decryption key [1408][L]."""
+        cls._require_inverse()
+        rk = np.ascontiguousarray(rk, dtype=np.uint64)
+        out = np.zeros((44 * 32, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aes_decrypt_key_raw(ctx._h, rk.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                                            N.TAE_MEM_HOST))
+        return out
+
+    @classmethod
+    def decrypt_blocks_raw(cls, ctx: FheContext, dk: np.ndarray, blocks: np.ndarray, rounds: int = ROUNDS) -> np.ndarray:
+        """Host arrays: dk [1408][L], blocks [n][128][L] -> [n][128][L]."""
+        cls._require_inverse()
+        dk = np.ascontiguousarray(dk, dtype=np.uint64)
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint64)
+        out = np.zeros_like(blocks)
+        check(lib().tae_aes_decrypt_blocks_raw(ctx._h, dk.ctypes.data_as(C.c_void_p), blocks.ctypes.data_as(C.c_void_p),
+                                               blocks.shape[0], rounds, out.ctypes.data_as(C.c_void_p), N.TAE_MEM_HOST))
+        return out
+
+    @classmethod
+    def decrypt_blocks_device(cls, ctx: FheContext, d_dk: int, d_blocks: int, nb: int, rounds: int, d_out: int):
+        """Device pointers (ints), inputs resident in HBM."""
+        cls._require_inverse()
+        check(lib().tae_aes_decrypt_blocks_raw(ctx._h, C.c_void_p(d_dk), C.c_void_p(d_blocks), nb, rounds,
+                                               C.c_void_p(d_out), N.TAE_MEM_DEVICE))
+
+    @classmethod
+    def cbc_transcipher(cls, ctx: FheContext, dk, iv: bytes, data: bytes):
+        """dk: decrypt_key's output; data: AES-128-CBC ciphertext bytes (whole blocks) -> [len][8] BitCt of
+        the plaintext bits, padding included."""
+        cls._require_inverse()
+        key = _flat_bits(dk)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        outs = (C.c_void_p * (8 * len(buf)))()
+        check(lib().tae_aes_cbc_transcipher(ctx._h, _handles(key), _iv16(iv), buf.ctypes.data_as(C.c_void_p), len(buf),
+                                            outs))
+        bits = [BitCt(h, ctx) for h in outs]
+        return [bits[8 * i:8 * i + 8] for i in range(len(buf))]
+
+    @classmethod
+    def cbc_transcipher_raw(cls, ctx: FheContext, dk: np.ndarray, iv: bytes, data: bytes) -> np.ndarray:
+        """Host arrays: dk [1408][L] -> [len][8][L] FHE encryptions of the plaintext bits (10 rounds)."""
+        cls._require_inverse()
+        dk = np.ascontiguousarray(dk, dtype=np.uint64)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        out = np.zeros((len(buf), 8, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aes_cbc_transcipher_raw(ctx._h, dk.ctypes.data_as(C.c_void_p), _iv16(iv),
+                                                buf.ctypes.data_as(C.c_void_p), len(buf),
+                                                out.ctypes.data_as(C.c_void_p), N.TAE_MEM_HOST))
+        return out
+
+    @classmethod
+    def cbc_transcipher_device(cls, ctx: FheContext, d_dk: int, iv: bytes, data: bytes, d_out: int):
+        """Device pointers (ints) for dk and the output [len][8][L]; iv and data are host bytes."""
+        cls._require_inverse()
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        check(lib().tae_aes_cbc_transcipher_raw(ctx._h, C.c_void_p(d_dk), _iv16(iv), buf.ctypes.data_as(C.c_void_p),
+                                                len(buf), C.c_void_p(d_out), N.TAE_MEM_DEVICE))
+
 
 class ShortintWoppbs1BitSboxPbsAesEncrypt(ShortintWoppbs1BitSboxGalMulPbsAesEncrypt):
     """fhe_impls/shortint_woppbs_1bit.rs:47-81: the generic fhe_sbox_pbs driver (fhe_sbox_pbs.rs:22-171) over
@@ -263,6 +439,7 @@ class ShortintWoppbs1BitSboxPbsAesEncrypt(ShortintWoppbs1BitSboxGalMulPbsAesEncr
     """
 
     _C = "tae_aes_sbox_pbs_"
+    _INVERSE = False  # decrypt_* / cbc_* raise TAE_E_PARAM here and in the two subclasses
 
 
 class ShortintWoppbs8BitSboxPbsAesEncrypt(ShortintWoppbs1BitSboxPbsAesEncrypt):
@@ -290,6 +467,19 @@ def noise_schedule_check(param_set: int, driver: int, rounds: int) -> None:
     """The round function's noise bookkeeping for fresh inputs, without a context or device: raises the
     error the reference panics with (NoiseNotIndependent / NoiseTooBig), else returns None."""
     check(lib().tae_aes_noise_schedule_check(param_set, driver, rounds))
+
+
+def decrypt_noise_schedule_check(param_set: int, rounds: int) -> None:
+    """The inverse cipher's noise bookkeeping for fresh inputs (the decryption-key derivation, then `rounds`
+    rounds with the derived key), without a context or device."""
+    check(lib().tae_aes_decrypt_noise_schedule_check(param_set, rounds))
+
+
+def _iv16(iv: bytes) -> bytes:
+    iv = bytes(iv)
+    if len(iv) != 16:
+        raise ValueError("iv must be 16 bytes")
+    return iv
 
 
 def _iv8(iv: bytes) -> bytes:
