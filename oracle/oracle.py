@@ -237,6 +237,23 @@ class Keys:
         lib().or_homomorphic_shift_boolean(self.sk, _p64(np.ascontiguousarray(small)), level, _p64(out))
         return out
 
+    def external_product_add(self, ggsw_f: np.ndarray, levels: int, base_log: int, glwe_in: np.ndarray,
+                             glwe_out: np.ndarray) -> np.ndarray:
+        """glwe_out += ggsw_f [x] glwe_in (add_external_product_assign on the plain transform, the CMux of
+        the vertical packing); ggsw_f is one Fourier GGSW of `levels` levels, glwe_out is updated in place"""
+        ggsw_f = np.ascontiguousarray(ggsw_f, dtype=np.complex128)
+        lib().or_external_product_add(self.sk, ggsw_f.ctypes.data_as(C.c_void_p), levels, base_log,
+                                      _p64(np.ascontiguousarray(glwe_in, dtype=np.uint64)), _p64(glwe_out))
+        return glwe_out
+
+    def bootstrap(self, small: np.ndarray, lut_glwe: np.ndarray) -> np.ndarray:
+        """Programmable bootstrap with the accumulator GLWE lut_glwe [(k+1)N] (blind rotation + sample
+        extraction, nothing added to the body before or after): the big-key LWE [k N + 1]"""
+        out = np.zeros(self.K + 1, dtype=np.uint64)
+        lib().or_bootstrap(self.sk, _p64(np.ascontiguousarray(small, dtype=np.uint64)),
+                           _p64(np.ascontiguousarray(lut_glwe, dtype=np.uint64)), _p64(out))
+        return out
+
     def pfks(self, q: int, big: np.ndarray) -> np.ndarray:
         out = np.zeros((self.p["k"] + 1) * self.p["N"], dtype=np.uint64)
         lib().or_pfks(self.sk, q, _p64(np.ascontiguousarray(big)), _p64(out))
@@ -384,13 +401,9 @@ class S1Keys(Keys):
                                 _p64(np.ascontiguousarray(ct1, dtype=np.uint64)), _p64(out))
         return out
 
-    def bootstrap_big(self, ct: np.ndarray, tv: np.ndarray) -> np.ndarray:
-        """apply_programmable_bootstrap alone (blind rotation + sample extraction, before the keyswitch):
-        the big-key LWE [k N + 1]"""
-        out = np.zeros(self.K + 1, dtype=np.uint64)
-        lib().or_bootstrap(self.sk, _p64(np.ascontiguousarray(ct, dtype=np.uint64)),
-                           _p64(np.ascontiguousarray(tv, dtype=np.uint64)), _p64(out))
-        return out
+    # apply_programmable_bootstrap alone, before the keyswitch (S1Keys.bootstrap below is the whole
+    # FheContext::bootstrap, keyswitch included)
+    bootstrap_big = Keys.bootstrap
 
     def bootstrap(self, ct: np.ndarray, tv: np.ndarray) -> np.ndarray:
         out = np.zeros(self.L, dtype=np.uint64)

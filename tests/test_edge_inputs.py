@@ -1,0 +1,181 @@
+"""The crafted inputs of tests/edge_inputs.py really sit on the edges they are built for (CPU oracle only).
+test_gpu_br_edges.py and test_gpu_vp_edges.py compare kernels with the oracle on these inputs; if a later
+change to the builders moved them off the edges those tests would still pass, and this file would not."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import edge_inputs as E
+
+MASK = (1 << 64) - 1
+
+
+@pytest.mark.parametrize("N,B", [(512, 12), (512, 6), (1024, 7)])
+@pytest.mark.parametrize("transform", ["fft", "lf"])
+def test_tie_digits_round_trip_hits_the_saturation(oracle_mod, N, B, transform):
+    """One row of an external product with a noiseless GGSW of 1: digits +-2^(B-1) (the decomposition's tie)
+    with random signs, times the gadget 2^(64-B) at coefficient 0, through the oracle's own transforms the way
+    ext_product_add runs them (forward of the digits, product with the key spectrum -- rescaled by conj(E2)
+    for the fused-twiddle transform, as lf_rescale does --, backward with the torus conversion).  The exact
+    product is +-2^63 per coefficient: +1/2 of the torus converts to 2^63, -1/2 saturates to 2^63 - 1, and
+    rounding moves the rest off by a few units.  Both exact values must occur."""
+    rng = np.random.default_rng(N + B)
+    digits = (rng.integers(0, 2, N).astype(np.int64) * 2 - 1) * np.int64(1 << (B - 1))
+    gadget = np.zeros(N, dtype=np.uint64)
+    gadget[0] = np.uint64(1 << (64 - B))
+    key = oracle_mod.FFT(N).fwd_torus(gadget)
+    if transform == "fft":
+        t = oracle_mod.FFT(N)
+    else:
+        t = oracle_mod.LfTransform(N)
+        key = key * t.conj_e2()
+    out = t.add_bwd_torus(t.fwd_int(digits) * key, np.zeros(N, dtype=np.uint64))
+    # every word within rounding of 2^63 (= -2^63) ...
+    assert int((out - np.uint64((1 << 63) - (1 << 20))).max()) < 1 << 21, "round trip left the neighbourhood of 2^63"
+    # ... and both exact conversions occur
+    assert np.count_nonzero(out == np.uint64(1 << 63)) >= 1
+    assert np.count_nonzero(out == np.uint64((1 << 63) - 1)) >= 1
+
+
+@pytest.mark.parametrize("N,B", [(512, 12), (512, 6), (1024, 7)])
+@pytest.mark.parametrize("m", [1, -1])
+def test_top_digit_is_never_negative_so_the_key_needs_minus_one(oracle_mod, N, B, m):
+    """What a difference of exactly 2^63 becomes in one blind-rotation step under a noiseless GGSW of m: the
+    decomposer's top digit is +2^(B-1), never -2^(B-1), so m = 1 gives tail inputs of +1/2 (2^63, no
+    saturation) and only m = -1 gives -1/2 (the saturated 2^63 - 1).  This is why key_pattern holds -1."""
+    assert oracle_mod.decompose(1 << 63, B, 2)[0] == 1 << (B - 1)
+    rng = np.random.default_rng(N + B + m)
+    digits = rng.integers(0, 2, N).astype(np.int64) * np.int64(1 << (B - 1))  # 0 or the tie, as a real step
+    gadget = np.zeros(N, dtype=np.uint64)
+    gadget[0] = np.uint64((m << (64 - B)) & MASK)
+    t = oracle_mod.LfTransform(N)
+    key = oracle_mod.FFT(N).fwd_torus(gadget) * t.conj_e2()
+    out = t.add_bwd_torus(t.fwd_int(digits) * key, np.zeros(N, dtype=np.uint64))
+    hit, other = ((1 << 63), (1 << 63) - 1) if m == 1 else ((1 << 63) - 1, (1 << 63))
+    assert np.count_nonzero(out == np.uint64(hit)) >= 1
+    assert np.count_nonzero(out == np.uint64(other)) == 0
+
+
+@pytest.mark.parametrize("m", [1, -1])
+def test_vertical_packing_cmux_reaches_the_saturation(noiseless, m):
+    """One CMux of the vertical packing (add_external_product_assign with the circuit bootstrap's levels)
+    with the trivial GGSW of m on a difference of 0 / 2^63, the S-box table's: m = -1 yields words equal to
+    2^63 - 1, m = 1 words equal to 2^63."""
+    p, keys = noiseless
+    k, N = p["k"], p["N"]
+    diff = np.zeros((k + 1) * N, dtype=np.uint64)
+    diff[k * N:] = np.random.default_rng(3).integers(0, 2, N).astype(np.uint64) << np.uint64(63)
+    out = keys.external_product_add(keys.ggsw_to_fourier(E.trivial_ggsw(p, m)), p["cbs_l"], p["cbs_b"], diff,
+                                    np.zeros((k + 1) * N, dtype=np.uint64))
+    assert not out[:k * N].any()
+    hit = (1 << 63) if m == 1 else (1 << 63) - 1
+    assert np.count_nonzero(out[k * N:] == np.uint64(hit)) >= 1
+
+
+def test_first_step_luts_reach_the_saturation_on_the_fast_path(noiseless):
+    """A one-input vertical packing with masked_ggsw(-1) on the first_step_lut polynomials the GPU test uses:
+    no word of the CMux's output, mask polynomials included, is small enough (|x| < 2^-12) for torus_add_fast
+    to refuse, so no wave goes to the fallback; and for at least half of the polynomials the tail input at
+    coefficient 0 is exactly -1/2: the extracted body is p[0] + 2^63 - 1."""
+    p, keys = noiseless
+    k, N = p["k"], p["N"]
+    gf = keys.ggsw_to_fourier(E.masked_ggsw(p, -1))
+    rng = np.random.default_rng(E.FIRST_STEP_SEED)
+    hits = 0
+    for _ in range(E.FIRST_STEP_LUTS):
+        lut = E.first_step_lut(N, rng)
+        diff = np.zeros((k + 1) * N, dtype=np.uint64)
+        diff[k * N:] = np.concatenate([lut[1:], np.uint64(0) - lut[:1]]) - lut  # X^-1 p - p
+        assert int(diff[k * N]) == 1 << 63
+        out = keys.external_product_add(gf, p["cbs_l"], p["cbs_b"], diff, np.zeros((k + 1) * N, dtype=np.uint64))
+        assert int(np.minimum(out, np.uint64(0) - out).min()) >= 1 << 52
+        hits += int(keys.vertical_packing(lut, gf, 1)[-1]) == (int(lut[0]) + (1 << 63) - 1) & MASK
+    assert hits >= E.FIRST_STEP_LUTS // 2, hits
+
+
+@pytest.fixture(scope="module", params=["lvl64", "8bit"])
+def noiseless(request, oracle_mod):
+    """(params, oracle keys) of a set under (zero ksk, noiseless bsk, zero pfpksk): a bootstrap reads the bsk
+    alone."""
+    pid = oracle_mod.PARAMS_SQRD_LVL_64 if request.param == "lvl64" else oracle_mod.PARAMS_WOPPBS_8BIT
+    p = oracle_mod.params(pid)
+    L = oracle_mod.lib()
+    pp = oracle_mod._Params()
+    assert L.or_params_get(pid, C.byref(pp)) == 0
+    ksk = np.zeros(L.or_ksk_len(C.byref(pp)), dtype=np.uint64)
+    pf = np.zeros(L.or_pfpksk_len(C.byref(pp)), dtype=np.uint64)
+    bsk = E.noiseless_bsk(p, E.key_pattern(p["n"]))
+    assert bsk.size == L.or_bsk_len(C.byref(pp))
+    return p, oracle_mod.Keys(pid, None, raw=(ksk, bsk, pf))
+
+
+def test_key_pattern_has_runs_of_every_value():
+    s = E.key_pattern(677)
+    assert set(s.tolist()) == {0, 1, MASK}
+    runs = np.diff(np.flatnonzero(s[1:] != s[:-1]))
+    assert runs.min() >= 3  # runs, not isolated values: whole steps of exact zeros follow each other
+
+
+def test_noiseless_bootstrap_stays_on_the_boundary(noiseless):
+    """Keys.bootstrap under the noiseless key with the constant-2^62 LUT: the mask polynomials stay exactly
+    zero (they take the fallback of the torus tail at every step) and the body ends within 2^32 of +-2^62,
+    i.e. every step's differences were 0 or +-2^63 up to rounding."""
+    p, keys = noiseless
+    rng = np.random.default_rng(5)
+    real = E.random_words(rng, (3, p["n"] + 1))
+    rows = E.crafted_small(p["n"], p["N"], real, 0)
+    lut = E.const_lut_glwe(p, 1 << 62)
+    for i in (1, 3, 6, 9):
+        out = keys.bootstrap(rows[i], lut)
+        assert not out[:-1].any(), i
+        body = int(out[-1])
+        assert min((body - (1 << 62)) & MASK, ((1 << 62) - body) & MASK,
+                   (body + (1 << 62)) & MASK, (-(1 << 62) - body) & MASK) < 1 << 32, (i, hex(body))
+
+
+@pytest.mark.parametrize("n,N", [(677, 512), (785, 1024)])
+@pytest.mark.parametrize("body_add", [0, 1 << 62])
+def test_crafted_rows_rotation_amounts(oracle_mod, n, N, body_add):
+    """or_pbs_modulus_switch of the crafted rows gives exactly what crafted_small's docstring promises."""
+    ms = lambda x: int(oracle_mod.lib().or_pbs_modulus_switch(int(x) & MASK, N))
+    real = E.random_words(np.random.default_rng(n), (3, n + 1))
+    real[:, 0] |= np.uint64(1 << 60)  # keep the test's own 'real' masks away from zero
+    rows = E.crafted_small(n, N, real, body_add)
+    assert rows.shape == (E.CRAFTED_ROWS, n + 1) and rows.dtype == np.uint64
+    u = E.rotation_unit(N)
+    assert not rows[0, :n].any()
+    assert [ms(x) for x in rows[1, :n]] == [0, N] * (n // 2) + [0] * (n % 2)
+    assert all(ms(x) == 2 * N and x != 0 for x in rows[2, :n])
+    assert all(ms(x) == 1 for x in rows[3, :n])
+    assert int(rows[3, 0]) == u and int(rows[3, 1]) == u // 2
+    assert ms(u // 2 - 1) == 0 and ms(u + u // 2 - 1) == 1 and ms(u + u // 2) == 2  # the boundaries themselves
+    for r, src in ((4, 0), (5, 1)):
+        assert not rows[r, :16].any() and np.array_equal(rows[r, 16:], real[src, 16:])
+    assert np.array_equal(rows[6], real[2])
+    for r, src, want in ((7, 0, 2 * N), (8, 1, 0), (9, 2, N)):
+        assert np.array_equal(rows[r, :n], real[src, :n])
+        assert ms(int(rows[r, n]) + body_add) == want, r
+    assert (int(rows[7, n]) + body_add) & MASK == MASK
+    assert (int(rows[8, n]) + body_add) & MASK == 0
+    assert (int(rows[9, n]) + body_add) & MASK == 1 << 63
+
+
+def test_trivial_ggsw_selects_through_vertical_packing(oracle_mod, noiseless):
+    """Vertical packing over the trivial GGSWs of a byte's bits returns LUT entry `byte` (within rounding of
+    0 / 2^63 for a generate_lut table), and all-zero spectra return entry 0 untouched."""
+    from tfhe_aes import aes_128
+    p, keys = noiseless
+    N = p["N"]
+    lut = oracle_mod.generate_lut(N, 8, 8, lambda v: aes_128.SBOX[v])
+    spec = {b: keys.ggsw_to_fourier(E.trivial_ggsw(p, b)) for b in (0, 1)}
+    assert not spec[0].any()
+    for byte in (0x00, 0xFF, 0xA7):
+        gf = np.concatenate([spec[b] for b in aes_128.u8_to_bits(byte)])
+        outs = [keys.vertical_packing(lut[j * N:(j + 1) * N], gf, 8) for j in range(8)]
+        assert all(not o[:-1].any() for o in outs)
+        bodies = [int(o[-1]) for o in outs]
+        assert all(min(b, (b - (1 << 63)) & MASK, ((1 << 63) - b) & MASK, (-b) & MASK) < 1 << 16 for b in bodies)
+        assert aes_128.bits_to_u8([((b + (1 << 62)) & MASK) >> 63 for b in bodies]) == aes_128.SBOX[byte]
+        if byte == 0:
+            assert bodies == [int(lut[j * N]) for j in range(8)]
