@@ -286,6 +286,63 @@ int tae_aes_cbc_transcipher_raw(const tae_context *ctx, const uint64_t *dk, cons
  * TAE_E_INDEP; parameter sets other than TAE_PARAMS_SQRD_LVL_* and rounds outside 1..=10 are TAE_E_PARAM */
 int tae_aes_decrypt_noise_schedule_check(int param_set, int rounds);
 
+/* ---- AES-128 / 192 / 256 by key size (FIPS-197 section 5.2 and figure 11) ---------------------------
+ * The reference is AES-128 only and has no counterpart of these functions; they are the tae_aes_* entry
+ * points above with `key_bits` after the context.  key_bits = 128 / 192 / 256 (anything else is TAE_E_PARAM)
+ * gives Nk = key_bits / 32 key words, Nr = Nk + 6 = 10 / 12 / 14 rounds and W = 4 (Nr + 1) = 44 / 52 / 60
+ * expanded words; every expanded or decryption key below is [W*32] bits in the layout of tae_aes_*, a handle
+ * array of another length is TAE_E_ARG, and `rounds` outside 1..=Nr is TAE_E_PARAM.  A run of `rounds` rounds
+ * uses round keys 0, 1..rounds-1 and Nr; the inverse uses Nr, rounds-1..1, 0.  The modes take `rounds` where
+ * their tae_aes_* namesakes fix 10.  Parameter sets: TAE_PARAMS_SQRD_LVL_* (gal-mul driver); 192 and 256 on
+ * TAE_PARAMS_WOPPBS_8BIT and TAE_PARAMS_SHORTINT_1BIT are TAE_E_PARAM.  With key_bits = 128 the cipher and
+ * the modes are the tae_aes_* paths themselves. */
+/* FIPS-197 figure 4 (no reference counterpart; no GPU): the number of expanded words W of a key size */
+int tae_aesx_expanded_words(int key_bits, size_t *words);
+/* FIPS-197 5.2 key expansion on handles (no reference counterpart): key[key_bits] bits -> expanded[W*32]; runs
+ * on the device, words from Nk on come out of an identity bootstrap (noise^2 = 1, new ids) */
+int tae_aesx_key_schedule(const tae_context *ctx, int key_bits, const tae_bit *const *key, tae_bit **expanded);
+/* FIPS-197 5.2 key expansion on raw fresh key bits [key_bits][L] -> [W*32][L] (no reference counterpart); with
+ * TAE_MEM_DEVICE no ciphertext leaves the device; at 128 bits the words equal tae_aes_key_schedule_raw's */
+int tae_aesx_key_schedule_raw(const tae_context *ctx, int key_bits, const uint64_t *key, uint64_t *expanded, int mem);
+/* FIPS-197 5.1 cipher on handles, figure 11 key sizes (no reference counterpart): blocks, out [n_blocks*128] */
+int tae_aesx_encrypt_blocks(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
+                            const tae_bit *const *blocks, size_t n_blocks, int rounds, tae_bit **out);
+/* FIPS-197 5.1 cipher on raw arrays (no reference counterpart): rk [W*32][L], blocks / out [n_blocks][128][L] */
+int tae_aesx_encrypt_blocks_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint64_t *blocks,
+                                size_t n_blocks, int rounds, uint64_t *out, int mem);
+/* tae_aes_ctr_keystream_raw with a FIPS-197 figure 11 key size (no reference counterpart): rk [W*32][L] */
+int tae_aesx_ctr_keystream_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint8_t iv[8],
+                               uint64_t first_counter, size_t n_blocks, int rounds, uint64_t *out, int mem);
+/* tae_aes_ctr_transcipher_raw with a FIPS-197 figure 11 key size and `rounds` (no reference counterpart) */
+int tae_aesx_ctr_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint8_t iv[8],
+                                 uint64_t first_counter, const uint8_t *data, size_t len, int rounds, uint64_t *out,
+                                 int mem);
+/* tae_aes_ctr_transcipher with a FIPS-197 figure 11 key size and `rounds` (no reference counterpart) */
+int tae_aesx_ctr_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
+                             const uint8_t iv[8], uint64_t first_counter, const uint8_t *data, size_t len, int rounds,
+                             tae_bit **out /*[len*8]*/);
+/* FIPS-197 5.3.5 decryption key on handles (no reference counterpart): words 0..3 and 4Nr..4Nr+3 are copies,
+ * words 4r..4r+3 (r = 1..Nr-1) = InvMixColumns(rk[r]) with noise^2 = 1 and new ids */
+int tae_aesx_decrypt_key(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key, tae_bit **dk);
+/* FIPS-197 5.3.5 decryption key on raw arrays (no reference counterpart): rk, dk [W*32][L]; dk must not be rk */
+int tae_aesx_decrypt_key_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, uint64_t *dk, int mem);
+/* FIPS-197 5.3 inverse cipher on handles (no reference counterpart); TAE_E_INDEP as tae_aes_decrypt_blocks */
+int tae_aesx_decrypt_blocks(const tae_context *ctx, int key_bits, const tae_bit *const *dk, const tae_bit *const *blocks,
+                            size_t n_blocks, int rounds, tae_bit **out);
+/* FIPS-197 5.3 inverse cipher on raw arrays (no reference counterpart): dk [W*32][L] */
+int tae_aesx_decrypt_blocks_raw(const tae_context *ctx, int key_bits, const uint64_t *dk, const uint64_t *blocks,
+                                size_t n_blocks, int rounds, uint64_t *out, int mem);
+/* tae_aes_cbc_transcipher with a FIPS-197 figure 11 key size and `rounds` (no reference counterpart) */
+int tae_aesx_cbc_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *dk, const uint8_t iv[16],
+                             const uint8_t *data, size_t len, int rounds, tae_bit **out /*[len*8]*/);
+/* tae_aes_cbc_transcipher_raw with a FIPS-197 figure 11 key size and `rounds` (no reference counterpart) */
+int tae_aesx_cbc_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *dk, const uint8_t iv[16],
+                                 const uint8_t *data, size_t len, int rounds, uint64_t *out, int mem);
+/* noise bookkeeping for a fresh key and block (FIPS-197 5.2, then 5.1 or 5.3; no reference counterpart; no GPU):
+ * the key expansion, then `rounds` cipher rounds, or with inverse != 0 the decryption-key derivation and `rounds`
+ * inverse rounds.  TAE_OK, TAE_E_NOISE or TAE_E_INDEP; other models than the 1-bit one are TAE_E_PARAM */
+int tae_aesx_noise_schedule_check(int param_set, int key_bits, int rounds, int inverse);
+
 /* ---- Aes128Encrypt for the fhe_sbox_pbs driver (src/aes_128/fhe/fhe_sbox_pbs.rs:22-171) ------------
  * ShortintWoppbs1BitSboxPbsAesEncrypt on the 1-bit model (fhe_impls/shortint_woppbs_1bit.rs:47-81:
  * SubBytes = one 8 -> 8 circuit bootstrap per byte, MixColumns = gf_256_mul by BitCt XORs) and

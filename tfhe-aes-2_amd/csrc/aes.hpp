@@ -8,7 +8,14 @@ namespace tae {
 
 extern const uint8_t kSbox[256];
 extern const uint8_t kRcon[11];
-constexpr int kAesRounds = 10;
+constexpr int kAesRounds = 10;  // AES-128, the default everywhere
+
+// FIPS-197 figure 4 for key_bits = 128 / 192 / 256: Nk key words, Nr = Nk + 6 rounds, 4 (Nr + 1) expanded words
+// (44 / 52 / 60).  kRcon's 11 entries cover every size (the last index used is 10, 8 and 7).
+constexpr bool aes_key_bits_ok(int key_bits) { return key_bits == 128 || key_bits == 192 || key_bits == 256; }
+constexpr int aes_nk(int key_bits) { return key_bits / 32; }
+constexpr int aes_nr(int key_bits) { return key_bits / 32 + 6; }
+constexpr int aes_words(int key_bits) { return 4 * (aes_nr(key_bits) + 1); }
 
 // gf_256_mul exactly as the reference writes it, including its reduction quirk (it XORs 0x1b
 // when the high bit is CLEAR, aes_128.rs:50).  The x2/x3 LUT outputs inherit the quirk; the two
@@ -24,5 +31,7 @@ void mix_column_terms(int terms[32][32]);
 
 // plain key expansion into 176 bytes (word-major), plain.rs:106-132
 void plain_key_schedule(const uint8_t key[16], uint8_t rk[176]);
+// FIPS-197 5.2 for nk = 4 / 6 / 8 key words: key [4 nk] -> rk [16 (nk + 7)] bytes
+void plain_key_schedule(const uint8_t *key, int nk, uint8_t *rk);
 
 }  // namespace tae

@@ -674,6 +674,154 @@ int tae_aes_decrypt_noise_schedule_check(int param_set, int rounds) {
     });
 }
 
+/* ---- AES-128 / 192 / 256 by key_bits (FIPS-197 5.2 and figure 11; no counterpart in the reference) ---- */
+namespace {
+// ciphertexts of an expanded key; key_bits is checked before any handle array is read at that length
+size_t key_cts(int key_bits) {
+    if (!tae::aes_key_bits_ok(key_bits)) throw tae::ModelError{TAE_E_PARAM, "key_bits must be 128, 192 or 256"};
+    return (size_t)tae::aes_words(key_bits) * 32;
+}
+constexpr tae::AesDriver kGalMul = tae::AesDriver::GalMul;
+}  // namespace
+
+int tae_aesx_expanded_words(int key_bits, size_t *words) {
+    return guarded([&] {
+        require(words != nullptr, "null");
+        *words = key_cts(key_bits) / 32;
+    });
+}
+
+int tae_aesx_key_schedule(const tae_context *ctx, int key_bits, const tae_bit *const *key, tae_bit **expanded) {
+    return guarded([&] {
+        require(ctx && key && expanded, "null");
+        key_cts(key_bits);
+        emit(ctx->ctx->aes_key_expand(unwrap(key, (size_t)key_bits), key_bits), expanded);
+    });
+}
+
+int tae_aesx_key_schedule_raw(const tae_context *ctx, int key_bits, const uint64_t *key, uint64_t *expanded, int mem) {
+    return guarded([&] {
+        require(ctx && key && expanded, "null");
+        ctx->ctx->aes_key_expand_raw(key, expanded, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesx_encrypt_blocks(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
+                            const tae_bit *const *blocks, size_t n_blocks, int rounds, tae_bit **out) {
+    return guarded([&] {
+        require(ctx && expanded_key && blocks && out, "null");
+        emit(ctx->ctx->aes_encrypt_blocks(unwrap(expanded_key, key_cts(key_bits)), unwrap(blocks, 128 * n_blocks),
+                                          n_blocks, rounds, kGalMul, key_bits),
+             out);
+    });
+}
+
+int tae_aesx_encrypt_blocks_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint64_t *blocks,
+                                size_t n_blocks, int rounds, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && rk && blocks && out, "null");
+        ctx->ctx->aes_encrypt_blocks_raw(rk, blocks, n_blocks, rounds, out, mem == TAE_MEM_DEVICE, kGalMul, key_bits);
+    });
+}
+
+int tae_aesx_ctr_keystream_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint8_t iv[8],
+                               uint64_t first_counter, size_t n_blocks, int rounds, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && rk && iv && (out || !n_blocks), "null");
+        ctx->ctx->aes_ctr_keystream_raw(rk, iv, first_counter, n_blocks, rounds, out, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesx_ctr_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint8_t iv[8],
+                                 uint64_t first_counter, const uint8_t *data, size_t len, int rounds, uint64_t *out,
+                                 int mem) {
+    return guarded([&] {
+        require(ctx && rk && iv && ((data && out) || !len), "null");
+        ctx->ctx->aes_ctr_transcipher_raw(rk, iv, first_counter, data, len, rounds, out, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesx_ctr_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
+                             const uint8_t iv[8], uint64_t first_counter, const uint8_t *data, size_t len, int rounds,
+                             tae_bit **out) {
+    return guarded([&] {
+        require(ctx && expanded_key && iv && ((data && out) || !len), "null");
+        emit(ctx->ctx->aes_ctr_transcipher(unwrap(expanded_key, key_cts(key_bits)), iv, first_counter, data, len, rounds,
+                                           key_bits),
+             out);
+    });
+}
+
+int tae_aesx_decrypt_key(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key, tae_bit **dk) {
+    return guarded([&] {
+        require(ctx && expanded_key && dk, "null");
+        emit(ctx->ctx->aes_decrypt_key(unwrap(expanded_key, key_cts(key_bits)), key_bits), dk);
+    });
+}
+
+int tae_aesx_decrypt_key_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, uint64_t *dk, int mem) {
+    return guarded([&] {
+        require(ctx && rk && dk, "null");
+        ctx->ctx->aes_decrypt_key_raw(rk, dk, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesx_decrypt_blocks(const tae_context *ctx, int key_bits, const tae_bit *const *dk, const tae_bit *const *blocks,
+                            size_t n_blocks, int rounds, tae_bit **out) {
+    return guarded([&] {
+        require(ctx && dk && (n_blocks == 0 || (blocks && out)), "null");
+        emit(ctx->ctx->aes_decrypt_blocks(unwrap(dk, key_cts(key_bits)), unwrap(blocks, 128 * n_blocks), n_blocks, rounds,
+                                          key_bits),
+             out);
+    });
+}
+
+int tae_aesx_decrypt_blocks_raw(const tae_context *ctx, int key_bits, const uint64_t *dk, const uint64_t *blocks,
+                                size_t n_blocks, int rounds, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && dk && (n_blocks == 0 || (blocks && out)), "null");
+        ctx->ctx->aes_decrypt_blocks_raw(dk, blocks, n_blocks, rounds, out, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesx_cbc_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *dk, const uint8_t iv[16],
+                             const uint8_t *data, size_t len, int rounds, tae_bit **out) {
+    return guarded([&] {
+        require(ctx && dk && iv && ((data && out) || !len), "null");
+        emit(ctx->ctx->aes_cbc_transcipher(unwrap(dk, key_cts(key_bits)), iv, data, len, rounds, key_bits), out);
+    });
+}
+
+int tae_aesx_cbc_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *dk, const uint8_t iv[16],
+                                 const uint8_t *data, size_t len, int rounds, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && dk && iv && ((data && out) || !len), "null");
+        ctx->ctx->aes_cbc_transcipher_raw(dk, iv, data, len, rounds, out, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesx_noise_schedule_check(int param_set, int key_bits, int rounds, int inverse) {
+    return guarded([&] {
+        const tae::Params p = params_of(param_set);
+        const size_t kw = key_cts(key_bits);
+        const int nk = tae::aes_nk(key_bits), nr = tae::aes_nr(key_bits);
+        if (p.model != 1)
+            throw tae::ModelError{TAE_E_PARAM, "AES by key_bits runs on the 1-bit WoP-PBS parameter sets only"};
+        if (rounds < 1 || rounds > nr)
+            throw tae::ModelError{TAE_E_PARAM, "rounds must be in 1..=" + std::to_string(nr)};
+        std::vector<tae::NoiseLevel> key((size_t)nk * 32), blk(128);
+        for (auto &x : key) x = tae::NoiseLevel::with_noise_level(1, tae::next_ct_id());
+        for (auto &x : blk) x = tae::NoiseLevel::with_noise_level(1, tae::next_ct_id());
+        const std::vector<tae::NoiseLevel> rk = tae::aes_key_expand_noise_schedule(key, nk, p.max_noise_sq);
+        require(rk.size() == kw, "expanded key size");
+        if (inverse)
+            tae::aes_decrypt_noise_schedule(tae::aes_decrypt_key_noise_schedule(rk, p.max_noise_sq, nr), blk, rounds,
+                                            p.max_noise_sq, nr);
+        else
+            tae::aes_noise_schedule(rk, blk, rounds, p.max_noise_sq, nr);
+    });
+}
+
 int tae_aes_sbox_pbs_encrypt_blocks(const tae_context *ctx, const tae_bit *const *expanded_key,
                                     const tae_bit *const *blocks, size_t n_blocks, int rounds, tae_bit **out) {
     return guarded([&] {

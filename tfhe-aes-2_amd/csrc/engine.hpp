@@ -99,9 +99,17 @@ class Engine {
                              uint64_t *d_out);
 
     // ---- AES driver (fhe_sbox_gal_mul_pbs::encrypt_block_for_rounds over many blocks) ----
-    // rk [44*32][K+1] (expanded key words, word-major, MSB-first bits), blocks [nb][128][K+1]
+    // rk [44*32][K+1] (expanded key words, word-major, MSB-first bits), blocks [nb][128][K+1].
+    // nr = 10 / 12 / 14 is the round count of the key size (AES-128 / 192 / 256), here and in the modes below:
+    // rk has 4 (nr + 1) words, rounds may go up to nr, and a run of `rounds` rounds uses round keys 0,
+    // 1..rounds-1 and nr (the last one at word 4 nr)
     void aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, size_t nb, int rounds,
-                            uint64_t *d_out);
+                            uint64_t *d_out, int nr = 10);
+    // key expansion on the device (FIPS-197 5.2, figure 11; fhe_sbox_gal_mul_pbs::key_schedule for nk = 4):
+    // key [nk*32][K+1], nk = 4 / 6 / 8 -> rk [4 (nk + 7) * 32][K+1].  Words below nk are copied; word i is
+    // rk[i-nk] + rk[i-1], with SubWord (one 4-group 8 -> 8 bootstrap), RotWord and Rcon when i % nk == 0 and
+    // SubWord alone when nk == 8 and i % 8 == 4, then one identity bootstrap of its 32 bits.  1-bit model only
+    void aes_key_expand(const uint64_t *d_key, int nk, uint64_t *d_rk);
 
     // ---- AES-128-CTR with public counters (main.rs:108-128; ctr_plan.hpp) ----
     // The keystream blocks of one plan (nb blocks) for the 1-bit model: round 0 builds the plan's U
@@ -110,26 +118,30 @@ class Engine {
     // Writes the first out_bytes (<= 16 nb) keystream bytes [out_bytes][8][K+1]; with d_data (out_bytes
     // public bytes on the device) each output is keystream xor data (transciphering).
     void aes_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
-                        size_t out_bytes, uint64_t *d_out);
+                        size_t out_bytes, uint64_t *d_out, int nr = 10);
     // the same for the 8-bit model (small-key bits [n+1], bootstrap_bytes8 + the gf_256_mul network)
     void aes8_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
-                         size_t out_bytes, uint64_t *d_out);
+                         size_t out_bytes, uint64_t *d_out, int nr = 10);
     // counters first_counter .. first_counter + nb - 1 in consecutive chunks of ctr_chunk_ blocks, each with
     // its own plan, on the model of the parameter set (1-bit or 8-bit)
     void aes_ctr(const uint64_t *d_rk, const uint8_t iv[8], uint64_t first_counter, size_t nb, int rounds,
-                 const uint8_t *d_data, size_t out_bytes, uint64_t *d_out);
+                 const uint8_t *d_data, size_t out_bytes, uint64_t *d_out, int nr = 10);
 
     // ---- AES-128 inverse cipher on the 1-bit model (FIPS-197 5.3; the reference has no decryption).  The
     // algorithm is in aes_inv.hpp: InvSubBytes and InvMixColumns' multiples {14,11,13,9} in one 8 -> 32 circuit
     // bootstrap per byte and middle round, one 8 -> 8 for the last: `rounds` bootstraps per block, as encryption ----
-    // dk [44*32][K+1] (aes_decrypt_key), blocks / out [nb][128][K+1]; inverts aes_encrypt_blocks(rounds)
-    void aes_decrypt_blocks(const uint64_t *d_dk, const uint64_t *d_blocks, size_t nb, int rounds, uint64_t *d_out);
+    // dk [44*32][K+1] (aes_decrypt_key), blocks / out [nb][128][K+1]; inverts aes_encrypt_blocks(rounds): round
+    // keys nr, rounds-1 .. 1, 0 of a key of 4 (nr + 1) words
+    void aes_decrypt_blocks(const uint64_t *d_dk, const uint64_t *d_blocks, size_t nb, int rounds, uint64_t *d_out,
+                            int nr = 10);
     // decryption key: words 0..3 and 40..43 copied, words 4r..4r+3 = InvMixColumns(rk[r]) by one 8 -> 32 bootstrap
-    // of the 144 bytes (multiples only), the 4-term sums and one identity bootstrap of the 1152 bits.  d_dk != d_rk
-    void aes_decrypt_key(const uint64_t *d_rk, uint64_t *d_dk);
+    // of the 144 bytes (multiples only), the 4-term sums and one identity bootstrap of the 1152 bits.  d_dk != d_rk.
+    // With nr: words 4 nr .. 4 nr + 3 are the last copy, and the middle is 16 (nr - 1) bytes, 128 (nr - 1) bits
+    void aes_decrypt_key(const uint64_t *d_rk, uint64_t *d_dk, int nr = 10);
     // CBC with a public ciphertext: d_iv_data = iv[16] || nb blocks of ciphertext bytes on the device; out
     // [nb][128][K+1] = Dec(C_i) ^ C_{i-1}.  Round 0 and the last XOR come from the public bytes: no input ciphertexts
-    void aes_cbc_transcipher(const uint64_t *d_dk, const uint8_t *d_iv_data, size_t nb, int rounds, uint64_t *d_out);
+    void aes_cbc_transcipher(const uint64_t *d_dk, const uint8_t *d_iv_data, size_t nb, int rounds, uint64_t *d_out,
+                             int nr = 10);
 
     // ---- shortint_1bit model (src/tfhe/shortint_1bit.rs; param set SHORTINT_1BIT) ----
     // FheContext::bootstrap / bootstrap_assign (:257-291): PBS with test vector d_tvs + (b % lut_mod) (k+1)N, then the keyswitch
@@ -200,7 +212,7 @@ class Engine {
     uint64_t *d_lut24_ = nullptr, *d_lut8_ = nullptr;
     // inverse cipher (1-bit model): InvSbox * {14,11,13,9}, InvSbox, the multiples alone, the 1 -> 1 identity
     uint64_t *d_lut_inv32_ = nullptr, *d_lut_inv8_ = nullptr, *d_lut_mul32_ = nullptr, *d_lut_id1_ = nullptr;
-    void require_inverse(int rounds) const;
+    void require_inverse(int rounds, int nr) const;
     void aes_decrypt_rounds(const uint64_t *d_dk, size_t nb, int rounds, const uint8_t *d_xor, uint64_t *d_out);
     uint64_t *d_wlut_sbox_ = nullptr, *d_wlut_id_ = nullptr;  // 8-bit model
     uint64_t *d_lut_x_ = nullptr;                             // extract_bits accumulators [nbits][glwe]

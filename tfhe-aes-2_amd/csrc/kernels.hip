@@ -629,6 +629,24 @@ __global__ void aes_inv_round0_public_kernel(const uint64_t *__restrict__ rk_las
     }
 }
 
+// ---- key expansion (FIPS-197 5.2, figure 11): one word before its identity bootstrap ----
+// t = back + other (+ Rcon), whole ciphertexts: back = rk[i-Nk], other = rk[i-1] or SubWord(rk[i-1]), both
+// [4 bytes][8 bits][L].  SubWord works byte by byte, so RotWord is applied here, on the read of its output:
+// rot = 1 takes byte (b + 1) % 4 of `other`.  rcon != 0 adds bit b of it (MSB first) << 63 on the body of bit b
+// of byte 0, as Context::trivial does.  Consecutive threads walk the coefficients of one ciphertext.
+__global__ void aes_ks_word_kernel(const uint64_t *__restrict__ back, const uint64_t *__restrict__ other, int rot,
+                                   int rcon, uint64_t *__restrict__ out, int L) {
+    const size_t total = 32 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t coef = t % L;
+        const int ct = (int)(t / L);  // byte*8 + bit
+        const int bit = ct & 7, byte = ct >> 3;
+        uint64_t w = back[t] + other[(size_t)(((byte + rot) & 3) * 8 + bit) * L + coef];
+        if (byte == 0 && coef == (size_t)L - 1) w += (uint64_t)((rcon >> (7 - bit)) & 1) << 63;
+        out[t] = w;
+    }
+}
+
 __global__ void lwe_add_kernel(uint64_t *__restrict__ a, const uint64_t *__restrict__ b, size_t count) {
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (size_t)gridDim.x * blockDim.x)
         a[t] += b[t];
@@ -1683,10 +1701,16 @@ void Engine::aes8_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks,
     HIPC(hipGetLastError());
 }
 
+// nr = 10 / 12 / 14 (AES-128 / 192 / 256) and 1 <= rounds <= nr, or a runtime_error
+static void require_rounds(int rounds, int nr) {
+    if (nr != 10 && nr != 12 && nr != 14) throw std::runtime_error("the round count of the key size must be 10, 12 or 14");
+    if (rounds < 1 || rounds > nr) throw std::runtime_error("rounds must be in 1..=" + std::to_string(nr));
+}
+
 void Engine::aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, size_t nb, int rounds,
-                                uint64_t *d_out) {
+                                uint64_t *d_out, int nr) {
     if (!nb) return;
-    if (rounds < 1 || rounds > 10) throw std::runtime_error("rounds must be in 1..=10");
+    require_rounds(rounds, nr);
     const int L = (int)p_.big_len();
     const size_t state_len = nb * 128 * (size_t)L;
     times_ = StageTimes{};
@@ -1702,8 +1726,8 @@ void Engine::aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, 
         HIPC(hipGetLastError());
     }
     circuit_bootstrap(d_state_, nb * 16, 8, d_lut8_, 8, d_muls_);
-    aes_final_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_rk + (size_t)160 * byte_stride, d_out,
-                                                                     nb, L);
+    aes_final_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_rk + (size_t)16 * nr * byte_stride,
+                                                                     d_out, nb, L);
     HIPC(hipGetLastError());
 }
 
@@ -1720,10 +1744,10 @@ void Engine::upload_ctr_plan(const CtrPlan &plan, size_t nb) {
 }
 
 void Engine::aes_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
-                            size_t out_bytes, uint64_t *d_out) {
+                            size_t out_bytes, uint64_t *d_out, int nr) {
     if (!nb) return;
     if (p_.model != 1) throw std::runtime_error("aes_ctr_blocks needs the 1-bit model parameters");
-    if (rounds < 1 || rounds > 10) throw std::runtime_error("rounds must be in 1..=10");
+    require_rounds(rounds, nr);
     if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
     const int L = (int)p_.big_len();
     const size_t U = plan.groups.size();
@@ -1751,16 +1775,16 @@ void Engine::aes_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb
     circuit_bootstrap(d_state_, G, 8, d_lut8_, 8, d_muls_);
     if (out_bytes) {
         aes_ctr_final_kernel<<<grid_for(out_bytes * 8 * (size_t)L), kThreads, 0, stream_>>>(
-            d_muls_, map, d_rk + (size_t)160 * byte_stride, d_data, d_out, out_bytes, L);
+            d_muls_, map, d_rk + (size_t)16 * nr * byte_stride, d_data, d_out, out_bytes, L);
         HIPC(hipGetLastError());
     }
 }
 
 void Engine::aes8_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
-                             size_t out_bytes, uint64_t *d_out) {
+                             size_t out_bytes, uint64_t *d_out, int nr) {
     if (!nb) return;
     if (p_.model != 8) throw std::runtime_error("aes8_ctr_blocks needs the 8-bit model parameters");
-    if (rounds < 1 || rounds > 10) throw std::runtime_error("rounds must be in 1..=10");
+    require_rounds(rounds, nr);
     if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
     const int L = (int)p_.small_len();
     const size_t U = plan.groups.size();
@@ -1789,13 +1813,13 @@ void Engine::aes8_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t n
     bootstrap_bytes8(d_state_, G, d_wlut_sbox_, d_muls_);
     if (out_bytes) {
         aes_ctr_final_kernel<<<grid_for(out_bytes * 8 * (size_t)L), kThreads, 0, stream_>>>(
-            d_muls_, map, d_rk + (size_t)160 * byte_stride, d_data, d_out, out_bytes, L);
+            d_muls_, map, d_rk + (size_t)16 * nr * byte_stride, d_data, d_out, out_bytes, L);
         HIPC(hipGetLastError());
     }
 }
 
 void Engine::aes_ctr(const uint64_t *d_rk, const uint8_t iv[8], uint64_t first_counter, size_t nb, int rounds,
-                     const uint8_t *d_data, size_t out_bytes, uint64_t *d_out) {
+                     const uint8_t *d_data, size_t out_bytes, uint64_t *d_out, int nr) {
     if (!nb) return;
     if (p_.model != 1 && p_.model != 8) throw std::runtime_error("counter mode runs on the 1-bit and 8-bit models");
     if (!ctr_range_ok(first_counter, nb)) throw std::runtime_error("counter range wraps past 2^64 - 1");
@@ -1814,14 +1838,14 @@ void Engine::aes_ctr(const uint64_t *d_rk, const uint8_t iv[8], uint64_t first_c
         const uint8_t *data = d_data ? d_data + byte0 : nullptr;
         uint64_t *out = d_out + byte0 * 8 * L;
         if (p_.model == 8)
-            aes8_ctr_blocks(d_rk, ctr_plans_.back(), cn, rounds, data, cbytes, out);
+            aes8_ctr_blocks(d_rk, ctr_plans_.back(), cn, rounds, data, cbytes, out, nr);
         else
-            aes_ctr_blocks(d_rk, ctr_plans_.back(), cn, rounds, data, cbytes, out);
+            aes_ctr_blocks(d_rk, ctr_plans_.back(), cn, rounds, data, cbytes, out, nr);
     }
 }
 
 // ---- AES-128 inverse cipher (FIPS-197 5.3; aes_inv.hpp) ----
-// rounds R-1 .. 1 and the last round on d_state_ = block ^ dk[40..43]: R circuit bootstraps per block
+// rounds R-1 .. 1 and the last round on d_state_ = block ^ dk[4 nr ..]: R circuit bootstraps per block
 void Engine::aes_decrypt_rounds(const uint64_t *d_dk, size_t nb, int rounds, const uint8_t *d_xor, uint64_t *d_out) {
     const int L = (int)p_.big_len();
     const size_t state_len = nb * 128 * (size_t)L, byte_stride = 8 * (size_t)L;
@@ -1841,32 +1865,32 @@ void Engine::aes_decrypt_rounds(const uint64_t *d_dk, size_t nb, int rounds, con
     collect_times();
 }
 
-void Engine::require_inverse(int rounds) const {
+void Engine::require_inverse(int rounds, int nr) const {
     if (p_.model != 1 || !d_lut_inv32_) throw std::runtime_error("the inverse cipher needs the 1-bit model parameters");
-    if (rounds < 1 || rounds > 10) throw std::runtime_error("rounds must be in 1..=10");
+    require_rounds(rounds, nr);
 }
 
 void Engine::aes_decrypt_blocks(const uint64_t *d_dk, const uint64_t *d_blocks, size_t nb, int rounds,
-                                uint64_t *d_out) {
+                                uint64_t *d_out, int nr) {
     if (!nb) return;
-    require_inverse(rounds);
+    require_inverse(rounds, nr);
     const int L = (int)p_.big_len();
     const size_t state_len = nb * 128 * (size_t)L;
     times_ = StageTimes{};
     grow(d_state_, cap_state_, state_len);
     grow(d_muls_, cap_muls_, nb * 16 * (size_t)(rounds > 1 ? 32 : 8) * L);
     timed(ST_LINEAR, [&] {
-        aes_ark0_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_blocks, d_dk + (size_t)160 * 8 * L, d_state_,
-                                                                        nb, L);
+        aes_ark0_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_blocks, d_dk + (size_t)16 * nr * 8 * L,
+                                                                        d_state_, nb, L);
         HIPC(hipGetLastError());
     });
     aes_decrypt_rounds(d_dk, nb, rounds, nullptr, d_out);
 }
 
 void Engine::aes_cbc_transcipher(const uint64_t *d_dk, const uint8_t *d_iv_data, size_t nb, int rounds,
-                                 uint64_t *d_out) {
+                                 uint64_t *d_out, int nr) {
     if (!nb) return;
-    require_inverse(rounds);
+    require_inverse(rounds, nr);
     const int L = (int)p_.big_len();
     const size_t state_len = nb * 128 * (size_t)L;
     times_ = StageTimes{};
@@ -1874,29 +1898,64 @@ void Engine::aes_cbc_transcipher(const uint64_t *d_dk, const uint8_t *d_iv_data,
     grow(d_muls_, cap_muls_, nb * 16 * (size_t)(rounds > 1 ? 32 : 8) * L);
     // d_iv_data = iv || C_0 .. C_{nb-1}: block i is decrypted from bytes 16 (i + 1) .. and XORed with bytes 16 i ..
     timed(ST_LINEAR, [&] {
-        aes_inv_round0_public_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_dk + (size_t)160 * 8 * L,
+        aes_inv_round0_public_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_dk + (size_t)16 * nr * 8 * L,
                                                                                      d_iv_data + 16, d_state_, nb, L);
         HIPC(hipGetLastError());
     });
     aes_decrypt_rounds(d_dk, nb, rounds, d_iv_data, d_out);
 }
 
-void Engine::aes_decrypt_key(const uint64_t *d_rk, uint64_t *d_dk) {
-    require_inverse(10);
+void Engine::aes_decrypt_key(const uint64_t *d_rk, uint64_t *d_dk, int nr) {
+    require_inverse(nr, nr);
     if (d_rk == d_dk) throw std::runtime_error("the decryption key cannot be derived in place");
     const int L = (int)p_.big_len();
-    const size_t word = 32 * (size_t)L, mid = 36 * word;  // words 4..39: 144 bytes = 9 round keys
+    // words 4 .. 4 nr - 1: nr - 1 round keys of 16 bytes
+    const size_t word = 32 * (size_t)L, mid = 4 * (size_t)(nr - 1) * word, last = 4 * (size_t)nr * word;
     times_ = StageTimes{};
     grow(d_state_, cap_state_, mid);
-    grow(d_muls_, cap_muls_, 144 * 32 * (size_t)L);
+    grow(d_muls_, cap_muls_, 16 * (size_t)(nr - 1) * 32 * L);
     HIPC(hipMemcpyAsync(d_dk, d_rk, 4 * word * 8, hipMemcpyDeviceToDevice, stream_));
-    HIPC(hipMemcpyAsync(d_dk + 40 * word, d_rk + 40 * word, 4 * word * 8, hipMemcpyDeviceToDevice, stream_));
-    circuit_bootstrap(d_rk + 4 * word, 144, 8, d_lut_mul32_, 32, d_muls_);
+    HIPC(hipMemcpyAsync(d_dk + last, d_rk + last, 4 * word * 8, hipMemcpyDeviceToDevice, stream_));
+    circuit_bootstrap(d_rk + 4 * word, 16 * (size_t)(nr - 1), 8, d_lut_mul32_, 32, d_muls_);
     timed(ST_LINEAR, [&] {
-        aes_inv_mix_kernel<<<grid_for(mid), kThreads, 0, stream_>>>(d_muls_, nullptr, d_state_, 9, L, 0);
+        aes_inv_mix_kernel<<<grid_for(mid), kThreads, 0, stream_>>>(d_muls_, nullptr, d_state_, nr - 1, L, 0);
         HIPC(hipGetLastError());
     });
-    circuit_bootstrap(d_state_, 36 * 32, 1, d_lut_id1_, 1, d_dk + 4 * word);
+    circuit_bootstrap(d_state_, 128 * (size_t)(nr - 1), 1, d_lut_id1_, 1, d_dk + 4 * word);
+    collect_times();
+}
+
+// ---- key expansion on the device (FIPS-197 5.2, figure 11), nk = 4 / 6 / 8 key words ----
+// Every new word is bootstrapped (identity, 32 one-bit groups) before the next word reads it, as
+// Context::aes_key_schedule does on the host; the stages of a word are launches on the engine stream and no
+// ciphertext leaves the device.
+void Engine::aes_key_expand(const uint64_t *d_key, int nk, uint64_t *d_rk) {
+    if (p_.model != 1 || !d_lut_id1_) throw std::runtime_error("the key expansion needs the 1-bit model parameters");
+    if (nk != 4 && nk != 6 && nk != 8) throw std::runtime_error("the key must be 4, 6 or 8 words");
+    const int L = (int)p_.big_len(), words = 4 * (nk + 7);
+    const size_t word = 32 * (size_t)L;
+    times_ = StageTimes{};
+    grow(d_state_, cap_state_, word);
+    grow(d_muls_, cap_muls_, word);
+    if (d_key != d_rk) HIPC(hipMemcpyAsync(d_rk, d_key, nk * word * 8, hipMemcpyDeviceToDevice, stream_));
+    for (int i = nk; i < words; i++) {
+        const uint64_t *back = d_rk + (size_t)(i - nk) * word, *other = d_rk + (size_t)(i - 1) * word;
+        int rot = 0, rcon = 0;
+        if (i % nk == 0 || (nk == 8 && i % 8 == 4)) {
+            // SubWord of rk[i-1] where it lies; RotWord and Rcon on the words that start a key-sized group
+            circuit_bootstrap(other, 4, 8, d_lut8_, 8, d_muls_);
+            other = d_muls_;
+            if (i % nk == 0) {
+                rot = 1;
+                rcon = kRcon[i / nk];
+            }
+        }
+        timed(ST_LINEAR, [&] {
+            aes_ks_word_kernel<<<grid_for(word), kThreads, 0, stream_>>>(back, other, rot, rcon, d_state_, L);
+            HIPC(hipGetLastError());
+        });
+        circuit_bootstrap(d_state_, 32, 1, d_lut_id1_, 1, d_rk + (size_t)i * word);
+    }
     collect_times();
 }
 

@@ -13,27 +13,6 @@
 
 namespace tae {
 
-// ---------------------------------------------------------------------------------------------
-// AES constants (src/aes_128.rs)
-// ---------------------------------------------------------------------------------------------
-const uint8_t kSbox[256] = {
-    0x63, 0x7c, 0x77, 0x7b, 0xf2, 0x6b, 0x6f, 0xc5, 0x30, 0x01, 0x67, 0x2b, 0xfe, 0xd7, 0xab, 0x76, 0xca, 0x82,
-    0xc9, 0x7d, 0xfa, 0x59, 0x47, 0xf0, 0xad, 0xd4, 0xa2, 0xaf, 0x9c, 0xa4, 0x72, 0xc0, 0xb7, 0xfd, 0x93, 0x26,
-    0x36, 0x3f, 0xf7, 0xcc, 0x34, 0xa5, 0xe5, 0xf1, 0x71, 0xd8, 0x31, 0x15, 0x04, 0xc7, 0x23, 0xc3, 0x18, 0x96,
-    0x05, 0x9a, 0x07, 0x12, 0x80, 0xe2, 0xeb, 0x27, 0xb2, 0x75, 0x09, 0x83, 0x2c, 0x1a, 0x1b, 0x6e, 0x5a, 0xa0,
-    0x52, 0x3b, 0xd6, 0xb3, 0x29, 0xe3, 0x2f, 0x84, 0x53, 0xd1, 0x00, 0xed, 0x20, 0xfc, 0xb1, 0x5b, 0x6a, 0xcb,
-    0xbe, 0x39, 0x4a, 0x4c, 0x58, 0xcf, 0xd0, 0xef, 0xaa, 0xfb, 0x43, 0x4d, 0x33, 0x85, 0x45, 0xf9, 0x02, 0x7f,
-    0x50, 0x3c, 0x9f, 0xa8, 0x51, 0xa3, 0x40, 0x8f, 0x92, 0x9d, 0x38, 0xf5, 0xbc, 0xb6, 0xda, 0x21, 0x10, 0xff,
-    0xf3, 0xd2, 0xcd, 0x0c, 0x13, 0xec, 0x5f, 0x97, 0x44, 0x17, 0xc4, 0xa7, 0x7e, 0x3d, 0x64, 0x5d, 0x19, 0x73,
-    0x60, 0x81, 0x4f, 0xdc, 0x22, 0x2a, 0x90, 0x88, 0x46, 0xee, 0xb8, 0x14, 0xde, 0x5e, 0x0b, 0xdb, 0xe0, 0x32,
-    0x3a, 0x0a, 0x49, 0x06, 0x24, 0x5c, 0xc2, 0xd3, 0xac, 0x62, 0x91, 0x95, 0xe4, 0x79, 0xe7, 0xc8, 0x37, 0x6d,
-    0x8d, 0xd5, 0x4e, 0xa9, 0x6c, 0x56, 0xf4, 0xea, 0x65, 0x7a, 0xae, 0x08, 0xba, 0x78, 0x25, 0x2e, 0x1c, 0xa6,
-    0xb4, 0xc6, 0xe8, 0xdd, 0x74, 0x1f, 0x4b, 0xbd, 0x8b, 0x8a, 0x70, 0x3e, 0xb5, 0x66, 0x48, 0x03, 0xf6, 0x0e,
-    0x61, 0x35, 0x57, 0xb9, 0x86, 0xc1, 0x1d, 0x9e, 0xe1, 0xf8, 0x98, 0x11, 0x69, 0xd9, 0x8e, 0x94, 0x9b, 0x1e,
-    0x87, 0xe9, 0xce, 0x55, 0x28, 0xdf, 0x8c, 0xa1, 0x89, 0x0d, 0xbf, 0xe6, 0x42, 0x68, 0x41, 0x99, 0x2d, 0x0f,
-    0xb0, 0x54, 0xbb, 0x16};
-const uint8_t kRcon[11] = {0x00, 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80, 0x1B, 0x36};
-
 void gf_256_mul_bit_terms(uint8_t b, int terms[8][8]) {
     int a[8][8] = {}, res[8][8] = {};
     for (int i = 0; i < 8; i++) a[i][i] = 1;
@@ -69,34 +48,6 @@ void mix_column_terms(int terms[32][32]) {
                 terms[8 * r + o][8 * ((r + 2) % 4) + x] += g[1][o][x];
                 terms[8 * r + o][8 * ((r + 1) % 4) + x] += g[3][o][x];
             }
-}
-
-uint8_t gf_256_mul(uint8_t a, uint8_t b) {
-    uint8_t res = 0;
-    for (int i = 0; i < 8; i++) {
-        if (b & 1) res ^= a;
-        const uint8_t high_bit = a & 0x80;
-        a = (uint8_t)(a << 1);
-        if (high_bit != 0x80) a ^= 0x1b;  // sic: aes_128.rs:50
-        b >>= 1;
-    }
-    return res;
-}
-
-void plain_key_schedule(const uint8_t key[16], uint8_t rk[176]) {
-    std::memcpy(rk, key, 16);
-    for (int i = 4; i < 44; i++) {
-        uint8_t t[4];
-        std::memcpy(t, rk + 4 * (i - 1), 4);
-        if (i % 4 == 0) {
-            const uint8_t first = t[0];
-            t[0] = (uint8_t)(kSbox[t[1]] ^ kRcon[i / 4]);
-            t[1] = kSbox[t[2]];
-            t[2] = kSbox[t[3]];
-            t[3] = kSbox[first];
-        }
-        for (int j = 0; j < 4; j++) rk[4 * i + j] = rk[4 * (i - 4) + j] ^ t[j];
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -295,9 +246,9 @@ std::vector<BitCt> Context::circuit_bootstrap(const std::vector<const BitCt *> &
 // ---------------------------------------------------------------------------------------------
 // AES (fhe_sbox_gal_mul_pbs.rs)
 // ---------------------------------------------------------------------------------------------
-// Metadata-only replay of encrypt_block_for_rounds for ONE block: rk [44*32], block [128].
+// Metadata-only replay of encrypt_block_for_rounds for ONE block: rk [4 (nr + 1) * 32], block [128].
 std::vector<NoiseLevel> aes_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &block,
-                                           int rounds, uint64_t max) {
+                                           int rounds, uint64_t max, int nr) {
     auto key_bit = [&](int word, int byte, int bit) -> const NoiseLevel & { return rk[(word * 4 + byte) * 8 + bit]; };
     std::vector<NoiseLevel> st = block;  // index (4*col + row)*8 + bit
     for (int c = 0; c < 4; c++)
@@ -329,7 +280,7 @@ std::vector<NoiseLevel> aes_noise_schedule(const std::vector<NoiseLevel> &rk, co
         for (int r = 0; r < 4; r++)
             for (int b = 0; b < 8; b++) {
                 NoiseLevel v = sb[(4 * ((c + r) % 4) + r) * 8 + b];
-                v.add_assign(key_bit(40 + c, r, b), max);
+                v.add_assign(key_bit(4 * nr + c, r, b), max);
                 st[(4 * c + r) * 8 + b] = std::move(v);
             }
     return st;
@@ -431,7 +382,7 @@ std::vector<NoiseLevel> sbox_pbs_noise_schedule(const std::vector<NoiseLevel> &r
 }
 
 std::vector<NoiseLevel> Context::block_noise_schedule(AesDriver driver, const std::vector<NoiseLevel> &rk,
-                                                      const std::vector<NoiseLevel> &block, int rounds) const {
+                                                      const std::vector<NoiseLevel> &block, int rounds, int nr) const {
     const uint64_t max = params().max_noise_sq;
     // shortint_1bit: XOR is shortint unchecked_add (shortint_1bit.rs:103-116) and SubBytes a fresh
     // bootstrap: nothing is validated, so the round function cannot fail on noise bookkeeping (its
@@ -439,14 +390,35 @@ std::vector<NoiseLevel> Context::block_noise_schedule(AesDriver driver, const st
     if (params().model == 2) return std::vector<NoiseLevel>(128);
     if (params().model == 8) return aes8_noise_schedule(rk, block, rounds, max);
     return driver == AesDriver::SboxPbs ? sbox_pbs_noise_schedule(rk, block, rounds, max)
-                                        : aes_noise_schedule(rk, block, rounds, max);
+                                        : aes_noise_schedule(rk, block, rounds, max, nr);
+}
+
+// key_bits in {128, 192, 256} or TAE_E_PARAM; 192 and 256 on the 1-bit model with the gal-mul driver only (the
+// scope of the inverse cipher).  Returns Nr.
+int Context::require_key_bits(int key_bits, AesDriver driver) const {
+    if (!aes_key_bits_ok(key_bits)) throw ModelError{TAE_E_PARAM, "key_bits must be 128, 192 or 256"};
+    if (key_bits != 128 && (params().model != 1 || driver != AesDriver::GalMul))
+        throw ModelError{TAE_E_PARAM,
+                         "AES-192 and AES-256 run on the 1-bit WoP-PBS parameter sets (gal-mul driver) only"};
+    return aes_nr(key_bits);
+}
+
+static void require_rounds(int rounds, int nr) {
+    if (rounds < 1 || rounds > nr) throw ModelError{TAE_E_PARAM, "rounds must be in 1..=" + std::to_string(nr)};
+}
+
+static void require_key_words(size_t bits, int nr, const char *what) {
+    const int words = 4 * (nr + 1);
+    if (bits != (size_t)words * 32)
+        throw ModelError{TAE_E_ARG, std::string(what) + " must be " + std::to_string(words) + " words (" +
+                                        std::to_string(words * 32) + " bits)"};
 }
 
 // The device round functions.  1-bit model: Engine::aes_encrypt_blocks (fhe_sbox_gal_mul_pbs rounds, its
 // last round = SubBytes 8 -> 8, ShiftRows, AddRoundKey).  The 1-bit fhe_sbox_pbs driver only gets here
 // with rounds == 1 (its schedule raises at the first MixColumns), where it is exactly that last round.
 void Context::run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint64_t *d_in, size_t n_blocks, int rounds,
-                             uint64_t *d_out) {
+                             uint64_t *d_out, int nr) {
     if (params().model == 8) {
         engine_->aes8_encrypt_blocks(d_rk, d_in, n_blocks, rounds, d_out);
         return;
@@ -457,33 +429,35 @@ void Context::run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint6
     }
     if (driver == AesDriver::SboxPbs && rounds != 1)
         throw ModelError{TAE_E_INDEP, "noise components not independent"};
-    engine_->aes_encrypt_blocks(d_rk, d_in, n_blocks, rounds, d_out);
+    engine_->aes_encrypt_blocks(d_rk, d_in, n_blocks, rounds, d_out, nr);
 }
 
 void Context::aes_encrypt_blocks_raw(const uint64_t *rk, const uint64_t *blocks, size_t n_blocks, int rounds,
-                                     uint64_t *out, bool device_mem, AesDriver driver) {
-    if (rounds < 1 || rounds > kAesRounds) throw ModelError{TAE_E_PARAM, "rounds must be in 1..=10"};
+                                     uint64_t *out, bool device_mem, AesDriver driver, int key_bits) {
+    const int nr = require_key_bits(key_bits, driver);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;  // ciphertexts of the expanded key
+    require_rounds(rounds, nr);
     {
         // static validation of the fixed noise schedule for fresh inputs (noise^2 = 1, own ids)
-        std::vector<NoiseLevel> krk(44 * 32), kbl(128);
+        std::vector<NoiseLevel> krk(kw), kbl(128);
         for (auto &x : krk) x = params().model != 1 ? NoiseLevel{1, {}} : NoiseLevel::with_noise_level(1, next_ct_id());
         for (auto &x : kbl) x = params().model != 1 ? NoiseLevel{1, {}} : NoiseLevel::with_noise_level(1, next_ct_id());
-        block_noise_schedule(driver, krk, kbl, rounds);
+        block_noise_schedule(driver, krk, kbl, rounds, nr);
     }
     const size_t S = bit_len();
     std::lock_guard<std::mutex> g(mu_);
     hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
     if (device_mem) {
         engine_->order_after_caller();
-        run_aes_blocks(driver, rk, blocks, n_blocks, rounds, out);
+        run_aes_blocks(driver, rk, blocks, n_blocks, rounds, out, nr);
         engine_->synchronize();
         return;
     }
-    DevBuf d_rk(44 * 32 * S * 8), d_in(n_blocks * 128 * S * 8), d_out(n_blocks * 128 * S * 8);
-    hip_check(hipMemcpyAsync(d_rk.p, rk, 44 * 32 * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload rk");
+    DevBuf d_rk(kw * S * 8), d_in(n_blocks * 128 * S * 8), d_out(n_blocks * 128 * S * 8);
+    hip_check(hipMemcpyAsync(d_rk.p, rk, kw * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload rk");
     hip_check(hipMemcpyAsync(d_in.p, blocks, n_blocks * 128 * S * 8, hipMemcpyHostToDevice, engine_->stream()),
               "upload blocks");
-    run_aes_blocks(driver, d_rk.as<uint64_t>(), d_in.as<uint64_t>(), n_blocks, rounds, d_out.as<uint64_t>());
+    run_aes_blocks(driver, d_rk.as<uint64_t>(), d_in.as<uint64_t>(), n_blocks, rounds, d_out.as<uint64_t>(), nr);
     hip_check(hipMemcpyAsync(out, d_out.p, n_blocks * 128 * S * 8, hipMemcpyDeviceToHost, engine_->stream()),
               "download");
     engine_->synchronize();
@@ -491,25 +465,27 @@ void Context::aes_encrypt_blocks_raw(const uint64_t *rk, const uint64_t *blocks,
 
 std::vector<BitCt> Context::aes_encrypt_blocks(const std::vector<const BitCt *> &expanded_key,
                                                const std::vector<const BitCt *> &blocks, size_t n_blocks,
-                                               int rounds, AesDriver driver) {
-    if (expanded_key.size() != 44 * 32) throw ModelError{TAE_E_ARG, "expanded key must be 44 words (1408 bits)"};
+                                               int rounds, AesDriver driver, int key_bits) {
+    const int nr = require_key_bits(key_bits, driver);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    require_key_words(expanded_key.size(), nr, "expanded key");
     if (blocks.size() != n_blocks * 128) throw ModelError{TAE_E_ARG, "blocks must be 128 bits each"};
-    if (rounds < 1 || rounds > kAesRounds) throw ModelError{TAE_E_PARAM, "rounds must be in 1..=10"};
+    require_rounds(rounds, nr);
     const size_t L = bit_len();
     for (const BitCt *b : expanded_key)
         if (b->ct.size() != L) throw ModelError{TAE_E_ARG, "ciphertext size mismatch"};
     for (const BitCt *b : blocks)
         if (b->ct.size() != L) throw ModelError{TAE_E_ARG, "ciphertext size mismatch"};
-    std::vector<NoiseLevel> krk(44 * 32);
+    std::vector<NoiseLevel> krk(kw);
     for (size_t i = 0; i < krk.size(); i++) krk[i] = expanded_key[i]->noise;
     std::vector<std::vector<NoiseLevel>> out_noise(n_blocks);
     for (size_t blk = 0; blk < n_blocks; blk++) {
         std::vector<NoiseLevel> kb(128);
         for (int i = 0; i < 128; i++) kb[i] = blocks[blk * 128 + i]->noise;
-        out_noise[blk] = block_noise_schedule(driver, krk, kb, rounds);
+        out_noise[blk] = block_noise_schedule(driver, krk, kb, rounds, nr);
     }
-    std::vector<uint64_t> rk(44 * 32 * L), in(n_blocks * 128 * L), out(n_blocks * 128 * L);
-    for (size_t i = 0; i < 44 * 32; i++) std::memcpy(&rk[i * L], expanded_key[i]->ct.data(), L * 8);
+    std::vector<uint64_t> rk(kw * L), in(n_blocks * 128 * L), out(n_blocks * 128 * L);
+    for (size_t i = 0; i < kw; i++) std::memcpy(&rk[i * L], expanded_key[i]->ct.data(), L * 8);
     for (size_t i = 0; i < n_blocks * 128; i++) std::memcpy(&in[i * L], blocks[i]->ct.data(), L * 8);
     {
         std::lock_guard<std::mutex> g(mu_);
@@ -517,7 +493,7 @@ std::vector<BitCt> Context::aes_encrypt_blocks(const std::vector<const BitCt *> 
         DevBuf d_rk(rk.size() * 8), d_in(in.size() * 8), d_out(out.size() * 8);
         hip_check(hipMemcpyAsync(d_rk.p, rk.data(), rk.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
         hip_check(hipMemcpyAsync(d_in.p, in.data(), in.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
-        run_aes_blocks(driver, d_rk.as<uint64_t>(), d_in.as<uint64_t>(), n_blocks, rounds, d_out.as<uint64_t>());
+        run_aes_blocks(driver, d_rk.as<uint64_t>(), d_in.as<uint64_t>(), n_blocks, rounds, d_out.as<uint64_t>(), nr);
         hip_check(hipMemcpyAsync(out.data(), d_out.p, out.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
         engine_->synchronize();
     }
@@ -534,15 +510,15 @@ std::vector<BitCt> Context::aes_encrypt_blocks(const std::vector<const BitCt *> 
 // AES-128-CTR with public counters (main.rs:108-128)
 // ---------------------------------------------------------------------------------------------
 std::vector<std::vector<NoiseLevel>> aes_ctr_noise_schedule(const std::vector<NoiseLevel> &rk, const CtrPlan &plan,
-                                                            size_t n_blocks, int rounds, uint64_t max) {
+                                                            size_t n_blocks, int rounds, uint64_t max, int nr) {
     const std::vector<NoiseLevel> triv(128, NoiseLevel::trivial());
     std::vector<std::vector<NoiseLevel>> out(n_blocks);
     if (rounds != 1) {
-        for (auto &o : out) o = aes_noise_schedule(rk, triv, rounds, max);
+        for (auto &o : out) o = aes_noise_schedule(rk, triv, rounds, max, nr);
         return out;
     }
     // one round: ARK(rk0) on trivial bits, SubBytes 8 -> 8 of every group (noise^2 = 8, one id per output
-    // bit of a GROUP), ShiftRows, ARK(rk10)
+    // bit of a GROUP), ShiftRows, ARK(the last round key)
     std::vector<NoiseLevel> sb(plan.groups.size() * 8);
     for (auto &x : sb) x = NoiseLevel::with_noise_level(8, next_ct_id());
     for (size_t blk = 0; blk < n_blocks; blk++) {
@@ -551,7 +527,7 @@ std::vector<std::vector<NoiseLevel>> aes_ctr_noise_schedule(const std::vector<No
             for (int r = 0; r < 4; r++)
                 for (int b = 0; b < 8; b++) {
                     NoiseLevel v = sb[(size_t)plan.map[blk * 16 + 4 * ((c + r) % 4) + r] * 8 + b];
-                    v.add_assign(rk[((40 + c) * 4 + r) * 8 + b], max);
+                    v.add_assign(rk[((4 * nr + c) * 4 + r) * 8 + b], max);
                     out[blk][(4 * c + r) * 8 + b] = std::move(v);
                 }
     }
@@ -559,19 +535,21 @@ std::vector<std::vector<NoiseLevel>> aes_ctr_noise_schedule(const std::vector<No
 }
 
 // argument checks and the static noise validation, before any device work
-void Context::check_ctr(uint64_t first_counter, size_t n_blocks, int rounds) const {
+int Context::check_ctr(uint64_t first_counter, size_t n_blocks, int rounds, int key_bits) const {
     if (params().model == 2)
         throw ModelError{TAE_E_PARAM, "counter mode is not available for the shortint_1bit parameter set"};
-    if (rounds < 1 || rounds > kAesRounds) throw ModelError{TAE_E_PARAM, "rounds must be in 1..=10"};
+    const int nr = require_key_bits(key_bits, AesDriver::GalMul);
+    require_rounds(rounds, nr);
     if (!ctr_range_ok(first_counter, n_blocks)) throw ModelError{TAE_E_ARG, "counter range wraps past 2^64 - 1"};
-    std::vector<NoiseLevel> krk(44 * 32), kbl(128, NoiseLevel::trivial());
+    std::vector<NoiseLevel> krk((size_t)aes_words(key_bits) * 32), kbl(128, NoiseLevel::trivial());
     for (auto &x : krk) x = params().model != 1 ? NoiseLevel{1, {}} : NoiseLevel::with_noise_level(1, next_ct_id());
-    block_noise_schedule(AesDriver::GalMul, krk, kbl, rounds);
+    block_noise_schedule(AesDriver::GalMul, krk, kbl, rounds, nr);
+    return nr;
 }
 
 void Context::run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
-                          const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem) {
-    const size_t S = bit_len();
+                          const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem, int nr) {
+    const size_t S = bit_len(), kw = (size_t)4 * (nr + 1) * 32;
     std::lock_guard<std::mutex> g(mu_);
     hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
     DevBuf d_data(data ? out_bytes : 0);  // the public bytes are a host array, always
@@ -580,55 +558,59 @@ void Context::run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t firs
     const uint8_t *dd = data ? d_data.as<uint8_t>() : nullptr;
     if (device_mem) {
         engine_->order_after_caller();
-        engine_->aes_ctr(rk, iv, first_counter, n_blocks, rounds, dd, out_bytes, out);
+        engine_->aes_ctr(rk, iv, first_counter, n_blocks, rounds, dd, out_bytes, out, nr);
         engine_->synchronize();
         return;
     }
-    DevBuf d_rk(44 * 32 * S * 8), d_out(out_bytes * 8 * S * 8);
-    hip_check(hipMemcpyAsync(d_rk.p, rk, 44 * 32 * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload rk");
-    engine_->aes_ctr(d_rk.as<uint64_t>(), iv, first_counter, n_blocks, rounds, dd, out_bytes, d_out.as<uint64_t>());
+    DevBuf d_rk(kw * S * 8), d_out(out_bytes * 8 * S * 8);
+    hip_check(hipMemcpyAsync(d_rk.p, rk, kw * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload rk");
+    engine_->aes_ctr(d_rk.as<uint64_t>(), iv, first_counter, n_blocks, rounds, dd, out_bytes, d_out.as<uint64_t>(), nr);
     hip_check(hipMemcpyAsync(out, d_out.p, out_bytes * 8 * S * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
     engine_->synchronize();
 }
 
 void Context::aes_ctr_keystream_raw(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks,
-                                    int rounds, uint64_t *out, bool device_mem) {
-    check_ctr(first_counter, n_blocks, rounds);
+                                    int rounds, uint64_t *out, bool device_mem, int key_bits) {
+    const int nr = check_ctr(first_counter, n_blocks, rounds, key_bits);
     if (!n_blocks) return;
-    run_aes_ctr(rk, iv, first_counter, n_blocks, rounds, nullptr, n_blocks * 16, out, device_mem);
+    run_aes_ctr(rk, iv, first_counter, n_blocks, rounds, nullptr, n_blocks * 16, out, device_mem, nr);
 }
 
 void Context::aes_ctr_transcipher_raw(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter,
-                                      const uint8_t *data, size_t len, int rounds, uint64_t *out, bool device_mem) {
+                                      const uint8_t *data, size_t len, int rounds, uint64_t *out, bool device_mem,
+                                      int key_bits) {
     const size_t n_blocks = len / 16 + (len % 16 != 0);
-    check_ctr(first_counter, n_blocks, rounds);
+    const int nr = check_ctr(first_counter, n_blocks, rounds, key_bits);
     if (!len) return;
-    run_aes_ctr(rk, iv, first_counter, n_blocks, rounds, data, len, out, device_mem);
+    run_aes_ctr(rk, iv, first_counter, n_blocks, rounds, data, len, out, device_mem, nr);
 }
 
 std::vector<BitCt> Context::aes_ctr_transcipher(const std::vector<const BitCt *> &expanded_key, const uint8_t iv[8],
-                                                uint64_t first_counter, const uint8_t *data, size_t len, int rounds) {
-    if (expanded_key.size() != 44 * 32) throw ModelError{TAE_E_ARG, "expanded key must be 44 words (1408 bits)"};
+                                                uint64_t first_counter, const uint8_t *data, size_t len, int rounds,
+                                                int key_bits) {
+    require_key_bits(key_bits, AesDriver::GalMul);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    require_key_words(expanded_key.size(), aes_nr(key_bits), "expanded key");
     const size_t L = bit_len();
     for (const BitCt *b : expanded_key)
         if (b->ct.size() != L) throw ModelError{TAE_E_ARG, "ciphertext size mismatch"};
     const size_t n_blocks = len / 16 + (len % 16 != 0);
-    check_ctr(first_counter, n_blocks, rounds);
+    const int nr = check_ctr(first_counter, n_blocks, rounds, key_bits);
     if (!len) return {};
-    std::vector<NoiseLevel> krk(44 * 32);
+    std::vector<NoiseLevel> krk(kw);
     for (size_t i = 0; i < krk.size(); i++) krk[i] = expanded_key[i]->noise;
     std::vector<std::vector<NoiseLevel>> out_noise(n_blocks);
     if (params().model == 1) {
         CtrPlan plan;
         ctr_plan(iv, first_counter, n_blocks, plan);
-        out_noise = aes_ctr_noise_schedule(krk, plan, n_blocks, rounds, params().max_noise_sq);
+        out_noise = aes_ctr_noise_schedule(krk, plan, n_blocks, rounds, params().max_noise_sq, nr);
     } else {
         const std::vector<NoiseLevel> triv(128, NoiseLevel::trivial());
-        for (auto &o : out_noise) o = block_noise_schedule(AesDriver::GalMul, krk, triv, rounds);
+        for (auto &o : out_noise) o = block_noise_schedule(AesDriver::GalMul, krk, triv, rounds, nr);
     }
-    std::vector<uint64_t> rk(44 * 32 * L), out(len * 8 * L);
-    for (size_t i = 0; i < 44 * 32; i++) std::memcpy(&rk[i * L], expanded_key[i]->ct.data(), L * 8);
-    run_aes_ctr(rk.data(), iv, first_counter, n_blocks, rounds, data, len, out.data(), false);
+    std::vector<uint64_t> rk(kw * L), out(len * 8 * L);
+    for (size_t i = 0; i < kw; i++) std::memcpy(&rk[i * L], expanded_key[i]->ct.data(), L * 8);
+    run_aes_ctr(rk.data(), iv, first_counter, n_blocks, rounds, data, len, out.data(), false, nr);
     std::vector<BitCt> res(len * 8);
     for (size_t i = 0; i < res.size(); i++) {
         res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
@@ -641,14 +623,14 @@ std::vector<BitCt> Context::aes_ctr_transcipher(const std::vector<const BitCt *>
 // ---------------------------------------------------------------------------------------------
 // AES-128 inverse cipher (FIPS-197 5.3; aes_inv.hpp).  The reference has no decryption.
 // ---------------------------------------------------------------------------------------------
-// Metadata-only replay of decrypt_block_for_rounds for ONE block: dk [44*32], block [128].
+// Metadata-only replay of decrypt_block_for_rounds for ONE block: dk [4 (nr + 1) * 32], block [128].
 std::vector<NoiseLevel> aes_decrypt_noise_schedule(const std::vector<NoiseLevel> &dk, const std::vector<NoiseLevel> &block,
-                                                   int rounds, uint64_t max) {
+                                                   int rounds, uint64_t max, int nr) {
     auto key_bit = [&](int word, int byte, int bit) -> const NoiseLevel & { return dk[(word * 4 + byte) * 8 + bit]; };
     std::vector<NoiseLevel> st = block;  // index (4*col + row)*8 + bit
     for (int c = 0; c < 4; c++)
         for (int r = 0; r < 4; r++)
-            for (int b = 0; b < 8; b++) st[(4 * c + r) * 8 + b].add_assign(key_bit(40 + c, r, b), max);
+            for (int b = 0; b < 8; b++) st[(4 * c + r) * 8 + b].add_assign(key_bit(4 * nr + c, r, b), max);
     auto cbs_outputs = [&](int n_out) {
         std::vector<NoiseLevel> o((size_t)16 * n_out);
         for (auto &x : o) x = NoiseLevel::with_noise_level(8, next_ct_id());
@@ -676,13 +658,13 @@ std::vector<NoiseLevel> aes_decrypt_noise_schedule(const std::vector<NoiseLevel>
     return st;
 }
 
-// The decryption-key derivation on metadata: words 0..3 and 40..43 keep the expanded key's levels; every bit
-// of words 4..39 is a 4-term sum of fresh 8 -> 32 outputs (noise^2 = 32, validated), then bootstrapped.
-std::vector<NoiseLevel> aes_decrypt_key_noise_schedule(const std::vector<NoiseLevel> &rk, uint64_t max) {
+// The decryption-key derivation on metadata: words 0..3 and 4 nr .. 4 nr + 3 keep the expanded key's levels; every
+// bit of words 4 .. 4 nr - 1 is a 4-term sum of fresh 8 -> 32 outputs (noise^2 = 32, validated), then bootstrapped.
+std::vector<NoiseLevel> aes_decrypt_key_noise_schedule(const std::vector<NoiseLevel> &rk, uint64_t max, int nr) {
     std::vector<NoiseLevel> dk = rk;
-    std::vector<NoiseLevel> muls((size_t)144 * 32);
+    std::vector<NoiseLevel> muls((size_t)16 * (nr - 1) * 32);
     for (auto &x : muls) x = NoiseLevel::with_noise_level(8, next_ct_id());
-    for (int w = 4; w < 40; w++)
+    for (int w = 4; w < 4 * nr; w++)
         for (int r = 0; r < 4; r++)
             for (int b = 0; b < 8; b++) {
                 const int blk = w / 4 - 1, c = w % 4;
@@ -694,10 +676,13 @@ std::vector<NoiseLevel> aes_decrypt_key_noise_schedule(const std::vector<NoiseLe
     return dk;
 }
 
-void Context::require_inverse(int rounds) const {
+// rounds < 0: the full round count of the key size.  Returns Nr.
+int Context::require_inverse(int rounds, int key_bits) const {
     if (params().model != 1)
         throw ModelError{TAE_E_PARAM, "the inverse cipher runs on the 1-bit WoP-PBS parameter sets (gal-mul driver) only"};
-    if (rounds < 1 || rounds > kAesRounds) throw ModelError{TAE_E_PARAM, "rounds must be in 1..=10"};
+    const int nr = require_key_bits(key_bits, AesDriver::GalMul);
+    if (rounds >= 0) require_rounds(rounds, nr);
+    return nr;
 }
 
 static std::vector<NoiseLevel> fresh_levels(size_t n) {
@@ -715,10 +700,11 @@ static std::vector<uint64_t> gather_bits(const std::vector<const BitCt *> &bits,
     return a;
 }
 
-// host or device arrays through the engine: in (in_len words, may be null), fixed (1408 key words), out
+// host or device arrays through the engine: in (in_len words, may be null), the key (key_cts ciphertexts), out
 void Context::run_inverse(const uint64_t *key, const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes,
                           uint64_t *out, size_t out_len, bool device_mem,
-                          const std::function<void(const uint64_t *, const uint64_t *, const uint8_t *, uint64_t *)> &fn) {
+                          const std::function<void(const uint64_t *, const uint64_t *, const uint8_t *, uint64_t *)> &fn,
+                          size_t key_cts) {
     const size_t S = bit_len();
     std::lock_guard<std::mutex> g(mu_);
     hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
@@ -731,34 +717,38 @@ void Context::run_inverse(const uint64_t *key, const uint64_t *in, size_t in_len
         engine_->synchronize();
         return;
     }
-    DevBuf d_key(44 * 32 * S * 8), d_in(in_len * 8), d_out(out_len * 8);
-    hip_check(hipMemcpyAsync(d_key.p, key, 44 * 32 * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
+    DevBuf d_key(key_cts * S * 8), d_in(in_len * 8), d_out(out_len * 8);
+    hip_check(hipMemcpyAsync(d_key.p, key, key_cts * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
     if (in_len) hip_check(hipMemcpyAsync(d_in.p, in, in_len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload");
     fn(d_key.as<uint64_t>(), d_in.as<uint64_t>(), d_bytes.as<uint8_t>(), d_out.as<uint64_t>());
     hip_check(hipMemcpyAsync(out, d_out.p, out_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
     engine_->synchronize();
 }
 
-void Context::aes_decrypt_key_raw(const uint64_t *rk, uint64_t *dk, bool device_mem) {
-    require_inverse(kAesRounds);
-    aes_decrypt_key_noise_schedule(fresh_levels(44 * 32), params().max_noise_sq);
+void Context::aes_decrypt_key_raw(const uint64_t *rk, uint64_t *dk, bool device_mem, int key_bits) {
+    const int nr = require_inverse(-1, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    aes_decrypt_key_noise_schedule(fresh_levels(kw), params().max_noise_sq, nr);
     if (device_mem && rk == dk) throw ModelError{TAE_E_ARG, "the decryption key cannot be derived in place"};
-    run_inverse(rk, nullptr, 0, nullptr, 0, dk, 44 * 32 * bit_len(), device_mem,
-                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) { engine_->aes_decrypt_key(k, o); });
+    run_inverse(rk, nullptr, 0, nullptr, 0, dk, kw * bit_len(), device_mem,
+                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) { engine_->aes_decrypt_key(k, o, nr); },
+                kw);
 }
 
-std::vector<BitCt> Context::aes_decrypt_key(const std::vector<const BitCt *> &expanded_key) {
-    require_inverse(kAesRounds);
-    if (expanded_key.size() != 44 * 32) throw ModelError{TAE_E_ARG, "expanded key must be 44 words (1408 bits)"};
+std::vector<BitCt> Context::aes_decrypt_key(const std::vector<const BitCt *> &expanded_key, int key_bits) {
+    const int nr = require_inverse(-1, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    require_key_words(expanded_key.size(), nr, "expanded key");
     const size_t L = bit_len();
     const std::vector<uint64_t> rk = gather_bits(expanded_key, L);
-    std::vector<NoiseLevel> krk(44 * 32);
+    std::vector<NoiseLevel> krk(kw);
     for (size_t i = 0; i < krk.size(); i++) krk[i] = expanded_key[i]->noise;
-    const std::vector<NoiseLevel> kdk = aes_decrypt_key_noise_schedule(krk, params().max_noise_sq);
+    const std::vector<NoiseLevel> kdk = aes_decrypt_key_noise_schedule(krk, params().max_noise_sq, nr);
     std::vector<uint64_t> dk(rk.size());
     run_inverse(rk.data(), nullptr, 0, nullptr, 0, dk.data(), dk.size(), false,
-                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) { engine_->aes_decrypt_key(k, o); });
-    std::vector<BitCt> res(44 * 32);
+                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) { engine_->aes_decrypt_key(k, o, nr); },
+                kw);
+    std::vector<BitCt> res(kw);
     for (size_t i = 0; i < res.size(); i++) {
         res[i].ct.assign(dk.begin() + i * L, dk.begin() + (i + 1) * L);
         res[i].noise = kdk[i];
@@ -768,39 +758,44 @@ std::vector<BitCt> Context::aes_decrypt_key(const std::vector<const BitCt *> &ex
 }
 
 void Context::aes_decrypt_blocks_raw(const uint64_t *dk, const uint64_t *blocks, size_t n_blocks, int rounds,
-                                     uint64_t *out, bool device_mem) {
-    require_inverse(rounds);
+                                     uint64_t *out, bool device_mem, int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
     // static validation of the fixed schedule for a derived key and fresh blocks (noise^2 = 1, own ids)
-    aes_decrypt_noise_schedule(fresh_levels(44 * 32), fresh_levels(128), rounds, params().max_noise_sq);
+    aes_decrypt_noise_schedule(fresh_levels(kw), fresh_levels(128), rounds, params().max_noise_sq, nr);
     if (!n_blocks) return;
     const size_t len = n_blocks * 128 * bit_len();
     run_inverse(dk, blocks, len, nullptr, 0, out, len, device_mem,
                 [&](const uint64_t *k, const uint64_t *i, const uint8_t *, uint64_t *o) {
-                    engine_->aes_decrypt_blocks(k, i, n_blocks, rounds, o);
-                });
+                    engine_->aes_decrypt_blocks(k, i, n_blocks, rounds, o, nr);
+                },
+                kw);
 }
 
 std::vector<BitCt> Context::aes_decrypt_blocks(const std::vector<const BitCt *> &dk,
-                                               const std::vector<const BitCt *> &blocks, size_t n_blocks, int rounds) {
-    require_inverse(rounds);
-    if (dk.size() != 44 * 32) throw ModelError{TAE_E_ARG, "decryption key must be 44 words (1408 bits)"};
+                                               const std::vector<const BitCt *> &blocks, size_t n_blocks, int rounds,
+                                               int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    require_key_words(dk.size(), nr, "decryption key");
     if (blocks.size() != n_blocks * 128) throw ModelError{TAE_E_ARG, "blocks must be 128 bits each"};
     const size_t L = bit_len();
     const std::vector<uint64_t> key = gather_bits(dk, L), in = gather_bits(blocks, L);
-    std::vector<NoiseLevel> kdk(44 * 32);
+    std::vector<NoiseLevel> kdk(kw);
     for (size_t i = 0; i < kdk.size(); i++) kdk[i] = dk[i]->noise;
     std::vector<std::vector<NoiseLevel>> out_noise(n_blocks);
     for (size_t blk = 0; blk < n_blocks; blk++) {
         std::vector<NoiseLevel> kb(128);
         for (int i = 0; i < 128; i++) kb[i] = blocks[blk * 128 + i]->noise;
-        out_noise[blk] = aes_decrypt_noise_schedule(kdk, kb, rounds, params().max_noise_sq);
+        out_noise[blk] = aes_decrypt_noise_schedule(kdk, kb, rounds, params().max_noise_sq, nr);
     }
     std::vector<uint64_t> out(in.size());
     if (n_blocks)
         run_inverse(key.data(), in.data(), in.size(), nullptr, 0, out.data(), out.size(), false,
                     [&](const uint64_t *k, const uint64_t *i, const uint8_t *, uint64_t *o) {
-                        engine_->aes_decrypt_blocks(k, i, n_blocks, rounds, o);
-                    });
+                        engine_->aes_decrypt_blocks(k, i, n_blocks, rounds, o, nr);
+                    },
+                    kw);
     std::vector<BitCt> res(n_blocks * 128);
     for (size_t i = 0; i < res.size(); i++) {
         res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
@@ -820,38 +815,42 @@ static std::vector<uint8_t> cbc_public_bytes(const uint8_t iv[16], const uint8_t
 }
 
 void Context::aes_cbc_transcipher_raw(const uint64_t *dk, const uint8_t iv[16], const uint8_t *data, size_t len,
-                                      int rounds, uint64_t *out, bool device_mem) {
-    require_inverse(rounds);
+                                      int rounds, uint64_t *out, bool device_mem, int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
     const std::vector<uint8_t> pub = cbc_public_bytes(iv, data, len);
-    aes_decrypt_noise_schedule(fresh_levels(44 * 32), std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds,
-                               params().max_noise_sq);
+    aes_decrypt_noise_schedule(fresh_levels(kw), std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds,
+                               params().max_noise_sq, nr);
     if (!len) return;
     const size_t n_blocks = len / 16;
     run_inverse(dk, nullptr, 0, pub.data(), pub.size(), out, len * 8 * bit_len(), device_mem,
                 [&](const uint64_t *k, const uint64_t *, const uint8_t *b, uint64_t *o) {
-                    engine_->aes_cbc_transcipher(k, b, n_blocks, rounds, o);
-                });
+                    engine_->aes_cbc_transcipher(k, b, n_blocks, rounds, o, nr);
+                },
+                kw);
 }
 
 std::vector<BitCt> Context::aes_cbc_transcipher(const std::vector<const BitCt *> &dk, const uint8_t iv[16],
-                                                const uint8_t *data, size_t len, int rounds) {
-    require_inverse(rounds);
-    if (dk.size() != 44 * 32) throw ModelError{TAE_E_ARG, "decryption key must be 44 words (1408 bits)"};
+                                                const uint8_t *data, size_t len, int rounds, int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    require_key_words(dk.size(), nr, "decryption key");
     const size_t L = bit_len();
     const std::vector<uint64_t> key = gather_bits(dk, L);
     const std::vector<uint8_t> pub = cbc_public_bytes(iv, data, len);
-    std::vector<NoiseLevel> kdk(44 * 32);
+    std::vector<NoiseLevel> kdk(kw);
     for (size_t i = 0; i < kdk.size(); i++) kdk[i] = dk[i]->noise;
     const size_t n_blocks = len / 16;
     const std::vector<NoiseLevel> triv(128, NoiseLevel::trivial());
     std::vector<std::vector<NoiseLevel>> out_noise(n_blocks);
-    for (auto &o : out_noise) o = aes_decrypt_noise_schedule(kdk, triv, rounds, params().max_noise_sq);
+    for (auto &o : out_noise) o = aes_decrypt_noise_schedule(kdk, triv, rounds, params().max_noise_sq, nr);
     if (!len) return {};
     std::vector<uint64_t> out(len * 8 * L);
     run_inverse(key.data(), nullptr, 0, pub.data(), pub.size(), out.data(), out.size(), false,
                 [&](const uint64_t *k, const uint64_t *, const uint8_t *b, uint64_t *o) {
-                    engine_->aes_cbc_transcipher(k, b, n_blocks, rounds, o);
-                });
+                    engine_->aes_cbc_transcipher(k, b, n_blocks, rounds, o, nr);
+                },
+                kw);
     std::vector<BitCt> res(len * 8);
     for (size_t i = 0; i < res.size(); i++) {
         res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
@@ -1054,6 +1053,84 @@ void Context::aes_key_schedule_raw(const uint64_t *key, uint64_t *expanded, bool
         engine_->synchronize();
     } else
         std::memcpy(expanded, he.data(), he.size() * 8);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Key expansion on the device for 128 / 192 / 256-bit keys (FIPS-197 5.2, figure 11; Engine::aes_key_expand)
+// ---------------------------------------------------------------------------------------------
+// The expansion on metadata: key [nk*32] -> rk [4 (nk + 7) * 32].  Words below nk keep the key's levels and ids.
+// The word before its bootstrap is rk[i-nk] + a fresh SubWord output (noise^2 = 8) on SubWord steps and
+// rk[i-nk] + rk[i-1] otherwise (Rcon is trivial), validated; every word from nk on leaves the identity bootstrap
+// at noise^2 = 1 with fresh ids.
+std::vector<NoiseLevel> aes_key_expand_noise_schedule(const std::vector<NoiseLevel> &key, int nk, uint64_t max) {
+    const int words = 4 * (nk + 7);
+    std::vector<NoiseLevel> rk((size_t)words * 32);
+    std::copy(key.begin(), key.end(), rk.begin());
+    for (int i = nk; i < words; i++) {
+        const bool sub = i % nk == 0 || (nk == 8 && i % 8 == 4);
+        for (int t = 0; t < 32; t++) {
+            NoiseLevel v = rk[(size_t)(i - nk) * 32 + t];
+            v.add_assign(sub ? NoiseLevel::with_noise_level(8, next_ct_id()) : rk[(size_t)(i - 1) * 32 + t], max);
+        }
+        for (int t = 0; t < 32; t++) rk[(size_t)i * 32 + t] = NoiseLevel::with_noise_level(1, next_ct_id());
+    }
+    return rk;
+}
+
+// the scope of the device key expansion; returns Nk
+int Context::require_key_expand(int key_bits) const {
+    if (!aes_key_bits_ok(key_bits)) throw ModelError{TAE_E_PARAM, "key_bits must be 128, 192 or 256"};
+    if (params().model != 1)
+        throw ModelError{TAE_E_PARAM,
+                         "the device key expansion runs on the 1-bit WoP-PBS parameter sets (gal-mul driver) only"};
+    return aes_nk(key_bits);
+}
+
+void Context::aes_key_expand_raw(const uint64_t *key, uint64_t *expanded, bool device_mem, int key_bits) {
+    const int nk = require_key_expand(key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
+    aes_key_expand_noise_schedule(fresh_levels((size_t)nk * 32), nk, params().max_noise_sq);
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    if (device_mem) {
+        engine_->order_after_caller();
+        engine_->aes_key_expand(key, nk, expanded);
+        engine_->synchronize();
+        return;
+    }
+    DevBuf d_rk(kw * L * 8);  // the key is uploaded into its place, words 0 .. nk - 1
+    hip_check(hipMemcpyAsync(d_rk.p, key, (size_t)nk * 32 * L * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
+    engine_->aes_key_expand(d_rk.as<uint64_t>(), nk, d_rk.as<uint64_t>());
+    hip_check(hipMemcpyAsync(expanded, d_rk.p, kw * L * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+std::vector<BitCt> Context::aes_key_expand(const std::vector<const BitCt *> &key, int key_bits) {
+    const int nk = require_key_expand(key_bits);
+    if (key.size() != (size_t)nk * 32)
+        throw ModelError{TAE_E_ARG, "key must be " + std::to_string(4 * nk) + " bytes (" + std::to_string(32 * nk) + " bits)"};
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
+    const std::vector<uint64_t> hk = gather_bits(key, L);
+    std::vector<NoiseLevel> kn(key.size());
+    for (size_t i = 0; i < kn.size(); i++) kn[i] = key[i]->noise;
+    const std::vector<NoiseLevel> krk = aes_key_expand_noise_schedule(kn, nk, params().max_noise_sq);
+    std::vector<uint64_t> rk(kw * L);
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+        DevBuf d_rk(rk.size() * 8);
+        hip_check(hipMemcpyAsync(d_rk.p, hk.data(), hk.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
+        engine_->aes_key_expand(d_rk.as<uint64_t>(), nk, d_rk.as<uint64_t>());
+        hip_check(hipMemcpyAsync(rk.data(), d_rk.p, rk.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
+        engine_->synchronize();
+    }
+    std::vector<BitCt> res(kw);
+    for (size_t i = 0; i < res.size(); i++) {
+        res[i].ct.assign(rk.begin() + i * L, rk.begin() + (i + 1) * L);
+        res[i].noise = krk[i];
+        res[i].max_noise_sq = params().max_noise_sq;
+    }
+    return res;
 }
 
 

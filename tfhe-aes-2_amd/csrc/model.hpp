@@ -79,17 +79,26 @@ class Context {  // FheContext
     // GalMul = fhe_sbox_gal_mul_pbs (ShortintWoppbs1BitSboxGalMulPbsAesEncrypt); SboxPbs = fhe_sbox_pbs
     // (ShortintWoppbs1BitSboxPbsAesEncrypt on the 1-bit model).  The 8-bit model has fhe_sbox_pbs only
     // (ShortintWoppbs8BitSboxPbsAesEncrypt) and ignores the flag.
+    // key_bits (here and below) = 128 / 192 / 256, anything else is TAE_E_PARAM: the key has W = 44 / 52 / 60
+    // words (another size is TAE_E_ARG) and rounds goes up to Nr = 10 / 12 / 14.  192 and 256 run on the 1-bit
+    // model with the gal-mul driver only (TAE_E_PARAM elsewhere).
     std::vector<BitCt> aes_encrypt_blocks(const std::vector<const BitCt *> &expanded_key,
                                           const std::vector<const BitCt *> &blocks, size_t n_blocks, int rounds,
-                                          AesDriver driver = AesDriver::GalMul);
+                                          AesDriver driver = AesDriver::GalMul, int key_bits = 128);
     // key_schedule: fhe_sbox_gal_mul_pbs (:134-164) or fhe_sbox_pbs (:123-171)
     std::vector<BitCt> aes_key_schedule(const std::vector<const BitCt *> &key, AesDriver driver = AesDriver::GalMul);
     // raw arrays, fresh inputs; static noise-schedule validation
     void aes_encrypt_blocks_raw(const uint64_t *rk, const uint64_t *blocks, size_t n_blocks, int rounds,
-                                uint64_t *out, bool device_mem, AesDriver driver = AesDriver::GalMul);
+                                uint64_t *out, bool device_mem, AesDriver driver = AesDriver::GalMul, int key_bits = 128);
     // raw key schedule: key [128][bit_len] fresh bits -> [44*32][bit_len]
     void aes_key_schedule_raw(const uint64_t *key, uint64_t *expanded, bool device_mem,
                               AesDriver driver = AesDriver::GalMul);
+    // FIPS-197 5.2 key expansion on the device (Engine::aes_key_expand), 1-bit model only: key [Nk*32] ->
+    // [W*32].  Words below Nk are the key's bits; every later word leaves its identity bootstrap at noise^2 = 1
+    // with fresh ids.  At 128 bits the words equal aes_key_schedule's.  The BitCt variant replays the
+    // bookkeeping (aes_key_expand_noise_schedule) before any device work, the raw one for a fresh key.
+    std::vector<BitCt> aes_key_expand(const std::vector<const BitCt *> &key, int key_bits);
+    void aes_key_expand_raw(const uint64_t *key, uint64_t *expanded, bool device_mem, int key_bits);
 
     // ---- AES-128-CTR with public counters (main.rs:108-128): counter block i = iv || be64(first_counter + i)
     // is public, so no counter ciphertexts exist and round 1 is bootstrapped once per distinct (position,
@@ -97,35 +106,36 @@ class Context {  // FheContext
     // SHORTINT_1BIT is TAE_E_PARAM.  The noise schedule is validated statically for trivial blocks. ----
     // keystream blocks [n_blocks][128][bit_len]; rk / out host or device, iv host
     void aes_ctr_keystream_raw(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks,
-                               int rounds, uint64_t *out, bool device_mem);
+                               int rounds, uint64_t *out, bool device_mem, int key_bits = 128);
     // data (host bytes, AES-CTR ciphertext) -> [len][8][bit_len] encryptions of the plaintext bits
     void aes_ctr_transcipher_raw(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, const uint8_t *data,
-                                 size_t len, int rounds, uint64_t *out, bool device_mem);
+                                 size_t len, int rounds, uint64_t *out, bool device_mem, int key_bits = 128);
     // BitCt variant, [len*8] bits with the schedule's noise; with rounds == 1 outputs that share a round-1
     // group share its component id
     std::vector<BitCt> aes_ctr_transcipher(const std::vector<const BitCt *> &expanded_key, const uint8_t iv[8],
                                            uint64_t first_counter, const uint8_t *data, size_t len,
-                                           int rounds = 10);
+                                           int rounds = 10, int key_bits = 128);
 
     // ---- AES-128 inverse cipher, FIPS-197 5.3 (the reference has no decryption; aes_inv.hpp): InvSubBytes and
     // InvMixColumns' multiples {14,11,13,9} in one 8 -> 32 circuit bootstrap per byte, `rounds` bootstraps per
     // block.  1-bit WoP-PBS sets (gal-mul driver) only: every other model is TAE_E_PARAM. ----
     // decryption key [44*32]: words 0..3 / 40..43 unchanged, words 4r..4r+3 = InvMixColumns(rk[r]) with fresh
     // noise (noise^2 = 1, new ids)
-    std::vector<BitCt> aes_decrypt_key(const std::vector<const BitCt *> &expanded_key);
-    void aes_decrypt_key_raw(const uint64_t *rk, uint64_t *dk, bool device_mem);
-    // inverts aes_encrypt_blocks(rounds): round keys 10, rounds-1 .. 1, 0.  Noise bookkeeping per bit
+    // (with key_bits: words 0..3 and 4 Nr .. 4 Nr + 3 unchanged, words 4 .. 4 Nr - 1 derived)
+    std::vector<BitCt> aes_decrypt_key(const std::vector<const BitCt *> &expanded_key, int key_bits = 128);
+    void aes_decrypt_key_raw(const uint64_t *rk, uint64_t *dk, bool device_mem, int key_bits = 128);
+    // inverts aes_encrypt_blocks(rounds): round keys Nr (10), rounds-1 .. 1, 0.  Noise bookkeeping per bit
     std::vector<BitCt> aes_decrypt_blocks(const std::vector<const BitCt *> &dk, const std::vector<const BitCt *> &blocks,
-                                          size_t n_blocks, int rounds);
+                                          size_t n_blocks, int rounds, int key_bits = 128);
     // raw arrays; the schedule is validated statically for a derived key and fresh blocks
     void aes_decrypt_blocks_raw(const uint64_t *dk, const uint64_t *blocks, size_t n_blocks, int rounds, uint64_t *out,
-                                bool device_mem);
+                                bool device_mem, int key_bits = 128);
     // CBC with a public ciphertext: data (host bytes, len % 16 == 0 or TAE_E_ARG) -> [len][8][bit_len]
     // encryptions of P_i = Dec(C_i) ^ C_{i-1}, C_{-1} = iv; no input ciphertexts are made
     void aes_cbc_transcipher_raw(const uint64_t *dk, const uint8_t iv[16], const uint8_t *data, size_t len, int rounds,
-                                 uint64_t *out, bool device_mem);
+                                 uint64_t *out, bool device_mem, int key_bits = 128);
     std::vector<BitCt> aes_cbc_transcipher(const std::vector<const BitCt *> &dk, const uint8_t iv[16],
-                                           const uint8_t *data, size_t len, int rounds = 10);
+                                           const uint8_t *data, size_t len, int rounds = 10, int key_bits = 128);
 
     // ---- 8-bit model (src/tfhe/shortint_woppbs_8bit.rs, fhe_impls/shortint_woppbs_8bit.rs) ----
     size_t bit_len() const { return params().bit_len(); }
@@ -153,24 +163,28 @@ class Context {  // FheContext
     void run8(const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len, bool device_mem, F fn, const Lut *lut);
     std::vector<BitCt> sbox_pbs_key_schedule(const std::vector<const BitCt *> &key);
     std::vector<NoiseLevel> block_noise_schedule(AesDriver driver, const std::vector<NoiseLevel> &rk,
-                                                 const std::vector<NoiseLevel> &block, int rounds) const;
-    void check_ctr(uint64_t first_counter, size_t n_blocks, int rounds) const;
-    void require_inverse(int rounds) const;
+                                                 const std::vector<NoiseLevel> &block, int rounds, int nr = 10) const;
+    int require_key_bits(int key_bits, AesDriver driver) const;
+    int require_key_expand(int key_bits) const;
+    int check_ctr(uint64_t first_counter, size_t n_blocks, int rounds, int key_bits) const;
+    int require_inverse(int rounds, int key_bits) const;
     void run_inverse(const uint64_t *key, const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes,
                      uint64_t *out, size_t out_len, bool device_mem,
-                     const std::function<void(const uint64_t *, const uint64_t *, const uint8_t *, uint64_t *)> &fn);
+                     const std::function<void(const uint64_t *, const uint64_t *, const uint8_t *, uint64_t *)> &fn,
+                     size_t key_cts);
     void run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
-                     const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem);
+                     const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem, int nr);
     void run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint64_t *d_in, size_t n_blocks, int rounds,
-                        uint64_t *d_out);
+                        uint64_t *d_out, int nr);
     std::unique_ptr<Engine> engine_;
     std::mutex mu_;
 };
 
 // Noise bookkeeping of the AES round function on metadata only: returns output noise levels
 // (per bit) or throws ModelError exactly where the reference would panic.
+// nr = 10 / 12 / 14 (here and in the replays below): rk has 4 (nr + 1) words and the last round key is word 4 nr.
 std::vector<NoiseLevel> aes_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &block,
-                                           int rounds, uint64_t max_noise_sq);
+                                           int rounds, uint64_t max_noise_sq, int nr = 10);
 // fhe_sbox_pbs over the 1-bit model: raises TAE_E_INDEP at the first MixColumns (rounds >= 2).
 std::vector<NoiseLevel> sbox_pbs_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &block,
                                                 int rounds, uint64_t max_noise_sq);
@@ -182,15 +196,21 @@ std::vector<NoiseLevel> aes8_noise_schedule(const std::vector<NoiseLevel> &rk, c
 // The inverse cipher (aes_inv.hpp) on metadata, ONE block: dk [44*32], block [128] -> output levels [128].
 // CBS outputs are noise^2 = 8 with fresh ids: a middle round is 4 * 8 + the key bit, the output 8 + the key bit.
 std::vector<NoiseLevel> aes_decrypt_noise_schedule(const std::vector<NoiseLevel> &dk, const std::vector<NoiseLevel> &block,
-                                                   int rounds, uint64_t max_noise_sq);
+                                                   int rounds, uint64_t max_noise_sq, int nr = 10);
 // The decryption-key derivation on metadata: rk [44*32] -> dk [44*32]; the 4-term sums (noise^2 = 32) are
 // validated, words 4..39 come out of the identity bootstrap at noise^2 = 1 with fresh ids.
-std::vector<NoiseLevel> aes_decrypt_key_noise_schedule(const std::vector<NoiseLevel> &rk, uint64_t max_noise_sq);
+std::vector<NoiseLevel> aes_decrypt_key_noise_schedule(const std::vector<NoiseLevel> &rk, uint64_t max_noise_sq,
+                                                       int nr = 10);
+// The key expansion (FIPS-197 5.2) on metadata: key [nk*32], nk = 4 / 6 / 8 -> rk [4 (nk + 7) * 32].  The word
+// before its identity bootstrap is rk[i-nk] + 8 on SubWord steps and rk[i-nk] + rk[i-1] otherwise (validated);
+// words below nk keep the key's levels and ids, every later word is noise^2 = 1 with fresh ids.
+std::vector<NoiseLevel> aes_key_expand_noise_schedule(const std::vector<NoiseLevel> &key, int nk, uint64_t max_noise_sq);
 
 // Counter mode on the 1-bit model: output noise [n_blocks][128] of the gal-mul schedule for trivial counter
 // blocks.  rounds >= 2: aes_noise_schedule per block.  rounds == 1: the final SubBytes runs on the plan's
 // groups, so outputs that read the same group carry the same component id.
 std::vector<std::vector<NoiseLevel>> aes_ctr_noise_schedule(const std::vector<NoiseLevel> &rk, const CtrPlan &plan,
-                                                            size_t n_blocks, int rounds, uint64_t max_noise_sq);
+                                                            size_t n_blocks, int rounds, uint64_t max_noise_sq,
+                                                            int nr = 10);
 
 }  // namespace tae

@@ -41,6 +41,11 @@ EXPORTED = [
     "tae_aes_ctr_plan", "tae_aes_ctr_keystream_raw", "tae_aes_ctr_transcipher_raw", "tae_aes_ctr_transcipher",
     "tae_aes_decrypt_key", "tae_aes_decrypt_key_raw", "tae_aes_decrypt_blocks", "tae_aes_decrypt_blocks_raw",
     "tae_aes_cbc_transcipher", "tae_aes_cbc_transcipher_raw", "tae_aes_decrypt_noise_schedule_check",
+    "tae_aesx_expanded_words", "tae_aesx_key_schedule", "tae_aesx_key_schedule_raw", "tae_aesx_encrypt_blocks",
+    "tae_aesx_encrypt_blocks_raw", "tae_aesx_ctr_keystream_raw", "tae_aesx_ctr_transcipher_raw",
+    "tae_aesx_ctr_transcipher", "tae_aesx_decrypt_key", "tae_aesx_decrypt_key_raw", "tae_aesx_decrypt_blocks",
+    "tae_aesx_decrypt_blocks_raw", "tae_aesx_cbc_transcipher", "tae_aesx_cbc_transcipher_raw",
+    "tae_aesx_noise_schedule_check",
 ]
 TAE_DRIVER_GAL_MUL, TAE_DRIVER_SBOX_PBS = 0, 1
 TAE_KEYS_CLIENT, TAE_KEYS_SERVER = 1, 2
@@ -132,6 +137,21 @@ def lib() -> C.CDLL:
         "tae_aes_cbc_transcipher": ([vp, vp, C.c_char_p, vp, sz, vp], C.c_int),
         "tae_aes_cbc_transcipher_raw": ([vp, vp, C.c_char_p, vp, sz, vp, C.c_int], C.c_int),
         "tae_aes_decrypt_noise_schedule_check": ([C.c_int, C.c_int], C.c_int),
+        "tae_aesx_expanded_words": ([C.c_int, C.POINTER(sz)], C.c_int),
+        "tae_aesx_key_schedule": ([vp, C.c_int, vp, vp], C.c_int),
+        "tae_aesx_key_schedule_raw": ([vp, C.c_int, vp, vp, C.c_int], C.c_int),
+        "tae_aesx_encrypt_blocks": ([vp, C.c_int, vp, vp, sz, C.c_int, vp], C.c_int),
+        "tae_aesx_encrypt_blocks_raw": ([vp, C.c_int, vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesx_ctr_keystream_raw": ([vp, C.c_int, vp, C.c_char_p, u64, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesx_ctr_transcipher_raw": ([vp, C.c_int, vp, C.c_char_p, u64, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesx_ctr_transcipher": ([vp, C.c_int, vp, C.c_char_p, u64, vp, sz, C.c_int, vp], C.c_int),
+        "tae_aesx_decrypt_key": ([vp, C.c_int, vp, vp], C.c_int),
+        "tae_aesx_decrypt_key_raw": ([vp, C.c_int, vp, vp, C.c_int], C.c_int),
+        "tae_aesx_decrypt_blocks": ([vp, C.c_int, vp, vp, sz, C.c_int, vp], C.c_int),
+        "tae_aesx_decrypt_blocks_raw": ([vp, C.c_int, vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesx_cbc_transcipher": ([vp, C.c_int, vp, C.c_char_p, vp, sz, C.c_int, vp], C.c_int),
+        "tae_aesx_cbc_transcipher_raw": ([vp, C.c_int, vp, C.c_char_p, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesx_noise_schedule_check": ([C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
         "tae_stage_keyswitch": ([vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_pbs_shift_boolean": ([vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_stage_bootstrap": ([vp, vp, sz, vp, vp, C.c_int], C.c_int),

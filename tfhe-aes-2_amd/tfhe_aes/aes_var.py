@@ -1,0 +1,389 @@
+"""AES-128 / 192 / 256 over the 1-bit WoP-PBS model: key expansion on the device, cipher, counter mode, inverse
+cipher and CBC for every key size of FIPS-197 (section 5.2 and figure 11; the reference is AES-128 only).
+
+A key of Nk = 4 / 6 / 8 words expands to W = 4 (Nr + 1) = 44 / 52 / 60 words for Nr = Nk + 6 = 10 / 12 / 14
+rounds.  Ciphertext layouts, bit order and the `rounds` convention are those of `aes_128`: a run of `rounds`
+rounds uses round keys 0, 1..rounds-1 and Nr.  The FHE side runs on the GPU through the C-ABI (tae_aesx_*),
+gal-mul driver on the 1-bit parameter sets; the other models raise TaeError (TAE_E_PARAM) for 192 and 256.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import _native as N
+from ._native import check, lib
+from .aes_128 import (INV_SBOX, RC, SBOX, _flat_bits, _inv_mix_columns, _iv8, _iv16, counter_blocks, gf_256_mul)
+from .tfhe import BitCt, FheContext, _handles
+
+KEY_BITS = (128, 192, 256)
+
+
+def _key_bits_of_words(words: int) -> int:
+    if words not in (44, 52, 60):
+        raise N.TaeError(N.TAE_E_ARG, f"an expanded key has 44, 52 or 60 words, not {words}")
+    return 32 * (words // 4 - 7)
+
+
+def rounds(key) -> int:
+    """Nr of a key: 16 / 24 / 32 bytes, or an expanded key of 44 / 52 / 60 words -> 10 / 12 / 14."""
+    n = len(key)
+    if isinstance(key, (bytes, bytearray)) and n in (16, 24, 32):
+        return n // 4 + 6
+    return _key_bits_of_words(n) // 32 + 6
+
+
+def expanded_words(key_bits: int) -> int:
+    n = C.c_size_t(0)
+    check(lib().tae_aesx_expanded_words(key_bits, C.byref(n)))
+    return n.value
+
+
+# ---------------------------------------------------------------- plain, FIPS-197 5.1 - 5.3 ----
+def key_schedule_plain(key: bytes) -> List[bytes]:
+    """FIPS-197 5.2: 16 / 24 / 32 key bytes -> 44 / 52 / 60 words of 4 bytes."""
+    if len(key) not in (16, 24, 32):
+        raise ValueError("key must be 16, 24 or 32 bytes")
+    nk = len(key) // 4
+    w = [bytes(key[4 * i:4 * i + 4]) for i in range(nk)]
+    for i in range(nk, 4 * (nk + 7)):
+        t = list(w[i - 1])
+        if i % nk == 0:
+            t = [SBOX[t[1]] ^ RC[i // nk], SBOX[t[2]], SBOX[t[3]], SBOX[t[0]]]
+        elif nk == 8 and i % 8 == 4:
+            t = [SBOX[x] for x in t]
+        w.append(bytes(a ^ b for a, b in zip(w[i - nk], t)))
+    return w
+
+
+def encrypt_block_plain(expanded_key: Sequence[bytes], block: bytes, rounds: Optional[int] = None) -> bytes:
+    """aes_128.encrypt_block_plain for any key size; the last round always uses round key Nr."""
+    nr = len(expanded_key) // 4 - 1
+    rounds = nr if rounds is None else rounds
+    rk = b"".join(expanded_key)
+    s = [block[i] ^ rk[i] for i in range(16)]
+    for r in range(1, rounds + 1):
+        last = r == rounds
+        s = [SBOX[x] for x in s]
+        t = [s[4 * ((c + row) % 4) + row] for c in range(4) for row in range(4)]
+        if not last:
+            m = []
+            for c in range(4):
+                col = t[4 * c:4 * c + 4]
+                m += [gf_256_mul(col[i], 2) ^ col[(i + 3) % 4] ^ col[(i + 2) % 4] ^ gf_256_mul(col[(i + 1) % 4], 3)
+                      for i in range(4)]
+            t = m
+        k = rk[16 * nr:16 * nr + 16] if last else rk[16 * r:16 * r + 16]
+        s = [t[i] ^ k[i] for i in range(16)]
+    return bytes(s)
+
+
+def decrypt_key_plain(expanded_key: Sequence[bytes]) -> List[bytes]:
+    """The decryption key of FIPS-197 5.3.5: words 0..3 and 4Nr..4Nr+3 are the expanded key's, words 4r..4r+3
+    (r = 1..Nr-1) are InvMixColumns(rk[r])."""
+    nr = len(expanded_key) // 4 - 1
+    rk = b"".join(expanded_key)
+    dk = bytearray(rk)
+    for r in range(1, nr):
+        dk[16 * r:16 * r + 16] = bytes(_inv_mix_columns(rk[16 * r:16 * r + 16]))
+    return [bytes(dk[4 * i:4 * i + 4]) for i in range(len(expanded_key))]
+
+
+def decrypt_block_plain(expanded_key: Sequence[bytes], block: bytes, rounds: Optional[int] = None) -> bytes:
+    """The inverse cipher (FIPS-197 5.3) with the ENCRYPTION key: inverts encrypt_block_plain(., ., rounds)."""
+    nr = len(expanded_key) // 4 - 1
+    rounds = nr if rounds is None else rounds
+    rk = b"".join(expanded_key)
+    s = [block[i] ^ rk[16 * nr + i] for i in range(16)]
+    for r in range(rounds - 1, -1, -1):
+        s = [s[4 * ((c - row) % 4) + row] for c in range(4) for row in range(4)]  # InvShiftRows
+        s = [INV_SBOX[x] for x in s]
+        s = [s[i] ^ rk[16 * r + i] for i in range(16)]
+        if r:
+            s = _inv_mix_columns(s)
+    return bytes(s)
+
+
+def ctr_xor_plain(key: bytes, iv: bytes, first_counter: int, data: bytes) -> bytes:
+    """Plain AES-CTR with the counter blocks of aes_128.counter_blocks; encrypts and decrypts."""
+    ek = key_schedule_plain(key)
+    nb = (len(data) + 15) // 16
+    ks = b"".join(encrypt_block_plain(ek, b) for b in counter_blocks(_iv8(iv), nb, first=first_counter))
+    return bytes(d ^ k for d, k in zip(data, ks))
+
+
+def cbc_encrypt_plain(key: bytes, iv: bytes, data: bytes) -> bytes:
+    """Plain AES-CBC of whole blocks (no padding)."""
+    if len(iv) != 16 or len(data) % 16:
+        raise ValueError("iv must be 16 bytes and data whole 16-byte blocks")
+    ek, prev, out = key_schedule_plain(key), bytes(iv), []
+    for i in range(0, len(data), 16):
+        prev = encrypt_block_plain(ek, bytes(a ^ b for a, b in zip(data[i:i + 16], prev)))
+        out.append(prev)
+    return b"".join(out)
+
+
+def cbc_decrypt_plain(key: bytes, iv: bytes, data: bytes) -> bytes:
+    """P_i = Dec(C_i) ^ C_{i-1}, C_{-1} = iv."""
+    if len(iv) != 16 or len(data) % 16:
+        raise ValueError("iv must be 16 bytes and data whole 16-byte blocks")
+    ek, prev, out = key_schedule_plain(key), bytes(iv), []
+    for i in range(0, len(data), 16):
+        c = bytes(data[i:i + 16])
+        out.append(bytes(a ^ b for a, b in zip(decrypt_block_plain(ek, c), prev)))
+        prev = c
+    return b"".join(out)
+
+
+def noise_schedule_check(param_set: int, key_bits: int, rounds: int, inverse: bool = False) -> None:
+    """The noise bookkeeping for a fresh key and block, without a context or device: the key expansion, then
+    `rounds` cipher rounds, or with `inverse` the decryption-key derivation and `rounds` inverse rounds."""
+    check(lib().tae_aesx_noise_schedule_check(param_set, key_bits, rounds, int(bool(inverse))))
+
+
+# ---------------------------------------------------------------- FHE ----
+def _p(a: np.ndarray):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _raw_key(key: np.ndarray, key_bits: Optional[int]):
+    """An expanded or decryption key [W*32][L] as a contiguous array and its key size.  key_bits, when given,
+    must be the size the array has (TAE_E_ARG otherwise)."""
+    key = np.ascontiguousarray(key, dtype=np.uint64)
+    if key.ndim != 2 or key.shape[0] % 32:
+        raise N.TaeError(N.TAE_E_ARG, "a key is an array [words * 32][L]")
+    kb = _key_bits_of_words(key.shape[0] // 32)
+    if key_bits is not None and key_bits != kb:
+        raise N.TaeError(N.TAE_E_ARG, f"the key has {key.shape[0] // 32} words, AES-{key_bits} needs "
+                                      f"{expanded_words(key_bits)}")
+    return key, kb
+
+
+def _bit_key(key, key_bits: Optional[int]):
+    flat = _flat_bits(key)
+    if len(flat) % 32:
+        raise N.TaeError(N.TAE_E_ARG, "a key is whole 32-bit words")
+    kb = _key_bits_of_words(len(flat) // 32)
+    if key_bits is not None and key_bits != kb:
+        raise N.TaeError(N.TAE_E_ARG, f"the key has {len(flat) // 32} words, AES-{key_bits} needs "
+                                      f"{expanded_words(key_bits)}")
+    return flat, kb
+
+
+def _nr(kb: int, rounds: Optional[int]) -> int:
+    return kb // 32 + 6 if rounds is None else rounds
+
+
+def _words(bits: List[BitCt]):
+    return [[bits[w * 32 + 8 * b:w * 32 + 8 * b + 8] for b in range(4)] for w in range(len(bits) // 32)]
+
+
+class GalMulAes:
+    """The method set of aes_128.ShortintWoppbs1BitSboxGalMulPbsAesEncrypt for 128-, 192- and 256-bit keys.
+    The key size is read from what is passed: `key_schedule*` from the key (16 / 24 / 32 encrypted bytes), every
+    other method from the expanded or decryption key (44 / 52 / 60 words); an explicit `key_bits` that does not
+    match is TAE_E_ARG.  The `_device` variants take pointers and therefore `key_bits`.  `rounds` defaults to Nr.
+    """
+
+    # ---- key expansion (FIPS-197 5.2) on the device ----
+    @staticmethod
+    def key_schedule(ctx: FheContext, key):
+        """[16 | 24 | 32][8] BitCt (nested or flat) -> [44 | 52 | 60][4][8]."""
+        kb = _flat_bits(key)
+        if len(kb) not in KEY_BITS:
+            raise N.TaeError(N.TAE_E_ARG, "key must be 16, 24 or 32 encrypted bytes")
+        outs = (C.c_void_p * (expanded_words(len(kb)) * 32))()
+        check(lib().tae_aesx_key_schedule(ctx._h, len(kb), _handles(kb), outs))
+        return _words([BitCt(h, ctx) for h in outs])
+
+    @staticmethod
+    def key_schedule_raw(ctx: FheContext, key: np.ndarray) -> np.ndarray:
+        """Host arrays: fresh key bits [128 | 192 | 256][L] -> expanded [W*32][L]."""
+        key = np.ascontiguousarray(key, dtype=np.uint64)
+        if key.ndim != 2 or key.shape[0] not in KEY_BITS:
+            raise N.TaeError(N.TAE_E_ARG, "key must be [128 | 192 | 256][L] bits")
+        out = np.zeros((expanded_words(key.shape[0]) * 32, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_key_schedule_raw(ctx._h, key.shape[0], _p(key), _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def key_schedule_device(ctx: FheContext, key_bits: int, d_key: int, d_rk: int):
+        """Device pointers (ints): key [key_bits][L] -> rk [W*32][L]; no ciphertext leaves the device."""
+        check(lib().tae_aesx_key_schedule_raw(ctx._h, key_bits, C.c_void_p(d_key), C.c_void_p(d_rk), N.TAE_MEM_DEVICE))
+
+    # ---- cipher ----
+    @classmethod
+    def encrypt_block(cls, ctx: FheContext, expanded_key, block):
+        return cls.encrypt_blocks(ctx, expanded_key, [block])[0]
+
+    @classmethod
+    def encrypt_block_for_rounds(cls, ctx: FheContext, expanded_key, block, rounds: int):
+        return cls.encrypt_blocks(ctx, expanded_key, [block], rounds)[0]
+
+    @staticmethod
+    def encrypt_blocks(ctx: FheContext, expanded_key, blocks, rounds: Optional[int] = None,
+                       key_bits: Optional[int] = None):
+        ek, kb = _bit_key(expanded_key, key_bits)
+        flat = _flat_bits(blocks)
+        nb = len(flat) // 128
+        outs = (C.c_void_p * (128 * nb))()
+        check(lib().tae_aesx_encrypt_blocks(ctx._h, kb, _handles(ek), _handles(flat), nb, _nr(kb, rounds), outs))
+        bits = [BitCt(h, ctx) for h in outs]
+        return [[bits[b * 128 + 8 * i:b * 128 + 8 * i + 8] for i in range(16)] for b in range(nb)]
+
+    @staticmethod
+    def encrypt_blocks_raw(ctx: FheContext, rk: np.ndarray, blocks: np.ndarray, rounds: Optional[int] = None,
+                           key_bits: Optional[int] = None) -> np.ndarray:
+        """Host arrays: rk [W*32][L], blocks [n][128][L] -> [n][128][L]."""
+        rk, kb = _raw_key(rk, key_bits)
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint64)
+        out = np.zeros_like(blocks)
+        check(lib().tae_aesx_encrypt_blocks_raw(ctx._h, kb, _p(rk), _p(blocks), blocks.shape[0], _nr(kb, rounds),
+                                                _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def encrypt_blocks_device(ctx: FheContext, key_bits: int, d_rk: int, d_blocks: int, nb: int, rounds: int,
+                              d_out: int):
+        """Device pointers (ints), inputs resident in HBM."""
+        check(lib().tae_aesx_encrypt_blocks_raw(ctx._h, key_bits, C.c_void_p(d_rk), C.c_void_p(d_blocks), nb, rounds,
+                                                C.c_void_p(d_out), N.TAE_MEM_DEVICE))
+
+    # ---- counter mode with public counters ----
+    @staticmethod
+    def ctr_keystream_raw(ctx: FheContext, rk: np.ndarray, iv: bytes, first_counter: int, n_blocks: int,
+                          rounds: Optional[int] = None, key_bits: Optional[int] = None) -> np.ndarray:
+        """rk [W*32][L] -> keystream blocks [n_blocks][128][L], equal word for word to encrypt_blocks_raw on
+        trivial encryptions of the counter blocks."""
+        rk, kb = _raw_key(rk, key_bits)
+        out = np.zeros((n_blocks, 128, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_ctr_keystream_raw(ctx._h, kb, _p(rk), _iv8(iv), first_counter, n_blocks,
+                                               _nr(kb, rounds), _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def ctr_keystream_device(ctx: FheContext, key_bits: int, d_rk: int, iv: bytes, first_counter: int, n_blocks: int,
+                             rounds: int, d_out: int):
+        check(lib().tae_aesx_ctr_keystream_raw(ctx._h, key_bits, C.c_void_p(d_rk), _iv8(iv), first_counter, n_blocks,
+                                               rounds, C.c_void_p(d_out), N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def ctr_transcipher_raw(ctx: FheContext, rk: np.ndarray, iv: bytes, first_counter: int, data: bytes,
+                            rounds: Optional[int] = None, key_bits: Optional[int] = None) -> np.ndarray:
+        """data: AES-CTR ciphertext bytes -> [len][8][L] FHE encryptions of the plaintext bits."""
+        rk, kb = _raw_key(rk, key_bits)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        out = np.zeros((len(buf), 8, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_ctr_transcipher_raw(ctx._h, kb, _p(rk), _iv8(iv), first_counter, _p(buf), len(buf),
+                                                 _nr(kb, rounds), _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def ctr_transcipher_device(ctx: FheContext, key_bits: int, d_rk: int, iv: bytes, first_counter: int, data: bytes,
+                               rounds: int, d_out: int):
+        """Device pointers (ints) for rk and the output [len][8][L]; iv and data are host bytes."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        check(lib().tae_aesx_ctr_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_rk), _iv8(iv), first_counter, _p(buf),
+                                                 len(buf), rounds, C.c_void_p(d_out), N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def ctr_transcipher(ctx: FheContext, expanded_key, iv: bytes, first_counter: int, data: bytes,
+                        rounds: Optional[int] = None, key_bits: Optional[int] = None):
+        """expanded_key: [W][4][8] BitCt (nested or flat) -> [len][8] BitCt of the plaintext bits."""
+        ek, kb = _bit_key(expanded_key, key_bits)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        outs = (C.c_void_p * (8 * len(buf)))()
+        check(lib().tae_aesx_ctr_transcipher(ctx._h, kb, _handles(ek), _iv8(iv), first_counter, _p(buf), len(buf),
+                                             _nr(kb, rounds), outs))
+        bits = [BitCt(h, ctx) for h in outs]
+        return [bits[8 * i:8 * i + 8] for i in range(len(buf))]
+
+    # ---- inverse cipher and CBC (FIPS-197 5.3) ----
+    @staticmethod
+    def decrypt_key(ctx: FheContext, expanded_key, key_bits: Optional[int] = None):
+        """[W][4][8] BitCt -> the decryption key [W][4][8]: words 4 .. 4Nr-1 = InvMixColumns of the round keys,
+        derived on the device with fresh noise; words 0..3 and 4Nr..4Nr+3 are the expanded key's."""
+        ek, kb = _bit_key(expanded_key, key_bits)
+        outs = (C.c_void_p * len(ek))()
+        check(lib().tae_aesx_decrypt_key(ctx._h, kb, _handles(ek), outs))
+        return _words([BitCt(h, ctx) for h in outs])
+
+    @staticmethod
+    def decrypt_key_raw(ctx: FheContext, rk: np.ndarray, key_bits: Optional[int] = None) -> np.ndarray:
+        rk, kb = _raw_key(rk, key_bits)
+        out = np.zeros_like(rk)
+        check(lib().tae_aesx_decrypt_key_raw(ctx._h, kb, _p(rk), _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def decrypt_key_device(ctx: FheContext, key_bits: int, d_rk: int, d_dk: int):
+        check(lib().tae_aesx_decrypt_key_raw(ctx._h, key_bits, C.c_void_p(d_rk), C.c_void_p(d_dk), N.TAE_MEM_DEVICE))
+
+    @classmethod
+    def decrypt_block(cls, ctx: FheContext, dk, block):
+        return cls.decrypt_blocks(ctx, dk, [block])[0]
+
+    @classmethod
+    def decrypt_block_for_rounds(cls, ctx: FheContext, dk, block, rounds: int):
+        return cls.decrypt_blocks(ctx, dk, [block], rounds)[0]
+
+    @staticmethod
+    def decrypt_blocks(ctx: FheContext, dk, blocks, rounds: Optional[int] = None, key_bits: Optional[int] = None):
+        key, kb = _bit_key(dk, key_bits)
+        flat = _flat_bits(blocks)
+        nb = len(flat) // 128
+        outs = (C.c_void_p * (128 * nb))()
+        check(lib().tae_aesx_decrypt_blocks(ctx._h, kb, _handles(key), _handles(flat), nb, _nr(kb, rounds), outs))
+        bits = [BitCt(h, ctx) for h in outs]
+        return [[bits[b * 128 + 8 * i:b * 128 + 8 * i + 8] for i in range(16)] for b in range(nb)]
+
+    @staticmethod
+    def decrypt_blocks_raw(ctx: FheContext, dk: np.ndarray, blocks: np.ndarray, rounds: Optional[int] = None,
+                           key_bits: Optional[int] = None) -> np.ndarray:
+        """Host arrays: dk [W*32][L], blocks [n][128][L] -> [n][128][L]."""
+        dk, kb = _raw_key(dk, key_bits)
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint64)
+        out = np.zeros_like(blocks)
+        check(lib().tae_aesx_decrypt_blocks_raw(ctx._h, kb, _p(dk), _p(blocks), blocks.shape[0], _nr(kb, rounds),
+                                                _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def decrypt_blocks_device(ctx: FheContext, key_bits: int, d_dk: int, d_blocks: int, nb: int, rounds: int,
+                              d_out: int):
+        check(lib().tae_aesx_decrypt_blocks_raw(ctx._h, key_bits, C.c_void_p(d_dk), C.c_void_p(d_blocks), nb, rounds,
+                                                C.c_void_p(d_out), N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def cbc_transcipher(ctx: FheContext, dk, iv: bytes, data: bytes, rounds: Optional[int] = None,
+                        key_bits: Optional[int] = None):
+        """dk: decrypt_key's output; data: AES-CBC ciphertext bytes (whole blocks) -> [len][8] BitCt of the
+        plaintext bits, padding included."""
+        key, kb = _bit_key(dk, key_bits)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        outs = (C.c_void_p * (8 * len(buf)))()
+        check(lib().tae_aesx_cbc_transcipher(ctx._h, kb, _handles(key), _iv16(iv), _p(buf), len(buf), _nr(kb, rounds),
+                                             outs))
+        bits = [BitCt(h, ctx) for h in outs]
+        return [bits[8 * i:8 * i + 8] for i in range(len(buf))]
+
+    @staticmethod
+    def cbc_transcipher_raw(ctx: FheContext, dk: np.ndarray, iv: bytes, data: bytes, rounds: Optional[int] = None,
+                            key_bits: Optional[int] = None) -> np.ndarray:
+        """Host arrays: dk [W*32][L] -> [len][8][L] FHE encryptions of the plaintext bits."""
+        dk, kb = _raw_key(dk, key_bits)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        out = np.zeros((len(buf), 8, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_cbc_transcipher_raw(ctx._h, kb, _p(dk), _iv16(iv), _p(buf), len(buf), _nr(kb, rounds),
+                                                 _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def cbc_transcipher_device(ctx: FheContext, key_bits: int, d_dk: int, iv: bytes, data: bytes, rounds: int,
+                               d_out: int):
+        """Device pointers (ints) for dk and the output [len][8][L]; iv and data are host bytes."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        check(lib().tae_aesx_cbc_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_dk), _iv16(iv), _p(buf), len(buf),
+                                                 rounds, C.c_void_p(d_out), N.TAE_MEM_DEVICE))
