@@ -343,6 +343,81 @@ int tae_aesx_cbc_transcipher_raw(const tae_context *ctx, int key_bits, const uin
  * inverse rounds.  TAE_OK, TAE_E_NOISE or TAE_E_INDEP; other models than the 1-bit one are TAE_E_PARAM */
 int tae_aesx_noise_schedule_check(int param_set, int key_bits, int rounds, int inverse);
 
+/* ---- Multi-key batches: key expansion, cipher, CTR and CBC across AES keys -----------
+ * The reference encrypts under one AES key and has no counterpart of these functions.  One FHE key, many AES
+ * keys: a key table is n_keys expanded keys (or decryption keys) of one key size, contiguous as
+ * [n_keys][W*32][L] with W = 44 / 52 / 60 and L = tae_bit_len.  Slot s is, bit for bit, an expanded key in the
+ * layout of tae_aesx_*, and may be passed to any tae_aesx_* call as it is.  A slot that no block or stream of a
+ * call refers to is not read, so a table may hold stale slots.  Bootstraps are per ciphertext, so the bits of
+ * different keys share their launches, and every output word equals the one the tae_aesx_* call with that
+ * slot's key gives.  Scope of tae_aesx_*: TAE_PARAMS_SQRD_LVL_* (gal-mul driver), key_bits 128 / 192 / 256;
+ * every other model is TAE_E_PARAM, as are other key_bits and `rounds` outside 1..=Nr.  A slot index outside
+ * 0..n_keys-1 (so any work with n_keys == 0), a counter range that wraps and a CBC len % 16 != 0 are
+ * TAE_E_ARG.  n_blocks == 0, n_streams == 0 and, for the two key calls, n_keys == 0 are TAE_OK and write
+ * nothing; a stream with len == 0 contributes nothing.  key_of_block, the stream arrays and `data` are host
+ * pointers under either `mem`.  The noise schedule is the single-key one (no ciphertexts of different keys
+ * meet), validated statically before any device work. */
+/* one counter-mode stream: len bytes under slot `key`, counter blocks iv || be64(first_counter + i) */
+typedef struct {
+    int32_t key;
+    uint8_t iv[8];
+    uint64_t first_counter;
+    const uint8_t *data; /* len AES-CTR ciphertext bytes, or NULL for the keystream */
+    size_t len;
+} tae_ctr_stream;
+/* one CBC stream: len bytes (whole blocks) of ciphertext under slot `key` */
+typedef struct {
+    int32_t key;
+    uint8_t iv[16];
+    const uint8_t *data;
+    size_t len;
+} tae_cbc_stream;
+/* batched FIPS-197 5.2 key expansion (no reference counterpart): fresh keys [n_keys][key_bits][L] -> table
+ * [n_keys][W*32][L]; word i of all keys is bootstrapped together, so the chain of dependent bootstraps is that
+ * of one key (50 / 54 / 65) whatever n_keys is */
+int tae_aesm_key_schedule_raw(const tae_context *ctx, int key_bits, const uint64_t *keys, size_t n_keys, uint64_t *table,
+                              int mem);
+/* batched FIPS-197 5.3.5 decryption keys (no reference counterpart): table -> dtable, both [n_keys][W*32][L];
+ * dtable must not be table */
+int tae_aesm_decrypt_key_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys, uint64_t *dtable,
+                             int mem);
+/* FIPS-197 5.1 cipher, block i under slot key_of_block[i] (host int32 array; no reference counterpart): blocks /
+ * out [n_blocks][128][L] */
+int tae_aesm_encrypt_blocks_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys,
+                                const int32_t *key_of_block, const uint64_t *blocks, size_t n_blocks, int rounds,
+                                uint64_t *out, int mem);
+/* FIPS-197 5.3 inverse cipher, block i under slot key_of_block[i] of a table of decryption keys (no reference
+ * counterpart) */
+int tae_aesm_decrypt_blocks_raw(const tae_context *ctx, int key_bits, const uint64_t *dtable, size_t n_keys,
+                                const int32_t *key_of_block, const uint64_t *blocks, size_t n_blocks, int rounds,
+                                uint64_t *out, int mem);
+/* number of round-1 SBOX groups of a set of streams (host only, no context; no reference counterpart): the
+ * distinct (key, byte position, byte value) triples of their counter blocks.  Streams of one slot share groups,
+ * streams of different slots share none.  A negative slot or a wrapping range is TAE_E_ARG */
+int tae_aesm_ctr_plan(const tae_ctr_stream *streams, size_t n_streams, size_t *round1_groups);
+/* tae_aesx_ctr_transcipher_raw for several streams (no reference counterpart): out = the streams' bytes
+ * concatenated in stream order, [sum len][8][L]; data == NULL gives that stream's keystream.  Calls above
+ * TAE_CTR_CHUNK_BLOCKS blocks in total run in consecutive chunks, a boundary may fall inside a stream, and the
+ * result does not depend on the chunk size */
+int tae_aesm_ctr_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys,
+                                 const tae_ctr_stream *streams, size_t n_streams, int rounds, uint64_t *out, int mem);
+/* tae_aesx_cbc_transcipher_raw for several streams (no reference counterpart): out [sum len][8][L] in stream
+ * order, each stream chained from its own iv */
+int tae_aesm_cbc_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *dtable, size_t n_keys,
+                                 const tae_cbc_stream *streams, size_t n_streams, int rounds, uint64_t *out, int mem);
+/* batched key expansion on handles (no reference counterpart): keys[n_keys*key_bits] -> table[n_keys*W*32], the
+ * bookkeeping of tae_aesx_key_schedule applied key by key */
+int tae_aesm_key_schedule(const tae_context *ctx, int key_bits, const tae_bit *const *keys /*[n_keys*key_bits]*/,
+                          size_t n_keys, tae_bit **table /*[n_keys*W*32]*/);
+/* multi-stream CTR on handles (no reference counterpart): out[sum len * 8], the bookkeeping of
+ * tae_aesx_ctr_transcipher applied stream by stream; handles of unreferenced slots are not read */
+int tae_aesm_ctr_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *table, size_t n_keys,
+                             const tae_ctr_stream *streams, size_t n_streams, int rounds, tae_bit **out);
+/* multi-stream CBC on handles (no reference counterpart): out[sum len * 8], the bookkeeping of
+ * tae_aesx_cbc_transcipher applied stream by stream */
+int tae_aesm_cbc_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *dtable, size_t n_keys,
+                             const tae_cbc_stream *streams, size_t n_streams, int rounds, tae_bit **out);
+
 /* ---- Aes128Encrypt for the fhe_sbox_pbs driver (src/aes_128/fhe/fhe_sbox_pbs.rs:22-171) ------------
  * ShortintWoppbs1BitSboxPbsAesEncrypt on the 1-bit model (fhe_impls/shortint_woppbs_1bit.rs:47-81:
  * SubBytes = one 8 -> 8 circuit bootstrap per byte, MixColumns = gf_256_mul by BitCt XORs) and

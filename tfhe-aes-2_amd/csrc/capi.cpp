@@ -822,6 +822,155 @@ int tae_aesx_noise_schedule_check(int param_set, int key_bits, int rounds, int i
     });
 }
 
+/* ---- multi-key batches: key tables [n_keys][W*32][L] (no counterpart in the reference) ---- */
+extern "C++" {
+namespace {
+std::vector<tae::Context::CtrStreamIn> ctr_streams_in(const tae_ctr_stream *streams, size_t n_streams) {
+    require(streams || !n_streams, "null");
+    std::vector<tae::Context::CtrStreamIn> v(n_streams);
+    for (size_t i = 0; i < n_streams; i++) {
+        v[i].s.slot = streams[i].key;
+        std::memcpy(v[i].s.iv, streams[i].iv, 8);
+        v[i].s.first_counter = streams[i].first_counter;
+        v[i].s.len = streams[i].len;
+        v[i].data = streams[i].data;
+    }
+    return v;
+}
+
+std::vector<tae::Context::CbcStreamIn> cbc_streams_in(const tae_cbc_stream *streams, size_t n_streams) {
+    require(streams || !n_streams, "null");
+    std::vector<tae::Context::CbcStreamIn> v(n_streams);
+    for (size_t i = 0; i < n_streams; i++) {
+        require(streams[i].data || !streams[i].len, "null stream data");
+        v[i].slot = streams[i].key;
+        std::memcpy(v[i].iv, streams[i].iv, 16);
+        v[i].data = streams[i].data;
+        v[i].len = streams[i].len;
+    }
+    return v;
+}
+
+tae::Context::BitAt bit_at(const tae_bit *const *bits) {
+    return [bits](size_t i) {
+        require(bits[i] != nullptr, "null bit handle");
+        return &bits[i]->b;
+    };
+}
+}  // namespace
+}  // extern "C++"
+
+int tae_aesm_key_schedule_raw(const tae_context *ctx, int key_bits, const uint64_t *keys, size_t n_keys, uint64_t *table,
+                              int mem) {
+    return guarded([&] {
+        require(ctx && ((keys && table) || !n_keys), "null");
+        ctx->ctx->aes_key_expand_multi_raw(keys, n_keys, table, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesm_decrypt_key_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys, uint64_t *dtable,
+                             int mem) {
+    return guarded([&] {
+        require(ctx && ((table && dtable) || !n_keys), "null");
+        ctx->ctx->aes_decrypt_key_multi_raw(table, n_keys, dtable, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesm_encrypt_blocks_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys,
+                                const int32_t *key_of_block, const uint64_t *blocks, size_t n_blocks, int rounds,
+                                uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && ((table && key_of_block && blocks && out) || !n_blocks), "null");
+        ctx->ctx->aes_blocks_multi_raw(false, table, n_keys, key_of_block, blocks, n_blocks, rounds, out,
+                                       mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesm_decrypt_blocks_raw(const tae_context *ctx, int key_bits, const uint64_t *dtable, size_t n_keys,
+                                const int32_t *key_of_block, const uint64_t *blocks, size_t n_blocks, int rounds,
+                                uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && ((dtable && key_of_block && blocks && out) || !n_blocks), "null");
+        ctx->ctx->aes_blocks_multi_raw(true, dtable, n_keys, key_of_block, blocks, n_blocks, rounds, out,
+                                       mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesm_ctr_plan(const tae_ctr_stream *streams, size_t n_streams, size_t *round1_groups) {
+    return guarded([&] {
+        require(round1_groups != nullptr, "null");
+        const std::vector<tae::Context::CtrStreamIn> in = ctr_streams_in(streams, n_streams);
+        std::vector<tae::CtrStream> ss(in.size());
+        for (size_t i = 0; i < in.size(); i++) ss[i] = in[i].s;
+        std::vector<tae::CtrBlock> blocks;
+        switch (tae::ctr_flatten(ss.data(), ss.size(), -1, blocks)) {
+            case tae::CTR_FLAT_SLOT: throw tae::ModelError{TAE_E_ARG, "a stream's key slot is negative"};
+            case tae::CTR_FLAT_WRAP: throw tae::ModelError{TAE_E_ARG, "counter range wraps past 2^64 - 1"};
+            default: break;
+        }
+        tae::CtrPlanMulti plan;
+        tae::ctr_plan_multi(blocks.data(), blocks.size(), plan);
+        *round1_groups = plan.groups.size();
+    });
+}
+
+int tae_aesm_ctr_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys,
+                                 const tae_ctr_stream *streams, size_t n_streams, int rounds, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx != nullptr, "null");
+        const std::vector<tae::Context::CtrStreamIn> in = ctr_streams_in(streams, n_streams);
+        size_t total = 0;
+        for (const auto &s : in) total += s.s.len;
+        require((table && out) || !total, "null");
+        ctx->ctx->aes_ctr_multi_raw(table, n_keys, in, rounds, out, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesm_cbc_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *dtable, size_t n_keys,
+                                 const tae_cbc_stream *streams, size_t n_streams, int rounds, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx != nullptr, "null");
+        const std::vector<tae::Context::CbcStreamIn> in = cbc_streams_in(streams, n_streams);
+        size_t total = 0;
+        for (const auto &s : in) total += s.len;
+        require((dtable && out) || !total, "null");
+        ctx->ctx->aes_cbc_multi_raw(dtable, n_keys, in, rounds, out, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesm_key_schedule(const tae_context *ctx, int key_bits, const tae_bit *const *keys, size_t n_keys,
+                          tae_bit **table) {
+    return guarded([&] {
+        require(ctx && ((keys && table) || !n_keys), "null");
+        key_cts(key_bits);  // key_bits is checked before the handle array is read at that length
+        emit(ctx->ctx->aes_key_expand_multi(unwrap(keys, n_keys * (size_t)key_bits), n_keys, key_bits), table);
+    });
+}
+
+int tae_aesm_ctr_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *table, size_t n_keys,
+                             const tae_ctr_stream *streams, size_t n_streams, int rounds, tae_bit **out) {
+    return guarded([&] {
+        require(ctx != nullptr, "null");
+        const std::vector<tae::Context::CtrStreamIn> in = ctr_streams_in(streams, n_streams);
+        size_t total = 0;
+        for (const auto &s : in) total += s.s.len;
+        require((table && out) || !total, "null");
+        emit(ctx->ctx->aes_ctr_multi(bit_at(table), n_keys, in, rounds, key_bits), out);
+    });
+}
+
+int tae_aesm_cbc_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *dtable, size_t n_keys,
+                             const tae_cbc_stream *streams, size_t n_streams, int rounds, tae_bit **out) {
+    return guarded([&] {
+        require(ctx != nullptr, "null");
+        const std::vector<tae::Context::CbcStreamIn> in = cbc_streams_in(streams, n_streams);
+        size_t total = 0;
+        for (const auto &s : in) total += s.len;
+        require((dtable && out) || !total, "null");
+        emit(ctx->ctx->aes_cbc_multi(bit_at(dtable), n_keys, in, rounds, key_bits), out);
+    });
+}
+
 int tae_aes_sbox_pbs_encrypt_blocks(const tae_context *ctx, const tae_bit *const *expanded_key,
                                     const tae_bit *const *blocks, size_t n_blocks, int rounds, tae_bit **out) {
     return guarded([&] {

@@ -103,8 +103,10 @@ class Engine {
     // nr = 10 / 12 / 14 is the round count of the key size (AES-128 / 192 / 256), here and in the modes below:
     // rk has 4 (nr + 1) words, rounds may go up to nr, and a run of `rounds` rounds uses round keys 0,
     // 1..rounds-1 and nr (the last one at word 4 nr)
+    // d_key_of != nullptr (device, [nb]) is the keyed form: d_rk is a key table and block i reads the round keys
+    // of slot d_key_of[i] at d_rk + d_key_of[i] * key_stride (the same for aes_decrypt_blocks)
     void aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, size_t nb, int rounds,
-                            uint64_t *d_out, int nr = 10);
+                            uint64_t *d_out, int nr = 10, const int32_t *d_key_of = nullptr, size_t key_stride = 0);
     // key expansion on the device (FIPS-197 5.2, figure 11; fhe_sbox_gal_mul_pbs::key_schedule for nk = 4):
     // key [nk*32][K+1], nk = 4 / 6 / 8 -> rk [4 (nk + 7) * 32][K+1].  Words below nk are copied; word i is
     // rk[i-nk] + rk[i-1], with SubWord (one 4-group 8 -> 8 bootstrap), RotWord and Rcon when i % nk == 0 and
@@ -133,7 +135,7 @@ class Engine {
     // dk [44*32][K+1] (aes_decrypt_key), blocks / out [nb][128][K+1]; inverts aes_encrypt_blocks(rounds): round
     // keys nr, rounds-1 .. 1, 0 of a key of 4 (nr + 1) words
     void aes_decrypt_blocks(const uint64_t *d_dk, const uint64_t *d_blocks, size_t nb, int rounds, uint64_t *d_out,
-                            int nr = 10);
+                            int nr = 10, const int32_t *d_key_of = nullptr, size_t key_stride = 0);
     // decryption key: words 0..3 and 40..43 copied, words 4r..4r+3 = InvMixColumns(rk[r]) by one 8 -> 32 bootstrap
     // of the 144 bytes (multiples only), the 4-term sums and one identity bootstrap of the 1152 bits.  d_dk != d_rk.
     // With nr: words 4 nr .. 4 nr + 3 are the last copy, and the middle is 16 (nr - 1) bytes, 128 (nr - 1) bits
@@ -142,6 +144,29 @@ class Engine {
     // [nb][128][K+1] = Dec(C_i) ^ C_{i-1}.  Round 0 and the last XOR come from the public bytes: no input ciphertexts
     void aes_cbc_transcipher(const uint64_t *d_dk, const uint8_t *d_iv_data, size_t nb, int rounds, uint64_t *d_out,
                              int nr = 10);
+
+    // ---- multi-key batches on the 1-bit model (the reference has one key).  A key table is
+    // [n_keys][4 (nr + 1) * 32][K+1], slot s an expanded (or decryption) key in the layout above.  The bootstraps
+    // are per ciphertext, so bits of different keys share their launches; the linear layer reads the round key of
+    // each block's slot.  key_of (HOST, [nb], every entry a valid slot: the caller checks) is uploaded
+    // asynchronously.  A slot that no block refers to is not read.  Every output word equals the single-key path's. ----
+    // keys [n_keys][nk*32][K+1] -> table; word i of all keys per step, so the chain of circuit bootstraps is as
+    // long as for one key (50 / 54 / 65) whatever n_keys is
+    void aes_key_expand_multi(const uint64_t *d_keys, int nk, size_t n_keys, uint64_t *d_table);
+    // aes_decrypt_key for every slot in one pass of its three stages; d_dtable != d_table
+    void aes_decrypt_key_multi(const uint64_t *d_table, size_t n_keys, uint64_t *d_dtable, int nr);
+    void aes_encrypt_blocks_multi(const uint64_t *d_table, const int32_t *key_of, const uint64_t *d_blocks, size_t nb,
+                                  int rounds, uint64_t *d_out, int nr);
+    void aes_decrypt_blocks_multi(const uint64_t *d_dtable, const int32_t *key_of, const uint64_t *d_blocks, size_t nb,
+                                  int rounds, uint64_t *d_out, int nr);
+    // counter mode over the flattened blocks of several streams (ctr_flatten), in chunks of ctr_chunk_ blocks with
+    // a CtrPlanMulti each; writes each block's len bytes at out_byte of d_out [sum len][8][K+1]; d_data (nullptr:
+    // the keystream) holds the public bytes in output order
+    void aes_ctr_multi(const uint64_t *d_table, const std::vector<CtrBlock> &blocks, int rounds, const uint8_t *d_data,
+                       uint64_t *d_out, int nr);
+    // CBC: d_cur / d_prev [nb][16] public bytes on the device, block i = Dec_{key_of[i]}(cur_i) ^ prev_i
+    void aes_cbc_transcipher_multi(const uint64_t *d_dtable, const int32_t *key_of, const uint8_t *d_cur,
+                                   const uint8_t *d_prev, size_t nb, int rounds, uint64_t *d_out, int nr);
 
     // ---- shortint_1bit model (src/tfhe/shortint_1bit.rs; param set SHORTINT_1BIT) ----
     // FheContext::bootstrap / bootstrap_assign (:257-291): PBS with test vector d_tvs + (b % lut_mod) (k+1)N, then the keyswitch
@@ -213,7 +238,10 @@ class Engine {
     // inverse cipher (1-bit model): InvSbox * {14,11,13,9}, InvSbox, the multiples alone, the 1 -> 1 identity
     uint64_t *d_lut_inv32_ = nullptr, *d_lut_inv8_ = nullptr, *d_lut_mul32_ = nullptr, *d_lut_id1_ = nullptr;
     void require_inverse(int rounds, int nr) const;
-    void aes_decrypt_rounds(const uint64_t *d_dk, size_t nb, int rounds, const uint8_t *d_xor, uint64_t *d_out);
+    void aes_decrypt_rounds(const uint64_t *d_dk, size_t nb, int rounds, const uint8_t *d_xor, uint64_t *d_out,
+                            const int32_t *d_key_of, size_t key_stride);
+    void aes_cbc_blocks(const uint64_t *d_dk, const uint8_t *d_cur, const uint8_t *d_prev, size_t nb, int rounds,
+                        uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride);
     uint64_t *d_wlut_sbox_ = nullptr, *d_wlut_id_ = nullptr;  // 8-bit model
     uint64_t *d_lut_x_ = nullptr;                             // extract_bits accumulators [nbits][glwe]
     int lut_x_delta_ = -1, lut_x_bits_ = 0;
@@ -228,6 +256,18 @@ class Engine {
     size_t cap_ctr_groups_ = 0, cap_ctr_map_ = 0;
     std::vector<CtrPlan> ctr_plans_;
     void upload_ctr_plan(const CtrPlan &plan, size_t nb);
+    // multi-key batches: the per-block slots on the device and the host copy its pending upload reads; the
+    // parallel arrays of a CtrPlanMulti and the plans of the chunks in flight
+    int32_t *d_key_of_ = nullptr, *d_ctr_gslot_ = nullptr, *d_ctr_blen_ = nullptr;
+    int64_t *d_ctr_bout_ = nullptr;
+    size_t cap_key_of_ = 0, cap_ctr_gslot_ = 0, cap_ctr_blen_ = 0, cap_ctr_bout_ = 0;
+    std::vector<int32_t> key_of_host_;
+    std::vector<CtrPlanMulti> ctr_mplans_;
+    const int32_t *upload_key_of(const int32_t *key_of, size_t nb);
+    void aes_ctr_blocks_multi(const uint64_t *d_table, const CtrPlanMulti &plan, int rounds, const uint8_t *d_data,
+                              uint64_t *d_out, int nr);
+    void copy_rows(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t rows,
+                   size_t len);
     // shortint_1bit: S-box / identity test vectors and tree-level scratch
     uint64_t *d_s1_sbox_tv_ = nullptr, *d_s1_id_tv_ = nullptr, *d_s1_in_ = nullptr, *d_s1_out_ = nullptr,
              *d_s1_pks_ = nullptr, *d_s1_tv_ = nullptr;

@@ -1133,7 +1133,355 @@ std::vector<BitCt> Context::aes_key_expand(const std::vector<const BitCt *> &key
     return res;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Multi-key batches: key tables [n_keys][W*32][L].  The reference has one key.
+// ---------------------------------------------------------------------------------------------
+// the scope of the multi-key entry points; rounds < 0: no round count to check.  Returns Nr.
+int Context::require_multi(int key_bits, int rounds) const {
+    if (!aes_key_bits_ok(key_bits)) throw ModelError{TAE_E_PARAM, "key_bits must be 128, 192 or 256"};
+    if (params().model != 1)
+        throw ModelError{TAE_E_PARAM, "multi-key batches run on the 1-bit WoP-PBS parameter sets (gal-mul driver) only"};
+    const int nr = aes_nr(key_bits);
+    if (rounds >= 0) require_rounds(rounds, nr);
+    return nr;
+}
 
+static void require_slots(const int32_t *slots, size_t n, size_t n_keys) {
+    for (size_t i = 0; i < n; i++)
+        if (slots[i] < 0 || (uint64_t)slots[i] >= n_keys)
+            throw ModelError{TAE_E_ARG, "key slot " + std::to_string(slots[i]) + " outside 0.." + std::to_string(n_keys) + "-1"};
+}
+
+// the slots a call refers to, ascending; `slots` is rewritten to indices into that list
+static std::vector<int32_t> compact_slots(std::vector<int32_t> &slots) {
+    std::vector<int32_t> used(slots);
+    std::sort(used.begin(), used.end());
+    used.erase(std::unique(used.begin(), used.end()), used.end());
+    for (int32_t &s : slots) s = (int32_t)(std::lower_bound(used.begin(), used.end(), s) - used.begin());
+    return used;
+}
+
+// fn(d_table, slots, d_in, d_bytes, d_out) on the engine stream.  Device memory: the caller's table and slots as
+// they are.  Host memory: only the referenced slots of the table are uploaded, into a compact table, and fn gets
+// the slots renumbered to it, so a slot that nothing refers to is not read in either case.
+void Context::run_multi(const uint64_t *table, const std::vector<int32_t> &slots, bool device_mem, size_t key_cts,
+                        const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes, uint64_t *out,
+                        size_t out_len,
+                        const std::function<void(const uint64_t *, const int32_t *, const uint64_t *, const uint8_t *,
+                                                 uint64_t *)> &fn) {
+    const size_t stride = key_cts * bit_len();
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    DevBuf d_bytes(n_bytes);  // the public bytes are a host array, always
+    if (n_bytes)
+        hip_check(hipMemcpyAsync(d_bytes.p, bytes, n_bytes, hipMemcpyHostToDevice, engine_->stream()), "upload data");
+    const uint8_t *db = n_bytes ? d_bytes.as<uint8_t>() : nullptr;
+    if (device_mem) {
+        engine_->order_after_caller();
+        fn(table, slots.data(), in, db, out);
+        engine_->synchronize();
+        return;
+    }
+    std::vector<int32_t> local(slots);
+    const std::vector<int32_t> used = compact_slots(local);
+    DevBuf d_tab(used.size() * stride * 8), d_in(in_len * 8), d_out(out_len * 8);
+    for (size_t j = 0; j < used.size(); j++)
+        hip_check(hipMemcpyAsync(d_tab.as<uint64_t>() + j * stride, table + (size_t)used[j] * stride, stride * 8,
+                                 hipMemcpyHostToDevice, engine_->stream()),
+                  "upload key slot");
+    if (in_len) hip_check(hipMemcpyAsync(d_in.p, in, in_len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload");
+    fn(d_tab.as<uint64_t>(), local.data(), d_in.as<uint64_t>(), db, d_out.as<uint64_t>());
+    hip_check(hipMemcpyAsync(out, d_out.p, out_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+void Context::aes_key_expand_multi_raw(const uint64_t *keys, size_t n_keys, uint64_t *table, bool device_mem,
+                                       int key_bits) {
+    require_multi(key_bits, -1);
+    const int nk = aes_nk(key_bits);
+    if (!n_keys) return;
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
+    aes_key_expand_noise_schedule(fresh_levels((size_t)nk * 32), nk, params().max_noise_sq);
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    if (device_mem) {
+        engine_->order_after_caller();
+        engine_->aes_key_expand_multi(keys, nk, n_keys, table);
+        engine_->synchronize();
+        return;
+    }
+    const size_t key_len = n_keys * (size_t)nk * 32 * L, tab_len = n_keys * kw * L;
+    DevBuf d_keys(key_len * 8), d_tab(tab_len * 8);
+    hip_check(hipMemcpyAsync(d_keys.p, keys, key_len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload keys");
+    engine_->aes_key_expand_multi(d_keys.as<uint64_t>(), nk, n_keys, d_tab.as<uint64_t>());
+    hip_check(hipMemcpyAsync(table, d_tab.p, tab_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+std::vector<BitCt> Context::aes_key_expand_multi(const std::vector<const BitCt *> &keys, size_t n_keys, int key_bits) {
+    require_multi(key_bits, -1);
+    const int nk = aes_nk(key_bits);
+    if (keys.size() != n_keys * (size_t)nk * 32) throw ModelError{TAE_E_ARG, "keys must be n_keys * key_bits bits"};
+    if (!n_keys) return {};
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
+    const std::vector<uint64_t> hk = gather_bits(keys, L);
+    std::vector<NoiseLevel> noise;  // the single-key bookkeeping, key by key
+    noise.reserve(n_keys * kw);
+    for (size_t k = 0; k < n_keys; k++) {
+        std::vector<NoiseLevel> kn((size_t)nk * 32);
+        for (size_t i = 0; i < kn.size(); i++) kn[i] = keys[k * kn.size() + i]->noise;
+        for (NoiseLevel &x : aes_key_expand_noise_schedule(kn, nk, params().max_noise_sq)) noise.push_back(std::move(x));
+    }
+    std::vector<uint64_t> tab(n_keys * kw * L);
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+        DevBuf d_keys(hk.size() * 8), d_tab(tab.size() * 8);
+        hip_check(hipMemcpyAsync(d_keys.p, hk.data(), hk.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
+        engine_->aes_key_expand_multi(d_keys.as<uint64_t>(), nk, n_keys, d_tab.as<uint64_t>());
+        hip_check(hipMemcpyAsync(tab.data(), d_tab.p, tab.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
+        engine_->synchronize();
+    }
+    std::vector<BitCt> res(n_keys * kw);
+    for (size_t i = 0; i < res.size(); i++) {
+        res[i].ct.assign(tab.begin() + i * L, tab.begin() + (i + 1) * L);
+        res[i].noise = std::move(noise[i]);
+        res[i].max_noise_sq = params().max_noise_sq;
+    }
+    return res;
+}
+
+void Context::aes_decrypt_key_multi_raw(const uint64_t *table, size_t n_keys, uint64_t *dtable, bool device_mem,
+                                        int key_bits) {
+    const int nr = require_multi(key_bits, -1);
+    if (!n_keys) return;
+    const size_t kw = (size_t)aes_words(key_bits) * 32, len = n_keys * kw * bit_len();
+    aes_decrypt_key_noise_schedule(fresh_levels(kw), params().max_noise_sq, nr);
+    if (table == dtable) throw ModelError{TAE_E_ARG, "the decryption keys cannot be derived in place"};
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    if (device_mem) {
+        engine_->order_after_caller();
+        engine_->aes_decrypt_key_multi(table, n_keys, dtable, nr);
+        engine_->synchronize();
+        return;
+    }
+    DevBuf d_tab(len * 8), d_dtab(len * 8);
+    hip_check(hipMemcpyAsync(d_tab.p, table, len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload table");
+    engine_->aes_decrypt_key_multi(d_tab.as<uint64_t>(), n_keys, d_dtab.as<uint64_t>(), nr);
+    hip_check(hipMemcpyAsync(dtable, d_dtab.p, len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+void Context::aes_blocks_multi_raw(bool inverse, const uint64_t *table, size_t n_keys, const int32_t *key_of,
+                                   const uint64_t *blocks, size_t n_blocks, int rounds, uint64_t *out, bool device_mem,
+                                   int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    if (!n_blocks) return;
+    if (!n_keys) throw ModelError{TAE_E_ARG, "blocks but no keys"};
+    require_slots(key_of, n_blocks, n_keys);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    // the single-key schedule: batching keys mixes no ciphertexts of different keys
+    if (inverse)
+        aes_decrypt_noise_schedule(fresh_levels(kw), fresh_levels(128), rounds, params().max_noise_sq, nr);
+    else
+        aes_noise_schedule(fresh_levels(kw), fresh_levels(128), rounds, params().max_noise_sq, nr);
+    const size_t len = n_blocks * 128 * bit_len();
+    run_multi(table, std::vector<int32_t>(key_of, key_of + n_blocks), device_mem, kw, blocks, len, nullptr, 0, out, len,
+              [&](const uint64_t *t, const int32_t *ko, const uint64_t *in, const uint8_t *, uint64_t *o) {
+                  if (inverse)
+                      engine_->aes_decrypt_blocks_multi(t, ko, in, n_blocks, rounds, o, nr);
+                  else
+                      engine_->aes_encrypt_blocks_multi(t, ko, in, n_blocks, rounds, o, nr);
+              });
+}
+
+// the flattened blocks of the streams and their public bytes in output order (empty: every stream asks for the
+// keystream); slot and range errors are TAE_E_ARG
+static void ctr_streams(const std::vector<Context::CtrStreamIn> &streams, size_t n_keys, std::vector<CtrBlock> &blocks,
+                        std::vector<uint8_t> &pub, size_t &total) {
+    std::vector<CtrStream> ss(streams.size());
+    total = 0;
+    bool any = false;
+    for (size_t i = 0; i < streams.size(); i++) {
+        ss[i] = streams[i].s;
+        total += ss[i].len;
+        any = any || (ss[i].len && streams[i].data);
+    }
+    switch (ctr_flatten(ss.data(), ss.size(), (int64_t)n_keys, blocks)) {
+        case CTR_FLAT_SLOT: throw ModelError{TAE_E_ARG, "a stream's key slot is outside 0..n_keys-1"};
+        case CTR_FLAT_WRAP: throw ModelError{TAE_E_ARG, "counter range wraps past 2^64 - 1"};
+        default: break;
+    }
+    pub.clear();
+    if (!any) return;
+    pub.assign(total, 0);  // a stream without data adds zeros: its keystream
+    size_t at = 0;
+    for (const Context::CtrStreamIn &st : streams) {
+        if (st.s.len && st.data) std::memcpy(pub.data() + at, st.data, st.s.len);
+        at += st.s.len;
+    }
+}
+
+void Context::aes_ctr_multi_raw(const uint64_t *table, size_t n_keys, const std::vector<CtrStreamIn> &streams,
+                                int rounds, uint64_t *out, bool device_mem, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    std::vector<CtrBlock> blocks;
+    std::vector<uint8_t> pub;
+    size_t total = 0;
+    ctr_streams(streams, n_keys, blocks, pub, total);
+    if (blocks.empty()) return;
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    aes_noise_schedule(fresh_levels(kw), std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds,
+                       params().max_noise_sq, nr);
+    std::vector<int32_t> slots(blocks.size());
+    for (size_t i = 0; i < blocks.size(); i++) slots[i] = blocks[i].slot;
+    run_multi(table, slots, device_mem, kw, nullptr, 0, pub.data(), pub.size(), out, total * 8 * bit_len(),
+              [&](const uint64_t *t, const int32_t *ko, const uint64_t *, const uint8_t *b, uint64_t *o) {
+                  for (size_t i = 0; i < blocks.size(); i++) blocks[i].slot = ko[i];
+                  engine_->aes_ctr_multi(t, blocks, rounds, b, o, nr);
+              });
+}
+
+// the referenced slots of a handle table as a compact host table, with the noise of every bit; `slots` is renumbered
+static std::vector<uint64_t> gather_slots(const Context::BitAt &table, std::vector<int32_t> &slots, size_t kw, size_t L,
+                                          std::vector<std::vector<NoiseLevel>> &noise) {
+    const std::vector<int32_t> used = compact_slots(slots);
+    std::vector<uint64_t> tab(used.size() * kw * L);
+    noise.assign(used.size(), std::vector<NoiseLevel>(kw));
+    for (size_t j = 0; j < used.size(); j++)
+        for (size_t i = 0; i < kw; i++) {
+            const BitCt *b = table((size_t)used[j] * kw + i);
+            if (b->ct.size() != L) throw ModelError{TAE_E_ARG, "ciphertext size mismatch"};
+            std::memcpy(&tab[(j * kw + i) * L], b->ct.data(), L * 8);
+            noise[j][i] = b->noise;
+        }
+    return tab;
+}
+
+std::vector<BitCt> Context::aes_ctr_multi(const BitAt &table, size_t n_keys, const std::vector<CtrStreamIn> &streams,
+                                          int rounds, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    std::vector<CtrBlock> blocks;
+    std::vector<uint8_t> pub;
+    size_t total = 0;
+    ctr_streams(streams, n_keys, blocks, pub, total);
+    if (blocks.empty()) return {};
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
+    std::vector<int32_t> slots(blocks.size());
+    for (size_t i = 0; i < blocks.size(); i++) slots[i] = blocks[i].slot;
+    std::vector<std::vector<NoiseLevel>> knoise;
+    const std::vector<uint64_t> tab = gather_slots(table, slots, kw, L, knoise);
+    // the bookkeeping of aes_ctr_transcipher, stream by stream
+    std::vector<NoiseLevel> noise;
+    noise.reserve(total * 8);
+    size_t b0 = 0;
+    for (const CtrStreamIn &st : streams) {
+        if (!st.s.len) continue;
+        const size_t nb = st.s.len / 16 + (st.s.len % 16 != 0);
+        CtrPlan plan;
+        ctr_plan(st.s.iv, st.s.first_counter, nb, plan);
+        const std::vector<std::vector<NoiseLevel>> on =
+            aes_ctr_noise_schedule(knoise[(size_t)slots[b0]], plan, nb, rounds, params().max_noise_sq, nr);
+        for (size_t i = 0; i < st.s.len * 8; i++) noise.push_back(on[i / 128][i % 128]);
+        b0 += nb;
+    }
+    for (size_t i = 0; i < blocks.size(); i++) blocks[i].slot = slots[i];
+    std::vector<uint64_t> out(total * 8 * L);
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+        DevBuf d_tab(tab.size() * 8), d_pub(pub.size()), d_out(out.size() * 8);
+        hip_check(hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
+        if (!pub.empty())
+            hip_check(hipMemcpyAsync(d_pub.p, pub.data(), pub.size(), hipMemcpyHostToDevice, engine_->stream()), "up");
+        engine_->aes_ctr_multi(d_tab.as<uint64_t>(), blocks, rounds, pub.empty() ? nullptr : d_pub.as<uint8_t>(),
+                               d_out.as<uint64_t>(), nr);
+        hip_check(hipMemcpyAsync(out.data(), d_out.p, out.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
+        engine_->synchronize();
+    }
+    std::vector<BitCt> res(total * 8);
+    for (size_t i = 0; i < res.size(); i++) {
+        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
+        res[i].noise = std::move(noise[i]);  // xor with a public bit adds no noise
+        res[i].max_noise_sq = params().max_noise_sq;
+    }
+    return res;
+}
+
+// per block of the flattened streams: slot, the ciphertext block and the block before it (the iv first)
+static void cbc_streams(const std::vector<Context::CbcStreamIn> &streams, size_t n_keys, std::vector<int32_t> &slots,
+                        std::vector<uint8_t> &cur_prev) {
+    size_t nb = 0;
+    for (const Context::CbcStreamIn &st : streams) {
+        if (st.len % 16 != 0) throw ModelError{TAE_E_ARG, "CBC data must be whole 16-byte blocks"};
+        if (st.len && (st.slot < 0 || (uint64_t)st.slot >= n_keys))
+            throw ModelError{TAE_E_ARG, "a stream's key slot is outside 0..n_keys-1"};
+        nb += st.len / 16;
+    }
+    slots.clear();
+    cur_prev.assign(nb * 32, 0);  // [nb][16] ciphertext blocks, then [nb][16] previous blocks
+    size_t b = 0;
+    for (const Context::CbcStreamIn &st : streams)
+        for (size_t i = 0; i < st.len / 16; i++, b++) {
+            slots.push_back(st.slot);
+            std::memcpy(&cur_prev[b * 16], st.data + 16 * i, 16);
+            std::memcpy(&cur_prev[(nb + b) * 16], i ? st.data + 16 * (i - 1) : st.iv, 16);
+        }
+}
+
+void Context::aes_cbc_multi_raw(const uint64_t *dtable, size_t n_keys, const std::vector<CbcStreamIn> &streams,
+                                int rounds, uint64_t *out, bool device_mem, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    std::vector<int32_t> slots;
+    std::vector<uint8_t> pub;
+    cbc_streams(streams, n_keys, slots, pub);
+    const size_t nb = slots.size(), kw = (size_t)aes_words(key_bits) * 32;
+    if (!nb) return;
+    aes_decrypt_noise_schedule(fresh_levels(kw), std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds,
+                               params().max_noise_sq, nr);
+    run_multi(dtable, slots, device_mem, kw, nullptr, 0, pub.data(), pub.size(), out, nb * 128 * bit_len(),
+              [&](const uint64_t *t, const int32_t *ko, const uint64_t *, const uint8_t *b, uint64_t *o) {
+                  engine_->aes_cbc_transcipher_multi(t, ko, b, b + nb * 16, nb, rounds, o, nr);
+              });
+}
+
+std::vector<BitCt> Context::aes_cbc_multi(const BitAt &dtable, size_t n_keys, const std::vector<CbcStreamIn> &streams,
+                                          int rounds, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    std::vector<int32_t> slots;
+    std::vector<uint8_t> pub;
+    cbc_streams(streams, n_keys, slots, pub);
+    const size_t nb = slots.size(), kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
+    if (!nb) return {};
+    std::vector<std::vector<NoiseLevel>> knoise;
+    const std::vector<uint64_t> tab = gather_slots(dtable, slots, kw, L, knoise);
+    const std::vector<NoiseLevel> triv(128, NoiseLevel::trivial());
+    std::vector<NoiseLevel> noise;
+    noise.reserve(nb * 128);
+    for (size_t b = 0; b < nb; b++)
+        for (NoiseLevel &x : aes_decrypt_noise_schedule(knoise[(size_t)slots[b]], triv, rounds, params().max_noise_sq, nr))
+            noise.push_back(std::move(x));
+    std::vector<uint64_t> out(nb * 128 * L);
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+        DevBuf d_tab(tab.size() * 8), d_pub(pub.size()), d_out(out.size() * 8);
+        hip_check(hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
+        hip_check(hipMemcpyAsync(d_pub.p, pub.data(), pub.size(), hipMemcpyHostToDevice, engine_->stream()), "up");
+        engine_->aes_cbc_transcipher_multi(d_tab.as<uint64_t>(), slots.data(), d_pub.as<uint8_t>(),
+                                           d_pub.as<uint8_t>() + nb * 16, nb, rounds, d_out.as<uint64_t>(), nr);
+        hip_check(hipMemcpyAsync(out.data(), d_out.p, out.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
+        engine_->synchronize();
+    }
+    std::vector<BitCt> res(nb * 128);
+    for (size_t i = 0; i < res.size(); i++) {
+        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
+        res[i].noise = std::move(noise[i]);  // xor with a public bit adds no noise
+        res[i].max_noise_sq = params().max_noise_sq;
+    }
+    return res;
+}
 
 // ---------------------------------------------------------------------------------------------
 // shortint_1bit model (src/tfhe/shortint_1bit.rs)

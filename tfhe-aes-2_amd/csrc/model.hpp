@@ -137,6 +137,40 @@ class Context {  // FheContext
     std::vector<BitCt> aes_cbc_transcipher(const std::vector<const BitCt *> &dk, const uint8_t iv[16],
                                            const uint8_t *data, size_t len, int rounds = 10, int key_bits = 128);
 
+    // ---- multi-key batches (the reference has one key): a key table is n_keys expanded (or
+    // decryption) keys of one size, [n_keys][W*32][bit_len], slot s an expanded key as above.  1-bit model, gal-mul
+    // driver (TAE_E_PARAM elsewhere).  Slots, streams and public bytes are host arrays; a slot outside
+    // 0..n_keys-1 is TAE_E_ARG, a slot nothing refers to is not read.  The noise schedule is the single-key one,
+    // validated statically (raw) or per key / per stream (BitCt). ----
+    struct CtrStreamIn {
+        CtrStream s;
+        const uint8_t *data;  // len bytes, or nullptr for the keystream
+    };
+    struct CbcStreamIn {
+        int32_t slot;
+        uint8_t iv[16];
+        const uint8_t *data;
+        size_t len;  // whole blocks, or TAE_E_ARG
+    };
+    using BitAt = std::function<const BitCt *(size_t)>;  // bit i of a handle array, read for referenced slots only
+    // keys [n_keys][key_bits][bit_len] -> table
+    void aes_key_expand_multi_raw(const uint64_t *keys, size_t n_keys, uint64_t *table, bool device_mem, int key_bits);
+    std::vector<BitCt> aes_key_expand_multi(const std::vector<const BitCt *> &keys, size_t n_keys, int key_bits);
+    void aes_decrypt_key_multi_raw(const uint64_t *table, size_t n_keys, uint64_t *dtable, bool device_mem, int key_bits);
+    // block i under slot key_of[i]; inverse: the table holds decryption keys
+    void aes_blocks_multi_raw(bool inverse, const uint64_t *table, size_t n_keys, const int32_t *key_of,
+                              const uint64_t *blocks, size_t n_blocks, int rounds, uint64_t *out, bool device_mem,
+                              int key_bits);
+    // out = the streams' bytes concatenated in stream order [sum len][8][bit_len]
+    void aes_ctr_multi_raw(const uint64_t *table, size_t n_keys, const std::vector<CtrStreamIn> &streams, int rounds,
+                           uint64_t *out, bool device_mem, int key_bits);
+    std::vector<BitCt> aes_ctr_multi(const BitAt &table, size_t n_keys, const std::vector<CtrStreamIn> &streams,
+                                     int rounds, int key_bits);
+    void aes_cbc_multi_raw(const uint64_t *dtable, size_t n_keys, const std::vector<CbcStreamIn> &streams, int rounds,
+                           uint64_t *out, bool device_mem, int key_bits);
+    std::vector<BitCt> aes_cbc_multi(const BitAt &dtable, size_t n_keys, const std::vector<CbcStreamIn> &streams,
+                                     int rounds, int key_bits);
+
     // ---- 8-bit model (src/tfhe/shortint_woppbs_8bit.rs, fhe_impls/shortint_woppbs_8bit.rs) ----
     size_t bit_len() const { return params().bit_len(); }
     // FheContext::bootstrap_from_bits over G bytes: bits [G][8][n+1] -> int ciphertexts [G][K+1]
@@ -168,6 +202,11 @@ class Context {  // FheContext
     int require_key_expand(int key_bits) const;
     int check_ctr(uint64_t first_counter, size_t n_blocks, int rounds, int key_bits) const;
     int require_inverse(int rounds, int key_bits) const;
+    int require_multi(int key_bits, int rounds) const;
+    void run_multi(const uint64_t *table, const std::vector<int32_t> &slots, bool device_mem, size_t key_cts,
+                   const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes, uint64_t *out, size_t out_len,
+                   const std::function<void(const uint64_t *, const int32_t *, const uint64_t *, const uint8_t *,
+                                            uint64_t *)> &fn);
     void run_inverse(const uint64_t *key, const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes,
                      uint64_t *out, size_t out_len, bool device_mem,
                      const std::function<void(const uint64_t *, const uint64_t *, const uint8_t *, uint64_t *)> &fn,

@@ -46,6 +46,9 @@ EXPORTED = [
     "tae_aesx_ctr_transcipher", "tae_aesx_decrypt_key", "tae_aesx_decrypt_key_raw", "tae_aesx_decrypt_blocks",
     "tae_aesx_decrypt_blocks_raw", "tae_aesx_cbc_transcipher", "tae_aesx_cbc_transcipher_raw",
     "tae_aesx_noise_schedule_check",
+    "tae_aesm_key_schedule_raw", "tae_aesm_decrypt_key_raw", "tae_aesm_encrypt_blocks_raw",
+    "tae_aesm_decrypt_blocks_raw", "tae_aesm_ctr_plan", "tae_aesm_ctr_transcipher_raw",
+    "tae_aesm_cbc_transcipher_raw", "tae_aesm_key_schedule", "tae_aesm_ctr_transcipher", "tae_aesm_cbc_transcipher",
 ]
 TAE_DRIVER_GAL_MUL, TAE_DRIVER_SBOX_PBS = 0, 1
 TAE_KEYS_CLIENT, TAE_KEYS_SERVER = 1, 2
@@ -59,6 +62,17 @@ class TaeParams(C.Structure):
 
     def as_dict(self) -> dict:
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class TaeCtrStream(C.Structure):
+    """tae_ctr_stream: one counter-mode stream of a multi-key call."""
+    _fields_ = [("key", C.c_int32), ("iv", C.c_uint8 * 8), ("first_counter", C.c_uint64), ("data", C.c_void_p),
+                ("len", C.c_size_t)]
+
+
+class TaeCbcStream(C.Structure):
+    """tae_cbc_stream: one CBC stream of a multi-key call."""
+    _fields_ = [("key", C.c_int32), ("iv", C.c_uint8 * 16), ("data", C.c_void_p), ("len", C.c_size_t)]
 
 
 class TaeError(RuntimeError):
@@ -152,6 +166,16 @@ def lib() -> C.CDLL:
         "tae_aesx_cbc_transcipher": ([vp, C.c_int, vp, C.c_char_p, vp, sz, C.c_int, vp], C.c_int),
         "tae_aesx_cbc_transcipher_raw": ([vp, C.c_int, vp, C.c_char_p, vp, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_aesx_noise_schedule_check": ([C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
+        "tae_aesm_key_schedule_raw": ([vp, C.c_int, vp, sz, vp, C.c_int], C.c_int),
+        "tae_aesm_decrypt_key_raw": ([vp, C.c_int, vp, sz, vp, C.c_int], C.c_int),
+        "tae_aesm_encrypt_blocks_raw": ([vp, C.c_int, vp, sz, vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesm_decrypt_blocks_raw": ([vp, C.c_int, vp, sz, vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesm_ctr_plan": ([vp, sz, C.POINTER(sz)], C.c_int),
+        "tae_aesm_ctr_transcipher_raw": ([vp, C.c_int, vp, sz, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesm_cbc_transcipher_raw": ([vp, C.c_int, vp, sz, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesm_key_schedule": ([vp, C.c_int, vp, sz, vp], C.c_int),
+        "tae_aesm_ctr_transcipher": ([vp, C.c_int, vp, sz, vp, sz, C.c_int, vp], C.c_int),
+        "tae_aesm_cbc_transcipher": ([vp, C.c_int, vp, sz, vp, sz, C.c_int, vp], C.c_int),
         "tae_stage_keyswitch": ([vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_pbs_shift_boolean": ([vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_stage_bootstrap": ([vp, vp, sz, vp, vp, C.c_int], C.c_int),
