@@ -471,6 +471,10 @@ int tae_last_stage_times_v3(const tae_context *ctx, double *v10);
  * launches (median over each launch's workgroups of shader cycles / 100 MHz reference ticks, averaged over
  * the launches; MI355X_MICROARCH.md "DVFS give-back") and the number of launches it averages (0: none) */
 int tae_last_stage_times_v4(const tae_context *ctx, double *v12);
+/* name of the kernel that the context's last private functional keyswitch launched, NUL-terminated into
+ * name[cap]: "g6", "s16", "w32", "w16" (the K-layout int8 GEMMs, chosen by TAE_PFKS_GEMM at context creation),
+ * "rows" (the row-limb GEMM of small batches), "u64" (the scalar kernel) or "none" */
+int tae_last_pfks_kernel(const tae_context *ctx, char *name, size_t cap);
 
 #ifdef __cplusplus
 }

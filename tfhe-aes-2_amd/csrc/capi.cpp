@@ -1167,6 +1167,15 @@ int tae_last_stage_times_v4(const tae_context *ctx, double *v12) {
     });
 }
 
+int tae_last_pfks_kernel(const tae_context *ctx, char *name, size_t cap) {
+    return guarded([&] {
+        require(ctx && name && cap, "null");
+        const char *k = ctx->ctx->engine().last_pfks_kernel();
+        require(strlen(k) < cap, "name buffer too small");
+        strcpy(name, k);
+    });
+}
+
 int tae_last_stage_times_v2(const tae_context *ctx, float *ms8) {
     return guarded([&] {
         require(ctx && ms8, "null");

@@ -201,6 +201,9 @@ class Engine {
     // waits on an event recorded on this caller stream (no host sync, other streams not waited for)
     void set_caller_stream(hipStream_t s) { caller_stream_ = s; }
     const StageTimes &last_times() const { return times_; }
+    // the kernel of the last pfks_into_ggsw launch: "g6", "s16", "w32" or "w16" (K-layout GEMMs, TAE_PFKS_GEMM),
+    // "rows" (6-bit row-tile GEMM), "u64" (scalar kernel), "none" before the first
+    const char *last_pfks_kernel() const { return last_pfks_kernel_; }
     // 0 off, 1 HIP-event stage times, 2 stage times + in-kernel clock stamps of the blind rotations
     // (a diagnostic mode: each stamped launch is read back synchronously)
     void set_timing(int mode) {
@@ -301,6 +304,10 @@ class Engine {
     long pf_kl_min_ = 2048;
     int kp_pf_kl_ = 0;
     ksgemm::KSlots pf_slots_;
+    // K-layout GEMM kernel (TAE_PFKS_GEMM, read at init): 0 gemm_g6<6, 4, true>, 1.. the gemm_g7 variants;
+    // default "w16" (8 waves of 96 x 128, 16x16x64 MFMAs), the fastest by stage and by bench wall time
+    int pf_gemm_ = 3;
+    const char *last_pfks_kernel_ = "none";
     int8_t *d_pf_bt_kl_ = nullptr;
     uint64_t *d_pf_corr_ = nullptr;  // [ncols] digit-offset correction of the K layout
     uint32_t *d_pf_flags_ = nullptr;  // [B][words] clamped-digit flags of the K layout (kslots_build)

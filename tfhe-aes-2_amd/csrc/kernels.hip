@@ -47,6 +47,9 @@ constexpr int kG6WM = 4;  // PFKS GEMM: 96 x WM ciphertexts per workgroup tile, 
 #else
 constexpr int kG6WM = TAE_G6_WM;
 #endif
+// K-layout PFKS GEMM kernels by TAE_PFKS_GEMM name: gemm_g6<6, 4, true>, then gemm_g7<S16, WNW> (ksgemm.hpp)
+constexpr const char *kPfGemmNames[] = {"g6", "s16", "w32", "w16"};
+constexpr int kPfGemms = 4;
 constexpr size_t kS1Rows = 16384;  // shortint_1bit selector trees: level-0 bootstraps per chunk (at least)
 
 // ---------------------------------------------------------------------------------------------
@@ -923,8 +926,11 @@ T *Engine::grow(T *&ptr, size_t &cap, size_t count) {
 void Engine::init_common() {
     HIPC(hipSetDevice(device_));
     // TAE_CU_MASK (probe / A-B knob, scripts/probes/stage_overlap.py): "lo:N" or "hi:N" restricts the engine
-    // stream to the first / last N CUs of the device's CU mask (hipExtStreamCreateWithCUMask); batch rounds
-    // are then sized for N CUs
+    // stream to the N lowest / highest bits of the device's CU mask: two disjoint bit ranges (on a multi-XCD
+    // part consecutive mask bits are spread over the XCDs, so a range is not a contiguous block of CUs); batch
+    // rounds are then sized for N CUs.  hipExtStreamCreateWithCUMask takes no flags, so unlike the default
+    // engine stream the masked one is a blocking stream: it synchronises with the legacy null stream, which
+    // the probe must not use.
     int mask_cus = 0;
     if (const char *cm = getenv("TAE_CU_MASK")) {
         int total = 0;
@@ -933,14 +939,14 @@ void Engine::init_common() {
         if (!hi && strncmp(cm, "lo:", 3)) throw std::runtime_error("TAE_CU_MASK must be lo:N or hi:N");
         char *end = nullptr;
         const long nc = strtol(cm + 3, &end, 10);
-        if (end == cm + 3 || *end || nc < 1 || nc > total || total > 256)
+        if (end == cm + 3 || *end || nc < 1 || nc > total)
             throw std::runtime_error(std::string("TAE_CU_MASK: bad CU count in '") + cm + "'");
-        uint32_t mask[8] = {0};
+        std::vector<uint32_t> mask((size_t)(total + 31) / 32, 0u);
         for (int c = 0; c < nc; c++) {
             const int b = hi ? total - 1 - c : c;
             mask[b >> 5] |= 1u << (b & 31);
         }
-        HIPC(hipExtStreamCreateWithCUMask(&stream_, 8, mask));
+        HIPC(hipExtStreamCreateWithCUMask(&stream_, (uint32_t)mask.size(), mask.data()));
         mask_cus = (int)nc;
     } else {
         HIPC(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
@@ -1192,6 +1198,12 @@ void Engine::prepare_mfma_keys() {
                              (int)ksgemm::gemm_g6_lds<4>()));
     HIPC(hipFuncSetAttribute((const void *)ksgemm::gemm_g6<6, kG6WM, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)ksgemm::gemm_g6_lds<kG6WM>()));
+    HIPC(hipFuncSetAttribute((const void *)ksgemm::gemm_g7<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)ksgemm::gemm_g6_lds<4>()));
+    HIPC(hipFuncSetAttribute((const void *)ksgemm::gemm_g7<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)ksgemm::gemm_g6_lds<4>()));
+    HIPC(hipFuncSetAttribute((const void *)ksgemm::gemm_g7<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)ksgemm::gemm_g6_lds<4>()));
     // int8-MFMA keyswitches when the digits fit their limbs (PFKS 17-bit digits as 3 x 6-bit limbs,
     // KS digits as one byte); otherwise (params_sqrd_lvl_1: pfks base 2^24) the u64 VALU kernels
     mfma_ks_ = p_.pfks_b <= 16 && p_.ks_b <= 7;
@@ -1231,6 +1243,21 @@ void Engine::prepare_mfma_keys() {
     if (lay) {
         if (!strcmp(lay, "rows")) pf_kl_min_ = LONG_MAX;
         if (!strcmp(lay, "k") || k5) pf_kl_min_ = 0;
+    }
+    // TAE_PFKS_GEMM=<name>[:all] picks the K-layout GEMM kernel: "g6" (gemm_g6: 16 waves of 96 x 64, 32x32x32
+    // MFMAs), "s16" (the same waves with 16x16x64 MFMAs), "w32" / "w16" (8 waves of 96 x 128 with either shape);
+    // ":all" also sends every batch size to the K layout (the parity tests reach one-row tiles that way)
+    if (kG6WM != 4) pf_gemm_ = 0;  // a TAE_G6_WM build: gemm_g7 has the 384-row tile only
+    if (const char *gm = getenv("TAE_PFKS_GEMM")) {
+        const char *colon = strchr(gm, ':');
+        const std::string name = colon ? std::string(gm, colon) : std::string(gm);
+        pf_gemm_ = -1;
+        for (int i = 0; i < kPfGemms; i++)
+            if (name == kPfGemmNames[i]) pf_gemm_ = i;
+        if (pf_gemm_ < 0 || (colon && strcmp(colon, ":all")) || (pf_gemm_ && kG6WM != 4))
+            throw std::runtime_error(std::string("TAE_PFKS_GEMM must be g6, s16, w32 or w16, optionally with :all, not '") +
+                                     gm + "'");
+        if (colon) pf_kl_min_ = 0;
     }
     if (pf_kl_) {  // K-layout key rows (limbs in K) and the per-column offset correction
         kp_pf_kl_ = ((p_.K() + 1) * pf_slots_.S + ksgemm::TK - 1) / ksgemm::TK * ksgemm::TK;
@@ -1470,8 +1497,26 @@ void Engine::pfks_into_ggsw(const uint64_t *d_big, uint64_t *d_ggsw, size_t B, i
         const long out_stride = (long)p_.cbs_l * ncols;
         const long ntiles = ((long)ncols * 8 + ksgemm::BTN - 1) / ksgemm::BTN;
         uint64_t *dst = d_ggsw + (size_t)(level - 1) * ncols;
-        ksgemm::gemm_g6<6, kG6WM, true><<<(unsigned)(mt * ntiles), 256 * kG6WM, ksgemm::gemm_g6_lds<kG6WM>(), stream_>>>(
-            d_digits_, d_pf_bt_kl_, kp_pf_kl_, mt, ncols, dst, out_stride, (long)B, d_pf_corr_);
+        const unsigned grid = (unsigned)(mt * ntiles);
+        const size_t lds = ksgemm::gemm_g6_lds<kG6WM>();
+        switch (pf_gemm_) {
+        case 1:
+            ksgemm::gemm_g7<true, 4><<<grid, 1024, lds, stream_>>>(d_digits_, d_pf_bt_kl_, kp_pf_kl_, mt, ncols, dst,
+                                                                   out_stride, (long)B, d_pf_corr_);
+            break;
+        case 2:
+            ksgemm::gemm_g7<false, 2><<<grid, 512, lds, stream_>>>(d_digits_, d_pf_bt_kl_, kp_pf_kl_, mt, ncols, dst,
+                                                                   out_stride, (long)B, d_pf_corr_);
+            break;
+        case 3:
+            ksgemm::gemm_g7<true, 2><<<grid, 512, lds, stream_>>>(d_digits_, d_pf_bt_kl_, kp_pf_kl_, mt, ncols, dst,
+                                                                  out_stride, (long)B, d_pf_corr_);
+            break;
+        default:
+            ksgemm::gemm_g6<6, kG6WM, true><<<grid, 256 * kG6WM, lds, stream_>>>(
+                d_digits_, d_pf_bt_kl_, kp_pf_kl_, mt, ncols, dst, out_stride, (long)B, d_pf_corr_);
+        }
+        last_pfks_kernel_ = kPfGemmNames[pf_gemm_];
         if (clamp) {
             const long pf_blk = (long)(K + 1) * p_.pfks_l * glwe;
             ksgemm::pfks_clamp_fixup<<<(unsigned)((B + 3) / 4), 256, 0, stream_>>>(
@@ -1495,8 +1540,10 @@ void Engine::pfks_into_ggsw(const uint64_t *d_big, uint64_t *d_ggsw, size_t B, i
         ksgemm::gemm_g6<6, 4><<<(unsigned)(mt4 * ntiles), 1024, ksgemm::gemm_g6_lds<4>(), stream_>>>(
             d_digits_, d_pf_bt_, kp_pf_, mt4, ncols, dst, out_stride, (long)B);
         HIPC(hipGetLastError());
+        last_pfks_kernel_ = "rows";
         return;
     }
+    last_pfks_kernel_ = "u64";
     dim3 grid((unsigned)((glwe + kThreads - 1) / kThreads), (unsigned)(p_.k + 1), (unsigned)((B + PF_CT - 1) / PF_CT));
     pfks_kernel<<<grid, kThreads, 0, stream_>>>(d_big, d_ggsw, d_pfpksk_, B, p_.K(), glwe, p_.pfks_l, p_.pfks_b,
                                                 p_.cbs_l, level, p_.k);

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "kslots.hpp"
 
@@ -644,6 +645,199 @@ __global__ void __launch_bounds__(256 * WM, 1)
             const long b = b0 + (q & 3) + 8 * (q >> 2) + 4 * h;
             if (j == 0 && col < ncols && b < B) out[b * out_stride + col] = 0 - v;
         }
+    }
+}
+
+// ---- gemm_g7: gemm_g6<.., 4, true> with the MFMA shape and the wave tile as parameters ----
+// Same operands, 384 x 256 workgroup tile, ring, swizzle and tile order as the K-layout gemm_g6; the same
+// u64 words (every i32 partial sum is exact whatever the order of its terms).
+// - S16: v_mfma_i32_16x16x64_i8 instead of 32x32x32.  Lane l (r16 = l & 15, g = l >> 4) holds
+//   A[r16][16 g + t], B[16 g + t][r16]: one 16-byte chunk of a row's 64-byte K step, so a fragment is again
+//   one ds_read_b128 and a wave reads as many per step as with the 32 x 32 shape.  C reg q holds
+//   C[4 g + q][r16].  The rows of a 16-row tile are permuted over the MFMA rows (f16 below) so that the reads
+//   stay free of bank conflicts under the fixed swizzle.
+// - WNW waves along N (4 along M): WNW = 4 is the 96 x 64 wave tile of gemm_g6 (1024 threads); WNW = 2
+//   gives 8 waves of 96 x 128 (512 threads, two waves per SIMD, accumulators in 192 registers): 6 + 8
+//   fragment reads for 24 MFMAs (32 x 32) per step against 6 + 4 for 12, and the 40 DMA pieces of a stage
+//   5 per wave.
+template <bool S16, int WNW>
+__global__ void __launch_bounds__(256 * WNW, 1)
+    gemm_g7(const int8_t *__restrict__ A, const int8_t *__restrict__ Bt, int Kp, long mtiles, int ncols,
+            uint64_t *__restrict__ out, long out_stride, long B, const uint64_t *__restrict__ corr) {
+    constexpr int TMR = 384, NW = 4 * WNW, WTN = BTN / WNW;  // tile rows, waves, wave-tile columns
+    constexpr int SA = TMR * G4K, SAB = (TMR + BTN) * G4K;
+    constexpr int NPA = TMR / 16, NP = NPA + BTN / 16;
+    constexpr int TI = S16 ? 6 : 3, TJ = S16 ? WTN / 16 : WTN / 32;  // MFMA tiles of a wave
+    extern __shared__ __align__(16) int8_t smem_g[];
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int wm = wave / WNW, wn = wave % WNW;
+    const long ntiles = (((long)ncols * 8) + BTN - 1) / BTN;
+    constexpr long GN = 8;
+    // XCD-aware grouped tile order, as in gemm_g6
+    const long nwg = (long)gridDim.x, q8 = nwg >> 3, r8 = nwg & 7, x8 = blockIdx.x & 7;
+    const long bid = x8 * q8 + min(x8, r8) + (blockIdx.x >> 3);
+    const long gsz = GN * mtiles;
+    const long ng = bid / gsz, rr = bid - ng * gsz;
+    const long gw = min(GN, ntiles - ng * GN);
+    const long mt = rr / gw, nt = ng * GN + (rr - (rr / gw) * gw);
+    const long row0 = mt * TMR;
+    const long col8_0 = nt * BTN;
+    const long N8 = (long)ncols * 8;
+
+    const int nk = Kp / G4K;
+    // DMA sources: a wave-uniform base (tile origin + K step) plus a 32-bit lane offset per piece.  The 16-wave
+    // form (128 registers, 96 of them accumulators) recomputes the offsets from the lane number in every step:
+    // kept across the loop, the address pairs of a wave's three pieces spill.
+    const int8_t *a_tile = A + op_off(row0, 0, Kp, true), *b_tile = Bt + op_off(col8_0, 0, Kp, true);
+    auto stage = [&](int st, int ks) {
+        const long kofs = (long)ks * 2 * G4K;  // op_off of K step ks: 128 bytes per row pair and step
+        int8_t *base = smem_g + st * SAB;
+        int ln = lane;
+        if constexpr (WNW == 4) asm volatile("" : "+v"(ln));  // opaque: nothing derived from it is hoisted
+        const int lrow = ln >> 2, lch = ln & 3;
+#pragma unroll
+        for (int p = wave; p < NP; p += NW) {
+            const int row = 16 * p + lrow;
+            const int8_t *src;
+            if (p < NPA) {
+                const uint32_t off = (uint32_t)op_off(row, 0, Kp, true) + 16 * g4_swz(row, lch);
+                src = a_tile + kofs + off;
+            } else {
+                const int rb = row - TMR;
+                const int br = (int)min((long)rb, N8 - 1 - col8_0);  // rows past the last column feed unstored outputs
+                const uint32_t off = (uint32_t)op_off(br, 0, Kp, true) + 16 * g4_swz(rb, lch);
+                src = b_tile + kofs + off;
+            }
+            g4_glds(src, base + 16 * p * G4K);
+        }
+    };
+    const int per_wave = (NP / NW) + (wave < NP % NW ? 1 : 0);  // 5 (8 waves); 3 or 2 (16 waves)
+    auto wait_steps = [&](int keep) {
+        switch (per_wave * keep) {
+        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
+        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
+        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+        }
+    };
+    static_assert(G4S == 4, "wait_steps lists the vmcnt values of a 4-stage ring");
+
+    using acc_t = typename std::conditional<S16, v4i, v16i>::type;
+    acc_t acc[TI][TJ];
+#pragma unroll
+    for (int a = 0; a < TI; a++)
+#pragma unroll
+        for (int b = 0; b < TJ; b++) acc[a][b] = acc_t{0};
+
+    const int r = lane & 31, h = lane >> 5;    // 32 x 32 shape: row / column, K half
+    // 16 x 16 shape: MFMA row / column r16 and K quarter g16 of the lane.  MFMA row i of a tile is tile row
+    // f16 = 4 sigma(i >> 2) + (i & 3) with sigma = (0, 2, 3, 1), for A and B alike: a ds_read_b128 is served in
+    // the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ..., which mix two K quarters, and with rows in
+    // natural order the swizzled chunks of lanes 0-3 and 20-23 (and 12-15 and 24-27) share their banks.
+    const int r16 = lane & 15, g16 = lane >> 4;
+    const int f16 = 4 * ((0x78 >> (2 * (r16 >> 2))) & 3) + (r16 & 3), s16 = (0x78 >> (2 * g16)) & 3;
+    for (int ks = 0; ks < G4S - 1 && ks < nk; ks++) stage(ks, ks);
+    for (int ks = 0; ks < nk; ks++) {
+        wait_steps(min(G4S - 2, nk - 1 - ks));
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        if (ks + G4S - 1 < nk) stage((ks + G4S - 1) % G4S, ks + G4S - 1);
+        const int8_t *a_s = smem_g + (ks % G4S) * SAB, *b_s = a_s + SA;
+        if constexpr (S16) {
+            // B fragments up front, the A fragments one row of tiles ahead of the MFMAs that use them.  The 16
+            // waves have 128 registers, 96 of them accumulators: the scheduling barriers keep the A reads from
+            // being hoisted (all 10 fragments live at once spill in this loop).
+            v4i fa[TI], fb[TJ];
+            auto read_a = [&](int ti) {
+                const int row = wm * 96 + ti * 16 + f16;
+                fa[ti] = *reinterpret_cast<const v4i *>(a_s + row * G4K + 16 * g4_swz(row, g16));
+            };
+#pragma unroll
+            for (int tj = 0; tj < TJ; tj++) {
+                const int row = wn * WTN + tj * 16 + f16;
+                fb[tj] = *reinterpret_cast<const v4i *>(b_s + row * G4K + 16 * g4_swz(row, g16));
+            }
+            read_a(0);
+#pragma unroll
+            for (int ti = 0; ti < TI; ti++) {
+                if (ti + 1 < TI) read_a(ti + 1);
+                if constexpr (WNW == 4) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int tj = 0; tj < TJ; tj++)
+                    acc[ti][tj] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ti], fb[tj], acc[ti][tj], 0, 0, 0);
+                if constexpr (WNW == 4) __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            // both 32-byte halves are read up front: the second half lands while the first half's MFMAs issue
+            v4i fa[2][TI], fb[2][TJ];
+#pragma unroll
+            for (int kk = 0; kk < G4K / 32; kk++) {
+#pragma unroll
+                for (int m = 0; m < TI; m++) {
+                    const int row = wm * 96 + m * 32 + r;
+                    fa[kk][m] = *reinterpret_cast<const v4i *>(a_s + row * G4K + 16 * g4_swz(row, 2 * kk + h));
+                }
+#pragma unroll
+                for (int tj = 0; tj < TJ; tj++) {
+                    const int row = wn * WTN + tj * 32 + r;
+                    fb[kk][tj] = *reinterpret_cast<const v4i *>(b_s + row * G4K + 16 * g4_swz(row, 2 * kk + h));
+                }
+            }
+#pragma unroll
+            for (int kk = 0; kk < G4K / 32; kk++)
+#pragma unroll
+                for (int m = 0; m < TI; m++)
+#pragma unroll
+                    for (int tj = 0; tj < TJ; tj++)
+                        acc[m][tj] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[kk][m], fb[kk][tj], acc[m][tj], 0, 0, 0);
+        }
+    }
+
+    // Epilogue as in the K-layout gemm_g6: each 32-row block of the wave tile goes through this wave's part
+    // of the idle ring, E[row][column] with rows padded to WTN + 4 dwords, then every lane reads the 8 key
+    // limbs of whole outputs (2 x b128), recombines them and stores.
+    constexpr int ES = WTN + 4;
+    static_assert(NW * 32 * ES * 4 <= G4S * SAB, "epilogue fits the ring");
+    __syncthreads();  // every wave is done with the ring
+    int *E = reinterpret_cast<int *>(smem_g) + wave * 32 * ES;
+    const long b0 = row0 + wm * 96;
+    const long colb = (col8_0 + wn * WTN) >> 3;  // first key column of this wave
+#pragma unroll
+    for (int m = 0; m < 3; m++) {
+        if constexpr (S16) {
+#pragma unroll
+            for (int t2 = 0; t2 < 2; t2++)
+#pragma unroll
+                for (int tj = 0; tj < TJ; tj++)
+#pragma unroll
+                    for (int q = 0; q < 4; q++)
+                        E[(t2 * 16 + 4 * s16 + q) * ES + tj * 16 + f16] = acc[2 * m + t2][tj][q];
+        } else {
+#pragma unroll
+            for (int tj = 0; tj < TJ; tj++)
+#pragma unroll
+                for (int q = 0; q < 16; q++) E[((q & 3) + 8 * (q >> 2) + 4 * h) * ES + tj * 32 + r] = acc[m][tj][q];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-local hand-off
+#pragma unroll
+        for (int k = 0; k < WTN / 16; k++) {
+            const int row = lane & 31, g = (lane >> 5) + 2 * k;  // g: 8-column group = key column
+            const v4i lo = *reinterpret_cast<const v4i *>(E + row * ES + 8 * g);
+            const v4i hi = *reinterpret_cast<const v4i *>(E + row * ES + 8 * g + 4);
+            uint64_t v = 0;
+#pragma unroll
+            for (int jj = 0; jj < 4; jj++) {
+                v += (uint64_t)(int64_t)lo[jj] << (8 * jj);
+                v += (uint64_t)(int64_t)hi[jj] << (8 * (jj + 4));
+            }
+            const long b = b0 + 32 * m + row, col = colb + g;
+            if (col < ncols && b < B) out[b * out_stride + col] = 0 - (v + corr[col]);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next m overwrites
     }
 }
 

@@ -49,6 +49,7 @@ EXPORTED = [
     "tae_aesm_key_schedule_raw", "tae_aesm_decrypt_key_raw", "tae_aesm_encrypt_blocks_raw",
     "tae_aesm_decrypt_blocks_raw", "tae_aesm_ctr_plan", "tae_aesm_ctr_transcipher_raw",
     "tae_aesm_cbc_transcipher_raw", "tae_aesm_key_schedule", "tae_aesm_ctr_transcipher", "tae_aesm_cbc_transcipher",
+    "tae_last_pfks_kernel",
 ]
 TAE_DRIVER_GAL_MUL, TAE_DRIVER_SBOX_PBS = 0, 1
 TAE_KEYS_CLIENT, TAE_KEYS_SERVER = 1, 2
@@ -194,6 +195,7 @@ def lib() -> C.CDLL:
         "tae_last_stage_times_v2": ([vp, C.POINTER(C.c_float)], C.c_int),
         "tae_last_stage_times_v3": ([vp, C.POINTER(C.c_double)], C.c_int),
         "tae_last_stage_times_v4": ([vp, C.POINTER(C.c_double)], C.c_int),
+        "tae_last_pfks_kernel": ([vp, C.c_char_p, sz], C.c_int),
         "tae_generate_multivariate_luts": ([C.c_int, C.c_int, C.c_int, vp, vp, sz], C.c_int),
         "tae_xor_batch": ([vp, vp, vp, sz, vp, vp, vp, C.c_int], C.c_int),
         "tae_keys_save": ([C.c_char_p, C.c_int, vp, vp, vp, vp], C.c_int),

@@ -216,6 +216,13 @@ class FheContext:
             d["pbs_clock_ghz"], d["pbs_clock_launches"] = arr[10], int(arr[11])
         return d
 
+    def last_pfks_kernel(self) -> str:
+        """The kernel of this context's last private functional keyswitch: "g6", "s16", "w32", "w16" (K-layout
+        GEMMs, TAE_PFKS_GEMM), "rows", "u64" or "none"."""
+        buf = C.create_string_buffer(16)
+        check(lib().tae_last_pfks_kernel(self._h, buf, len(buf)))
+        return buf.value.decode()
+
     def xor_batch(self, lhs: np.ndarray, rhs: np.ndarray, lhs_noise_sq=None, rhs_noise_sq=None):
         """BitXorAssign over whole bit arrays (xor_state, data_model.rs:270-274): lhs += rhs in place
         (host arrays [count][lwe]); with squared noise levels given, NoiseTooBig is enforced and the
