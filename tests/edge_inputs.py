@@ -15,6 +15,9 @@ Every value here is an ordinary torus word or key word.  The edges aimed at:
 Why the key holds -1 as well: the signed decomposer never emits -2^(B-1) at its top level (decompose(2^63) is
 [+2^(B-1), 0, ...]), so a GGSW of 0 or 1 turns a difference of 2^63 into a tail input of +1/2 only, and the
 saturation is not reached.  A GGSW of -1 multiplies the same digit by -2^(64-B): the tail input is -1/2.
+
+The second half of the file holds the crafted keys and inputs of the integer keyswitches (test_gpu_ks_edges.py,
+pinned by test_ks_edge_inputs.py); see the comment there.
 """
 import numpy as np
 
@@ -168,3 +171,286 @@ def crafted_ggsw(params: dict) -> np.ndarray:
     """A GGSW-shaped array [cbs_l (k+1) (k+1) N] made of GGSW_EDGE_WORDS, repeated."""
     k, N = params["k"], params["N"]
     return np.resize(GGSW_EDGE_WORDS, params["cbs_l"] * (k + 1) * (k + 1) * N).copy()
+
+
+# ---- integer keyswitches (ksgemm.hpp): crafted keys, decomposer edges, saturating rows ------------------------
+# Shared by test_gpu_ks_edges.py (GPU against the oracle's u64 loops) and test_ks_edge_inputs.py (CPU pins).
+# A keyswitch is out = body - sum_kd d[kd] KEY[kd][col] mod 2^64.  The int8 GEMMs split d into signed limbs and
+# KEY into 8 balanced byte limbs and rely on every i32 partial sum being exact; under a real (uniform) key those
+# sums are random walks far below the design bounds, and key limb carry chains stay short.  The keys below are
+# plain u64 arrays in the layouts of the KSK [K][ks_l][n+1] and the PFPKSK [k+1][K+1][pfks_l][(k+1)N]
+# ([n][pfks_l][(k+1)N] for the shortint_1bit packing key); they decrypt nothing and need not.
+
+# the (base_log, levels) of every integer keyswitch of the six parameter sets: (ks_b, ks_l) and (pfks_b, pfks_l)
+KS_SHAPES = ((3, 4), (2, 6), (2, 8), (6, 2), (24, 1), (16, 2), (12, 3))
+
+_LIMB_CHAIN_WORDS = (
+    0x7F7F7F7F7F7F7F80,  # every balanced limb -128, a carry out of every byte
+    0x7F7F7F7F7F7F7F7F,  # every limb +127
+    0x8080808080808080,  # limb 0 = -128, then (0x80 + 1) = -127 with a carry, all the way up
+    0xFFFFFFFFFFFFFFFF,  # limb 0 = -1, every other limb 0: the carry chain that wraps mod 2^64
+    0x8000000000000000,  # only limb 7, at -128 (its carry is the one dropped mod 2^64)
+    0x0000000000000080,  # limb 0 = -128, limb 1 = +1
+    0x00000000000000FF,  # limb 0 = -1, limb 1 = +1
+    0x0100000000000000,  # only limb 7, at +1: shifted out by any pre-shift
+    0,
+    1,
+    0x9E3779B97F4A7C15,  # three full-size words (fixed; any would do)
+    0xC2B2AE3D27D4EB4F,
+    0x165667B19E3779F9,
+)
+
+
+def limb_chain_words() -> list:
+    """Thirteen fixed u64 key words aimed at key_limbs (ksgemm.hpp) and at prep_key_kl's pre-shift v << 8 limb:
+    the carry chains above, zero, one and three full-size words."""
+    return list(_LIMB_CHAIN_WORDS)
+
+
+def pattern_key(length: int) -> np.ndarray:
+    """limb_chain_words() repeated to `length` (np.resize).  The period is 13, a prime that divides none of the
+    strides of the key layouts: n + 1 = 672, 680, 678, 666, 786, 641 of the keyswitch keys, glwe_len = 2560 and 3072 of the
+    (packing) functional keys, and the (K+1) pfks_l glwe_len blocks of the k + 1 functional keys
+    (test_ks_edge_inputs.py checks this from get_params).  Key row r = (i, l) therefore starts at phase
+    r * stride mod 13 with stride invertible mod 13: any 13 consecutive rows are 13 different rotations of the
+    list, so neighbouring columns, the ks_l / pfks_l <= 8 levels of one coefficient, neighbouring coefficients
+    and the k + 1 functional keys all differ, and an index mix-up between any of them changes the result."""
+    return np.resize(np.array(_LIMB_CHAIN_WORDS, dtype=U64), length).copy()
+
+
+SATURATING_WORD = 0x7F7F7F7F7F7F7F80
+
+
+def saturating_key(length: int) -> np.ndarray:
+    """Every word 0x7F7F7F7F7F7F7F80: all eight balanced limbs are -128, and v << 8, v << 16 (what prep_key_kl
+    feeds the K-layout GEMM) keep -128 from the shifted position up, with zeros below."""
+    return np.full(length, SATURATING_WORD, dtype=U64)
+
+
+def digits_np(x, base_log: int, levels: int) -> np.ndarray:
+    """numpy model of the closest-representable signed decomposition (tfhe-rs SignedDecomposer; oracle.decompose
+    is the reference, test_ks_edge_inputs.py pins this model on it): int64 [..., levels], index 0 the most
+    significant level."""
+    x = np.asarray(x, dtype=U64)
+    nrb = 64 - base_log * levels
+    s = x >> U64(nrb - 1)
+    s = (s + (s & U64(1))) >> U64(1)
+    mask = U64((1 << base_log) - 1)
+    out = np.zeros(x.shape + (levels,), dtype=np.int64)
+    with np.errstate(over="ignore"):  # res - 1 wraps on purpose
+        for lev in range(levels, 0, -1):
+            res = s & mask
+            s = s >> U64(base_log)
+            carry = (((res - U64(1)) | s) & res) >> U64(base_log - 1)
+            s = s + carry
+            out[..., lev - 1] = res.astype(np.int64) - (carry.astype(np.int64) << base_log)
+    return out
+
+
+def compose_digits(digits, base_log: int) -> int:
+    """sum_l d_l 2^(64 - base_log (l + 1)) mod 2^64, digits most significant first."""
+    return sum(int(d) << (64 - base_log * (l + 1)) for l, d in enumerate(digits)) & MASK64
+
+
+def decomposer_edge_words(base_log: int, levels: int) -> dict:
+    """Coefficients on the edges of the closest-representable signed decomposition with `levels` levels of base
+    B = 2^base_log, as {name: word}.  half = B / 2, w_l = 2^(64 - base_log l) is the weight of level l (1 = most
+    significant), u = w_levels the weight of the last one.  Digits are listed most significant first:
+
+      zero             0                                  all digits 0
+      all_ones         2^64 - 1                           rounds up and wraps: all digits 0
+      top_bit          2^63                               [+half, 0, ..]: the top level's upper end (it has no -half)
+      tie_below        u/2 - 1                            just under the rounding tie: all digits 0
+      tie              u/2                                the exact tie rounds up: [0, .., 0, 1]
+      tie_above        u/2 + 1                            [0, .., 0, 1]
+      half_keep_l      half w_l            (l >= 2)       residue exactly half at level l and the residue above it
+                                                          below half (its top bit, the one the carry rule reads,
+                                                          clear): digit l stays +half, every other digit 0
+      half_carry_l     half (w_(l-1) + w_l)  (l >= 2)     the same residue with that bit set: digit l is -half, and
+                                                          the carry makes the residue above half + 1, i.e. digit
+                                                          l-1 = -half + 1 with a carry of its own (digit l-2 = 1;
+                                                          dropped when l-1 is the top level)
+      ripple           half (w_1 + .. + w_L)              a carry out of every level:
+                                                          [-half + 1, .., -half + 1, -half] (two neighbouring levels
+                                                          can never both hold +half or both -half)
+      wrap_minus_unit  2^64 - u                           raw digits all B - 1: [0, .., 0, -1], the carry runs up
+                                                          through every level and off the top
+      top_min          (half + 1) w_1                     the top level's lower end: [-half + 1, 0, ..]
+      top_max_low_min  half w_1 + (half + 1) w_L  (L >= 2)  the top level's upper end over a negative last digit:
+                                                          [+half, 0, .., 0, 1, -half + 1] (L > 2: the carry stops at
+                                                          level L-1); with L = 2 it reaches the top level:
+                                                          [-half + 1, -half + 1]
+
+    With levels = 1 the per-level entries do not exist and ripple = top_bit.  Built from the
+    definition; edge_word_digits gives the digits named here, and test_ks_edge_inputs.py holds oracle.decompose
+    against them."""
+    B, L = base_log, levels
+    half = 1 << (B - 1)
+    w = lambda l: 1 << (64 - B * l)
+    u = w(L)
+    words = {"zero": 0, "all_ones": MASK64, "top_bit": 1 << 63, "tie_below": u // 2 - 1, "tie": u // 2,
+             "tie_above": u // 2 + 1}
+    for l in range(2, L + 1):
+        words[f"half_keep_{l}"] = half * w(l)
+        words[f"half_carry_{l}"] = half * (w(l - 1) + w(l))
+    words["ripple"] = (half * sum(w(l) for l in range(1, L + 1))) & MASK64
+    words["wrap_minus_unit"] = (1 << 64) - u
+    words["top_min"] = ((half + 1) * w(1)) & MASK64
+    if L >= 2:
+        words["top_max_low_min"] = (half * w(1) + (half + 1) * w(L)) & MASK64
+    return words
+
+
+def edge_word_digits(base_log: int, levels: int) -> dict:
+    """{name: digits, most significant first} as the docstring of decomposer_edge_words names them."""
+    L, half = levels, 1 << (base_log - 1)
+    unit = lambda l, v: [v if i == l else 0 for i in range(1, L + 1)]
+    d = {"zero": [0] * L, "all_ones": [0] * L, "top_bit": unit(1, half), "tie_below": [0] * L, "tie": unit(L, 1),
+         "tie_above": unit(L, 1)}
+    for l in range(2, L + 1):
+        d[f"half_keep_{l}"] = unit(l, half)
+        d[f"half_carry_{l}"] = [{l: -half, l - 1: -half + 1, l - 2: 1}.get(i, 0) for i in range(1, L + 1)]
+    d["ripple"] = [-half + 1] * (L - 1) + [-half] if L > 1 else [half]
+    d["wrap_minus_unit"] = unit(L, -1)
+    d["top_min"] = unit(1, -half + 1)
+    if L > 2:
+        d["top_max_low_min"] = [half] + [0] * (L - 3) + [1, -half + 1]
+    elif L == 2:
+        d["top_max_low_min"] = [-half + 1, -half + 1]
+    return d
+
+
+def edge_row(base_log: int, levels: int, length: int) -> np.ndarray:
+    """decomposer_edge_words repeated to `length` words."""
+    return np.resize(np.array(list(decomposer_edge_words(base_log, levels).values()), dtype=U64), length).copy()
+
+
+# -- limb models of the three int8 operand layouts --
+def key_limbs_np(words) -> np.ndarray:
+    """Balanced signed byte limbs of u64 words (ksgemm.hpp key_limbs): int64 [..., 8], least significant first,
+    sum_j limb_j 256^j = word mod 2^64."""
+    k = np.asarray(words, dtype=U64).copy()
+    out = np.zeros(k.shape + (8,), dtype=np.int64)
+    with np.errstate(over="ignore"):  # mod 2^64
+        for j in range(8):
+            s = (k & U64(0xFF)).astype(np.uint8).astype(np.int8).astype(np.int64)
+            out[..., j] = s
+            k = (k - s.astype(U64)) >> U64(8)
+    return out
+
+
+def balanced_limbs(d, bits: int, n: int) -> np.ndarray:
+    """n balanced signed limbs of `bits` bits of int64 digits, least significant first, the last taking the rest
+    (prep_digits / prep_digits3 / kl_next_limb): int64 [..., n]."""
+    d = np.asarray(d, dtype=np.int64).copy()
+    out = np.zeros(d.shape + (n,), dtype=np.int64)
+    for m in range(n - 1):
+        limb = ((d + (1 << (bits - 1))) & ((1 << bits) - 1)) - (1 << (bits - 1))
+        out[..., m] = limb
+        d = (d - limb) >> bits
+    out[..., n - 1] = d
+    return out
+
+
+def _kslots_fit(lo: int, hi: int):
+    """kslots.hpp kslots_fit: the fewest byte limbs n and the offset c that hold the digits [lo, hi]."""
+    for n in range(1, 5):
+        span = (256 ** n - 1) // 255
+        mn, mx = -128 * span, 127 * span
+        c = max(hi - mx, 0)
+        if lo - c >= mn:
+            return n, c
+    return None
+
+
+def kslots_plan(base_log: int, levels: int, allow_clamp: bool = True) -> dict:
+    """numpy-side mirror of kslots.hpp kslots_build (test_ks_edge_inputs.py holds it against what
+    tests/native/kslots_test.cpp prints for the compiled plan): per level the limb count, the digit offset and
+    whether +half is stored as -half; S the slots per coefficient."""
+    half = 1 << (base_log - 1)
+    nlimb, off, clamp = [], [], []
+    for l in range(levels):
+        lo, hi = (-half + 1 if l == 0 else -half), half
+        n, c = _kslots_fit(lo, hi)
+        cl = False
+        if allow_clamp and l > 0:
+            alt = _kslots_fit(lo, hi - 1)
+            if alt and alt[0] < n:
+                (n, c), cl = alt, True
+        nlimb.append(n)
+        off.append(c)
+        clamp.append(cl)
+    assert sum(nlimb) <= 8
+    return {"S": sum(nlimb), "nlimb": nlimb, "off": off, "clamp": clamp}
+
+
+LIMB_MODELS = ("bytes", "rows6", "kslots")
+
+
+def digit_limbs(digits, level: int, base_log: int, levels: int, limb_model: str) -> np.ndarray:
+    """The signed limbs the GEMM's A operand holds for level `level` (0 = most significant) digits, int64 [..., n]:
+      bytes   the digit itself, one byte (prep_digits<1, 8>: the LWE and the packing keyswitch)
+      rows6   three balanced 6-bit limbs (prep_digits3<6>: the PFKS row layout, one GEMM row per limb)
+      kslots  the level's byte limbs of (digit - offset), +half stored as -half on a clamped level
+              (prep_digits_kl: the PFKS K layout)"""
+    d = np.asarray(digits, dtype=np.int64)
+    if limb_model == "bytes":
+        return d[..., None]
+    if limb_model == "rows6":
+        return balanced_limbs(d, 6, 3)
+    assert limb_model == "kslots"
+    plan, half = kslots_plan(base_log, levels), 1 << (base_log - 1)
+    if plan["clamp"][level]:
+        d = np.where(d == half, -half, d)
+    return balanced_limbs(d - plan["off"][level], 8, plan["nlimb"][level])
+
+
+def saturating_coefficient(base_log: int, levels: int, limb_model: str) -> int:
+    """The coefficient whose digit limbs have the largest sum of absolute values under `limb_model`, found by
+    search: every digit of every level's range is split by digit_limbs, the two best digits per level and sign
+    are combined, and the best combination that the decomposer really produces (digits_np of the composed word
+    gives the same digits back) wins.  Limbs of one sign are preferred (and decide ties): against a constant key
+    the partial sum of a GEMM column is the signed sum of the limbs."""
+    import itertools
+    half = 1 << (base_log - 1)
+    best = None
+    for sign in (-1, 1):
+        cands = []
+        for l in range(levels):
+            d = np.arange(-half + 1 if l == 0 else -half, half + 1, dtype=np.int64)
+            limbs = digit_limbs(d, l, base_log, levels, limb_model)
+            score = np.where((limbs * sign >= 0).all(axis=-1), np.abs(limbs).sum(axis=-1), -1)
+            order = np.argsort(-score, kind="stable")[:2]
+            cands.append([(int(d[i]), int(score[i])) for i in order if score[i] >= 0])
+        for combo in sorted(itertools.product(*cands), key=lambda c: -sum(s for _, s in c)):
+            digits = [d for d, _ in combo]
+            x = compose_digits(digits, base_log)
+            if digits_np(U64(x), base_log, levels).tolist() == digits:
+                total = sum(s for _, s in combo)
+                if best is None or total > best[0]:
+                    best = (total, x)
+                break
+    assert best is not None
+    return best[1]
+
+
+def modelled_partial_sums(row, key_col, base_log: int, levels: int, limb_model: str) -> np.ndarray:
+    """int64 model of the i32 accumulators of one output (one ciphertext row against one key column): `row` holds
+    the n_coef input coefficients, key_col the u64 key words [n_coef][levels] of that column.  Returns the partial
+    sums the GEMM forms before its epilogue: [8] (bytes), [3][8] (rows6: one per digit-limb row) or [8] (kslots),
+    the last axis the key limb j."""
+    dig = digits_np(row, base_log, levels)                       # [n_coef][levels]
+    key_col = np.asarray(key_col, dtype=U64).reshape(len(dig), levels)
+    if limb_model == "kslots":
+        plan = kslots_plan(base_log, levels)
+        acc = np.zeros(8, dtype=np.int64)
+        for l in range(levels):
+            limbs = digit_limbs(dig[:, l], l, base_log, levels, limb_model)  # [n_coef][nlimb]
+            for m in range(plan["nlimb"][l]):
+                acc += limbs[:, m] @ key_limbs_np(key_col[:, l] << U64(8 * m))  # the pre-shifted key row
+        return acc
+    kl = key_limbs_np(key_col)                                   # [n_coef][levels][8]
+    acc = 0
+    for l in range(levels):
+        acc = acc + np.einsum("im,ij->mj", digit_limbs(dig[:, l], l, base_log, levels, limb_model), kl[:, l])
+    return acc[0] if limb_model == "bytes" else acc
