@@ -449,6 +449,11 @@ int tae_stage_pfks_ggsw(const tae_context *ctx, const uint64_t *big, size_t coun
                         uint64_t *ggsw, int mem);
 int tae_stage_ggsw_fourier(const tae_context *ctx, const uint64_t *ggsw, size_t count,
                            double *ggsw_f /*complex interleaved*/, int mem);
+/* ggsw_f [groups][n_in] Fourier GGSWs (selector bits, MSB first), out [groups][n_out][K+1].  With
+ * tree = max(0, n_in - log2 N), lut is [n_out][N << tree] words: 2^tree polynomials per output, chosen by the
+ * first `tree` GGSWs through a CMux tree (one polynomial per output while n_in <= log2 N).  The length is the
+ * same for TAE_MEM_HOST, where that many words are staged, and for a TAE_MEM_DEVICE pointer.  n_in < 1,
+ * n_out < 1 or tree > 16 return TAE_E_ARG before any device work. */
 int tae_stage_vertical_packing(const tae_context *ctx, const double *ggsw_f, size_t groups, int n_in,
                                const uint64_t *lut, int n_out, uint64_t *out, int mem);
 

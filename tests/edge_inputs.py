@@ -17,7 +17,8 @@ Why the key holds -1 as well: the signed decomposer never emits -2^(B-1) at its 
 saturation is not reached.  A GGSW of -1 multiplies the same digit by -2^(64-B): the tail input is -1/2.
 
 The second half of the file holds the crafted keys and inputs of the integer keyswitches (test_gpu_ks_edges.py,
-pinned by test_ks_edge_inputs.py); see the comment there.
+pinned by test_ks_edge_inputs.py); see the comment there.  The last part holds the selector rows and LUTs of the
+vertical packing's CMux tree (test_gpu_vp_tree.py, pinned by test_edge_inputs.py).
 """
 import numpy as np
 
@@ -454,3 +455,66 @@ def modelled_partial_sums(row, key_col, base_log: int, levels: int, limb_model: 
     for l in range(levels):
         acc = acc + np.einsum("im,ij->mj", digit_limbs(dig[:, l], l, base_log, levels, limb_model), kl[:, l])
     return acc[0] if limb_model == "bytes" else acc
+
+
+# ---- vertical packing of LUTs wider than one polynomial (the CMux tree) -----------------------------------------
+# Shared by test_gpu_vp_tree.py (GPU against oracle.vertical_packing) and test_edge_inputs.py (CPU pins).  With
+# n_in = log2 N + tree inputs a LUT output holds 2^tree polynomials; the first `tree` GGSWs (the selector's most
+# significant bits) choose the polynomial through a tree of CMuxes, the rest rotate it.  Selector rows are lists
+# of n_in values from {0, 1, -1}, MSB first, standing for the trivial GGSWs of those values.
+
+TREE_DEPTHS = (1, 2, 3)
+TREE_N_OUT = (1, 3)
+# (tree, n_out) of the 16 -> n LUT shape of the N = 1024 sets: a 64-polynomial base
+DEEP_TREE, DEEP_N_OUT = 6, 2
+
+# the leading (tree) entries of the mixed rows read differently backwards from depth 2 on, so that a tree that
+# takes its GGSWs in the wrong order selects another polynomial (test_edge_inputs.py checks it)
+_MIXED_BITS = (1, 0, 0, 1, 0, 1, 1, 0, 1, 1, 1, 0, 0, 1, 0, 1, 1, 0)
+_NEGATED_CYCLES = ((-1,), (-1, 1, 1, 0, 1, 1, 0, -1), (1, -1))
+
+
+def tree_lut_fn(n_out: int):
+    """f(selector) of the 0 / 2^63 tables: a fixed multiplicative hash, so that the bits of neighbouring entries,
+    and with them neighbouring polynomials of one output, differ."""
+    return lambda v: (((v + 1) * 0x9E3779B1 & 0xFFFFFFFF) >> 15) & ((1 << n_out) - 1)
+
+
+def tree_selector_rows(n_in: int) -> list:
+    """Three rows of {0, 1}: all zero, all one and a fixed word whose leading (tree) bits are 1, 0, 0, 1, 0, 1."""
+    assert n_in <= len(_MIXED_BITS)
+    return [[0] * n_in, [1] * n_in, list(_MIXED_BITS[:n_in])]
+
+
+def tree_negated_rows(n_in: int) -> list:
+    """Three rows of {0, 1, -1} with -1 at tree positions too.  For every depth in TREE_DEPTHS the selector of the
+    leaf level (position tree - 1) is non-zero in every row, and both 1 and -1 occur there among the rows: a leaf
+    difference of 2^63 becomes a tail input of +1/2 in one group and of -1/2 in another."""
+    return [[c[i % len(c)] for i in range(n_in)] for c in _NEGATED_CYCLES]
+
+
+def selector_value(row) -> int:
+    """The LUT entry a row of {0, 1} selects (MSB first)."""
+    v = 0
+    for b in row:
+        assert b in (0, 1)
+        v = 2 * v + b
+    return v
+
+
+def tree_mixed_lut(n_out: int, N: int, tree: int, seed: int) -> np.ndarray:
+    """[n_out][2^tree][N] (flattened): polynomial 1 of output 0 is the constant 2^62; of the others, numbered
+    q = j 2^tree + i, those with q % 3 == 2 alternate 2^62 and random words in runs of eight and the rest are random
+    full-size words.  Every polynomial is seeded by (seed, j, i), so all of them differ, and a leaf, pair, output
+    or group mix-up changes the result."""
+    cnt = 1 << tree
+    lut = np.zeros((n_out, cnt, N), dtype=U64)
+    for j in range(n_out):
+        for i in range(cnt):
+            q = j * cnt + i
+            lut[j, i] = random_words(np.random.default_rng([seed, j, i]), N)
+            if q == 1:
+                lut[j, i] = U64(1 << 62)
+            elif q % 3 == 2:
+                lut[j, i, (np.arange(N) // 8) % 2 == 0] = U64(1 << 62)
+    return lut.reshape(-1)

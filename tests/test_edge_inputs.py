@@ -179,3 +179,74 @@ def test_trivial_ggsw_selects_through_vertical_packing(oracle_mod, noiseless):
         assert aes_128.bits_to_u8([((b + (1 << 62)) & MASK) >> 63 for b in bodies]) == aes_128.SBOX[byte]
         if byte == 0:
             assert bodies == [int(lut[j * N]) for j in range(8)]
+
+
+# ---- the CMux tree of wide LUTs (test_gpu_vp_tree.py) ----
+def _tree_shapes(N):
+    return [(t, n) for t in E.TREE_DEPTHS for n in E.TREE_N_OUT] + ([(E.DEEP_TREE, E.DEEP_N_OUT)] if N == 1024 else [])
+
+
+@pytest.mark.parametrize("tree", E.TREE_DEPTHS)
+def test_tree_selection_order(oracle_mod, noiseless, tree):
+    """Under trivial selectors from {0, 1}, oracle.vertical_packing over a 2^tree-polynomial LUT has a zero mask
+    and decodes to f(selector): selectors MSB first, the first `tree` GGSWs choosing the polynomial."""
+    p, keys = noiseless
+    N, n_out = p["N"], 3
+    n_in = E.log2_exact(N) + tree
+    small = N << tree
+    f = E.tree_lut_fn(n_out)
+    lut = oracle_mod.generate_lut(N, n_in, n_out, f)
+    assert lut.size == n_out * small
+    spec = {b: keys.ggsw_to_fourier(E.trivial_ggsw(p, b)) for b in (0, 1)}
+    rows = E.tree_selector_rows(n_in)
+    assert len({tuple(r[:tree]) for r in rows}) == (3 if tree > 1 else 2)  # the groups differ in the tree bits
+    if tree > 1:  # and one of them reads differently backwards: the order of the tree's GGSWs matters
+        assert any(r[:tree] != r[:tree][::-1] for r in rows)
+    for row in rows:
+        gf = np.concatenate([spec[b] for b in row])
+        outs = [keys.vertical_packing(lut[j * small:(j + 1) * small], gf, n_in) for j in range(n_out)]
+        assert all(not o[:-1].any() for o in outs)
+        got = [((int(o[-1]) + (1 << 62)) & MASK) >> 63 for o in outs]
+        v = E.selector_value(row)
+        assert got == [(f(v) >> (n_out - 1 - j)) & 1 for j in range(n_out)], row
+        # the polynomial is chosen by the leading bits alone: entry v sits in polynomial v >> log2 N
+        assert int(lut[(v >> E.log2_exact(N)) * N + (v & (N - 1))]) == (((f(v) >> (n_out - 1)) & 1) << 63)
+
+
+@pytest.mark.parametrize("N", [512, 1024])
+@pytest.mark.parametrize("tree", E.TREE_DEPTHS)
+@pytest.mark.parametrize("n_out", E.TREE_N_OUT)
+def test_tree_negated_rows_reach_the_edge(oracle_mod, N, tree, n_out):
+    """The 0 / 2^63 table under the negated rows.  Every group's leaf-level selector (position tree - 1) is 1 or
+    -1 and both occur among the groups; the leaf-level nodes of every group and output combine polynomial pairs
+    (2i, 2i + 1), and at least one of those differences has a coefficient of exactly 2^63 (every other one is 0):
+    the tie digit, times the gadget of 1 or -1 a tail input of +1/2 or -1/2.  One level up the exact CMux values
+    are 0 / 2^63 again (2^63 = -2^63), so the same holds for the upper levels up to the transform's rounding."""
+    n_in = E.log2_exact(N) + tree
+    rows = E.tree_negated_rows(n_in)
+    assert all(set(r) <= {0, 1, -1} for r in rows)
+    assert {r[tree - 1] for r in rows} == {1, -1}
+    assert any(-1 in r[:tree] for r in rows) and any(-1 in r[tree:] for r in rows)
+    assert tree == 1 or any(r[:tree] != r[:tree][::-1] for r in rows)
+    lut = oracle_mod.generate_lut(N, n_in, n_out, E.tree_lut_fn(n_out)).reshape(n_out, 1 << tree, N)
+    assert np.isin(lut, [0, 1 << 63]).all()
+    for row in rows:            # the leaves are shared; the selector decides what a difference of 2^63 becomes
+        assert row[tree - 1] in (1, -1)
+        for j in range(n_out):
+            diff = lut[j, 1::2] - lut[j, 0::2]
+            assert np.isin(diff, [0, 1 << 63]).all()
+            assert (diff == np.uint64(1 << 63)).any(), (row, j)
+
+
+@pytest.mark.parametrize("N", [512, 1024])
+def test_tree_mixed_lut_polynomials_differ(N):
+    """Every polynomial of every output of the mixed LUT is different from every other, at every shape the GPU
+    tests use, and the constant 2^62, full-size random words and runs of both are all present."""
+    for tree, n_out in _tree_shapes(N):
+        lut = E.tree_mixed_lut(n_out, N, tree, 7).reshape(n_out << tree, N)
+        assert len({row.tobytes() for row in lut}) == len(lut), (tree, n_out)
+        assert (lut[1] == np.uint64(1 << 62)).all()
+        assert (lut[0] >> np.uint64(60)).max() == 15 and len(np.unique(lut[0])) > N // 2
+        if len(lut) > 2:  # depth 1 with one output has two polynomials only
+            runs = lut[2]
+            assert (runs[:8] == np.uint64(1 << 62)).all() and not (runs[8:16] == np.uint64(1 << 62)).any()

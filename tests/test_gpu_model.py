@@ -8,6 +8,7 @@ import pytest
 
 import tfhe_aes
 from tfhe_aes import Cleartext, aes_128
+from tests import edge_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -104,21 +105,45 @@ def test_increment_8bit_adder(keys):
 def test_cmux_tree_lut_bit_exact(keys, oracle_keys):
     """A LUT with 10 > log2(512) inputs (generate_lookup_table :274-289 with a WopbsLUTBase of 2
     polynomials per output): the device CMux tree over the first GGSW, then the blind rotation over
-    the other 9 (tfhe-rs vertical_packing), equal to the oracle and decrypting to f(word)."""
+    the other 9 (tfhe-rs vertical_packing), equal to the oracle and decrypting to f(word).  f is a hash
+    of the whole word, so the two polynomials of every output differ and the tree's CMux decides the result."""
     ck, ctx = keys
-    f = lambda v: ((v * 37) ^ (v >> 3)) & 7
+    f = edge_inputs.tree_lut_fn(3)
     lut = ctx.generate_lookup_table(10, 3, f)
+    polys = lut.as_array().reshape(3, 2, 512)
+    assert all(not np.array_equal(polys[j, 0], polys[j, 1]) for j in range(3))
     for word, start in ((0b1011001110, 70_000), (0b0100110001, 70_100)):
         cts = ck.encrypt_bits_raw([(word >> (9 - i)) & 1 for i in range(10)], start_index=start)
         out = ctx.circuit_bootstrap_raw(cts.reshape(1, 10, -1), lut)
         got = ck.decrypt_bits_raw(out[0])
         assert [int(b) for b in got] == [(f(word) >> (2 - j)) & 1 for j in range(3)], bin(word)
-    assert np.array_equal(out[0], oracle_keys.circuit_bootstrap(cts, lut.as_array(), 3))
+        assert np.array_equal(out[0], oracle_keys.circuit_bootstrap(cts, lut.as_array(), 3)), bin(word)
 
 
-def test_multivariate_multivalues_xor_8bit():
+def test_cmux_tree_two_groups_bit_exact(keys, oracle_keys):
+    """11 inputs (a depth-2 tree, four polynomials per output), two words in one batched call: the tree levels
+    read and write per-group node arrays under real noise.  Both groups decrypt to f(word) and equal the
+    oracle word for word.  f is a hash of the whole word: the four polynomials of every output differ, and
+    the words differ in both tree bits."""
+    ck, ctx = keys
+    f = edge_inputs.tree_lut_fn(3)
+    lut = ctx.generate_lookup_table(11, 3, f)
+    polys = lut.as_array().reshape(3, 4, 512)
+    assert all(len({polys[j, i].tobytes() for i in range(4)}) == 4 for j in range(3))
+    words = (0b10110011101, 0b01001100010)
+    cts = np.stack([ck.encrypt_bits_raw([(w >> (10 - i)) & 1 for i in range(11)], start_index=76_000 + 100 * g)
+                    for g, w in enumerate(words)])
+    out = ctx.circuit_bootstrap_raw(cts, lut)
+    for g, word in enumerate(words):
+        got = ck.decrypt_bits_raw(out[g])
+        assert [int(b) for b in got] == [(f(word) >> (2 - j)) & 1 for j in range(3)], bin(word)
+        assert np.array_equal(out[g], oracle_keys.circuit_bootstrap(cts[g], lut.as_array(), 3)), bin(word)
+
+
+def test_multivariate_multivalues_xor_8bit(oracle_mod):
     """test_multivariate_multivalues_xor_8bit (:626-659): params_sqrd_lvl_1 (N = 1024), a 16 -> 8 LUT
-    b1 ^ b2 over a 64-polynomial WopbsLUTBase (6-level CMux tree + 10-step blind rotation)."""
+    b1 ^ b2 over a 64-polynomial WopbsLUTBase (6-level CMux tree + 10-step blind rotation).  The eight raw
+    outputs equal the oracle's (the generic path's only run with cbs_b = 10, and of depth 6 under noise)."""
     from tests.conftest import SEED
     ck, keys_raw = tfhe_aes.generate_keys_raw(tfhe_aes.PARAMS_SQRD_LVL_1, SEED, threads=16)
     ctx = tfhe_aes.context_from_raw(tfhe_aes.PARAMS_SQRD_LVL_1, keys_raw, device=0)
@@ -129,6 +154,11 @@ def test_multivariate_multivalues_xor_8bit():
     bits = [ck.encrypt(Cleartext(b)) for b in u16_to_bits(word)]
     out = ctx.circuit_bootstrap(bits, tv)
     assert aes_128.bits_to_u8([ck.decrypt(b).value for b in out]) == xor_fn(word)
+    p = tfhe_aes.get_params(tfhe_aes.PARAMS_SQRD_LVL_1)
+    big = p["k"] * p["N"] + 1
+    ok = oracle_mod.Keys(oracle_mod.PARAMS_SQRD_LVL_1, None, raw=keys_raw)
+    ref = ok.circuit_bootstrap(np.stack([b.data(big) for b in bits]), tv.as_array(), 8)
+    assert np.array_equal(np.stack([b.data(big) for b in out]), ref)
 
 
 def test_light_gal_mul(keys, golden):

@@ -1123,12 +1123,18 @@ int tae_stage_vertical_packing(const tae_context *ctx, const double *ggsw_f, siz
     return guarded([&] {
         require(ctx && ggsw_f && lut && out, "null");
         const auto &p = ctx->ctx->params();
+        require(n_in >= 1 && n_out >= 1, "n_in and n_out must be at least 1");
+        int log_n = 0;
+        while ((1 << log_n) < p.N) log_n++;
+        // n_in > log2 N: the LUT of every output holds 2^tree polynomials (the CMux tree's leaves)
+        const int tree = std::max(0, n_in - log_n);
+        require(tree <= 16, "n_in exceeds log2 N + 16");
         staged(
             ctx, ggsw_f, groups * n_in * p.cbs_ggsw_fourier_len() * 16, out, groups * n_out * p.big_len() * 8, mem,
             [&](const double *a, uint64_t *b, const uint64_t *l) {
                 ctx->ctx->engine().vertical_packing(reinterpret_cast<const tae::cplx *>(a), groups, n_in, l, n_out, b);
             },
-            lut, (size_t)n_out * p.N * 8);
+            lut, (size_t)n_out * ((size_t)p.N << tree) * 8);
     });
 }
 
