@@ -439,7 +439,48 @@ int tae_aes_sbox_pbs_key_schedule_raw(const tae_context *ctx, const uint64_t *ke
 #define TAE_DRIVER_SBOX_PBS 1 /* fhe_sbox_pbs */
 int tae_aes_noise_schedule_check(int param_set, int driver, int rounds);
 
+/* ---- packed ciphertext I/O (no reference counterpart) -------------------------
+ * A bit crosses the boundary as one coefficient of a GLWE instead of one big-key LWE: 40 bytes instead of 16392
+ * (20 in the 32-bit wire form).  TAE_PARAMS_SQRD_LVL_64 only: every other parameter set is TAE_E_PARAM.
+ * Format: `count` bits occupy G = ceil(count / N) GLWEs [G][(k+1)N] u64, mask polynomials first, body last;
+ * bit j sits at coefficient j % N of GLWE j / N, encoded bit << 63; unused coefficients of the last GLWE carry
+ * zero (plus noise).  count == 0 and null pointers are TAE_E_ARG before any device work.
+ *
+ * Uploads: the client encrypts 512 bits per GLWE (tae_encrypt_packed_raw) and the server sample-extracts them
+ * into big-key bits (tae_unpack_bits*), exactly: the big LWE key is the flattened GLWE key, no noise is added,
+ * and the GLWE noise is below a fresh bit's, so every extracted bit is a noise-level-1 bit.
+ * Results: the server packs any bits with the last private functional keyswitch key (plaintext polynomial -1)
+ * and a rotate-and-sum (tae_pack_bits*), the client decrypts the GLWEs (tae_decrypt_packed_raw).
+ * Server-packed GLWEs are terminal: they are for the client or for storage, the noise bookkeeping has no rule
+ * for them, and unpacking is defined for client-made GLWEs only. */
+/* G and G (k+1) N for `count` bits (either output may be NULL) */
+int tae_packed_len(int param_set, size_t count, size_t *glwes, size_t *words);
+/* bits[count] (0 / 1) -> glwes [G][(k+1)N]; GLWE g is encryption #start_index + g of the packed stream (its own
+ * index space: it shares no mask with the per-bit encryptions of the same index), TAE_INDEX_AUTO reserves G
+ * fresh indices from the key's counter */
+int tae_encrypt_packed_raw(const tae_client_key *ck, const uint8_t *bits, size_t count, uint64_t start_index,
+                           uint64_t *glwes);
+int tae_decrypt_packed_raw(const tae_client_key *ck, const uint64_t *glwes, size_t count, uint8_t *bits);
+/* the 32-bit wire form: narrow[i] = (wide[i] + 2^31) >> 32, and back wide[i] = narrow[i] << 32 (host arrays).
+ * Widen before tae_decrypt_packed_raw or tae_unpack_bits*; the rounding adds an error below 2^31 per word */
+int tae_packed_narrow(const uint64_t *wide, size_t words, uint32_t *narrow);
+int tae_packed_widen(const uint32_t *narrow, size_t words, uint64_t *wide);
+/* glwes [G][(k+1)N] -> bits [count][K+1]; without a GPU TAE_E_NODEV */
+int tae_unpack_bits_raw(const tae_context *ctx, const uint64_t *glwes, size_t count, uint64_t *bits, int mem);
+/* bits [count][K+1] -> glwes [G][(k+1)N]; without a GPU TAE_E_NODEV */
+int tae_pack_bits_raw(const tae_context *ctx, const uint64_t *bits, size_t count, uint64_t *glwes, int mem);
+/* handles: glwes is a host array; every bit comes out at noise level 1 with a fresh id */
+int tae_unpack_bits(const tae_context *ctx, const uint64_t *glwes, size_t count, tae_bit **out /*[count]*/);
+/* any valid bits, whatever their noise level; glwes is a host array */
+int tae_pack_bits(const tae_context *ctx, const tae_bit *const *bits, size_t count, uint64_t *glwes);
+/* ms of the keyswitch slice and the rotate-and-sum of the context's last tae_pack_bits* call (timing on);
+ * the per-stage slots of tae_last_stage_times* keep the values of the last batched call */
+int tae_last_pack_time(const tae_context *ctx, double *ms);
+
 /* ---- stage entry points (raw arrays; parity tests and profiling) ---------------------------- */
+/* the keyswitch of tae_pack_bits_raw before the sum: out [count][(k+1)N], row b the private functional
+ * keyswitch of bit b with key k (coefficient 0 of its body carries the bit's phase) */
+int tae_stage_pack_pfks(const tae_context *ctx, const uint64_t *bits, size_t count, uint64_t *out, int mem);
 int tae_stage_keyswitch(const tae_context *ctx, const uint64_t *in, size_t count, uint64_t *out, int mem);
 int tae_stage_pbs_shift_boolean(const tae_context *ctx, const uint64_t *small, size_t count, int level,
                                 uint64_t *big, int mem);

@@ -3,6 +3,7 @@
 // reference become status codes, HIP failures TAE_E_HIP.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -12,6 +13,7 @@
 #include "aes.hpp"
 #include "client.hpp"
 #include "engine.hpp"
+#include "glwe_pack.hpp"
 #include "cplx.hpp"
 #include "model.hpp"
 
@@ -1062,6 +1064,117 @@ int tae_s1_multivariate(const tae_context *ctx, const uint64_t *bits, size_t gro
     return guarded([&] {
         require(ctx && f_tables && (groups == 0 || (bits && out)), "null");
         if (groups) ctx->ctx->s1_multivariate_raw(bits, groups, nbits, f_tables, n_fn, out, mem == TAE_MEM_DEVICE);
+    });
+}
+
+/* ---- packed ciphertext I/O (glwe_pack.hpp) ---- */
+static tae::Params pack_params(int param_set) {
+    const tae::Params p = params_of(param_set);
+    if (p.id != tae::SQRD_LVL_64)
+        throw tae::ModelError{TAE_E_PARAM, "packed ciphertext I/O is built for params_sqrd_lvl_64 only"};
+    return p;
+}
+
+// A server call: the arguments first, then the device (a machine without one has no context to pass).
+static void require_pack_server(const tae_context *ctx, const void *in, size_t count, const void *out) {
+    require(in && out, "null");
+    require(count > 0, "a packed call needs at least one bit");
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0)
+        throw tae::ModelError{TAE_E_NODEV, "no GPU available: the HIP path has no CPU fallback"};
+    require(ctx != nullptr, "null");
+}
+
+int tae_packed_len(int param_set, size_t count, size_t *glwes, size_t *words) {
+    return guarded([&] {
+        const tae::Params p = pack_params(param_set);
+        require(count > 0, "a packed call needs at least one bit");
+        const size_t G = tae::glwe_pack::glwe_count(count, p.N);
+        if (glwes) *glwes = G;
+        if (words) *words = G * p.glwe_len();
+    });
+}
+
+int tae_encrypt_packed_raw(const tae_client_key *ck, const uint8_t *bits, size_t count, uint64_t start_index,
+                           uint64_t *glwes) {
+    return guarded([&] {
+        require(ck && bits && glwes, "null");
+        const tae::Params p = pack_params(ck->ck.p.id);
+        require(count > 0, "a packed call needs at least one bit");
+        for (size_t i = 0; i < count; i++) require(bits[i] < 2, "cleartext out of bounds");
+        const size_t G = tae::glwe_pack::glwe_count(count, p.N);
+        const uint64_t first = raw_index_range(ck, G, start_index);
+        for (size_t g = 0; g < G; g++)
+            ck->ck.encrypt_packed_at(bits + g * p.N, std::min<size_t>(p.N, count - g * p.N), first + g,
+                                     glwes + g * p.glwe_len());
+    });
+}
+
+int tae_decrypt_packed_raw(const tae_client_key *ck, const uint64_t *glwes, size_t count, uint8_t *bits) {
+    return guarded([&] {
+        require(ck && glwes && bits, "null");
+        const tae::Params p = pack_params(ck->ck.p.id);
+        require(count > 0, "a packed call needs at least one bit");
+        const size_t G = tae::glwe_pack::glwe_count(count, p.N);
+        for (size_t g = 0; g < G; g++)
+            ck->ck.decrypt_packed(glwes + g * p.glwe_len(), std::min<size_t>(p.N, count - g * p.N), bits + g * p.N);
+    });
+}
+
+int tae_packed_narrow(const uint64_t *wide, size_t words, uint32_t *narrow) {
+    return guarded([&] {
+        require(wide && narrow, "null");
+        for (size_t i = 0; i < words; i++) narrow[i] = tae::glwe_pack::narrow_word(wide[i]);
+    });
+}
+
+int tae_packed_widen(const uint32_t *narrow, size_t words, uint64_t *wide) {
+    return guarded([&] {
+        require(narrow && wide, "null");
+        for (size_t i = 0; i < words; i++) wide[i] = tae::glwe_pack::widen_word(narrow[i]);
+    });
+}
+
+int tae_unpack_bits_raw(const tae_context *ctx, const uint64_t *glwes, size_t count, uint64_t *bits, int mem) {
+    return guarded([&] {
+        require_pack_server(ctx, glwes, count, bits);
+        ctx->ctx->unpack_bits_raw(glwes, count, bits, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_pack_bits_raw(const tae_context *ctx, const uint64_t *bits, size_t count, uint64_t *glwes, int mem) {
+    return guarded([&] {
+        require_pack_server(ctx, bits, count, glwes);
+        ctx->ctx->pack_bits_raw(bits, count, glwes, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_unpack_bits(const tae_context *ctx, const uint64_t *glwes, size_t count, tae_bit **out) {
+    return guarded([&] {
+        require_pack_server(ctx, glwes, count, out);
+        emit(ctx->ctx->unpack_bits(glwes, count), out);
+    });
+}
+
+int tae_pack_bits(const tae_context *ctx, const tae_bit *const *bits, size_t count, uint64_t *glwes) {
+    return guarded([&] {
+        require_pack_server(ctx, bits, count, glwes);
+        ctx->ctx->require_pack(count);
+        ctx->ctx->pack_bits(unwrap(bits, count), glwes);
+    });
+}
+
+int tae_last_pack_time(const tae_context *ctx, double *ms) {
+    return guarded([&] {
+        require(ctx && ms, "null");
+        *ms = ctx->ctx->engine().last_times().pack;
+    });
+}
+
+int tae_stage_pack_pfks(const tae_context *ctx, const uint64_t *bits, size_t count, uint64_t *out, int mem) {
+    return guarded([&] {
+        require_pack_server(ctx, bits, count, out);
+        ctx->ctx->pack_pfks_raw(bits, count, out, mem == TAE_MEM_DEVICE);
     });
 }
 

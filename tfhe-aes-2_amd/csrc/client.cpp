@@ -89,6 +89,21 @@ void lwe_encrypt(const uint8_t seed[32], Purpose purpose, uint64_t idx, const ui
     out[dim] = body + msg + noise.next_gaussian_torus(sigma);
 }
 
+// acc[N] = sum_p A_p * S_p: the key is binary, so accumulate negacyclic rotations of A_p
+void glwe_mask_times_key(const uint64_t *mask, const uint64_t *S, int k, int N, uint64_t *acc) {
+    std::memset(acc, 0, sizeof(uint64_t) * N);
+    for (int p = 0; p < k; p++) {
+        const uint64_t *A = mask + (size_t)p * N;
+        const uint64_t *s = S + (size_t)p * N;
+        for (int i = 0; i < N; i++) {
+            if (!s[i]) continue;
+            const int split = N - i;
+            for (int j = 0; j < split; j++) acc[i + j] += A[j];
+            for (int j = split; j < N; j++) acc[i + j - N] -= A[j];
+        }
+    }
+}
+
 // GLWE encryption of plaintext polynomial `msg` (nullptr = 0) under the binary key S (k polys).
 void glwe_encrypt(const uint8_t seed[32], Purpose purpose, uint64_t idx, const uint64_t *S, int k,
                   int N, const uint64_t *msg, double sigma, uint64_t *out) {
@@ -97,18 +112,7 @@ void glwe_encrypt(const uint8_t seed[32], Purpose purpose, uint64_t idx, const u
     const size_t kN = (size_t)k * N;
     for (size_t t = 0; t < kN; t++) out[t] = mask.next_u64();
     uint64_t *body = out + kN;
-    std::memset(body, 0, sizeof(uint64_t) * N);
-    // body += A_p * S_p: the key is binary, so accumulate negacyclic rotations of A_p
-    for (int p = 0; p < k; p++) {
-        const uint64_t *A = out + (size_t)p * N;
-        const uint64_t *s = S + (size_t)p * N;
-        for (int i = 0; i < N; i++) {
-            if (!s[i]) continue;
-            const int split = N - i;
-            for (int j = 0; j < split; j++) body[i + j] += A[j];
-            for (int j = split; j < N; j++) body[i + j - N] -= A[j];
-        }
-    }
+    glwe_mask_times_key(out, S, k, N, body);
     for (int j = 0; j < N; j++) body[j] += (msg ? msg[j] : 0) + noise.next_gaussian_torus(sigma);
 }
 
@@ -135,6 +139,25 @@ void ClientKey::encrypt_small_bit_at(uint64_t bit, uint64_t index, uint64_t *out
 
 void ClientKey::encrypt_s1_bit_at(uint64_t bit, uint64_t index, uint64_t *out) const {
     lwe_encrypt(seed.data(), ENCRYPT, index, lwe_sk.data(), p.n, (bit & 1) << 62, p.lwe_std, out);
+}
+
+void ClientKey::encrypt_packed_at(const uint8_t *bits, size_t nbits, uint64_t index, uint64_t *glwe) const {
+    std::vector<uint64_t> msg(p.N, 0);
+    for (size_t j = 0; j < nbits; j++) msg[j] = encode_bit(bits[j] & 1);
+    // glwe_std is below a fresh bit's lwe_std, so an extracted bit is within noise level 1
+    glwe_encrypt(seed.data(), ENCRYPT_PACKED, index, glwe_sk.data(), p.k, p.N, msg.data(), p.glwe_std, glwe);
+}
+
+void ClientKey::glwe_phase(const uint64_t *glwe, uint64_t *phase) const {
+    glwe_mask_times_key(glwe, glwe_sk.data(), p.k, p.N, phase);
+    const uint64_t *body = glwe + (size_t)p.k * p.N;
+    for (int j = 0; j < p.N; j++) phase[j] = body[j] - phase[j];
+}
+
+void ClientKey::decrypt_packed(const uint64_t *glwe, size_t nbits, uint8_t *bits) const {
+    std::vector<uint64_t> ph(p.N);
+    glwe_phase(glwe, ph.data());
+    for (size_t j = 0; j < nbits; j++) bits[j] = (uint8_t)decode_bit(ph[j]);
 }
 
 uint64_t ClientKey::phase_small(const uint64_t *ct) const {

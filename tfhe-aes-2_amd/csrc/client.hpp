@@ -35,7 +35,8 @@ class ChaChaStream {
 };
 
 // Keygen stream purposes (DESIGN.md keygen spec).
-enum Purpose : uint64_t { LWE_SK = 1, GLWE_SK = 2, KSK = 3, BSK = 4, PFPKSK = 5, ENCRYPT = 6, ENCRYPT_INT = 7 };
+enum Purpose : uint64_t { LWE_SK = 1, GLWE_SK = 2, KSK = 3, BSK = 4, PFPKSK = 5, ENCRYPT = 6, ENCRYPT_INT = 7,
+                          ENCRYPT_PACKED = 8 };  // GLWE-packed bits, index = GLWE number
 constexpr uint64_t kCtStride = 1ull << 24;
 // Ciphertext #idx of purpose P starts its mask stream at ChaCha20(nonce = 2P | (idx >> 40) << 8,
 // counter = (idx mod 2^40) * 2^24) and its noise stream at nonce 2P + 1 (same high bits, same counter):
@@ -71,6 +72,13 @@ struct ClientKey {
     void encrypt_bit_at(uint64_t bit, uint64_t index, uint64_t *out) const;
     uint64_t phase(const uint64_t *ct) const;
     uint64_t decrypt_bit(const uint64_t *ct) const { return decode_bit(phase(ct)); }
+
+    // Packed ciphertext I/O (glwe_pack.hpp; 1-bit model): GLWE #index of the ENCRYPT_PACKED
+    // streams with nbits <= N bits, bit j encoded at coefficient j (the rest of the message is zero), glwe noise
+    void encrypt_packed_at(const uint8_t *bits, size_t nbits, uint64_t index, uint64_t *glwe) const;
+    // phase[N] = B - sum_p A_p S_p of one GLWE
+    void glwe_phase(const uint64_t *glwe, uint64_t *phase) const;
+    void decrypt_packed(const uint64_t *glwe, size_t nbits, uint8_t *bits) const;
 
     // 8-bit model (shortint_woppbs_8bit.rs:196-225): bits are LWEs under the SMALL key [n+1]
     void encrypt_small_bit_at(uint64_t bit, uint64_t index, uint64_t *out) const;

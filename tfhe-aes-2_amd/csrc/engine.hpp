@@ -30,6 +30,7 @@ void hip_check(hipError_t e, const char *what);
 // Timing of the most recent batched call, per stage (ms, HIP events on the engine stream).
 struct StageTimes {
     float keyswitch = 0, pbs = 0, pfks = 0, ggsw_fft = 0, vertical_packing = 0, extract = 0, linear = 0;
+    float pack = 0;  // the last pack_bits call (keyswitch slice + rotate-and-sum); the other slots keep their values
     int pbs_launches = 0;  // CBS-level PBS launches (one homomorphic_shift_boolean batch each)
     // the throughput blind-rotation kernel alone (br512x4 launches inside the PBS stage, without the
     // br512lat remainder) and the ciphertexts those launches processed
@@ -40,7 +41,7 @@ struct StageTimes {
     double pbs_clock_ghz_sum = 0;
     int pbs_clock_launches = 0;
 };
-enum Stage { ST_KS = 0, ST_PBS, ST_PFKS, ST_FFT, ST_VP, ST_EXTRACT, ST_LINEAR, ST_PBS_MAIN };
+enum Stage { ST_KS = 0, ST_PBS, ST_PFKS, ST_FFT, ST_VP, ST_EXTRACT, ST_LINEAR, ST_PBS_MAIN, ST_PACK };
 
 class Engine {
   public:
@@ -71,6 +72,15 @@ class Engine {
     // private functional keyswitches of level `level`: [B][K+1] -> GGSW rows of that level in
     // d_ggsw [B][cbs_l][k+1][(k+1)N]
     void pfks_into_ggsw(const uint64_t *d_big, uint64_t *d_ggsw, size_t B, int level);
+    // ---- packed ciphertext I/O (glwe_pack.hpp), params_sqrd_lvl_64 only ----
+    // sample extraction of `count` packed bits: GLWEs [ceil(count / N)][(k+1)N] -> big-key LWEs [count][K+1]
+    void unpack_bits(const uint64_t *d_glwes, size_t count, uint64_t *d_bits);
+    // the private functional keyswitch of key q = k alone (plaintext polynomial -1: coefficient 0 of the GLWE
+    // carries the LWE's phase): [B][K+1] -> [B][(k+1)N], on the path pfks_into_ggsw takes for B ciphertexts
+    void pack_pfks(const uint64_t *d_big, size_t B, uint64_t *d_out);
+    // GLWE g = sum_j X^j pack_pfks(bit g N + j): [count][K+1] -> [ceil(count / N)][(k+1)N], in chunks of at most
+    // glwe_pack::kChunkBits bits of keyswitch scratch
+    void pack_bits(const uint64_t *d_bits, size_t count, uint64_t *d_glwes);
     // fill_with_forward_fourier: [B][cbs_l][k+1][(k+1)N] -> [B][cbs_l][k+1][k+1][M]
     void ggsw_to_fourier(const uint64_t *d_ggsw, cplx *d_ggsw_f, size_t B);
     // vertical_packing for each group of n_in GGSWs: d_ggsw_f [G][n_in][...], d_lut
@@ -316,6 +326,10 @@ class Engine {
     size_t cap_digits_ = 0;
     int kp_pf_ = 0, kp_ks_ = 0;
     void prepare_mfma_keys();
+    void pfks_keys(const uint64_t *d_big, size_t B, int q0, int nq, uint64_t *dst, long out_stride);
+    void require_pack() const;
+    uint64_t *d_pack_ = nullptr;  // pack_bits: keyswitch outputs of one chunk [bits][(k+1)N]
+    size_t cap_pack_ = 0;
     // batched N=1024, k=2 blind rotation (br1024.hpp) for this set's (levels, base_log), or nullptr
     void (*br1024_pbs_)(const uint64_t *, int, const uint64_t *, int, const cplx *, int, uint64_t *, long, uint64_t,
                         uint64_t, const cplx *, const cplx *, const cplx *, const double *, uint64_t *) = nullptr;

@@ -31,6 +31,7 @@
 #include "ksgemm.hpp"
 #include "engine.hpp"
 #include "fft_device.hpp"
+#include "glwe_pack.hpp"
 
 namespace tae {
 
@@ -422,9 +423,10 @@ __global__ void __launch_bounds__(kThreads) keyswitch_kernel(const uint64_t *__r
 // ---------------------------------------------------------------------------------------------
 constexpr int PF_CT = 32, PF_CHUNK = 32;
 
-__global__ void __launch_bounds__(kThreads) pfks_kernel(const uint64_t *__restrict__ in, uint64_t *__restrict__ ggsw,
+// Key q = blockIdx.y of the gridDim.y keys at pfpksk goes to out[b * out_stride + q * glwe + col].
+__global__ void __launch_bounds__(kThreads) pfks_kernel(const uint64_t *__restrict__ in, uint64_t *__restrict__ out,
                                                      const uint64_t *__restrict__ pfpksk, size_t B, int K, int glwe,
-                                                     int pf_l, int pf_b, int cbs_l, int level, int k) {
+                                                     int pf_l, int pf_b, size_t out_stride) {
     __shared__ int32_t dig[PF_CT][PF_CHUNK][4];
     const int col = blockIdx.x * kThreads + threadIdx.x;
     const int q = blockIdx.y;
@@ -455,7 +457,48 @@ __global__ void __launch_bounds__(kThreads) pfks_kernel(const uint64_t *__restri
     }
     if (col < glwe)
         for (int c = 0; c < PF_CT; c++)
-            if (b0 + c < B) ggsw[(((b0 + c) * cbs_l + (level - 1)) * (k + 1) + q) * (size_t)glwe + col] = acc[c];
+            if (b0 + c < B) out[(b0 + c) * out_stride + (size_t)q * glwe + col] = acc[c];
+}
+
+// ---------------------------------------------------------------------------------------------
+// Packed ciphertext I/O (glwe_pack.hpp)
+// ---------------------------------------------------------------------------------------------
+// Sample extraction of every packed bit: grid (bit, polynomial); block (b, p < k) writes the N mask words of
+// polynomial p of LWE b, consecutive lanes on consecutive output words (the source run is A_p read backwards
+// from j, then from N - 1 with the sign flipped); block (b, k) writes the body.
+__global__ void __launch_bounds__(kThreads) unpack_bits_kernel(const uint64_t *__restrict__ glwes, uint64_t *__restrict__ out,
+                                                            size_t count, int k, int N) {
+    const size_t b = blockIdx.x;
+    const int p = blockIdx.y;
+    if (b >= count) return;
+    const size_t glwe = (size_t)(k + 1) * N;
+    const int j = (int)(b % (size_t)N);
+    const uint64_t *poly = glwes + (b / (size_t)N) * glwe + (size_t)p * N;
+    uint64_t *dst = out + b * ((size_t)k * N + 1);
+    if (p == k) {
+        if (threadIdx.x == 0) dst[(size_t)k * N] = poly[j];
+        return;
+    }
+    for (int i = threadIdx.x; i < N; i += blockDim.x) dst[(size_t)p * N + i] = glwe_pack::extract_word(poly, N, j, i);
+}
+
+// Rotate and sum: out GLWE g = sum_j X^j pf[g N + j] over the bits j of that GLWE (count_g = min(N, count - g N)).
+// Grid (GLWE, polynomial), one thread per output coefficient c; for each j the block reads the N words of one
+// polynomial of one keyswitch output as two contiguous runs.
+__global__ void __launch_bounds__(512) pack_rotate_sum_kernel(const uint64_t *__restrict__ pf, uint64_t *__restrict__ out,
+                                                             size_t count, int k, int N) {
+    const size_t g = blockIdx.x;
+    const int p = blockIdx.y;
+    const size_t glwe = (size_t)(k + 1) * N;
+    const size_t left = count - g * (size_t)N;
+    const int cnt = left < (size_t)N ? (int)left : N;
+    const uint64_t *src = pf + g * (size_t)N * glwe + (size_t)p * N;
+    for (int c = threadIdx.x; c < N; c += blockDim.x) {
+        uint64_t acc = 0;
+#pragma unroll 8
+        for (int j = 0; j < cnt; j++) acc += glwe_pack::rotate_word(src + (size_t)j * glwe, N, j, c);
+        out[g * glwe + (size_t)p * N + c] = acc;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1315,7 +1358,7 @@ Engine::~Engine() {
                     (void *)d_xsh_, (void *)d_xks_, (void *)d_xpbs_, (void *)d_ints_, (void *)d_s1_sbox_tv_,
                     (void *)d_s1_id_tv_, (void *)d_s1_in_, (void *)d_s1_out_, (void *)d_s1_pks_, (void *)d_s1_tv_, (void *)d_pf_flags_, (void *)d_clk_, (void *)d_lf_, (void *)d_acc_w_,
                     (void *)d_ctr_groups_, (void *)d_ctr_map_, (void *)d_key_of_, (void *)d_ctr_gslot_,
-                    (void *)d_ctr_blen_, (void *)d_ctr_bout_,
+                    (void *)d_ctr_blen_, (void *)d_ctr_bout_, (void *)d_pack_,
                     (void *)d_lut_inv32_, (void *)d_lut_inv8_, (void *)d_lut_mul32_, (void *)d_lut_id1_})
         if (q) hipFree(q);
     for (auto &e : ev_pool_) hipEventDestroy(e);
@@ -1474,8 +1517,19 @@ void Engine::pbs_shift_boolean(const uint64_t *d_small, uint64_t *d_big, size_t 
 }
 
 void Engine::pfks_into_ggsw(const uint64_t *d_big, uint64_t *d_ggsw, size_t B, int level) {
+    const size_t ncols = (size_t)(p_.k + 1) * p_.glwe_len();
+    pfks_keys(d_big, B, 0, p_.k + 1, d_ggsw + (size_t)(level - 1) * ncols, (long)p_.cbs_l * (long)ncols);
+}
+
+// The private functional keyswitches of keys q0 .. q0 + nq - 1: out[b * out_stride + (q - q0) * glwe + col].  The
+// GEMM paths take the column slice [q0 glwe, (q0 + nq) glwe) of the key operand (8 limb rows per column, an even
+// row offset in the row-pair interleaved layout), of corr[] and of the clamp fix-up's key.
+void Engine::pfks_keys(const uint64_t *d_big, size_t B, int q0, int nq, uint64_t *dst, long out_stride) {
     if (!B) return;
     const int glwe = (int)p_.glwe_len();
+    const int ncols = nq * glwe;
+    const long pf_blk = (long)(p_.K() + 1) * p_.pfks_l * glwe;
+    const uint64_t *key = d_pfpksk_ + (size_t)q0 * pf_blk;
     if (mfma_ks_ && pf_kl_ && (long)B >= pf_kl_min_) {
         // K layout: rows = ciphertexts, K = (K+1) x S limb slots (ksgemm.hpp KSlots)
         const int K = p_.K(), kd = (K + 1) * pf_slots_.S;
@@ -1493,34 +1547,32 @@ void Engine::pfks_into_ggsw(const uint64_t *d_big, uint64_t *d_ggsw, size_t B, i
         }
         ksgemm::prep_digits_kl<<<(unsigned)((thr + 255) / 256), 256, 0, stream_>>>(
             d_big, K + 1, d_digits_, (long)B, K + 1, kp_pf_kl_, p_.pfks_b, p_.pfks_l, pf_slots_, d_pf_flags_, fw);
-        const int ncols = (p_.k + 1) * glwe;
-        const long out_stride = (long)p_.cbs_l * ncols;
         const long ntiles = ((long)ncols * 8 + ksgemm::BTN - 1) / ksgemm::BTN;
-        uint64_t *dst = d_ggsw + (size_t)(level - 1) * ncols;
+        const int8_t *bt = d_pf_bt_kl_ + (size_t)q0 * glwe * 8 * kp_pf_kl_;
+        const uint64_t *corr = d_pf_corr_ + (size_t)q0 * glwe;
         const unsigned grid = (unsigned)(mt * ntiles);
         const size_t lds = ksgemm::gemm_g6_lds<kG6WM>();
         switch (pf_gemm_) {
         case 1:
-            ksgemm::gemm_g7<true, 4><<<grid, 1024, lds, stream_>>>(d_digits_, d_pf_bt_kl_, kp_pf_kl_, mt, ncols, dst,
-                                                                   out_stride, (long)B, d_pf_corr_);
+            ksgemm::gemm_g7<true, 4><<<grid, 1024, lds, stream_>>>(d_digits_, bt, kp_pf_kl_, mt, ncols, dst,
+                                                                   out_stride, (long)B, corr);
             break;
         case 2:
-            ksgemm::gemm_g7<false, 2><<<grid, 512, lds, stream_>>>(d_digits_, d_pf_bt_kl_, kp_pf_kl_, mt, ncols, dst,
-                                                                   out_stride, (long)B, d_pf_corr_);
+            ksgemm::gemm_g7<false, 2><<<grid, 512, lds, stream_>>>(d_digits_, bt, kp_pf_kl_, mt, ncols, dst,
+                                                                   out_stride, (long)B, corr);
             break;
         case 3:
-            ksgemm::gemm_g7<true, 2><<<grid, 512, lds, stream_>>>(d_digits_, d_pf_bt_kl_, kp_pf_kl_, mt, ncols, dst,
-                                                                  out_stride, (long)B, d_pf_corr_);
+            ksgemm::gemm_g7<true, 2><<<grid, 512, lds, stream_>>>(d_digits_, bt, kp_pf_kl_, mt, ncols, dst,
+                                                                  out_stride, (long)B, corr);
             break;
         default:
             ksgemm::gemm_g6<6, kG6WM, true><<<grid, 256 * kG6WM, lds, stream_>>>(
-                d_digits_, d_pf_bt_kl_, kp_pf_kl_, mt, ncols, dst, out_stride, (long)B, d_pf_corr_);
+                d_digits_, bt, kp_pf_kl_, mt, ncols, dst, out_stride, (long)B, corr);
         }
         last_pfks_kernel_ = kPfGemmNames[pf_gemm_];
         if (clamp) {
-            const long pf_blk = (long)(K + 1) * p_.pfks_l * glwe;
             ksgemm::pfks_clamp_fixup<<<(unsigned)((B + 3) / 4), 256, 0, stream_>>>(
-                d_pf_flags_, fw, (long)B, p_.pfks_l, p_.pfks_b, d_pfpksk_, ncols, glwe, glwe, pf_blk, dst, out_stride);
+                d_pf_flags_, fw, (long)B, p_.pfks_l, p_.pfks_b, key, ncols, glwe, glwe, pf_blk, dst, out_stride);
         }
         HIPC(hipGetLastError());
         return;
@@ -1533,21 +1585,56 @@ void Engine::pfks_into_ggsw(const uint64_t *d_big, uint64_t *d_ggsw, size_t B, i
         const size_t thr = B * (size_t)(K + 1);
         ksgemm::prep_digits3<6><<<(unsigned)((thr + 255) / 256), 256, 0, stream_>>>(
             d_big, K + 1, d_digits_, (long)B, K + 1, kp_pf_, p_.pfks_b, p_.pfks_l, true);
-        const int ncols = (p_.k + 1) * glwe;
-        const long out_stride = (long)p_.cbs_l * ncols;
         const long ntiles = ((long)ncols * 8 + ksgemm::BTN - 1) / ksgemm::BTN;
-        uint64_t *dst = d_ggsw + (size_t)(level - 1) * ncols;
         ksgemm::gemm_g6<6, 4><<<(unsigned)(mt4 * ntiles), 1024, ksgemm::gemm_g6_lds<4>(), stream_>>>(
-            d_digits_, d_pf_bt_, kp_pf_, mt4, ncols, dst, out_stride, (long)B);
+            d_digits_, d_pf_bt_ + (size_t)q0 * glwe * 8 * kp_pf_, kp_pf_, mt4, ncols, dst, out_stride, (long)B);
         HIPC(hipGetLastError());
         last_pfks_kernel_ = "rows";
         return;
     }
     last_pfks_kernel_ = "u64";
-    dim3 grid((unsigned)((glwe + kThreads - 1) / kThreads), (unsigned)(p_.k + 1), (unsigned)((B + PF_CT - 1) / PF_CT));
-    pfks_kernel<<<grid, kThreads, 0, stream_>>>(d_big, d_ggsw, d_pfpksk_, B, p_.K(), glwe, p_.pfks_l, p_.pfks_b,
-                                                p_.cbs_l, level, p_.k);
+    dim3 grid((unsigned)((glwe + kThreads - 1) / kThreads), (unsigned)nq, (unsigned)((B + PF_CT - 1) / PF_CT));
+    pfks_kernel<<<grid, kThreads, 0, stream_>>>(d_big, dst, key, B, p_.K(), glwe, p_.pfks_l, p_.pfks_b, (size_t)out_stride);
     HIPC(hipGetLastError());
+}
+
+// ---- packed ciphertext I/O (glwe_pack.hpp) ----
+void Engine::require_pack() const {
+    if (p_.id != SQRD_LVL_64)
+        throw std::runtime_error("packed ciphertext I/O is built for params_sqrd_lvl_64 only");
+}
+
+void Engine::unpack_bits(const uint64_t *d_glwes, size_t count, uint64_t *d_bits) {
+    require_pack();
+    if (!count) return;
+    if (count > (size_t)INT_MAX) throw std::runtime_error("unpack_bits: more than 2^31 - 1 bits in one call");  // grid.x
+    dim3 grid((unsigned)count, (unsigned)(p_.k + 1));
+    unpack_bits_kernel<<<grid, kThreads, 0, stream_>>>(d_glwes, d_bits, count, p_.k, p_.N);
+    HIPC(hipGetLastError());
+}
+
+void Engine::pack_pfks(const uint64_t *d_big, size_t B, uint64_t *d_out) {
+    require_pack();
+    pfks_keys(d_big, B, p_.k, 1, d_out, (long)p_.glwe_len());
+}
+
+void Engine::pack_bits(const uint64_t *d_bits, size_t count, uint64_t *d_glwes) {
+    require_pack();
+    times_.pack = 0;
+    if (!count) return;
+    const size_t glwe = p_.glwe_len(), N = (size_t)p_.N;
+    static_assert(glwe_pack::kChunkBits % 512 == 0, "chunks are whole GLWEs");
+    grow(d_pack_, cap_pack_, std::min(count, glwe_pack::kChunkBits) * glwe);
+    timed(ST_PACK, [&] {
+        for (size_t b0 = 0; b0 < count; b0 += glwe_pack::kChunkBits) {
+            const size_t n = std::min(glwe_pack::kChunkBits, count - b0);
+            pfks_keys(d_bits + b0 * p_.big_len(), n, p_.k, 1, d_pack_, (long)glwe);
+            dim3 grid((unsigned)((n + N - 1) / N), (unsigned)(p_.k + 1));
+            pack_rotate_sum_kernel<<<grid, 512, 0, stream_>>>(d_pack_, d_glwes + b0 / N * glwe, n, p_.k, p_.N);
+            HIPC(hipGetLastError());
+        }
+    });
+    collect_times();
 }
 
 void Engine::ggsw_to_fourier(const uint64_t *d_ggsw, cplx *d_ggsw_f, size_t B) {
@@ -1698,7 +1785,7 @@ void Engine::collect_times() {
         float ms = 0;
         HIPC(hipEventElapsedTime(&ms, sp.a, sp.b));
         float *dst[] = {&times_.keyswitch, &times_.pbs, &times_.pfks, &times_.ggsw_fft, &times_.vertical_packing,
-                        &times_.extract, &times_.linear, &times_.pbs_main};
+                        &times_.extract, &times_.linear, &times_.pbs_main, &times_.pack};
         *dst[sp.stage] += ms;
     }
     spans_.clear();

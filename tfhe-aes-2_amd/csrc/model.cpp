@@ -9,6 +9,7 @@
 #include "aes.hpp"
 #include "aes_inv.hpp"
 #include "cplx.hpp"
+#include "glwe_pack.hpp"
 #include "../../include/tfhe_aes_gpu.h"
 
 namespace tae {
@@ -1511,6 +1512,55 @@ void Context::s1_bootstrap_raw(const uint64_t *in, size_t B, const uint64_t *tvs
     engine_->s1_bootstrap(d_in.as<uint64_t>(), d_tv.as<uint64_t>(), n_tv, d_out.as<uint64_t>(), B);
     hip_check(hipMemcpyAsync(out, d_out.p, B * L * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
     engine_->synchronize();
+}
+
+// ---- packed ciphertext I/O (glwe_pack.hpp) ----
+void Context::require_pack(size_t count) const {
+    if (params().id != SQRD_LVL_64)
+        throw ModelError{TAE_E_PARAM, "packed ciphertext I/O is built for params_sqrd_lvl_64 only"};
+    if (!count) throw ModelError{TAE_E_ARG, "a packed call needs at least one bit"};
+}
+
+void Context::unpack_bits_raw(const uint64_t *glwes, size_t count, uint64_t *bits, bool device_mem) {
+    require_pack(count);
+    const size_t G = glwe_pack::glwe_count(count, params().N);
+    run8(glwes, G * params().glwe_len(), bits, count * bit_len(), device_mem,
+         [&](const uint64_t *i, uint64_t *o, const uint64_t *) { engine_->unpack_bits(i, count, o); }, nullptr);
+}
+
+std::vector<BitCt> Context::unpack_bits(const uint64_t *glwes, size_t count) {
+    require_pack(count);
+    std::vector<uint64_t> raw(count * bit_len());
+    unpack_bits_raw(glwes, count, raw.data(), false);
+    std::vector<BitCt> out;
+    out.reserve(count);
+    for (size_t i = 0; i < count; i++)
+        out.push_back(wrap(std::vector<uint64_t>(raw.begin() + i * bit_len(), raw.begin() + (i + 1) * bit_len()), 1));
+    return out;
+}
+
+void Context::pack_bits_raw(const uint64_t *bits, size_t count, uint64_t *glwes, bool device_mem) {
+    require_pack(count);
+    const size_t G = glwe_pack::glwe_count(count, params().N);
+    run8(bits, count * bit_len(), glwes, G * params().glwe_len(), device_mem,
+         [&](const uint64_t *i, uint64_t *o, const uint64_t *) { engine_->pack_bits(i, count, o); }, nullptr);
+}
+
+void Context::pack_bits(const std::vector<const BitCt *> &bits, uint64_t *glwes) {
+    require_pack(bits.size());
+    const size_t L = bit_len();
+    std::vector<uint64_t> raw(bits.size() * L);
+    for (size_t i = 0; i < bits.size(); i++) {
+        if (bits[i]->ct.size() != L) throw ModelError{TAE_E_ARG, "ciphertext size mismatch"};
+        std::copy(bits[i]->ct.begin(), bits[i]->ct.end(), raw.begin() + i * L);
+    }
+    pack_bits_raw(raw.data(), bits.size(), glwes, false);
+}
+
+void Context::pack_pfks_raw(const uint64_t *bits, size_t count, uint64_t *glwes, bool device_mem) {
+    require_pack(count);
+    run8(bits, count * bit_len(), glwes, count * params().glwe_len(), device_mem,
+         [&](const uint64_t *i, uint64_t *o, const uint64_t *) { engine_->pack_pfks(i, count, o); }, nullptr);
 }
 
 void Context::s1_packing_keyswitch_raw(const uint64_t *cts, size_t count, uint64_t *glwe, bool device_mem) {

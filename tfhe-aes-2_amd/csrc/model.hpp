@@ -191,6 +191,19 @@ class Context {  // FheContext
     void s1_multivariate_raw(const uint64_t *bits, size_t G, int nbits, const uint64_t *f_tables, int n_fn,
                              uint64_t *out, bool device_mem);
 
+    // ---- packed ciphertext I/O (glwe_pack.hpp): params_sqrd_lvl_64 only, TAE_E_PARAM elsewhere.
+    // count bits <-> ceil(count / N) GLWEs [(k+1)N]; count == 0 is TAE_E_ARG ----
+    // sample extraction of client-made GLWEs into big-key bits [count][K+1] (exact: no noise added)
+    void unpack_bits_raw(const uint64_t *glwes, size_t count, uint64_t *bits, bool device_mem);
+    // BitCt variant (host GLWEs): every bit at noise^2 = 1 with a fresh id, as a fresh encryption
+    std::vector<BitCt> unpack_bits(const uint64_t *glwes, size_t count);
+    // GLWE g = sum_j X^j PFKS_{q=k}(bit g N + j).  The result is terminal: for the client or for storage
+    void pack_bits_raw(const uint64_t *bits, size_t count, uint64_t *glwes, bool device_mem);
+    void pack_bits(const std::vector<const BitCt *> &bits, uint64_t *glwes);
+    // the per-bit GLWEs before the sum [count][(k+1)N]
+    void pack_pfks_raw(const uint64_t *bits, size_t count, uint64_t *glwes, bool device_mem);
+    void require_pack(size_t count) const;
+
   private:
     void require_s1() const;
     template <class F>

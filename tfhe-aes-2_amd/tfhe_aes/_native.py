@@ -50,6 +50,9 @@ EXPORTED = [
     "tae_aesm_decrypt_blocks_raw", "tae_aesm_ctr_plan", "tae_aesm_ctr_transcipher_raw",
     "tae_aesm_cbc_transcipher_raw", "tae_aesm_key_schedule", "tae_aesm_ctr_transcipher", "tae_aesm_cbc_transcipher",
     "tae_last_pfks_kernel",
+    "tae_packed_len", "tae_encrypt_packed_raw", "tae_decrypt_packed_raw", "tae_packed_narrow", "tae_packed_widen",
+    "tae_unpack_bits_raw", "tae_pack_bits_raw", "tae_unpack_bits", "tae_pack_bits", "tae_last_pack_time",
+    "tae_stage_pack_pfks",
 ]
 TAE_DRIVER_GAL_MUL, TAE_DRIVER_SBOX_PBS = 0, 1
 TAE_KEYS_CLIENT, TAE_KEYS_SERVER = 1, 2
@@ -196,6 +199,15 @@ def lib() -> C.CDLL:
         "tae_last_stage_times_v3": ([vp, C.POINTER(C.c_double)], C.c_int),
         "tae_last_stage_times_v4": ([vp, C.POINTER(C.c_double)], C.c_int),
         "tae_last_pfks_kernel": ([vp, C.c_char_p, sz], C.c_int),
+        "tae_packed_len": ([C.c_int, sz, C.POINTER(sz), C.POINTER(sz)], C.c_int),
+        "tae_encrypt_packed_raw": ([vp, vp, sz, u64, vp], C.c_int),
+        "tae_decrypt_packed_raw": ([vp, vp, sz, vp], C.c_int),
+        "tae_packed_narrow": ([vp, sz, vp], C.c_int), "tae_packed_widen": ([vp, sz, vp], C.c_int),
+        "tae_unpack_bits_raw": ([vp, vp, sz, vp, C.c_int], C.c_int),
+        "tae_pack_bits_raw": ([vp, vp, sz, vp, C.c_int], C.c_int),
+        "tae_unpack_bits": ([vp, vp, sz, vp], C.c_int), "tae_pack_bits": ([vp, vp, sz, vp], C.c_int),
+        "tae_last_pack_time": ([vp, C.POINTER(C.c_double)], C.c_int),
+        "tae_stage_pack_pfks": ([vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_generate_multivariate_luts": ([C.c_int, C.c_int, C.c_int, vp, vp, sz], C.c_int),
         "tae_xor_batch": ([vp, vp, vp, sz, vp, vp, vp, C.c_int], C.c_int),
         "tae_keys_save": ([C.c_char_p, C.c_int, vp, vp, vp, vp], C.c_int),

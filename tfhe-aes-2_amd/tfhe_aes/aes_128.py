@@ -18,7 +18,8 @@ import numpy as np
 
 from . import _native as N
 from ._native import check, lib
-from .tfhe import BitCt, ClientKey, Cleartext, FheContext, _handles
+from .tfhe import BitCt, ClientKey, Cleartext, FheContext, PackedBits, _handles
+from .tfhe import _flatten_bits as _flat_bits
 
 ROUNDS = 10
 
@@ -197,18 +198,19 @@ def decrypt_byte_array(client_key: ClientKey, array) -> bytes:
     return bytes(decrypt_byte(client_key, b) for b in array)
 
 
-def _flat_bits(x) -> List[BitCt]:
-    out = []
+def encrypt_byte_array_packed(client_key: ClientKey, array: bytes, start_index=None) -> PackedBits:
+    """encrypt_byte_array as one packed upload: 8 bits per byte, MSB first, 64 bytes per GLWE.  FheContext.unpack
+    turns it into the [len][8] bits that encrypt_byte_array returns."""
+    bits = [b for byte in bytes(array) for b in u8_to_bits(byte)]
+    return client_key.encrypt_packed(bits, start_index, group=8)
 
-    def rec(v):
-        if isinstance(v, BitCt):
-            out.append(v)
-        else:
-            for e in v:
-                rec(e)
 
-    rec(x)
-    return out
+def decrypt_byte_array_packed(client_key: ClientKey, packed: PackedBits) -> bytes:
+    """The bytes of a packed upload or of FheContext.pack of [len][8] bits (MSB first)."""
+    if packed.count % 8:
+        raise ValueError("a packed byte array holds a multiple of 8 bits")
+    bits = client_key.decrypt_packed(packed)
+    return bytes(bits_to_u8(bits[i:i + 8]) for i in range(0, packed.count, 8))
 
 
 # ---------------------------------------------------------------- Aes128Encrypt ----

@@ -19,7 +19,7 @@ from ._native import check, lib
 
 __all__ = ["Cleartext", "BitCt", "FheContext", "ClientKey", "WopbsLUT", "encode_bit", "decode_bit",
            "generate_keys", "generate_keys_raw", "client_key_from_seed", "context_from_raw", "server_key_sizes",
-           "generate_multivariate_luts"]
+           "generate_multivariate_luts", "PackedBits"]
 
 
 @dataclass(frozen=True)
@@ -83,6 +83,59 @@ class BitCt:
         arr = np.zeros(lwe_size, dtype=np.uint64)
         check(lib().tae_bit_data(self._h, arr.ctypes.data_as(C.c_void_p), lwe_size))
         return arr
+
+
+def _flatten_bits(x) -> list:
+    out = []
+
+    def rec(v):
+        if isinstance(v, BitCt):
+            out.append(v)
+        else:
+            for e in v:
+                rec(e)
+
+    rec(x)
+    return out
+
+
+class PackedBits:
+    """`count` bits packed 512 to a GLWE (include/tfhe_aes_gpu.h "packed ciphertext I/O"):
+    data [ceil(count / N)][(k+1)N] uint64, bit j at coefficient j % N of GLWE j // N.  origin is "client" (an
+    upload: FheContext.unpack extracts its bits) or "server" (a result of FheContext.pack: terminal, for
+    ClientKey.decrypt_packed or storage).  group = 8 marks bytes, so that unpack returns the [len][8] shape of
+    the AES drivers."""
+
+    __slots__ = ("data", "count", "origin", "group")
+
+    def __init__(self, data: np.ndarray, count: int, origin: str, group: int = 0):
+        if origin not in ("client", "server"):
+            raise ValueError('origin is "client" or "server"')
+        data = np.ascontiguousarray(data, dtype=np.uint64)
+        if data.ndim != 2 or count < 1 or data.shape[0] * 512 < count or (data.shape[0] - 1) * 512 >= count:
+            raise ValueError("data must be [ceil(count / N)][(k+1)N]")
+        self.data, self.count, self.origin, self.group = data, int(count), origin, int(group)
+
+    def narrow(self) -> np.ndarray:
+        """The 32-bit wire form: every word rounded to its top 32 bits, [G][(k+1)N] uint32."""
+        out = np.zeros(self.data.shape, dtype=np.uint32)
+        check(lib().tae_packed_narrow(self.data.ctypes.data_as(C.c_void_p), self.data.size,
+                                      out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    @classmethod
+    def from_narrow(cls, words: np.ndarray, count: int, origin: str, group: int = 0) -> "PackedBits":
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        out = np.zeros(words.shape, dtype=np.uint64)
+        check(lib().tae_packed_widen(words.ctypes.data_as(C.c_void_p), words.size, out.ctypes.data_as(C.c_void_p)))
+        return cls(out, count, origin, group)
+
+
+def packed_len(param_set: int, count: int) -> tuple:
+    """(GLWEs, u64 words) that `count` packed bits occupy (tae_packed_len)."""
+    g, w = C.c_size_t(), C.c_size_t()
+    check(lib().tae_packed_len(param_set, count, C.byref(g), C.byref(w)))
+    return g.value, w.value
 
 
 def _handles(bits: Sequence[BitCt]):
@@ -223,6 +276,66 @@ class FheContext:
         check(lib().tae_last_pfks_kernel(self._h, buf, len(buf)))
         return buf.value.decode()
 
+    # ---- packed ciphertext I/O (params_sqrd_lvl_64) ----
+    def _packed_shape(self, count: int) -> tuple:
+        g, w = packed_len(self.param_set, count)
+        return g, w // g
+
+    def unpack_raw(self, packed: PackedBits) -> np.ndarray:
+        """Sample extraction of a client-made upload: -> [count][K+1] (host array), no noise added."""
+        if packed.origin != "client":
+            raise ValueError("unpacking is defined for client-made GLWEs only (server-packed results are terminal)")
+        if packed.data.shape != self._packed_shape(packed.count):
+            raise ValueError("packed data does not have the shape of its count")
+        out = np.zeros((packed.count, self.lwe_size), dtype=np.uint64)
+        check(lib().tae_unpack_bits_raw(self._h, packed.data.ctypes.data_as(C.c_void_p), packed.count,
+                                        out.ctypes.data_as(C.c_void_p), N.TAE_MEM_HOST))
+        return out
+
+    def unpack(self, packed: PackedBits):
+        """Client-made upload -> BitCt handles at noise level 1 (fresh ids): a flat list, or [count / group][group]
+        when the upload marks a group (bytes: the [len][8] shape of the AES drivers)."""
+        if packed.origin != "client":
+            raise ValueError("unpacking is defined for client-made GLWEs only (server-packed results are terminal)")
+        if packed.data.shape != self._packed_shape(packed.count):
+            raise ValueError("packed data does not have the shape of its count")
+        outs = (C.c_void_p * packed.count)()
+        check(lib().tae_unpack_bits(self._h, packed.data.ctypes.data_as(C.c_void_p), packed.count, outs))
+        bits = [BitCt(h, self) for h in outs]
+        g = packed.group
+        if g and packed.count % g == 0:
+            return [bits[i:i + g] for i in range(0, packed.count, g)]
+        return bits
+
+    def pack(self, bits) -> PackedBits:
+        """BitCt handles (nested or flat) or a host array [...][K+1] -> PackedBits of origin "server"."""
+        if isinstance(bits, np.ndarray):
+            arr = np.ascontiguousarray(bits, dtype=np.uint64).reshape(-1, self.lwe_size)
+            count = arr.shape[0]
+            out = np.zeros(self._packed_shape(count), dtype=np.uint64)
+            check(lib().tae_pack_bits_raw(self._h, arr.ctypes.data_as(C.c_void_p), count,
+                                          out.ctypes.data_as(C.c_void_p), N.TAE_MEM_HOST))
+        else:
+            flat = _flatten_bits(bits)
+            count = len(flat)
+            out = np.zeros(self._packed_shape(count), dtype=np.uint64)
+            check(lib().tae_pack_bits(self._h, _handles(flat), count, out.ctypes.data_as(C.c_void_p)))
+        return PackedBits(out, count, "server", 8 if count % 8 == 0 else 0)
+
+    def pack_device(self, d_bits: int, count: int, d_glwes: int) -> None:
+        """Device pointers (ints): bits [count][K+1] -> GLWEs [ceil(count / N)][(k+1)N], nothing leaves the device."""
+        check(lib().tae_pack_bits_raw(self._h, C.c_void_p(d_bits), count, C.c_void_p(d_glwes), N.TAE_MEM_DEVICE))
+
+    def unpack_device(self, d_glwes: int, count: int, d_bits: int) -> None:
+        """Device pointers (ints) of a client-made upload: GLWEs -> bits [count][K+1]."""
+        check(lib().tae_unpack_bits_raw(self._h, C.c_void_p(d_glwes), count, C.c_void_p(d_bits), N.TAE_MEM_DEVICE))
+
+    def last_pack_time(self) -> float:
+        """ms of the last pack call's keyswitch slice and rotate-and-sum (set_timing on)."""
+        v = C.c_double()
+        check(lib().tae_last_pack_time(self._h, C.byref(v)))
+        return v.value
+
     def xor_batch(self, lhs: np.ndarray, rhs: np.ndarray, lhs_noise_sq=None, rhs_noise_sq=None):
         """BitXorAssign over whole bit arrays (xor_state, data_model.rs:270-274): lhs += rhs in place
         (host arrays [count][lwe]); with squared noise levels given, NoiseTooBig is enforced and the
@@ -288,6 +401,25 @@ class ClientKey:
         out = np.zeros(cts.shape[0], dtype=np.uint8)
         check(lib().tae_decrypt_bits_raw(self._h, cts.ctypes.data_as(C.c_void_p), cts.shape[0],
                                          out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    # ---- packed ciphertext I/O (params_sqrd_lvl_64) ----
+    def encrypt_packed(self, bits, start_index: int | None = None, group: int = 0) -> PackedBits:
+        """512 bits per GLWE; GLWE g is packed encryption #start_index + g (explicit, below 2^63, an index space
+        of its own) or, with start_index=None, takes fresh indices from the key."""
+        start_index = N.TAE_INDEX_AUTO if start_index is None else start_index
+        bits = np.ascontiguousarray(np.asarray(bits, dtype=np.uint8).ravel())
+        g, w = packed_len(self.param_set, bits.size)
+        out = np.zeros((g, w // g), dtype=np.uint64)
+        check(lib().tae_encrypt_packed_raw(self._h, bits.ctypes.data_as(C.c_void_p), bits.size, start_index,
+                                           out.ctypes.data_as(C.c_void_p)))
+        return PackedBits(out, bits.size, "client", group)
+
+    def decrypt_packed(self, packed: PackedBits) -> np.ndarray:
+        """The `count` bits of an upload or of a server-packed result, uint8."""
+        out = np.zeros(packed.count, dtype=np.uint8)
+        check(lib().tae_decrypt_packed_raw(self._h, packed.data.ctypes.data_as(C.c_void_p), packed.count,
+                                           out.ctypes.data_as(C.c_void_p)))
         return out
 
     # 8-bit model integers: shortint encrypt_without_padding / decrypt_without_padding
