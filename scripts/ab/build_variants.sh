@@ -6,7 +6,8 @@ set -e
 cd "$(dirname "$0")/../../tfhe-aes-2_amd"
 make -s
 mkdir -p dbg
-# the kernel units and their Makefile flag variables (kernels.hip: none); the variant flags go last
+# the kernel units and their Makefile flag variables (kernels.hip: none; aes_engine.hip has no variants: the
+# working tree's object is linked); the variant flags go last
 mkvar() { make -s --no-print-directory -f Makefile -f - <<<"print-var: ; @echo \$($1)" print-var; }
 X4FLAGS=$(mkvar X4FLAGS); LATFLAGS=$(mkvar LATFLAGS); B1KFLAGS=$(mkvar B1KFLAGS); P16FLAGS=$(mkvar P16FLAGS)
 HC="/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -w --offload-arch=gfx950 -munsafe-fp-atomics"
@@ -22,7 +23,7 @@ wait
 for spec in "$@"; do
   name=${spec%%=*}
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o dbg/$name.so dbg/$name.o dbg/$name.x4.o dbg/$name.lat.o dbg/$name.b1k.o dbg/$name.p16.o \
-    build/client.o build/model.o build/capi.o build/keyio.o -lpthread
+    build/aes_engine.o build/client.o build/aes_plain.o build/model.o build/capi.o build/keyio.o -lpthread
   rm dbg/$name.o dbg/$name.x4.o dbg/$name.lat.o dbg/$name.b1k.o dbg/$name.p16.o
 done
 ls dbg

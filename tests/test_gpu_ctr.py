@@ -12,7 +12,7 @@ import pytest
 
 import tfhe_aes
 from tfhe_aes import _native as N
-from tfhe_aes import aes_128
+from tfhe_aes import aes_128, aes_var
 from tests.conftest import SEED
 
 pytestmark = pytest.mark.gpu
@@ -21,6 +21,7 @@ BIG = 4 * 512 + 1
 SMALL = 786
 E = aes_128.ShortintWoppbs1BitSboxGalMulPbsAesEncrypt
 A8 = aes_128.ShortintWoppbs8BitSboxPbsAesEncrypt
+V = aes_var.GalMulAes  # the entry points that take `rounds` where the AES-128 ones run all ten
 CARRY_FIRST, CARRY_BLOCKS = 0xFE, 3
 
 
@@ -108,6 +109,31 @@ def test_transcipher_37_bytes(gpu_context, client, readme_setup):
     assert E.ctr_keystream_raw(gpu_context, rk, iv, 1, 0).shape == (0, 128, BIG)
 
 
+def _check_one_round_transcipher(ctx, client, rk, key, iv, n_bytes, driver, lwe_size):
+    """n_bytes from counter CARRY_FIRST with rounds=1: round 1 is the last, so the final kernel reads the SubBytes
+    output through the plan's map, adds the data and stops at n_bytes.  Word for word the keystream's first n_bytes
+    with the data bits << 63 on the body, and the plain one-round counter mode once decrypted."""
+    nb = (n_bytes + 15) // 16
+    msg = bytes((53 * i + 7) & 255 for i in range(n_bytes))
+    blocks = aes_128.counter_blocks(iv, nb, first=CARRY_FIRST)
+    ks_plain = b"".join(aes_128.expand_key_and_encrypt_blocks(key, blocks, 1))
+    data = bytes(m ^ k for m, k in zip(msg, ks_plain))
+    out = V.ctr_transcipher_raw(ctx, rk, iv, CARRY_FIRST, data, rounds=1)
+    assert out.shape == (n_bytes, 8, lwe_size)
+    want = driver.ctr_keystream_raw(ctx, rk, iv, CARRY_FIRST, nb, rounds=1).reshape(nb * 16, 8, lwe_size)[:n_bytes].copy()
+    dbits = np.array([aes_128.u8_to_bits(d) for d in data], dtype=np.uint64)
+    want[:, :, -1] += dbits << np.uint64(63)
+    assert np.array_equal(out, want)
+    bits = client.decrypt_bits_raw(out).reshape(n_bytes, 8)
+    assert bytes(aes_128.bits_to_u8(b) for b in bits) == msg
+
+
+def test_transcipher_one_round_21_bytes(gpu_context, client, readme_setup):
+    """2 blocks, the second cut after 5 bytes."""
+    key, iv, rk = readme_setup
+    _check_one_round_transcipher(gpu_context, client, rk, key, iv, 21, E, BIG)
+
+
 def test_transcipher_handles_noise_levels(gpu_context, client, readme_setup):
     """The handle variant on 5 bytes: the noise levels E.encrypt_blocks reports for 10 rounds on
     ctx.trivial inputs, and the raw entry point's words."""
@@ -160,6 +186,14 @@ def test_8bit_model(gpu_context8, oracle_keys8, product_raw8, readme_setup):
     assert got == aes_128.expand_key_and_encrypt_blocks(key, blocks, 2)
     one = A8.ctr_keystream_raw(gpu_context8, rk, iv, CARRY_FIRST, CARRY_BLOCKS, rounds=1)
     assert np.array_equal(one[0], oracle_keys8.aes8_encrypt_block(rk, cts[0], 1, threads=16))
+
+
+def test_8bit_model_transcipher(gpu_context8, product_raw8, readme_setup):
+    """The 8-bit model's transciphering with data: 5 bytes, one round."""
+    key, iv, _ = readme_setup
+    client8 = product_raw8[0]
+    rk = client8.encrypt_bits_raw(_expanded_key_bits(key), start_index=310_000)
+    _check_one_round_transcipher(gpu_context8, client8, rk, key, iv, 5, A8, SMALL)
 
 
 def test_shortint_1bit_is_param_error(readme_setup):

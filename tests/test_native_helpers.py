@@ -2,7 +2,8 @@
 (fft_device.hpp from_torus_bits, decompose16) against the CPU oracle's tfhe-rs restatement
 (or_from_torus, or_decompose) on random and edge-case inputs (tests/native/torus_helpers_test.cpp), and
 the K-layout PFKS slot plan (kslots.hpp, tests/native/kslots_test.cpp), and the fused-twiddle transforms'
-constant tables of the product against the oracle's plans (tests/native/lf_tables_test.cpp)."""
+constant tables of the product against the oracle's plans (tests/native/lf_tables_test.cpp), and the forward
+cipher's linear layer (aes_linear.hpp, tests/native/aes_linear_test.cpp)."""
 import os
 import subprocess
 
@@ -28,6 +29,18 @@ def test_pfks_slot_plan(tmp_path):
     subprocess.run(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "native", "kslots_test.cpp"), "-o", exe],
                    check=True)
     r = subprocess.run([exe, "2000000"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "OK" in r.stdout
+
+
+def test_aes_linear_layer(tmp_path):
+    """The per-word functions of the AES linear-layer kernels (csrc/aes_linear.hpp) in host loops on trivial
+    ciphertexts against plain AES rounds: the map, the key slots, the public data, the byte bound and the
+    per-block placement each taken both ways (tests/native/aes_linear_test.cpp)."""
+    exe = str(tmp_path / "aes_linear_test")
+    subprocess.run(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "native", "aes_linear_test.cpp"),
+                    os.path.join(ROOT, "tfhe-aes-2_amd", "csrc", "aes_plain.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "OK" in r.stdout
 

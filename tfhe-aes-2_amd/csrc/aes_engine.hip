@@ -1,0 +1,563 @@
+// The AES application layer of the Engine: the linear layers between the circuit bootstraps as HIP kernels
+// (ShiftRows / MixColumns / AddRoundKey as LWE additions: fhe_sbox_gal_mul_pbs.rs:61-132, data_model.rs:270-281;
+// the arithmetic of a word is in aes_linear.hpp and aes_inv.hpp) and the drivers of every mode: the forward
+// cipher on the three models, counter mode, the inverse cipher, CBC, multi-key batches and the two key
+// derivations.  The generic TFHE stages they call are in kernels.hip.
+#include <cstring>
+#include <stdexcept>
+
+#include "aes.hpp"
+#include "aes_linear.hpp"
+#include "engine_detail.hpp"
+
+namespace tae {
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// Linear-layer kernels: consecutive threads walk the coefficients of one ciphertext, so every read and the
+// write coalesce.  The nullable arguments are described in aes_linear.hpp.
+// ---------------------------------------------------------------------------------------------
+// state [n_cts][L] = round key + input: n_cts = nb * 128, or U * 8 with `groups`
+__global__ void aes_round0_kernel(const uint64_t *__restrict__ rk, const uint64_t *__restrict__ blocks,
+                                  const uint8_t *__restrict__ bytes, const uint16_t *__restrict__ groups,
+                                  uint64_t *__restrict__ state, size_t n_cts, int L,
+                                  const int32_t *__restrict__ key_of, size_t key_stride) {
+    const size_t total = n_cts * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+        state[t] = aes_round0_word(rk, blocks, bytes, groups, t, L, key_of, key_stride);
+}
+
+__global__ void aes_mix_kernel(const uint64_t *__restrict__ muls, const int32_t *__restrict__ map,
+                               const uint64_t *__restrict__ rk_round, uint64_t *__restrict__ state, size_t nb, int L,
+                               const int32_t *__restrict__ key_of, size_t key_stride) {
+    const size_t total = nb * 128 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+        state[t] = aes_mix_word(muls, map, rk_round, t, L, key_of, key_stride);
+}
+
+__global__ void aes8_mix_kernel(const uint64_t *__restrict__ sb, const int32_t *__restrict__ map,
+                                const uint64_t *__restrict__ rk_round, uint64_t *__restrict__ state, size_t nb, int L,
+                                MixTerms T) {
+    const size_t total = nb * 128 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+        state[t] = aes8_mix_word(sb, map, rk_round, t, L, T);
+}
+
+__global__ void aes_final_kernel(const uint64_t *__restrict__ sb, const int32_t *__restrict__ map,
+                                 const uint64_t *__restrict__ rk_round, const uint8_t *__restrict__ data,
+                                 uint64_t *__restrict__ out, size_t n_bytes, int L,
+                                 const int32_t *__restrict__ key_of, size_t key_stride,
+                                 const int64_t *__restrict__ blk_out, const int32_t *__restrict__ blk_len, bool inverse) {
+    const size_t total = n_bytes * 8 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+        aes_final_word(sb, map, rk_round, data, out, t, L, key_of, key_stride, blk_out, blk_len, inverse);
+}
+
+// ---- AES-128 inverse cipher (FIPS-197 5.3; aes_inv.hpp has the algorithm and the source-byte indices) ----
+// InvShiftRows (shift_rows != 0), InvMixColumns and AddRoundKey on the four InvSubBytes*{14,11,13,9} states:
+// muls [nb*16][32][L], multiple m at ciphertexts 8m..8m+7 of a byte.  rk_round == nullptr adds no key and
+// shift_rows == 0 skips InvShiftRows: InvMixColumns alone, which derives the decryption key from nb round keys.
+__global__ void aes_inv_mix_kernel(const uint64_t *__restrict__ muls, const uint64_t *__restrict__ rk_round,
+                                   uint64_t *__restrict__ state, size_t nb, int L, int shift_rows,
+                                   const int32_t *__restrict__ key_of = nullptr, size_t key_stride = 0) {
+    const size_t total = nb * 128 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const AesWord w = aes_word(t, L);
+        const int c = w.pos >> 2, row = w.pos & 3;
+        uint64_t acc =
+            rk_round ? keyed_rk(rk_round, key_of, key_stride, w.blk)[(size_t)(w.pos * 8 + w.bit) * L + w.coef] : 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int byte = inv_mix_src_byte(row, c, j, shift_rows != 0);
+            acc += muls[(((w.blk * 16 + byte) * 32) + 8 * j + w.bit) * (size_t)L + w.coef];
+        }
+        state[t] = acc;
+    }
+}
+
+// ---- key expansion (FIPS-197 5.2, figure 11): one word before its identity bootstrap ----
+// t = back + other (+ Rcon), whole ciphertexts: back = rk[i-Nk], other = rk[i-1] or SubWord(rk[i-1]), both
+// [4 bytes][8 bits][L].  SubWord works byte by byte, so RotWord is applied here, on the read of its output:
+// rot = 1 takes byte (b + 1) % 4 of `other`.  rcon != 0 adds bit b of it (MSB first) << 63 on the body of bit b
+// of byte 0, as Context::trivial does.  The same word of n_keys keys at once, key k reading
+// back + k * back_stride and other + k * other_stride and writing out [n_keys][32][L].
+__global__ void aes_ks_word_kernel(const uint64_t *__restrict__ back, const uint64_t *__restrict__ other, int rot,
+                                   int rcon, uint64_t *__restrict__ out, int L, size_t n_keys, size_t back_stride,
+                                   size_t other_stride) {
+    const size_t word = 32 * (size_t)L, total = n_keys * word;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t key = t / word, within = t - key * word;
+        const size_t coef = within % L;
+        const int ct = (int)(within / L);  // byte*8 + bit
+        const int bit = ct & 7, byte = ct >> 3;
+        uint64_t w = back[key * back_stride + within] +
+                     other[key * other_stride + (size_t)(((byte + rot) & 3) * 8 + bit) * L + coef];
+        if (byte == 0 && coef == (size_t)L - 1) w += public_bit(rcon, bit);
+        out[t] = w;
+    }
+}
+
+// nr = 10 / 12 / 14 (AES-128 / 192 / 256) and 1 <= rounds <= nr, or a runtime_error
+void require_rounds(int rounds, int nr) {
+    if (nr != 10 && nr != 12 && nr != 14) throw std::runtime_error("the round count of the key size must be 10, 12 or 14");
+    if (rounds < 1 || rounds > nr) throw std::runtime_error("rounds must be in 1..=" + std::to_string(nr));
+}
+
+// the two arrays every counter plan has, against its U groups and nb blocks
+void check_ctr_plan(size_t U, const std::vector<int32_t> &map, size_t nb) {
+    if (map.size() != nb * 16 || !U) throw std::runtime_error("counter plan does not match the blocks");
+    for (int32_t g : map)
+        if (g < 0 || (size_t)g >= U) throw std::runtime_error("counter plan: group index out of range");
+}
+
+}  // namespace
+
+// Byte::bootstrap_with_lut of the 8-bit model: the circuit bootstrap into one 8-bit int per byte, then its bits
+void Engine::bootstrap_bytes8(const uint64_t *d_bytes, size_t G, const uint64_t *d_lut, uint64_t *d_out) {
+    if (!G) return;
+    grow(d_ints_, cap_ints_, G * p_.big_len());
+    cbs_vp(d_bytes, G, 8, d_lut, 1, d_ints_);
+    timed(ST_EXTRACT, [&] { extract_bits(d_ints_, G, 56, 8, d_out); });
+    collect_times();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The forward cipher: one round loop for every model and mode
+// ---------------------------------------------------------------------------------------------
+// What a forward entry point asks of aes_forward.  Round 0 has the ciphertexts `blocks`, or (blocks == nullptr)
+// the U deduplicated groups of a counter plan whose arrays are on the device (d_ctr_groups_, d_ctr_map_; the
+// groups' slots in group_key).  `sub` is the model's SubBytes step.  The key slots and the output placement are
+// aes_linear.hpp's nullable arguments.
+struct Engine::AesRun {
+    enum Sub { GAL_MUL, BYTES8, SHORTINT1 } sub;  // circuit_bootstrap 8 -> 24 / 8 -> 8, bootstrap_bytes8, s1_multivariate
+    const uint64_t *rk;
+    size_t nb;
+    int rounds, nr;
+    const uint64_t *blocks = nullptr;
+    size_t U = 0;
+    const int32_t *group_key = nullptr;
+    const int32_t *key_of = nullptr;
+    size_t key_stride = 0;
+    bool time_linear = false;  // the linear launches are ST_LINEAR spans, collected at the end (keyed calls)
+    const uint8_t *data = nullptr;
+    size_t out_bytes = 0;  // the first out_bytes bytes of the blocks are written
+    const int64_t *blk_out = nullptr;
+    const int32_t *blk_len = nullptr;
+    uint64_t *out = nullptr;
+};
+
+// fhe_sbox_gal_mul_pbs::encrypt_block_for_rounds / fhe_sbox_pbs::encrypt_block_for_rounds over nb blocks.  Round 0
+// leaves G groups of 8 bits in d_state_; each middle round is SubBytes of the G groups and the mix, which reads
+// them through the plan's map once (round 1 of counter mode) and leaves 16 nb groups; the last SubBytes and the
+// final kernel close the call.
+void Engine::aes_forward(const AesRun &a) {
+    const bool gal = a.sub == AesRun::GAL_MUL;
+    const int L = (int)(gal ? p_.big_len() : p_.small_len());
+    const size_t nb = a.nb, state_len = nb * 128 * (size_t)L, byte_stride = 8 * (size_t)L;
+    const bool plan = !a.blocks;
+    size_t G = plan ? a.U : nb * 16;
+    const int32_t *map = plan ? d_ctr_map_ : nullptr;
+    // one round of a plan works on its U groups alone; the per-block state and the 24 SubBytes multiples of the
+    // 1-bit model exist from round 2 on
+    const bool groups_only = plan && a.rounds == 1;
+    grow(d_state_, cap_state_, groups_only ? G * byte_stride : state_len);
+    grow(d_muls_, cap_muls_, groups_only ? G * byte_stride : nb * 16 * (gal ? 24 : 8) * (size_t)L);
+    MixTerms T;
+    std::memcpy(T.idx, mix_idx_, sizeof(T.idx));
+    auto linear = [&](auto launch) {
+        if (a.time_linear) {
+            timed(ST_LINEAR, launch);
+        } else {
+            launch();
+        }
+    };
+    auto sub_bytes = [&](bool last) {
+        if (gal)
+            circuit_bootstrap(d_state_, G, 8, last ? d_lut8_ : d_lut24_, last ? 8 : 24, d_muls_);
+        else if (a.sub == AesRun::BYTES8)
+            bootstrap_bytes8(d_state_, G, d_wlut_sbox_, d_muls_);
+        else
+            s1_multivariate(d_state_, G, 8, d_s1_sbox_tv_, 8, d_muls_);
+    };
+    linear([&] {
+        aes_round0_kernel<<<grid_for(G * byte_stride), kThreads, 0, stream_>>>(
+            a.rk, a.blocks, nullptr, plan ? d_ctr_groups_ : nullptr, d_state_, G * 8, L, plan ? a.group_key : a.key_of,
+            a.key_stride);
+        HIPC(hipGetLastError());
+    });
+    for (int r = 1; r < a.rounds; r++) {
+        sub_bytes(false);
+        const uint64_t *rk_r = a.rk + (size_t)16 * r * byte_stride;
+        linear([&] {
+            if (gal)
+                aes_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, map, rk_r, d_state_, nb, L, a.key_of,
+                                                                               a.key_stride);
+            else
+                aes8_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, map, rk_r, d_state_, nb, L, T);
+            HIPC(hipGetLastError());
+        });
+        G = nb * 16;
+        map = nullptr;
+    }
+    sub_bytes(true);
+    if (a.out_bytes)
+        linear([&] {
+            aes_final_kernel<<<grid_for(a.out_bytes * byte_stride), kThreads, 0, stream_>>>(
+                d_muls_, map, a.rk + (size_t)16 * a.nr * byte_stride, a.data, a.out, a.out_bytes, L, a.key_of, a.key_stride,
+                a.blk_out, a.blk_len, false);
+            HIPC(hipGetLastError());
+        });
+    if (a.time_linear) collect_times();
+}
+
+void Engine::aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, size_t nb, int rounds,
+                                uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride) {
+    if (!nb) return;
+    require_rounds(rounds, nr);
+    times_ = StageTimes{};
+    AesRun a{AesRun::GAL_MUL, d_rk, nb, rounds, nr};
+    a.blocks = d_blocks;
+    a.key_of = d_key_of;
+    a.key_stride = key_stride;
+    a.time_linear = d_key_of != nullptr;  // the single-key path keeps its launches as they were: no event records
+    a.out_bytes = nb * 16;
+    a.out = d_out;
+    aes_forward(a);
+}
+
+void Engine::aes8_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, size_t nb, int rounds,
+                                 uint64_t *d_out) {
+    if (!nb) return;
+    if (p_.model != 8) throw std::runtime_error("aes8_encrypt_blocks needs the 8-bit model parameters");
+    require_rounds(rounds, 10);
+    times_ = StageTimes{};
+    AesRun a{AesRun::BYTES8, d_rk, nb, rounds, 10};
+    a.blocks = d_blocks;
+    a.out_bytes = nb * 16;
+    a.out = d_out;
+    aes_forward(a);
+}
+
+// fhe_sbox_pbs::encrypt_block_for_rounds (fhe_sbox_pbs.rs:75-121) over nb blocks of shortint_1bit bits with
+// ByteT::sbox_substitute = 8 multivariate functions per byte (fhe_impls/shortint_1bit.rs:32-50); MixColumns
+// and AddRoundKey are the same LWE-addition network as the 8-bit model's (shortint unchecked_add,
+// shortint_1bit.rs:109-120)
+void Engine::s1_aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, size_t nb, int rounds,
+                                   uint64_t *d_out) {
+    require_s1();
+    if (!nb) return;
+    require_rounds(rounds, 10);
+    times_ = StageTimes{};
+    AesRun a{AesRun::SHORTINT1, d_rk, nb, rounds, 10};
+    a.blocks = d_blocks;
+    a.out_bytes = nb * 16;
+    a.out = d_out;
+    aes_forward(a);
+    collect_times();  // the spans of s1_bootstrap
+}
+
+// ---- multi-key batches: a key table [n_keys][4 (nr + 1) * 32][L], block i under slot key_of[i] ----
+// An asynchronous upload of a host array into a grown device buffer: the host array must live until the next call
+template <class T>
+const T *Engine::upload(T *&d_buf, size_t &cap, const T *host, size_t count) {
+    grow(d_buf, cap, count);
+    HIPC(hipMemcpyAsync(d_buf, host, count * sizeof(T), hipMemcpyHostToDevice, stream_));
+    return d_buf;
+}
+
+const int32_t *Engine::upload_key_of(const int32_t *key_of, size_t nb) {
+    key_of_host_.assign(key_of, key_of + nb);
+    return upload(d_key_of_, cap_key_of_, key_of_host_.data(), nb);
+}
+
+void Engine::aes_encrypt_blocks_multi(const uint64_t *d_table, const int32_t *key_of, const uint64_t *d_blocks,
+                                      size_t nb, int rounds, uint64_t *d_out, int nr) {
+    if (!nb) return;
+    if (p_.model != 1) throw std::runtime_error("multi-key batches need the 1-bit model parameters");
+    require_rounds(rounds, nr);
+    aes_encrypt_blocks(d_table, d_blocks, nb, rounds, d_out, nr, upload_key_of(key_of, nb),
+                       (size_t)4 * (nr + 1) * 32 * p_.big_len());
+}
+
+// ---- AES-128-CTR with public counters (ctr_plan.hpp): round 1 runs on U deduplicated groups ----
+// One chunk of a single-key call on the model of the parameter set: no input ciphertexts, the first out_bytes
+// (<= 16 nb) keystream bytes, xor d_data if given
+void Engine::aes_ctr_chunk(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
+                           size_t out_bytes, uint64_t *d_out, int nr) {
+    require_rounds(rounds, nr);
+    if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
+    check_ctr_plan(plan.groups.size(), plan.map, nb);
+    upload(d_ctr_groups_, cap_ctr_groups_, plan.groups.data(), plan.groups.size());
+    upload(d_ctr_map_, cap_ctr_map_, plan.map.data(), plan.map.size());
+    AesRun a{p_.model == 8 ? AesRun::BYTES8 : AesRun::GAL_MUL, d_rk, nb, rounds, nr};
+    a.U = plan.groups.size();
+    a.data = d_data;
+    a.out_bytes = out_bytes;
+    a.out = d_out;
+    aes_forward(a);
+}
+
+void Engine::aes_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
+                            size_t out_bytes, uint64_t *d_out, int nr) {
+    if (!nb) return;
+    if (p_.model != 1) throw std::runtime_error("aes_ctr_blocks needs the 1-bit model parameters");
+    aes_ctr_chunk(d_rk, plan, nb, rounds, d_data, out_bytes, d_out, nr);
+}
+
+void Engine::aes8_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
+                             size_t out_bytes, uint64_t *d_out, int nr) {
+    if (!nb) return;
+    if (p_.model != 8) throw std::runtime_error("aes8_ctr_blocks needs the 8-bit model parameters");
+    aes_ctr_chunk(d_rk, plan, nb, rounds, d_data, out_bytes, d_out, nr);
+}
+
+void Engine::aes_ctr(const uint64_t *d_rk, const uint8_t iv[8], uint64_t first_counter, size_t nb, int rounds,
+                     const uint8_t *d_data, size_t out_bytes, uint64_t *d_out, int nr) {
+    if (!nb) return;
+    if (p_.model != 1 && p_.model != 8) throw std::runtime_error("counter mode runs on the 1-bit and 8-bit models");
+    if (!ctr_range_ok(first_counter, nb)) throw std::runtime_error("counter range wraps past 2^64 - 1");
+    if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
+    times_ = StageTimes{};
+    const size_t L = p_.bit_len();
+    // the uploads of a plan are asynchronous: every chunk's plan lives until the next call
+    ctr_plans_.clear();
+    ctr_plans_.reserve((nb + ctr_chunk_ - 1) / ctr_chunk_);
+    for (size_t b0 = 0; b0 < nb; b0 += ctr_chunk_) {
+        const size_t cn = std::min(ctr_chunk_, nb - b0);
+        const size_t byte0 = b0 * 16;
+        const size_t cbytes = out_bytes > byte0 ? std::min(cn * 16, out_bytes - byte0) : 0;
+        ctr_plans_.emplace_back();
+        ctr_plan(iv, first_counter + b0, cn, ctr_plans_.back());
+        const uint8_t *data = d_data ? d_data + byte0 : nullptr;
+        uint64_t *out = d_out + byte0 * 8 * L;
+        aes_ctr_chunk(d_rk, ctr_plans_.back(), cn, rounds, data, cbytes, out, nr);
+    }
+}
+
+// One chunk of a multi-stream call: the round keys of every block and group are read from their slot of the key
+// table, and the final kernel writes each block's bytes at its place in the concatenated output
+void Engine::aes_ctr_blocks_multi(const uint64_t *d_table, const CtrPlanMulti &plan, int rounds, const uint8_t *d_data,
+                                  uint64_t *d_out, int nr) {
+    const size_t nb = plan.block_slot.size(), U = plan.groups.size();
+    if (!nb) return;
+    if (plan.group_slot.size() != U || plan.block_out.size() != nb || plan.block_len.size() != nb)
+        throw std::runtime_error("counter plan does not match the blocks");
+    check_ctr_plan(U, plan.map, nb);
+    for (int32_t n : plan.block_len)
+        if (n < 1 || n > 16) throw std::runtime_error("counter plan: block length out of range");
+    upload(d_ctr_groups_, cap_ctr_groups_, plan.groups.data(), U);
+    upload(d_ctr_map_, cap_ctr_map_, plan.map.data(), nb * 16);
+    AesRun a{AesRun::GAL_MUL, d_table, nb, rounds, nr};
+    a.U = U;
+    a.group_key = upload(d_ctr_gslot_, cap_ctr_gslot_, plan.group_slot.data(), U);
+    a.key_of = upload(d_key_of_, cap_key_of_, plan.block_slot.data(), nb);
+    a.key_stride = (size_t)4 * (nr + 1) * 32 * p_.big_len();
+    a.time_linear = true;
+    a.data = d_data;
+    a.out_bytes = nb * 16;
+    a.blk_out = upload(d_ctr_bout_, cap_ctr_bout_, plan.block_out.data(), nb);
+    a.blk_len = upload(d_ctr_blen_, cap_ctr_blen_, plan.block_len.data(), nb);
+    a.out = d_out;
+    aes_forward(a);
+}
+
+void Engine::aes_ctr_multi(const uint64_t *d_table, const std::vector<CtrBlock> &blocks, int rounds,
+                           const uint8_t *d_data, uint64_t *d_out, int nr) {
+    if (blocks.empty()) return;
+    if (p_.model != 1) throw std::runtime_error("multi-key batches need the 1-bit model parameters");
+    require_rounds(rounds, nr);
+    times_ = StageTimes{};
+    // the uploads of a plan are asynchronous: every chunk's plan lives until the next call.  A chunk boundary may
+    // fall inside a stream: a block carries its slot, counter and output place with it.
+    ctr_mplans_.clear();
+    ctr_mplans_.reserve((blocks.size() + ctr_chunk_ - 1) / ctr_chunk_);
+    for (size_t b0 = 0; b0 < blocks.size(); b0 += ctr_chunk_) {
+        const size_t cn = std::min(ctr_chunk_, blocks.size() - b0);
+        ctr_mplans_.emplace_back();
+        ctr_plan_multi(blocks.data() + b0, cn, ctr_mplans_.back());
+        aes_ctr_blocks_multi(d_table, ctr_mplans_.back(), rounds, d_data, d_out, nr);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// AES inverse cipher (FIPS-197 5.3; aes_inv.hpp)
+// ---------------------------------------------------------------------------------------------
+void Engine::require_inverse(int rounds, int nr) const {
+    if (p_.model != 1 || !d_lut_inv32_) throw std::runtime_error("the inverse cipher needs the 1-bit model parameters");
+    require_rounds(rounds, nr);
+}
+
+// Round 0 on the ciphertexts d_blocks or (nullptr) on the public blocks d_cur, rounds R-1 .. 1 and the last
+// round, which XORs the public blocks d_xor in if given: R circuit bootstraps per block
+void Engine::aes_decrypt_rounds(const uint64_t *d_dk, const uint64_t *d_blocks, const uint8_t *d_cur, size_t nb,
+                                int rounds, const uint8_t *d_xor, uint64_t *d_out, int nr, const int32_t *d_key_of,
+                                size_t key_stride) {
+    const int L = (int)p_.big_len();
+    const size_t state_len = nb * 128 * (size_t)L, byte_stride = 8 * (size_t)L;
+    times_ = StageTimes{};
+    grow(d_state_, cap_state_, state_len);
+    grow(d_muls_, cap_muls_, nb * 16 * (size_t)(rounds > 1 ? 32 : 8) * L);
+    timed(ST_LINEAR, [&] {
+        aes_round0_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_dk + (size_t)16 * nr * byte_stride, d_blocks,
+                                                                          d_cur, nullptr, d_state_, nb * 128, L, d_key_of,
+                                                                          key_stride);
+        HIPC(hipGetLastError());
+    });
+    for (int r = rounds - 1; r >= 1; r--) {
+        circuit_bootstrap(d_state_, nb * 16, 8, d_lut_inv32_, 32, d_muls_);
+        timed(ST_LINEAR, [&] {
+            aes_inv_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_dk + (size_t)16 * r * byte_stride,
+                                                                               d_state_, nb, L, 1, d_key_of, key_stride);
+            HIPC(hipGetLastError());
+        });
+    }
+    circuit_bootstrap(d_state_, nb * 16, 8, d_lut_inv8_, 8, d_muls_);
+    timed(ST_LINEAR, [&] {
+        aes_final_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, nullptr, d_dk, d_xor, d_out, nb * 16, L,
+                                                                         d_key_of, key_stride, nullptr, nullptr, true);
+        HIPC(hipGetLastError());
+    });
+    collect_times();
+}
+
+void Engine::aes_decrypt_blocks(const uint64_t *d_dk, const uint64_t *d_blocks, size_t nb, int rounds,
+                                uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride) {
+    if (!nb) return;
+    require_inverse(rounds, nr);
+    aes_decrypt_rounds(d_dk, d_blocks, nullptr, nb, rounds, nullptr, d_out, nr, d_key_of, key_stride);
+}
+
+void Engine::aes_decrypt_blocks_multi(const uint64_t *d_dtable, const int32_t *key_of, const uint64_t *d_blocks,
+                                      size_t nb, int rounds, uint64_t *d_out, int nr) {
+    if (!nb) return;
+    require_inverse(rounds, nr);
+    aes_decrypt_blocks(d_dtable, d_blocks, nb, rounds, d_out, nr, upload_key_of(key_of, nb),
+                       (size_t)4 * (nr + 1) * 32 * p_.big_len());
+}
+
+void Engine::aes_cbc_transcipher(const uint64_t *d_dk, const uint8_t *d_iv_data, size_t nb, int rounds,
+                                 uint64_t *d_out, int nr) {
+    if (!nb) return;
+    require_inverse(rounds, nr);
+    // d_iv_data = iv || C_0 .. C_{nb-1}: block i is decrypted from bytes 16 (i + 1) .. and XORed with bytes 16 i ..
+    aes_decrypt_rounds(d_dk, nullptr, d_iv_data + 16, nb, rounds, d_iv_data, d_out, nr, nullptr, 0);
+}
+
+// d_cur / d_prev [nb][16]: the ciphertext block and the block before it (the stream's iv for its first block)
+void Engine::aes_cbc_transcipher_multi(const uint64_t *d_dtable, const int32_t *key_of, const uint8_t *d_cur,
+                                       const uint8_t *d_prev, size_t nb, int rounds, uint64_t *d_out, int nr) {
+    if (!nb) return;
+    require_inverse(rounds, nr);
+    aes_decrypt_rounds(d_dtable, nullptr, d_cur, nb, rounds, d_prev, d_out, nr, upload_key_of(key_of, nb),
+                       (size_t)4 * (nr + 1) * 32 * p_.big_len());
+}
+
+// ---------------------------------------------------------------------------------------------
+// Key derivations on a key table [n_keys][W*32][L].  A table of one key is contiguous: its words
+// are read and bootstrapped where they lie, and nothing is gathered or scattered.
+// ---------------------------------------------------------------------------------------------
+void Engine::copy_rows(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t rows,
+                       size_t len) {
+    timed(ST_LINEAR, [&] {
+        copy_rows_strided_kernel<<<grid_for(rows * len), kThreads, 0, stream_>>>(d_src, src_stride, d_dst, dst_stride,
+                                                                                  rows, len);
+        HIPC(hipGetLastError());
+    });
+}
+
+// `len` words at the same place of every key: an asynchronous copy for one key (none in place), a row copy for more
+void Engine::copy_key_words(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t n_keys,
+                            size_t len) {
+    if (n_keys > 1)
+        copy_rows(d_src, src_stride, d_dst, dst_stride, n_keys, len);
+    else if (d_src != d_dst)
+        HIPC(hipMemcpyAsync(d_dst, d_src, len * 8, hipMemcpyDeviceToDevice, stream_));
+}
+
+void Engine::aes_decrypt_key(const uint64_t *d_rk, uint64_t *d_dk, int nr) {
+    require_inverse(nr, nr);
+    if (d_rk == d_dk) throw std::runtime_error("the decryption key cannot be derived in place");
+    aes_decrypt_key_multi(d_rk, 1, d_dk, nr);
+}
+
+void Engine::aes_decrypt_key_multi(const uint64_t *d_table, size_t n_keys, uint64_t *d_dtable, int nr) {
+    require_inverse(nr, nr);
+    if (d_table == d_dtable) throw std::runtime_error("the decryption keys cannot be derived in place");
+    if (!n_keys) return;
+    const int L = (int)p_.big_len();
+    // words 4 .. 4 nr - 1: nr - 1 round keys of 16 bytes
+    const size_t word = 32 * (size_t)L, mid = 4 * (size_t)(nr - 1) * word, last = 4 * (size_t)nr * word;
+    const size_t stride = last + 4 * word;
+    const bool one = n_keys == 1;
+    times_ = StageTimes{};
+    grow(d_state_, cap_state_, n_keys * mid);
+    grow(d_muls_, cap_muls_, n_keys * 16 * (size_t)(nr - 1) * 32 * L);
+    copy_key_words(d_table, stride, d_dtable, stride, n_keys, 4 * word);
+    copy_key_words(d_table + last, stride, d_dtable + last, stride, n_keys, 4 * word);
+    const uint64_t *middle = d_table + 4 * word;
+    if (!one) {
+        copy_rows(middle, stride, d_state_, mid, n_keys, mid);
+        middle = d_state_;
+    }
+    circuit_bootstrap(middle, n_keys * 16 * (size_t)(nr - 1), 8, d_lut_mul32_, 32, d_muls_);
+    timed(ST_LINEAR, [&] {
+        aes_inv_mix_kernel<<<grid_for(n_keys * mid), kThreads, 0, stream_>>>(d_muls_, nullptr, d_state_,
+                                                                              n_keys * (size_t)(nr - 1), L, 0);
+        HIPC(hipGetLastError());
+    });
+    circuit_bootstrap(d_state_, n_keys * 128 * (size_t)(nr - 1), 1, d_lut_id1_, 1, one ? d_dtable + 4 * word : d_muls_);
+    if (!one) copy_rows(d_muls_, mid, d_dtable + 4 * word, stride, n_keys, mid);
+    collect_times();
+}
+
+void Engine::aes_key_expand(const uint64_t *d_key, int nk, uint64_t *d_rk) { aes_key_expand_multi(d_key, nk, 1, d_rk); }
+
+// Key expansion (FIPS-197 5.2, figure 11), nk = 4 / 6 / 8 key words, word i of all keys at once: the bootstraps
+// of a word run over n_keys times the bits, so the number of chained circuit bootstraps is that of one key.
+// Every new word is bootstrapped (identity, 32 one-bit groups per key) before the next word reads it, as
+// Context::aes_key_schedule does on the host; the stages of a word are launches on the engine stream and no
+// ciphertext leaves the device.  The table is key-major: for several keys, word i - 1 of every key is gathered
+// for SubWord and the bootstrapped word scattered into the table rows.
+void Engine::aes_key_expand_multi(const uint64_t *d_keys, int nk, size_t n_keys, uint64_t *d_table) {
+    if (p_.model != 1 || !d_lut_id1_) throw std::runtime_error("the key expansion needs the 1-bit model parameters");
+    if (nk != 4 && nk != 6 && nk != 8) throw std::runtime_error("the key must be 4, 6 or 8 words");
+    if (!n_keys) return;
+    const int L = (int)p_.big_len(), words = 4 * (nk + 7);
+    const size_t word = 32 * (size_t)L, stride = (size_t)words * word, batch = n_keys * word;
+    const bool one = n_keys == 1;
+    times_ = StageTimes{};
+    grow(d_state_, cap_state_, batch);
+    grow(d_muls_, cap_muls_, batch);
+    copy_key_words(d_keys, (size_t)nk * word, d_table, stride, n_keys, (size_t)nk * word);
+    for (int i = nk; i < words; i++) {
+        const uint64_t *back = d_table + (size_t)(i - nk) * word, *other = d_table + (size_t)(i - 1) * word;
+        size_t other_stride = stride;
+        int rot = 0, rcon = 0;
+        if (i % nk == 0 || (nk == 8 && i % 8 == 4)) {
+            // SubWord of rk[i-1]; RotWord and Rcon on the words that start a key-sized group
+            if (!one) {
+                copy_rows(other, stride, d_state_, word, n_keys, word);
+                other = d_state_;
+            }
+            circuit_bootstrap(other, 4 * n_keys, 8, d_lut8_, 8, d_muls_);
+            other = d_muls_;
+            other_stride = word;
+            if (i % nk == 0) {
+                rot = 1;
+                rcon = kRcon[i / nk];
+            }
+        }
+        timed(ST_LINEAR, [&] {
+            aes_ks_word_kernel<<<grid_for(batch), kThreads, 0, stream_>>>(back, other, rot, rcon, d_state_, L, n_keys,
+                                                                           stride, other_stride);
+            HIPC(hipGetLastError());
+        });
+        uint64_t *dst = d_table + (size_t)i * word;
+        circuit_bootstrap(d_state_, 32 * n_keys, 1, d_lut_id1_, 1, one ? dst : d_muls_);
+        if (!one) copy_rows(d_muls_, word, dst, stride, n_keys, word);
+    }
+    collect_times();
+}
+
+}  // namespace tae

@@ -251,10 +251,11 @@ class Engine {
     // inverse cipher (1-bit model): InvSbox * {14,11,13,9}, InvSbox, the multiples alone, the 1 -> 1 identity
     uint64_t *d_lut_inv32_ = nullptr, *d_lut_inv8_ = nullptr, *d_lut_mul32_ = nullptr, *d_lut_id1_ = nullptr;
     void require_inverse(int rounds, int nr) const;
-    void aes_decrypt_rounds(const uint64_t *d_dk, size_t nb, int rounds, const uint8_t *d_xor, uint64_t *d_out,
-                            const int32_t *d_key_of, size_t key_stride);
-    void aes_cbc_blocks(const uint64_t *d_dk, const uint8_t *d_cur, const uint8_t *d_prev, size_t nb, int rounds,
-                        uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride);
+    void aes_decrypt_rounds(const uint64_t *d_dk, const uint64_t *d_blocks, const uint8_t *d_cur, size_t nb, int rounds,
+                            const uint8_t *d_xor, uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride);
+    // the forward cipher's one round loop (aes_engine.hip): every forward entry point fills an AesRun
+    struct AesRun;
+    void aes_forward(const AesRun &run);
     uint64_t *d_wlut_sbox_ = nullptr, *d_wlut_id_ = nullptr;  // 8-bit model
     uint64_t *d_lut_x_ = nullptr;                             // extract_bits accumulators [nbits][glwe]
     int lut_x_delta_ = -1, lut_x_bits_ = 0;
@@ -268,7 +269,10 @@ class Engine {
     int32_t *d_ctr_map_ = nullptr;
     size_t cap_ctr_groups_ = 0, cap_ctr_map_ = 0;
     std::vector<CtrPlan> ctr_plans_;
-    void upload_ctr_plan(const CtrPlan &plan, size_t nb);
+    void aes_ctr_chunk(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
+                       size_t out_bytes, uint64_t *d_out, int nr);
+    template <class T>
+    const T *upload(T *&d_buf, size_t &cap, const T *host, size_t count);
     // multi-key batches: the per-block slots on the device and the host copy its pending upload reads; the
     // parallel arrays of a CtrPlanMulti and the plans of the chunks in flight
     int32_t *d_key_of_ = nullptr, *d_ctr_gslot_ = nullptr, *d_ctr_blen_ = nullptr;
@@ -281,6 +285,8 @@ class Engine {
                               uint64_t *d_out, int nr);
     void copy_rows(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t rows,
                    size_t len);
+    void copy_key_words(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t n_keys,
+                        size_t len);
     // shortint_1bit: S-box / identity test vectors and tree-level scratch
     uint64_t *d_s1_sbox_tv_ = nullptr, *d_s1_id_tv_ = nullptr, *d_s1_in_ = nullptr, *d_s1_out_ = nullptr,
              *d_s1_pks_ = nullptr, *d_s1_tv_ = nullptr;

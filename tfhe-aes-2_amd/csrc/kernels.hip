@@ -1,4 +1,5 @@
-// HIP kernels for gfx950 (CDNA4) and the Engine that drives them.
+// HIP kernels of the generic TFHE stages for gfx950 (CDNA4) and the core of the Engine that drives them.  The AES
+// application layer (linear-layer kernels, round loops, key derivations) is aes_engine.hip.
 //
 // Hot path, batched over every input bit of every SBOX of a round:
 //   keyswitch_kernel      tfhe keyswitch_lwe_ciphertext            (extract_dual_bit_from_bit,
@@ -7,8 +8,6 @@
 //                         tfhe wop_pbs::vertical_packing           (blind_rotate_assign, VP flavour)
 //   pfks_kernel           tfhe private_functional_keyswitch_lwe_ciphertext_into_glwe_ciphertext
 //   fft_torus_kernel      tfhe FourierGgswCiphertext::fill_with_forward_fourier (and the BSK)
-//   aes_*_kernel          ShiftRows / MixColumns / AddRoundKey as LWE additions
-//                         (fhe_sbox_gal_mul_pbs.rs:61-132, data_model.rs:270-281)
 #include <hip/hip_runtime.h>
 
 #include <cerrno>
@@ -29,7 +28,7 @@
 #include "br1024w.hpp"
 #include "br1024lat.hpp"
 #include "ksgemm.hpp"
-#include "engine.hpp"
+#include "engine_detail.hpp"
 #include "fft_device.hpp"
 #include "glwe_pack.hpp"
 
@@ -38,11 +37,9 @@ namespace tae {
 void hip_check(hipError_t e, const char *what) {
     if (e != hipSuccess) throw HipError{std::string(what) + ": " + hipGetErrorString(e)};
 }
-#define HIPC(x) hip_check((x), #x)
 
 namespace {
 
-constexpr int kThreads = 256;
 #ifndef TAE_G6_WM
 constexpr int kG6WM = 4;  // PFKS GEMM: 96 x WM ciphertexts per workgroup tile, 256 x WM threads
 #else
@@ -501,249 +498,6 @@ __global__ void __launch_bounds__(512) pack_rotate_sum_kernel(const uint64_t *__
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// AES linear layer as LWE additions (state = [blk][16 bytes][8 bits][K+1])
-// ---------------------------------------------------------------------------------------------
-// Keyed form of the kernels below (multi-key batches): with key_of != nullptr the round key of
-// block blk is read at rk + key_of[blk] * key_stride, the same round of slot key_of[blk] of a key table
-// [n_keys][W*32][L]; with nullptr it is rk, the single-key form.  The slot is uniform over the L coefficients of
-// a ciphertext, so the reads stay contiguous runs per wave.
-__device__ __forceinline__ const uint64_t *keyed_rk(const uint64_t *rk, const int32_t *key_of, size_t key_stride,
-                                                    size_t blk) {
-    return key_of ? rk + (size_t)key_of[blk] * key_stride : rk;
-}
-
-// state = blocks + rk[round 0]   (xor_state, data_model.rs:270-274)
-__global__ void aes_ark0_kernel(const uint64_t *__restrict__ blocks, const uint64_t *__restrict__ rk,
-                                uint64_t *__restrict__ state, size_t nb, int L,
-                                const int32_t *__restrict__ key_of = nullptr, size_t key_stride = 0) {
-    const size_t total = nb * 128 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t within = t % (128 * (size_t)L);
-        state[t] = blocks[t] + keyed_rk(rk, key_of, key_stride, t / (128 * (size_t)L))[within];
-    }
-}
-
-// ShiftRows on the three SubBytes*{1,2,3} states, MixColumns, AddRoundKey:
-// out[r][c] = 2s[r][c'] + s[r+3][.] + s[r+2][.] + 3s[r+1][.]  (fhe_sbox_gal_mul_pbs.rs:61-82)
-__global__ void aes_mix_kernel(const uint64_t *__restrict__ muls, const uint64_t *__restrict__ rk_round,
-                               uint64_t *__restrict__ state, size_t nb, int L,
-                               const int32_t *__restrict__ key_of = nullptr, size_t key_stride = 0) {
-    const size_t total = nb * 128 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;  // blk*128 + pos*8 + bit
-        const int bit = (int)(ct & 7);
-        const int pos = (int)((ct >> 3) & 15);
-        const size_t blk = ct >> 7;
-        const int c = pos >> 2, row = pos & 3;
-        // after ShiftRows, element (rr, c) comes from SubBytes output byte 4*((c+rr)%4) + rr
-        auto src = [&](int rr, int m) {
-            const int byte = 4 * ((c + rr) & 3) + rr;
-            return muls[(((blk * 16 + byte) * 24) + 8 * m + bit) * (size_t)L + coef];
-        };
-        state[t] = src(row, 1) + src((row + 3) & 3, 0) + src((row + 2) & 3, 0) + src((row + 1) & 3, 2) +
-                   keyed_rk(rk_round, key_of, key_stride, blk)[(size_t)(pos * 8 + bit) * L + coef];
-    }
-}
-
-// last round: SubBytes (8->8), ShiftRows, AddRoundKey(rk[40..44])
-__global__ void aes_final_kernel(const uint64_t *__restrict__ sb, const uint64_t *__restrict__ rk_round,
-                                 uint64_t *__restrict__ out, size_t nb, int L,
-                                 const int32_t *__restrict__ key_of = nullptr, size_t key_stride = 0) {
-    const size_t total = nb * 128 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;
-        const int bit = (int)(ct & 7);
-        const int pos = (int)((ct >> 3) & 15);
-        const size_t blk = ct >> 7;
-        const int c = pos >> 2, row = pos & 3;
-        const int byte = 4 * ((c + row) & 3) + row;
-        out[t] = sb[((blk * 16 + byte) * 8 + bit) * (size_t)L + coef] +
-                 keyed_rk(rk_round, key_of, key_stride, blk)[(size_t)(pos * 8 + bit) * L + coef];
-    }
-}
-
-// ---- AES-128-CTR with public counters (ctr_plan.hpp): round 1 runs on U deduplicated groups ----
-// Round 0 without input ciphertexts: the SubBytes input of group g = (pos, v) is rk0[pos] + trivial(v),
-// i.e. bit b is rk0[pos*8 + b] with ((v >> (7-b)) & 1) << 63 on the body (what aes_ark0_kernel computes for
-// a trivial counter block).  groups [U] = (pos << 8) | v, state [U][8][L].  Keyed form: group g belongs to slot
-// group_key[g] (the slot does not fit the 16-bit group word, so it is a parallel array).
-__global__ void aes_ctr_round0_kernel(const uint64_t *__restrict__ rk, const uint16_t *__restrict__ groups,
-                                      uint64_t *__restrict__ state, size_t U, int L,
-                                      const int32_t *__restrict__ group_key = nullptr, size_t key_stride = 0) {
-    const size_t total = U * 8 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;  // g*8 + bit
-        const int bit = (int)(ct & 7);
-        const uint16_t g = groups[ct >> 3];
-        const int pos = g >> 8, v = g & 0xff;
-        uint64_t w = keyed_rk(rk, group_key, key_stride, ct >> 3)[(size_t)(pos * 8 + bit) * L + coef];
-        if (coef == (size_t)L - 1) w += (uint64_t)((v >> (7 - bit)) & 1) << 63;
-        state[t] = w;
-    }
-}
-
-// aes_mix_kernel with the SubBytes*{1,2,3} outputs of (blk, byte) at group map[blk*16 + byte]: muls [U][24][L]
-__global__ void aes_mix_idx_kernel(const uint64_t *__restrict__ muls, const int32_t *__restrict__ map,
-                                   const uint64_t *__restrict__ rk_round, uint64_t *__restrict__ state, size_t nb,
-                                   int L, const int32_t *__restrict__ key_of = nullptr, size_t key_stride = 0) {
-    const size_t total = nb * 128 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;  // blk*128 + pos*8 + bit
-        const int bit = (int)(ct & 7);
-        const int pos = (int)((ct >> 3) & 15);
-        const size_t blk = ct >> 7;
-        const int c = pos >> 2, row = pos & 3;
-        auto src = [&](int rr, int m) {
-            const int byte = 4 * ((c + rr) & 3) + rr;
-            const size_t g = (size_t)map[blk * 16 + byte];
-            return muls[((g * 24) + 8 * m + bit) * (size_t)L + coef];
-        };
-        state[t] = src(row, 1) + src((row + 3) & 3, 0) + src((row + 2) & 3, 0) + src((row + 1) & 3, 2) +
-                   keyed_rk(rk_round, key_of, key_stride, blk)[(size_t)(pos * 8 + bit) * L + coef];
-    }
-}
-
-// aes_final_kernel for counter mode: the first n_bytes keystream bytes (block order) only, SubBytes output
-// of (blk, byte) at group map[blk*16 + byte] (map == nullptr: at blk*16 + byte), and with data != nullptr
-// the public byte data[i] XORed in: bit b of it << 63 on the body of keystream bit b of byte i
-__global__ void aes_ctr_final_kernel(const uint64_t *__restrict__ sb, const int32_t *__restrict__ map,
-                                     const uint64_t *__restrict__ rk_round, const uint8_t *__restrict__ data,
-                                     uint64_t *__restrict__ out, size_t n_bytes, int L) {
-    const size_t total = n_bytes * 8 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;
-        const int bit = (int)(ct & 7);
-        const int pos = (int)((ct >> 3) & 15);
-        const size_t blk = ct >> 7;
-        const int c = pos >> 2, row = pos & 3;
-        const int byte = 4 * ((c + row) & 3) + row;
-        const size_t g = map ? (size_t)map[blk * 16 + byte] : blk * 16 + byte;
-        uint64_t w = sb[(g * 8 + bit) * (size_t)L + coef] + rk_round[(size_t)(pos * 8 + bit) * L + coef];
-        if (data && coef == (size_t)L - 1) w += (uint64_t)((data[ct >> 3] >> (7 - bit)) & 1) << 63;
-        out[t] = w;
-    }
-}
-
-// Keyed form of aes_ctr_final_kernel for several streams (ctr_plan.hpp CtrPlanMulti): block blk of the flattened
-// list belongs to slot key_of[blk] and writes its first blk_len[blk] bytes at byte blk_out[blk] of the
-// concatenated output; data (nullptr: the keystream) is indexed like the output.  Every written ciphertext is
-// one contiguous run of L words.
-__global__ void aes_ctr_final_streams_kernel(const uint64_t *__restrict__ sb, const int32_t *__restrict__ map,
-                                             const uint64_t *__restrict__ rk_round, const uint8_t *__restrict__ data,
-                                             uint64_t *__restrict__ out, size_t nb, int L,
-                                             const int32_t *__restrict__ key_of, size_t key_stride,
-                                             const int64_t *__restrict__ blk_out, const int32_t *__restrict__ blk_len) {
-    const size_t total = nb * 128 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;
-        const int bit = (int)(ct & 7);
-        const int pos = (int)((ct >> 3) & 15);
-        const size_t blk = ct >> 7;
-        if (pos >= blk_len[blk]) continue;
-        const int c = pos >> 2, row = pos & 3;
-        const int byte = 4 * ((c + row) & 3) + row;
-        const size_t g = map ? (size_t)map[blk * 16 + byte] : blk * 16 + byte;
-        const size_t obyte = (size_t)blk_out[blk] + pos;
-        uint64_t w = sb[(g * 8 + bit) * (size_t)L + coef] +
-                     keyed_rk(rk_round, key_of, key_stride, blk)[(size_t)(pos * 8 + bit) * L + coef];
-        if (data && coef == (size_t)L - 1) w += (uint64_t)((data[obyte] >> (7 - bit)) & 1) << 63;
-        out[(obyte * 8 + bit) * (size_t)L + coef] = w;
-    }
-}
-
-// ---- AES-128 inverse cipher (FIPS-197 5.3; aes_inv.hpp has the algorithm and the source-byte indices) ----
-// InvShiftRows (shift_rows != 0), InvMixColumns and AddRoundKey on the four InvSubBytes*{14,11,13,9} states:
-// muls [nb*16][32][L], multiple m at ciphertexts 8m..8m+7 of a byte.  rk_round == nullptr adds no key and
-// shift_rows == 0 skips InvShiftRows: InvMixColumns alone, which derives the decryption key from nb round
-// keys.  Consecutive threads walk the coefficients of one ciphertext, so every read and the write coalesce.
-__global__ void aes_inv_mix_kernel(const uint64_t *__restrict__ muls, const uint64_t *__restrict__ rk_round,
-                                   uint64_t *__restrict__ state, size_t nb, int L, int shift_rows,
-                                   const int32_t *__restrict__ key_of = nullptr, size_t key_stride = 0) {
-    const size_t total = nb * 128 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;  // blk*128 + pos*8 + bit
-        const int bit = (int)(ct & 7);
-        const int pos = (int)((ct >> 3) & 15);
-        const size_t blk = ct >> 7;
-        const int c = pos >> 2, row = pos & 3;
-        uint64_t acc = rk_round ? keyed_rk(rk_round, key_of, key_stride, blk)[(size_t)(pos * 8 + bit) * L + coef] : 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int byte = inv_mix_src_byte(row, c, j, shift_rows != 0);
-            acc += muls[(((blk * 16 + byte) * 32) + 8 * j + bit) * (size_t)L + coef];
-        }
-        state[t] = acc;
-    }
-}
-
-// last round of the inverse cipher: InvSubBytes (8 -> 8), InvShiftRows, AddRoundKey(dk[0..3]); with
-// xor_bytes != nullptr (nb*16 public bytes) bit b of byte blk*16 + pos is XORed in as well, << 63 on the
-// body (CBC: the previous ciphertext block)
-__global__ void aes_inv_final_kernel(const uint64_t *__restrict__ sb, const uint64_t *__restrict__ rk_round,
-                                     const uint8_t *__restrict__ xor_bytes, uint64_t *__restrict__ out, size_t nb,
-                                     int L, const int32_t *__restrict__ key_of = nullptr, size_t key_stride = 0) {
-    const size_t total = nb * 128 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;
-        const int bit = (int)(ct & 7);
-        const int pos = (int)((ct >> 3) & 15);
-        const size_t blk = ct >> 7;
-        const int byte = inv_final_src_byte(pos & 3, pos >> 2);
-        uint64_t w = sb[((blk * 16 + byte) * 8 + bit) * (size_t)L + coef] +
-                     keyed_rk(rk_round, key_of, key_stride, blk)[(size_t)(pos * 8 + bit) * L + coef];
-        if (xor_bytes && coef == (size_t)L - 1) w += (uint64_t)((xor_bytes[ct >> 3] >> (7 - bit)) & 1) << 63;
-        out[t] = w;
-    }
-}
-
-// round 0 of the inverse cipher on public blocks (nb*16 bytes): rk_last (dk words 40..43) + trivial(byte),
-// what aes_ark0_kernel computes for trivial encryptions of the blocks
-__global__ void aes_inv_round0_public_kernel(const uint64_t *__restrict__ rk_last, const uint8_t *__restrict__ bytes,
-                                             uint64_t *__restrict__ state, size_t nb, int L,
-                                             const int32_t *__restrict__ key_of = nullptr, size_t key_stride = 0) {
-    const size_t total = nb * 128 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;
-        const int bit = (int)(ct & 7);
-        uint64_t w = keyed_rk(rk_last, key_of, key_stride, ct >> 7)[(ct & 127) * (size_t)L + coef];
-        if (coef == (size_t)L - 1) w += (uint64_t)((bytes[ct >> 3] >> (7 - bit)) & 1) << 63;
-        state[t] = w;
-    }
-}
-
-// ---- key expansion (FIPS-197 5.2, figure 11): one word before its identity bootstrap ----
-// t = back + other (+ Rcon), whole ciphertexts: back = rk[i-Nk], other = rk[i-1] or SubWord(rk[i-1]), both
-// [4 bytes][8 bits][L].  SubWord works byte by byte, so RotWord is applied here, on the read of its output:
-// rot = 1 takes byte (b + 1) % 4 of `other`.  rcon != 0 adds bit b of it (MSB first) << 63 on the body of bit b
-// of byte 0, as Context::trivial does.  Consecutive threads walk the coefficients of one ciphertext.
-// Keyed form: the same word of n_keys keys at once, key k reading back + k * back_stride and
-// other + k * other_stride and writing out [n_keys][32][L].
-__global__ void aes_ks_word_kernel(const uint64_t *__restrict__ back, const uint64_t *__restrict__ other, int rot,
-                                   int rcon, uint64_t *__restrict__ out, int L, size_t n_keys = 1,
-                                   size_t back_stride = 0, size_t other_stride = 0) {
-    const size_t word = 32 * (size_t)L, total = n_keys * word;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t key = t / word, within = t - key * word;
-        const size_t coef = within % L;
-        const int ct = (int)(within / L);  // byte*8 + bit
-        const int bit = ct & 7, byte = ct >> 3;
-        uint64_t w = back[key * back_stride + within] +
-                     other[key * other_stride + (size_t)(((byte + rot) & 3) * 8 + bit) * L + coef];
-        if (byte == 0 && coef == (size_t)L - 1) w += (uint64_t)((rcon >> (7 - bit)) & 1) << 63;
-        out[t] = w;
-    }
-}
-
 __global__ void lwe_add_kernel(uint64_t *__restrict__ a, const uint64_t *__restrict__ b, size_t count) {
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (size_t)gridDim.x * blockDim.x)
         a[t] += b[t];
@@ -760,83 +514,6 @@ __global__ void lwe_shl_kernel(const uint64_t *__restrict__ in, uint64_t *__rest
 __global__ void lwe_sub_kernel(uint64_t *__restrict__ a, const uint64_t *__restrict__ b, size_t count) {
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (size_t)gridDim.x * blockDim.x)
         a[t] -= b[t];
-}
-
-// dst[r * dst_stride + j] = src[r * len + j]
-__global__ void copy_rows_kernel(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, size_t rows, int len,
-                                 size_t dst_stride) {
-    const size_t total = rows * (size_t)len;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = t / len, j = t - r * len;
-        dst[r * dst_stride + j] = src[t];
-    }
-}
-
-// dst[r * dst_stride + j] = src[r * src_stride + j]: rows of a key table gathered into a batch or scattered back
-__global__ void copy_rows_strided_kernel(const uint64_t *__restrict__ src, size_t src_stride, uint64_t *__restrict__ dst,
-                                         size_t dst_stride, size_t rows, size_t len) {
-    const size_t total = rows * len;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = t / len, j = t - r * len;
-        dst[r * dst_stride + j] = src[r * src_stride + j];
-    }
-}
-
-// ShiftRows + MixColumns (fhe_sbox_pbs.rs:33-73: gf_256_mul as shifts and XORs of bits, i.e. LWE
-// additions) + AddRoundKey on small-key bits.  sb = SubBytes output [blk][16 bytes][8 bits][L];
-// T.idx[o][*] = the input bits (column-local, byte-major, MSB-first, -1 terminated) summed into
-// output bit o of a column (or_mix_column_terms in the oracle).
-struct MixTerms {
-    int8_t idx[32][8];
-};
-
-__global__ void aes8_mix_kernel(const uint64_t *__restrict__ sb, const uint64_t *__restrict__ rk_round,
-                                uint64_t *__restrict__ state, size_t nb, int L, MixTerms T) {
-    const size_t total = nb * 128 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;
-        const int bit = (int)(ct & 7);
-        const int pos = (int)((ct >> 3) & 15);
-        const size_t blk = ct >> 7;
-        const int c = pos >> 2, row = pos & 3, o = 8 * row + bit;
-        uint64_t acc = rk_round[(size_t)(pos * 8 + bit) * L + coef];
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int i = T.idx[o][q];
-            if (i < 0) break;
-            const int ri = i >> 3, bi = i & 7;
-            const int byte = 4 * ((c + ri) & 3) + ri;  // ShiftRows: state[ri][c] = sb[ri][(c + ri) % 4]
-            acc += sb[((blk * 16 + byte) * 8 + bi) * (size_t)L + coef];
-        }
-        state[t] = acc;
-    }
-}
-
-// aes8_mix_kernel with the SubBytes output of (blk, byte) at group map[blk*16 + byte]: sb [U][8][L]
-__global__ void aes8_mix_idx_kernel(const uint64_t *__restrict__ sb, const int32_t *__restrict__ map,
-                                    const uint64_t *__restrict__ rk_round, uint64_t *__restrict__ state, size_t nb,
-                                    int L, MixTerms T) {
-    const size_t total = nb * 128 * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
-        const size_t coef = t % L;
-        const size_t ct = t / L;
-        const int bit = (int)(ct & 7);
-        const int pos = (int)((ct >> 3) & 15);
-        const size_t blk = ct >> 7;
-        const int c = pos >> 2, row = pos & 3, o = 8 * row + bit;
-        uint64_t acc = rk_round[(size_t)(pos * 8 + bit) * L + coef];
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int i = T.idx[o][q];
-            if (i < 0) break;
-            const int ri = i >> 3, bi = i & 7;
-            const int byte = 4 * ((c + ri) & 3) + ri;
-            const size_t g = (size_t)map[blk * 16 + byte];
-            acc += sb[(g * 8 + bi) * (size_t)L + coef];
-        }
-        state[t] = acc;
-    }
 }
 
 // ---- shortint_1bit model (src/tfhe/shortint_1bit.rs) ----
@@ -932,8 +609,6 @@ __global__ void __launch_bounds__(kThreads) lf_rescale_kernel(cplx *__restrict__
         g[t] = cmul(g[t], e2[t & (M - 1)]);
 }
 
-unsigned grid_for(size_t total) { return (unsigned)std::min<size_t>((total + kThreads - 1) / kThreads, 65536); }
-
 constexpr int kBrC = 3;  // ciphertexts per workgroup in the batched N=512 blind rotation
 
 template <int N>
@@ -952,18 +627,6 @@ void *Engine::alloc(size_t bytes) {
     void *p = nullptr;
     HIPC(hipMalloc(&p, std::max<size_t>(bytes, 16)));
     return p;
-}
-
-template <class T>
-T *Engine::grow(T *&ptr, size_t &cap, size_t count) {
-    if (count > cap) {
-        if (ptr) HIPC(hipFree(ptr));
-        ptr = nullptr;  // a failing alloc below must not leave a freed pointer for ~Engine
-        cap = 0;
-        ptr = static_cast<T *>(alloc(count * sizeof(T)));
-        cap = count;
-    }
-    return ptr;
 }
 
 void Engine::init_common() {
@@ -1743,19 +1406,6 @@ hipEvent_t Engine::next_event() {
     return ev_pool_[ev_used_++];
 }
 
-template <class F>
-void Engine::timed(int stage, F fn) {
-    if (!timing_) {
-        fn();
-        return;
-    }
-    Span sp{next_event(), next_event(), stage};
-    HIPC(hipEventRecord(sp.a, stream_));
-    fn();
-    HIPC(hipEventRecord(sp.b, stream_));
-    spans_.push_back(sp);
-}
-
 uint64_t *Engine::clock_buffer(size_t wgs) {
     if (!clock_) return nullptr;
     grow(d_clk_, cap_clk_, 2 * wgs);
@@ -1849,8 +1499,8 @@ void Engine::extract_bits(const uint64_t *d_in, size_t B, int delta_log, int nbi
         lwe_shl_kernel<<<grid_for(B * L), kThreads, 0, stream_>>>(d_xbuf_, d_xsh_, B * L, 64 - delta_log - bit_idx - 1);
         HIPC(hipGetLastError());
         keyswitch(d_xsh_, d_xks_, B);
-        copy_rows_kernel<<<grid_for(B * S), kThreads, 0, stream_>>>(d_xks_, d_out + (size_t)(nbits - 1 - bit_idx) * S, B,
-                                                                  (int)S, (size_t)nbits * S);
+        copy_rows_strided_kernel<<<grid_for(B * S), kThreads, 0, stream_>>>(
+            d_xks_, S, d_out + (size_t)(nbits - 1 - bit_idx) * S, (size_t)nbits * S, B, S);
         HIPC(hipGetLastError());
         if (bit_idx == nbits - 1) break;
         // PBS of (ks + q/4) with accumulator -alpha, + alpha: an encryption of the bit at alpha * 2;
@@ -1860,511 +1510,6 @@ void Engine::extract_bits(const uint64_t *d_in, size_t B, int delta_log, int nbi
         lwe_sub_kernel<<<grid_for(B * L), kThreads, 0, stream_>>>(d_xbuf_, d_xpbs_, B * L);
         HIPC(hipGetLastError());
     }
-}
-
-void Engine::bootstrap_bytes8(const uint64_t *d_bytes, size_t G, const uint64_t *d_lut, uint64_t *d_out) {
-    if (!G) return;
-    grow(d_ints_, cap_ints_, G * p_.big_len());
-    cbs_vp(d_bytes, G, 8, d_lut, 1, d_ints_);
-    timed(ST_EXTRACT, [&] { extract_bits(d_ints_, G, 56, 8, d_out); });
-    collect_times();
-}
-
-void Engine::aes8_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, size_t nb, int rounds,
-                                 uint64_t *d_out) {
-    if (!nb) return;
-    if (p_.model != 8) throw std::runtime_error("aes8_encrypt_blocks needs the 8-bit model parameters");
-    if (rounds < 1 || rounds > 10) throw std::runtime_error("rounds must be in 1..=10");
-    const int L = (int)p_.small_len();
-    const size_t state_len = nb * 128 * (size_t)L;
-    times_ = StageTimes{};
-    grow(d_state_, cap_state_, state_len);
-    grow(d_muls_, cap_muls_, state_len);
-    const size_t byte_stride = 8 * (size_t)L;
-    MixTerms T;
-    std::memcpy(T.idx, mix_idx_, sizeof(T.idx));
-    aes_ark0_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_blocks, d_rk, d_state_, nb, L);
-    HIPC(hipGetLastError());
-    for (int r = 1; r < rounds; r++) {
-        bootstrap_bytes8(d_state_, nb * 16, d_wlut_sbox_, d_muls_);
-        aes8_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_rk + (size_t)16 * r * byte_stride,
-                                                                        d_state_, nb, L, T);
-        HIPC(hipGetLastError());
-    }
-    bootstrap_bytes8(d_state_, nb * 16, d_wlut_sbox_, d_muls_);
-    aes_final_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_rk + (size_t)160 * byte_stride, d_out,
-                                                                     nb, L);
-    HIPC(hipGetLastError());
-}
-
-// nr = 10 / 12 / 14 (AES-128 / 192 / 256) and 1 <= rounds <= nr, or a runtime_error
-static void require_rounds(int rounds, int nr) {
-    if (nr != 10 && nr != 12 && nr != 14) throw std::runtime_error("the round count of the key size must be 10, 12 or 14");
-    if (rounds < 1 || rounds > nr) throw std::runtime_error("rounds must be in 1..=" + std::to_string(nr));
-}
-
-void Engine::aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, size_t nb, int rounds,
-                                uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride) {
-    if (!nb) return;
-    require_rounds(rounds, nr);
-    const int L = (int)p_.big_len();
-    const size_t state_len = nb * 128 * (size_t)L;
-    times_ = StageTimes{};
-    grow(d_state_, cap_state_, state_len);
-    grow(d_muls_, cap_muls_, nb * 16 * 24 * (size_t)L);
-    const size_t byte_stride = 8 * (size_t)L;
-    // the keyed launches are timed as ST_LINEAR; the single-key path keeps its launches as they were
-    auto linear = [&](auto launch) {
-        if (d_key_of) {
-            timed(ST_LINEAR, launch);
-        } else {
-            launch();
-        }
-    };
-    linear([&] {
-        aes_ark0_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_blocks, d_rk, d_state_, nb, L, d_key_of,
-                                                                        key_stride);
-        HIPC(hipGetLastError());
-    });
-    for (int r = 1; r < rounds; r++) {
-        circuit_bootstrap(d_state_, nb * 16, 8, d_lut24_, 24, d_muls_);
-        linear([&] {
-            aes_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_rk + (size_t)16 * r * byte_stride,
-                                                                           d_state_, nb, L, d_key_of, key_stride);
-            HIPC(hipGetLastError());
-        });
-    }
-    circuit_bootstrap(d_state_, nb * 16, 8, d_lut8_, 8, d_muls_);
-    linear([&] {
-        aes_final_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_rk + (size_t)16 * nr * byte_stride,
-                                                                         d_out, nb, L, d_key_of, key_stride);
-        HIPC(hipGetLastError());
-    });
-    if (d_key_of) collect_times();
-}
-
-// ---- multi-key batches: a key table [n_keys][4 (nr + 1) * 32][L], block i under slot key_of[i] ----
-const int32_t *Engine::upload_key_of(const int32_t *key_of, size_t nb) {
-    // the upload is asynchronous: the host copy lives until the next call
-    key_of_host_.assign(key_of, key_of + nb);
-    grow(d_key_of_, cap_key_of_, nb);
-    HIPC(hipMemcpyAsync(d_key_of_, key_of_host_.data(), nb * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    return d_key_of_;
-}
-
-void Engine::aes_encrypt_blocks_multi(const uint64_t *d_table, const int32_t *key_of, const uint64_t *d_blocks,
-                                      size_t nb, int rounds, uint64_t *d_out, int nr) {
-    if (!nb) return;
-    if (p_.model != 1) throw std::runtime_error("multi-key batches need the 1-bit model parameters");
-    require_rounds(rounds, nr);
-    aes_encrypt_blocks(d_table, d_blocks, nb, rounds, d_out, nr, upload_key_of(key_of, nb),
-                       (size_t)4 * (nr + 1) * 32 * p_.big_len());
-}
-
-// ---- AES-128-CTR with public counters ----
-void Engine::upload_ctr_plan(const CtrPlan &plan, size_t nb) {
-    if (plan.map.size() != nb * 16 || plan.groups.empty()) throw std::runtime_error("counter plan does not match the blocks");
-    for (int32_t g : plan.map)
-        if (g < 0 || (size_t)g >= plan.groups.size()) throw std::runtime_error("counter plan: group index out of range");
-    grow(d_ctr_groups_, cap_ctr_groups_, plan.groups.size());
-    grow(d_ctr_map_, cap_ctr_map_, plan.map.size());
-    HIPC(hipMemcpyAsync(d_ctr_groups_, plan.groups.data(), plan.groups.size() * sizeof(uint16_t), hipMemcpyHostToDevice,
-                        stream_));
-    HIPC(hipMemcpyAsync(d_ctr_map_, plan.map.data(), plan.map.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-}
-
-void Engine::aes_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
-                            size_t out_bytes, uint64_t *d_out, int nr) {
-    if (!nb) return;
-    if (p_.model != 1) throw std::runtime_error("aes_ctr_blocks needs the 1-bit model parameters");
-    require_rounds(rounds, nr);
-    if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
-    const int L = (int)p_.big_len();
-    const size_t U = plan.groups.size();
-    upload_ctr_plan(plan, nb);
-    // round 1 works on U groups; the per-block state and the 24 SubBytes multiples exist from round 2 on
-    const size_t state_len = nb * 128 * (size_t)L;
-    grow(d_state_, cap_state_, rounds == 1 ? U * 8 * (size_t)L : state_len);
-    grow(d_muls_, cap_muls_, rounds == 1 ? U * 8 * (size_t)L : nb * 16 * 24 * (size_t)L);
-    const size_t byte_stride = 8 * (size_t)L;
-    aes_ctr_round0_kernel<<<grid_for(U * 8 * (size_t)L), kThreads, 0, stream_>>>(d_rk, d_ctr_groups_, d_state_, U, L);
-    HIPC(hipGetLastError());
-    size_t G = U;
-    const int32_t *map = d_ctr_map_;
-    for (int r = 1; r < rounds; r++) {
-        circuit_bootstrap(d_state_, G, 8, d_lut24_, 24, d_muls_);
-        const uint64_t *rk_r = d_rk + (size_t)16 * r * byte_stride;
-        if (map)
-            aes_mix_idx_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, map, rk_r, d_state_, nb, L);
-        else
-            aes_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, rk_r, d_state_, nb, L);
-        HIPC(hipGetLastError());
-        G = nb * 16;
-        map = nullptr;
-    }
-    circuit_bootstrap(d_state_, G, 8, d_lut8_, 8, d_muls_);
-    if (out_bytes) {
-        aes_ctr_final_kernel<<<grid_for(out_bytes * 8 * (size_t)L), kThreads, 0, stream_>>>(
-            d_muls_, map, d_rk + (size_t)16 * nr * byte_stride, d_data, d_out, out_bytes, L);
-        HIPC(hipGetLastError());
-    }
-}
-
-void Engine::aes8_ctr_blocks(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
-                             size_t out_bytes, uint64_t *d_out, int nr) {
-    if (!nb) return;
-    if (p_.model != 8) throw std::runtime_error("aes8_ctr_blocks needs the 8-bit model parameters");
-    require_rounds(rounds, nr);
-    if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
-    const int L = (int)p_.small_len();
-    const size_t U = plan.groups.size();
-    upload_ctr_plan(plan, nb);
-    const size_t state_len = nb * 128 * (size_t)L;
-    grow(d_state_, cap_state_, rounds == 1 ? U * 8 * (size_t)L : state_len);
-    grow(d_muls_, cap_muls_, rounds == 1 ? U * 8 * (size_t)L : state_len);
-    const size_t byte_stride = 8 * (size_t)L;
-    MixTerms T;
-    std::memcpy(T.idx, mix_idx_, sizeof(T.idx));
-    aes_ctr_round0_kernel<<<grid_for(U * 8 * (size_t)L), kThreads, 0, stream_>>>(d_rk, d_ctr_groups_, d_state_, U, L);
-    HIPC(hipGetLastError());
-    size_t G = U;
-    const int32_t *map = d_ctr_map_;
-    for (int r = 1; r < rounds; r++) {
-        bootstrap_bytes8(d_state_, G, d_wlut_sbox_, d_muls_);
-        const uint64_t *rk_r = d_rk + (size_t)16 * r * byte_stride;
-        if (map)
-            aes8_mix_idx_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, map, rk_r, d_state_, nb, L, T);
-        else
-            aes8_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, rk_r, d_state_, nb, L, T);
-        HIPC(hipGetLastError());
-        G = nb * 16;
-        map = nullptr;
-    }
-    bootstrap_bytes8(d_state_, G, d_wlut_sbox_, d_muls_);
-    if (out_bytes) {
-        aes_ctr_final_kernel<<<grid_for(out_bytes * 8 * (size_t)L), kThreads, 0, stream_>>>(
-            d_muls_, map, d_rk + (size_t)16 * nr * byte_stride, d_data, d_out, out_bytes, L);
-        HIPC(hipGetLastError());
-    }
-}
-
-void Engine::aes_ctr(const uint64_t *d_rk, const uint8_t iv[8], uint64_t first_counter, size_t nb, int rounds,
-                     const uint8_t *d_data, size_t out_bytes, uint64_t *d_out, int nr) {
-    if (!nb) return;
-    if (p_.model != 1 && p_.model != 8) throw std::runtime_error("counter mode runs on the 1-bit and 8-bit models");
-    if (!ctr_range_ok(first_counter, nb)) throw std::runtime_error("counter range wraps past 2^64 - 1");
-    if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
-    times_ = StageTimes{};
-    const size_t L = p_.bit_len();
-    // the uploads of a plan are asynchronous: every chunk's plan lives until the next call
-    ctr_plans_.clear();
-    ctr_plans_.reserve((nb + ctr_chunk_ - 1) / ctr_chunk_);
-    for (size_t b0 = 0; b0 < nb; b0 += ctr_chunk_) {
-        const size_t cn = std::min(ctr_chunk_, nb - b0);
-        const size_t byte0 = b0 * 16;
-        const size_t cbytes = out_bytes > byte0 ? std::min(cn * 16, out_bytes - byte0) : 0;
-        ctr_plans_.emplace_back();
-        ctr_plan(iv, first_counter + b0, cn, ctr_plans_.back());
-        const uint8_t *data = d_data ? d_data + byte0 : nullptr;
-        uint64_t *out = d_out + byte0 * 8 * L;
-        if (p_.model == 8)
-            aes8_ctr_blocks(d_rk, ctr_plans_.back(), cn, rounds, data, cbytes, out, nr);
-        else
-            aes_ctr_blocks(d_rk, ctr_plans_.back(), cn, rounds, data, cbytes, out, nr);
-    }
-}
-
-// One chunk of a multi-stream call: aes_ctr_blocks with the round keys of every block and group read from their
-// slot of the key table, and the final kernel writing each block's bytes at its place in the concatenated output
-void Engine::aes_ctr_blocks_multi(const uint64_t *d_table, const CtrPlanMulti &plan, int rounds, const uint8_t *d_data,
-                                  uint64_t *d_out, int nr) {
-    const size_t nb = plan.block_slot.size(), U = plan.groups.size();
-    if (!nb) return;
-    if (plan.map.size() != nb * 16 || !U || plan.group_slot.size() != U || plan.block_out.size() != nb ||
-        plan.block_len.size() != nb)
-        throw std::runtime_error("counter plan does not match the blocks");
-    for (int32_t g : plan.map)
-        if (g < 0 || (size_t)g >= U) throw std::runtime_error("counter plan: group index out of range");
-    for (int32_t n : plan.block_len)
-        if (n < 1 || n > 16) throw std::runtime_error("counter plan: block length out of range");
-    const int L = (int)p_.big_len();
-    const size_t key_stride = (size_t)4 * (nr + 1) * 32 * L;
-    grow(d_ctr_groups_, cap_ctr_groups_, U);
-    grow(d_ctr_map_, cap_ctr_map_, nb * 16);
-    grow(d_ctr_gslot_, cap_ctr_gslot_, U);
-    grow(d_key_of_, cap_key_of_, nb);
-    grow(d_ctr_bout_, cap_ctr_bout_, nb);
-    grow(d_ctr_blen_, cap_ctr_blen_, nb);
-    HIPC(hipMemcpyAsync(d_ctr_groups_, plan.groups.data(), U * sizeof(uint16_t), hipMemcpyHostToDevice, stream_));
-    HIPC(hipMemcpyAsync(d_ctr_map_, plan.map.data(), nb * 16 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    HIPC(hipMemcpyAsync(d_ctr_gslot_, plan.group_slot.data(), U * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    HIPC(hipMemcpyAsync(d_key_of_, plan.block_slot.data(), nb * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    HIPC(hipMemcpyAsync(d_ctr_bout_, plan.block_out.data(), nb * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
-    HIPC(hipMemcpyAsync(d_ctr_blen_, plan.block_len.data(), nb * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    const size_t state_len = nb * 128 * (size_t)L;
-    grow(d_state_, cap_state_, rounds == 1 ? U * 8 * (size_t)L : state_len);
-    grow(d_muls_, cap_muls_, rounds == 1 ? U * 8 * (size_t)L : nb * 16 * 24 * (size_t)L);
-    const size_t byte_stride = 8 * (size_t)L;
-    timed(ST_LINEAR, [&] {
-        aes_ctr_round0_kernel<<<grid_for(U * 8 * (size_t)L), kThreads, 0, stream_>>>(d_table, d_ctr_groups_, d_state_, U, L,
-                                                                                     d_ctr_gslot_, key_stride);
-        HIPC(hipGetLastError());
-    });
-    size_t G = U;
-    const int32_t *map = d_ctr_map_;
-    for (int r = 1; r < rounds; r++) {
-        circuit_bootstrap(d_state_, G, 8, d_lut24_, 24, d_muls_);
-        const uint64_t *rk_r = d_table + (size_t)16 * r * byte_stride;
-        timed(ST_LINEAR, [&] {
-            if (map)
-                aes_mix_idx_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, map, rk_r, d_state_, nb, L,
-                                                                                   d_key_of_, key_stride);
-            else
-                aes_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, rk_r, d_state_, nb, L, d_key_of_,
-                                                                               key_stride);
-            HIPC(hipGetLastError());
-        });
-        G = nb * 16;
-        map = nullptr;
-    }
-    circuit_bootstrap(d_state_, G, 8, d_lut8_, 8, d_muls_);
-    timed(ST_LINEAR, [&] {
-        aes_ctr_final_streams_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(
-            d_muls_, map, d_table + (size_t)16 * nr * byte_stride, d_data, d_out, nb, L, d_key_of_, key_stride,
-            d_ctr_bout_, d_ctr_blen_);
-        HIPC(hipGetLastError());
-    });
-    collect_times();
-}
-
-void Engine::aes_ctr_multi(const uint64_t *d_table, const std::vector<CtrBlock> &blocks, int rounds,
-                           const uint8_t *d_data, uint64_t *d_out, int nr) {
-    if (blocks.empty()) return;
-    if (p_.model != 1) throw std::runtime_error("multi-key batches need the 1-bit model parameters");
-    require_rounds(rounds, nr);
-    times_ = StageTimes{};
-    // the uploads of a plan are asynchronous: every chunk's plan lives until the next call.  A chunk boundary may
-    // fall inside a stream: a block carries its slot, counter and output place with it.
-    ctr_mplans_.clear();
-    ctr_mplans_.reserve((blocks.size() + ctr_chunk_ - 1) / ctr_chunk_);
-    for (size_t b0 = 0; b0 < blocks.size(); b0 += ctr_chunk_) {
-        const size_t cn = std::min(ctr_chunk_, blocks.size() - b0);
-        ctr_mplans_.emplace_back();
-        ctr_plan_multi(blocks.data() + b0, cn, ctr_mplans_.back());
-        aes_ctr_blocks_multi(d_table, ctr_mplans_.back(), rounds, d_data, d_out, nr);
-    }
-}
-
-// ---- AES-128 inverse cipher (FIPS-197 5.3; aes_inv.hpp) ----
-// rounds R-1 .. 1 and the last round on d_state_ = block ^ dk[4 nr ..]: R circuit bootstraps per block
-void Engine::aes_decrypt_rounds(const uint64_t *d_dk, size_t nb, int rounds, const uint8_t *d_xor, uint64_t *d_out,
-                                const int32_t *d_key_of, size_t key_stride) {
-    const int L = (int)p_.big_len();
-    const size_t state_len = nb * 128 * (size_t)L, byte_stride = 8 * (size_t)L;
-    for (int r = rounds - 1; r >= 1; r--) {
-        circuit_bootstrap(d_state_, nb * 16, 8, d_lut_inv32_, 32, d_muls_);
-        timed(ST_LINEAR, [&] {
-            aes_inv_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_dk + (size_t)16 * r * byte_stride,
-                                                                               d_state_, nb, L, 1, d_key_of, key_stride);
-            HIPC(hipGetLastError());
-        });
-    }
-    circuit_bootstrap(d_state_, nb * 16, 8, d_lut_inv8_, 8, d_muls_);
-    timed(ST_LINEAR, [&] {
-        aes_inv_final_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_dk, d_xor, d_out, nb, L, d_key_of,
-                                                                             key_stride);
-        HIPC(hipGetLastError());
-    });
-    collect_times();
-}
-
-void Engine::require_inverse(int rounds, int nr) const {
-    if (p_.model != 1 || !d_lut_inv32_) throw std::runtime_error("the inverse cipher needs the 1-bit model parameters");
-    require_rounds(rounds, nr);
-}
-
-void Engine::aes_decrypt_blocks(const uint64_t *d_dk, const uint64_t *d_blocks, size_t nb, int rounds,
-                                uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride) {
-    if (!nb) return;
-    require_inverse(rounds, nr);
-    const int L = (int)p_.big_len();
-    const size_t state_len = nb * 128 * (size_t)L;
-    times_ = StageTimes{};
-    grow(d_state_, cap_state_, state_len);
-    grow(d_muls_, cap_muls_, nb * 16 * (size_t)(rounds > 1 ? 32 : 8) * L);
-    timed(ST_LINEAR, [&] {
-        aes_ark0_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_blocks, d_dk + (size_t)16 * nr * 8 * L,
-                                                                        d_state_, nb, L, d_key_of, key_stride);
-        HIPC(hipGetLastError());
-    });
-    aes_decrypt_rounds(d_dk, nb, rounds, nullptr, d_out, d_key_of, key_stride);
-}
-
-void Engine::aes_decrypt_blocks_multi(const uint64_t *d_dtable, const int32_t *key_of, const uint64_t *d_blocks,
-                                      size_t nb, int rounds, uint64_t *d_out, int nr) {
-    if (!nb) return;
-    require_inverse(rounds, nr);
-    aes_decrypt_blocks(d_dtable, d_blocks, nb, rounds, d_out, nr, upload_key_of(key_of, nb),
-                       (size_t)4 * (nr + 1) * 32 * p_.big_len());
-}
-
-// round 0 on the public blocks d_cur and the rounds, the last one XORing the public blocks d_prev in
-void Engine::aes_cbc_blocks(const uint64_t *d_dk, const uint8_t *d_cur, const uint8_t *d_prev, size_t nb, int rounds,
-                            uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride) {
-    const int L = (int)p_.big_len();
-    const size_t state_len = nb * 128 * (size_t)L;
-    times_ = StageTimes{};
-    grow(d_state_, cap_state_, state_len);
-    grow(d_muls_, cap_muls_, nb * 16 * (size_t)(rounds > 1 ? 32 : 8) * L);
-    timed(ST_LINEAR, [&] {
-        aes_inv_round0_public_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(
-            d_dk + (size_t)16 * nr * 8 * L, d_cur, d_state_, nb, L, d_key_of, key_stride);
-        HIPC(hipGetLastError());
-    });
-    aes_decrypt_rounds(d_dk, nb, rounds, d_prev, d_out, d_key_of, key_stride);
-}
-
-void Engine::aes_cbc_transcipher(const uint64_t *d_dk, const uint8_t *d_iv_data, size_t nb, int rounds,
-                                 uint64_t *d_out, int nr) {
-    if (!nb) return;
-    require_inverse(rounds, nr);
-    // d_iv_data = iv || C_0 .. C_{nb-1}: block i is decrypted from bytes 16 (i + 1) .. and XORed with bytes 16 i ..
-    aes_cbc_blocks(d_dk, d_iv_data + 16, d_iv_data, nb, rounds, d_out, nr, nullptr, 0);
-}
-
-// d_cur / d_prev [nb][16]: the ciphertext block and the block before it (the stream's iv for its first block)
-void Engine::aes_cbc_transcipher_multi(const uint64_t *d_dtable, const int32_t *key_of, const uint8_t *d_cur,
-                                       const uint8_t *d_prev, size_t nb, int rounds, uint64_t *d_out, int nr) {
-    if (!nb) return;
-    require_inverse(rounds, nr);
-    aes_cbc_blocks(d_dtable, d_cur, d_prev, nb, rounds, d_out, nr, upload_key_of(key_of, nb),
-                   (size_t)4 * (nr + 1) * 32 * p_.big_len());
-}
-
-void Engine::aes_decrypt_key(const uint64_t *d_rk, uint64_t *d_dk, int nr) {
-    require_inverse(nr, nr);
-    if (d_rk == d_dk) throw std::runtime_error("the decryption key cannot be derived in place");
-    const int L = (int)p_.big_len();
-    // words 4 .. 4 nr - 1: nr - 1 round keys of 16 bytes
-    const size_t word = 32 * (size_t)L, mid = 4 * (size_t)(nr - 1) * word, last = 4 * (size_t)nr * word;
-    times_ = StageTimes{};
-    grow(d_state_, cap_state_, mid);
-    grow(d_muls_, cap_muls_, 16 * (size_t)(nr - 1) * 32 * L);
-    HIPC(hipMemcpyAsync(d_dk, d_rk, 4 * word * 8, hipMemcpyDeviceToDevice, stream_));
-    HIPC(hipMemcpyAsync(d_dk + last, d_rk + last, 4 * word * 8, hipMemcpyDeviceToDevice, stream_));
-    circuit_bootstrap(d_rk + 4 * word, 16 * (size_t)(nr - 1), 8, d_lut_mul32_, 32, d_muls_);
-    timed(ST_LINEAR, [&] {
-        aes_inv_mix_kernel<<<grid_for(mid), kThreads, 0, stream_>>>(d_muls_, nullptr, d_state_, nr - 1, L, 0);
-        HIPC(hipGetLastError());
-    });
-    circuit_bootstrap(d_state_, 128 * (size_t)(nr - 1), 1, d_lut_id1_, 1, d_dk + 4 * word);
-    collect_times();
-}
-
-// ---- key expansion on the device (FIPS-197 5.2, figure 11), nk = 4 / 6 / 8 key words ----
-// Every new word is bootstrapped (identity, 32 one-bit groups) before the next word reads it, as
-// Context::aes_key_schedule does on the host; the stages of a word are launches on the engine stream and no
-// ciphertext leaves the device.
-void Engine::aes_key_expand(const uint64_t *d_key, int nk, uint64_t *d_rk) {
-    if (p_.model != 1 || !d_lut_id1_) throw std::runtime_error("the key expansion needs the 1-bit model parameters");
-    if (nk != 4 && nk != 6 && nk != 8) throw std::runtime_error("the key must be 4, 6 or 8 words");
-    const int L = (int)p_.big_len(), words = 4 * (nk + 7);
-    const size_t word = 32 * (size_t)L;
-    times_ = StageTimes{};
-    grow(d_state_, cap_state_, word);
-    grow(d_muls_, cap_muls_, word);
-    if (d_key != d_rk) HIPC(hipMemcpyAsync(d_rk, d_key, nk * word * 8, hipMemcpyDeviceToDevice, stream_));
-    for (int i = nk; i < words; i++) {
-        const uint64_t *back = d_rk + (size_t)(i - nk) * word, *other = d_rk + (size_t)(i - 1) * word;
-        int rot = 0, rcon = 0;
-        if (i % nk == 0 || (nk == 8 && i % 8 == 4)) {
-            // SubWord of rk[i-1] where it lies; RotWord and Rcon on the words that start a key-sized group
-            circuit_bootstrap(other, 4, 8, d_lut8_, 8, d_muls_);
-            other = d_muls_;
-            if (i % nk == 0) {
-                rot = 1;
-                rcon = kRcon[i / nk];
-            }
-        }
-        timed(ST_LINEAR, [&] {
-            aes_ks_word_kernel<<<grid_for(word), kThreads, 0, stream_>>>(back, other, rot, rcon, d_state_, L);
-            HIPC(hipGetLastError());
-        });
-        circuit_bootstrap(d_state_, 32, 1, d_lut_id1_, 1, d_rk + (size_t)i * word);
-    }
-    collect_times();
-}
-
-// ---- the same two derivations for a key table [n_keys][W*32][L] ----
-void Engine::copy_rows(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t rows,
-                       size_t len) {
-    timed(ST_LINEAR, [&] {
-        copy_rows_strided_kernel<<<grid_for(rows * len), kThreads, 0, stream_>>>(d_src, src_stride, d_dst, dst_stride,
-                                                                                  rows, len);
-        HIPC(hipGetLastError());
-    });
-}
-
-// Word i of all keys at once: the bootstraps of a word run over n_keys times the bits, so the number of chained
-// circuit bootstraps is that of one key.  The table is key-major: word i - 1 of every key is gathered for
-// SubWord and the bootstrapped word scattered into the table rows.
-void Engine::aes_key_expand_multi(const uint64_t *d_keys, int nk, size_t n_keys, uint64_t *d_table) {
-    if (p_.model != 1 || !d_lut_id1_) throw std::runtime_error("the key expansion needs the 1-bit model parameters");
-    if (nk != 4 && nk != 6 && nk != 8) throw std::runtime_error("the key must be 4, 6 or 8 words");
-    if (!n_keys) return;
-    const int L = (int)p_.big_len(), words = 4 * (nk + 7);
-    const size_t word = 32 * (size_t)L, stride = (size_t)words * word, batch = n_keys * word;
-    times_ = StageTimes{};
-    grow(d_state_, cap_state_, batch);
-    grow(d_muls_, cap_muls_, batch);
-    copy_rows(d_keys, (size_t)nk * word, d_table, stride, n_keys, (size_t)nk * word);
-    for (int i = nk; i < words; i++) {
-        const uint64_t *back = d_table + (size_t)(i - nk) * word, *other = d_table + (size_t)(i - 1) * word;
-        size_t other_stride = stride;
-        int rot = 0, rcon = 0;
-        if (i % nk == 0 || (nk == 8 && i % 8 == 4)) {
-            copy_rows(other, stride, d_state_, word, n_keys, word);
-            circuit_bootstrap(d_state_, 4 * n_keys, 8, d_lut8_, 8, d_muls_);
-            other = d_muls_;
-            other_stride = word;
-            if (i % nk == 0) {
-                rot = 1;
-                rcon = kRcon[i / nk];
-            }
-        }
-        timed(ST_LINEAR, [&] {
-            aes_ks_word_kernel<<<grid_for(batch), kThreads, 0, stream_>>>(back, other, rot, rcon, d_state_, L, n_keys,
-                                                                           stride, other_stride);
-            HIPC(hipGetLastError());
-        });
-        circuit_bootstrap(d_state_, 32 * n_keys, 1, d_lut_id1_, 1, d_muls_);
-        copy_rows(d_muls_, word, d_table + (size_t)i * word, stride, n_keys, word);
-    }
-    collect_times();
-}
-
-void Engine::aes_decrypt_key_multi(const uint64_t *d_table, size_t n_keys, uint64_t *d_dtable, int nr) {
-    require_inverse(nr, nr);
-    if (d_table == d_dtable) throw std::runtime_error("the decryption keys cannot be derived in place");
-    if (!n_keys) return;
-    const int L = (int)p_.big_len();
-    const size_t word = 32 * (size_t)L, mid = 4 * (size_t)(nr - 1) * word, last = 4 * (size_t)nr * word;
-    const size_t stride = last + 4 * word;
-    times_ = StageTimes{};
-    grow(d_state_, cap_state_, n_keys * mid);
-    grow(d_muls_, cap_muls_, n_keys * 16 * (size_t)(nr - 1) * 32 * L);
-    copy_rows(d_table, stride, d_dtable, stride, n_keys, 4 * word);
-    copy_rows(d_table + last, stride, d_dtable + last, stride, n_keys, 4 * word);
-    copy_rows(d_table + 4 * word, stride, d_state_, mid, n_keys, mid);
-    circuit_bootstrap(d_state_, n_keys * 16 * (size_t)(nr - 1), 8, d_lut_mul32_, 32, d_muls_);
-    timed(ST_LINEAR, [&] {
-        aes_inv_mix_kernel<<<grid_for(n_keys * mid), kThreads, 0, stream_>>>(d_muls_, nullptr, d_state_,
-                                                                              n_keys * (size_t)(nr - 1), L, 0);
-        HIPC(hipGetLastError());
-    });
-    circuit_bootstrap(d_state_, n_keys * 128 * (size_t)(nr - 1), 1, d_lut_id1_, 1, d_muls_);
-    copy_rows(d_muls_, mid, d_dtable + 4 * word, stride, n_keys, mid);
-    collect_times();
 }
 
 // ---- shortint_1bit model ----
@@ -2478,38 +1623,6 @@ void Engine::s1_multivariate_chunk(const uint64_t *d_bits, size_t G, int nbits, 
         tvs = d_s1_tv_;
         lut_mod = B;
     }
-}
-
-// fhe_sbox_pbs::encrypt_block_for_rounds (fhe_sbox_pbs.rs:75-121) over nb blocks of shortint_1bit bits with
-// ByteT::sbox_substitute = 8 multivariate functions per byte (fhe_impls/shortint_1bit.rs:32-50); MixColumns
-// and AddRoundKey are the same LWE-addition network as the 8-bit model's (shortint unchecked_add,
-// shortint_1bit.rs:109-120)
-void Engine::s1_aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_blocks, size_t nb, int rounds,
-                                   uint64_t *d_out) {
-    require_s1();
-    if (!nb) return;
-    if (rounds < 1 || rounds > 10) throw std::runtime_error("rounds must be in 1..=10");
-    const int L = (int)p_.small_len();
-    const size_t state_len = nb * 128 * (size_t)L;
-    times_ = StageTimes{};
-    grow(d_state_, cap_state_, state_len);
-    grow(d_muls_, cap_muls_, state_len);
-    const size_t byte_stride = 8 * (size_t)L;
-    MixTerms T;
-    std::memcpy(T.idx, mix_idx_, sizeof(T.idx));
-    aes_ark0_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_blocks, d_rk, d_state_, nb, L);
-    HIPC(hipGetLastError());
-    for (int r = 1; r < rounds; r++) {
-        s1_multivariate(d_state_, nb * 16, 8, d_s1_sbox_tv_, 8, d_muls_);
-        aes8_mix_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_rk + (size_t)16 * r * byte_stride,
-                                                                        d_state_, nb, L, T);
-        HIPC(hipGetLastError());
-    }
-    s1_multivariate(d_state_, nb * 16, 8, d_s1_sbox_tv_, 8, d_muls_);
-    aes_final_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_muls_, d_rk + (size_t)160 * byte_stride, d_out,
-                                                                     nb, L);
-    HIPC(hipGetLastError());
-    collect_times();
 }
 
 void Engine::lwe_add(uint64_t *d_a, const uint64_t *d_b, size_t count) {
