@@ -343,6 +343,56 @@ int tae_aesx_cbc_transcipher_raw(const tae_context *ctx, int key_bits, const uin
  * inverse rounds.  TAE_OK, TAE_E_NOISE or TAE_E_INDEP; other models than the 1-bit one are TAE_E_PARAM */
 int tae_aesx_noise_schedule_check(int param_set, int key_bits, int rounds, int inverse);
 
+/* ---- XTS-AES decryption of a public ciphertext (IEEE 1619 / NIST SP 800-38E) ---------
+ * The reference has no XTS and no counterpart of these functions.  Data at rest: the server holds the
+ * decryption key of K1 (tae_aesx_decrypt_key) and the expanded key of K2 under FHE, one key_bits for both
+ * (XTS-AES-128 is two 16-byte keys, XTS-AES-256 two 32-byte keys), and the ciphertext in the clear.  For a data
+ * unit the tweak is 16 public bytes (the unit number, little-endian, in IEEE 1619); block j of the unit is
+ *     P_j = Dec_K1(C_j ^ M_j) ^ M_j,   M_j = alpha^j T,   T = Enc_K2(tweak),
+ * alpha^j being the multiplication by x^j in GF(2^128) modulo x^128 + x^7 + x^2 + x + 1 with coefficient k at
+ * bit k & 7 (from the LSB) of byte k >> 3.  T is refreshed by one identity bootstrap (noise^2 = 1, new ids), a
+ * mask bit is the LWE sum of the tweak bits in its row of the GF(2) matrix of alpha^j and has noise^2 = its row
+ * weight <= w(j), and an output bit has 8 + 1 + its row weight: a call with a block index whose 9 + w(j) is above
+ * the parameter set's cap (w(j) > 55 at TAE_PARAMS_SQRD_LVL_64) is TAE_E_NOISE before any device work.  w(j) is
+ * not monotonic: it is at most 9 below block 256 (4 KiB units) and first exceeds 55 at block 1721.  `rounds` (1..=Nr) applies to both ciphers.  Scope of tae_aesx_* decryption: TAE_PARAMS_SQRD_LVL_*,
+ * gal-mul driver; the other models are TAE_E_PARAM.  Ciphertext stealing is not supported: a unit's len must be a
+ * positive multiple of 16, else TAE_E_PARAM.  Arguments are checked first; then a machine without a GPU answers
+ * TAE_E_NODEV. */
+/* one data unit, or a range of its blocks (no reference counterpart): `data` is the ciphertext from block
+ * first_block of the unit on, len bytes */
+typedef struct {
+    uint8_t tweak[16];
+    uint64_t first_block;
+    const uint8_t *data;
+    size_t len;
+} tae_xts_unit;
+/* w(j), the largest row weight of the GF(2) matrix of alpha^j (no reference counterpart; no GPU) */
+int tae_aesx_xts_row_weight(uint64_t block_index, int *weight);
+/* noise bookkeeping of XTS decryption for fresh keys (no reference counterpart; no GPU): both key expansions, the
+ * decryption key of K1, the tweak cipher with its refresh, and block max_block_index of a unit, that block alone
+ * (w(j) is not monotonic; the compute calls check every block index they are given).  TAE_OK or TAE_E_NOISE;
+ * other models than the 1-bit one are TAE_E_PARAM */
+int tae_aesx_xts_noise_schedule_check(int param_set, int key_bits, int rounds, uint64_t max_block_index);
+/* T = Enc_K2(tweak) for n tweaks, each refreshed by the identity bootstrap (no reference counterpart): rk2
+ * [W*32][L] and out [n][128][L] follow `mem`, tweaks [n][16] is a host pointer.  Equal tweaks are computed once and
+ * come out as identical words */
+int tae_aesx_xts_tweaks_raw(const tae_context *ctx, int key_bits, const uint64_t *rk2, const uint8_t *tweaks /*[n][16]*/,
+                            size_t n, int rounds, uint64_t *out /*[n][128][L]*/, int mem);
+/* the mask stage alone (no reference counterpart): masks [nb][128][L], block b = alpha^block_index[b] applied to
+ * the tweak ciphertexts of unit unit_of_block[b] of tweaks_ct [n_units][128][L]; the two index arrays are host
+ * pointers, a unit outside 0..n_units-1 is TAE_E_ARG.  A stage call: no noise rule is applied */
+int tae_stage_xts_masks(const tae_context *ctx, const uint64_t *tweaks_ct, size_t n_units, const int32_t *unit_of_block,
+                        const uint64_t *block_index, size_t nb, uint64_t *masks, int mem);
+/* XTS decryption on raw arrays (no reference counterpart): dk1, rk2 [W*32][L] and out [sum len][8][L] (units in
+ * order) follow `mem`; the units and their data are host pointers.  Units with equal tweaks share one T.  Calls
+ * above TAE_CTR_CHUNK_BLOCKS blocks run in consecutive chunks with the tweaks resident */
+int tae_aesx_xts_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *dk1, const uint64_t *rk2,
+                                 const tae_xts_unit *units, size_t n_units, int rounds, uint64_t *out, int mem);
+/* XTS decryption on handles (no reference counterpart): dk1, ek2 [W*32], out[sum len * 8].  An output bit carries
+ * the ids of the tweak bits in its row, so XORing outputs that share tweak bits is TAE_E_INDEP */
+int tae_aesx_xts_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *dk1, const tae_bit *const *ek2,
+                             const tae_xts_unit *units, size_t n_units, int rounds, tae_bit **out);
+
 /* ---- Multi-key batches: key expansion, cipher, CTR and CBC across AES keys -----------
  * The reference encrypts under one AES key and has no counterpart of these functions.  One FHE key, many AES
  * keys: a key table is n_keys expanded keys (or decryption keys) of one key size, contiguous as

@@ -8,6 +8,7 @@
 
 #include "aes.hpp"
 #include "aes_linear.hpp"
+#include "aes_xts.hpp"
 #include "engine_detail.hpp"
 
 namespace tae {
@@ -76,6 +77,16 @@ __global__ void aes_inv_mix_kernel(const uint64_t *__restrict__ muls, const uint
     }
 }
 
+// ---- XTS (aes_xts.hpp): masks [nb][128][L] = the row sums of the tweaks [n_units][128][L], block blk reading data
+// unit unit_of[blk] through row-list set set_of[blk] of rows [n_sets][128][width] ----
+__global__ void aes_xts_mask_kernel(const uint64_t *__restrict__ tweaks, const int16_t *__restrict__ rows, int width,
+                                    const int32_t *__restrict__ unit_of, const int32_t *__restrict__ set_of,
+                                    uint64_t *__restrict__ masks, size_t nb, int L) {
+    const size_t total = nb * 128 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+        masks[t] = xts_mask_word(tweaks, rows, width, unit_of, set_of, t, L);
+}
+
 // ---- key expansion (FIPS-197 5.2, figure 11): one word before its identity bootstrap ----
 // t = back + other (+ Rcon), whole ciphertexts: back = rk[i-Nk], other = rk[i-1] or SubWord(rk[i-1]), both
 // [4 bytes][8 bits][L].  SubWord works byte by byte, so RotWord is applied here, on the read of its output:
@@ -125,9 +136,9 @@ void Engine::bootstrap_bytes8(const uint64_t *d_bytes, size_t G, const uint64_t 
 // ---------------------------------------------------------------------------------------------
 // The forward cipher: one round loop for every model and mode
 // ---------------------------------------------------------------------------------------------
-// What a forward entry point asks of aes_forward.  Round 0 has the ciphertexts `blocks`, or (blocks == nullptr)
-// the U deduplicated groups of a counter plan whose arrays are on the device (d_ctr_groups_, d_ctr_map_; the
-// groups' slots in group_key).  `sub` is the model's SubBytes step.  The key slots and the output placement are
+// What a forward entry point asks of aes_forward.  Round 0 has the ciphertexts `blocks`, the public blocks `bytes`
+// [nb*16] on the device (the XTS tweaks) or, with neither, the U deduplicated groups of a counter plan whose
+// arrays are on the device (d_ctr_groups_, d_ctr_map_; the groups' slots in group_key).  `sub` is the model's SubBytes step.  The key slots and the output placement are
 // aes_linear.hpp's nullable arguments.
 struct Engine::AesRun {
     enum Sub { GAL_MUL, BYTES8, SHORTINT1 } sub;  // circuit_bootstrap 8 -> 24 / 8 -> 8, bootstrap_bytes8, s1_multivariate
@@ -135,6 +146,7 @@ struct Engine::AesRun {
     size_t nb;
     int rounds, nr;
     const uint64_t *blocks = nullptr;
+    const uint8_t *bytes = nullptr;
     size_t U = 0;
     const int32_t *group_key = nullptr;
     const int32_t *key_of = nullptr;
@@ -155,7 +167,7 @@ void Engine::aes_forward(const AesRun &a) {
     const bool gal = a.sub == AesRun::GAL_MUL;
     const int L = (int)(gal ? p_.big_len() : p_.small_len());
     const size_t nb = a.nb, state_len = nb * 128 * (size_t)L, byte_stride = 8 * (size_t)L;
-    const bool plan = !a.blocks;
+    const bool plan = !a.blocks && !a.bytes;
     size_t G = plan ? a.U : nb * 16;
     const int32_t *map = plan ? d_ctr_map_ : nullptr;
     // one round of a plan works on its U groups alone; the per-block state and the 24 SubBytes multiples of the
@@ -182,7 +194,7 @@ void Engine::aes_forward(const AesRun &a) {
     };
     linear([&] {
         aes_round0_kernel<<<grid_for(G * byte_stride), kThreads, 0, stream_>>>(
-            a.rk, a.blocks, nullptr, plan ? d_ctr_groups_ : nullptr, d_state_, G * 8, L, plan ? a.group_key : a.key_of,
+            a.rk, a.blocks, a.bytes, plan ? d_ctr_groups_ : nullptr, d_state_, G * 8, L, plan ? a.group_key : a.key_of,
             a.key_stride);
         HIPC(hipGetLastError());
     });
@@ -388,14 +400,15 @@ void Engine::require_inverse(int rounds, int nr) const {
     require_rounds(rounds, nr);
 }
 
-// Round 0 on the ciphertexts d_blocks or (nullptr) on the public blocks d_cur, rounds R-1 .. 1 and the last
-// round, which XORs the public blocks d_xor in if given: R circuit bootstraps per block
+// Round 0 on the ciphertexts d_blocks, on the public blocks d_cur or on both (XTS: the masks and C), rounds
+// R-1 .. 1 and the last round, which XORs the public blocks d_xor in if given: R circuit bootstraps per block.
+// keep_times: the stage times add to those of the call's earlier passes.
 void Engine::aes_decrypt_rounds(const uint64_t *d_dk, const uint64_t *d_blocks, const uint8_t *d_cur, size_t nb,
                                 int rounds, const uint8_t *d_xor, uint64_t *d_out, int nr, const int32_t *d_key_of,
-                                size_t key_stride) {
+                                size_t key_stride, bool keep_times) {
     const int L = (int)p_.big_len();
     const size_t state_len = nb * 128 * (size_t)L, byte_stride = 8 * (size_t)L;
-    times_ = StageTimes{};
+    if (!keep_times) times_ = StageTimes{};
     grow(d_state_, cap_state_, state_len);
     grow(d_muls_, cap_muls_, nb * 16 * (size_t)(rounds > 1 ? 32 : 8) * L);
     timed(ST_LINEAR, [&] {
@@ -451,6 +464,88 @@ void Engine::aes_cbc_transcipher_multi(const uint64_t *d_dtable, const int32_t *
     require_inverse(rounds, nr);
     aes_decrypt_rounds(d_dtable, nullptr, d_cur, nb, rounds, d_prev, d_out, nr, upload_key_of(key_of, nb),
                        (size_t)4 * (nr + 1) * 32 * p_.big_len());
+}
+
+// ---------------------------------------------------------------------------------------------
+// XTS-AES decryption of a public ciphertext (aes_xts.hpp)
+// ---------------------------------------------------------------------------------------------
+// T = Enc_K2(tweak) for n public tweaks: the forward cipher on public blocks, left in d_state_, and one identity
+// bootstrap of the 128 n bits, which brings every tweak bit to noise^2 = 1 whatever the unit size
+void Engine::xts_tweak_pass(const uint64_t *d_rk2, const uint8_t *d_tweaks, size_t n, int rounds, uint64_t *d_out,
+                            int nr) {
+    AesRun a{AesRun::GAL_MUL, d_rk2, n, rounds, nr};
+    a.bytes = d_tweaks;
+    a.time_linear = true;
+    a.out_bytes = n * 16;
+    // the final kernel reads d_muls_ and the key alone, so the state buffer is free to take the cipher's output
+    a.out = grow(d_state_, cap_state_, n * 128 * p_.big_len());
+    aes_forward(a);
+    circuit_bootstrap(d_state_, n * 128, 1, d_lut_id1_, 1, d_out);
+}
+
+void Engine::aes_xts_tweaks(const uint64_t *d_rk2, const uint8_t *d_tweaks, size_t n, int rounds, uint64_t *d_out,
+                            int nr) {
+    if (!n) return;
+    require_inverse(rounds, nr);
+    times_ = StageTimes{};
+    xts_tweak_pass(d_rk2, d_tweaks, n, rounds, d_out, nr);
+}
+
+// the plan's arrays are uploaded asynchronously: it lives until the next call
+void Engine::xts_mask_pass(const uint64_t *d_tweak_cts, size_t n_units, const XtsPlan &plan, uint64_t *d_masks) {
+    const size_t nb = plan.unit_of.size();
+    if (plan.set_of.size() != nb || plan.width < 1 || plan.rows.size() % (128 * (size_t)plan.width))
+        throw std::runtime_error("XTS plan does not match the blocks");
+    for (size_t b = 0; b < nb; b++)
+        if (plan.unit_of[b] < 0 || (size_t)plan.unit_of[b] >= n_units || plan.set_of[b] < 0 ||
+            (size_t)plan.set_of[b] >= plan.n_sets())
+            throw std::runtime_error("XTS plan: unit or row-list index out of range");
+    for (int16_t src : plan.rows)
+        if (src < -1 || src > 127) throw std::runtime_error("XTS plan: source ciphertext out of range");
+    const int16_t *rows = upload(d_xts_rows_, cap_xts_rows_, plan.rows.data(), plan.rows.size());
+    const int32_t *unit_of = upload(d_xts_unit_, cap_xts_unit_, plan.unit_of.data(), nb);
+    const int32_t *set_of = upload(d_xts_set_, cap_xts_set_, plan.set_of.data(), nb);
+    const int L = (int)p_.big_len();
+    timed(ST_LINEAR, [&] {
+        aes_xts_mask_kernel<<<grid_for(nb * 128 * (size_t)L), kThreads, 0, stream_>>>(d_tweak_cts, rows, plan.width,
+                                                                                       unit_of, set_of, d_masks, nb, L);
+        HIPC(hipGetLastError());
+    });
+}
+
+void Engine::aes_xts_masks(const uint64_t *d_tweak_cts, size_t n_units, const XtsPlan &plan, uint64_t *d_masks) {
+    if (plan.unit_of.empty()) return;
+    if (p_.model != 1) throw std::runtime_error("XTS runs on the 1-bit model parameters");
+    times_ = StageTimes{};
+    xts_plans_.clear();
+    xts_plans_.push_back(plan);
+    xts_mask_pass(d_tweak_cts, n_units, xts_plans_.back(), d_masks);
+    collect_times();
+}
+
+void Engine::aes_xts_transcipher(const uint64_t *d_dk1, const uint64_t *d_rk2, const uint8_t *d_tweaks, size_t n_tweaks,
+                                 const int32_t *tweak_of, const uint64_t *block_index, const uint8_t *d_data, size_t nb,
+                                 int rounds, uint64_t *d_out, int nr) {
+    if (!nb) return;
+    require_inverse(rounds, nr);
+    const size_t block_len = 128 * p_.big_len();
+    times_ = StageTimes{};
+    grow(d_xts_tweaks_, cap_xts_tweaks_, n_tweaks * block_len);
+    xts_tweak_pass(d_rk2, d_tweaks, n_tweaks, rounds, d_xts_tweaks_, nr);
+    // the tweaks stay resident across the chunks; every chunk's plan lives until the next call
+    xts_plans_.clear();
+    xts_plans_.reserve((nb + ctr_chunk_ - 1) / ctr_chunk_);
+    grow(d_xts_masks_, cap_xts_masks_, std::min(ctr_chunk_, nb) * block_len);
+    for (size_t b0 = 0; b0 < nb; b0 += ctr_chunk_) {
+        const size_t cn = std::min(ctr_chunk_, nb - b0);
+        uint64_t *out = d_out + b0 * block_len;
+        xts_plans_.emplace_back();
+        xts_plan(tweak_of + b0, block_index + b0, cn, xts_plans_.back());
+        xts_mask_pass(d_xts_tweaks_, n_tweaks, xts_plans_.back(), d_xts_masks_);
+        aes_decrypt_rounds(d_dk1, d_xts_masks_, d_data + b0 * 16, cn, rounds, nullptr, out, nr, nullptr, 0, true);
+        timed(ST_LINEAR, [&] { lwe_add(out, d_xts_masks_, cn * block_len); });
+    }
+    collect_times();
 }
 
 // ---------------------------------------------------------------------------------------------

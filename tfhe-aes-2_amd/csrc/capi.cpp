@@ -824,6 +824,110 @@ int tae_aesx_noise_schedule_check(int param_set, int key_bits, int rounds, int i
     });
 }
 
+/* ---- XTS-AES decryption of a public ciphertext (IEEE 1619; no counterpart in the reference) ---- */
+extern "C++" {
+namespace {
+// A compute call: the arguments first, then the device (a machine without one has no context to pass)
+void require_xts_server(const tae_context *ctx) {
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0)
+        throw tae::ModelError{TAE_E_NODEV, "no GPU available: the HIP path has no CPU fallback"};
+    require(ctx != nullptr, "null");
+}
+
+std::vector<tae::Context::XtsUnitIn> xts_units_in(const tae_xts_unit *units, size_t n_units) {
+    require(units || !n_units, "null");
+    std::vector<tae::Context::XtsUnitIn> v(n_units);
+    for (size_t i = 0; i < n_units; i++) {
+        if (!units[i].len || units[i].len % 16)
+            throw tae::ModelError{TAE_E_PARAM, "an XTS data unit is a positive number of whole 16-byte blocks"};
+        require(units[i].data != nullptr, "null unit data");
+        std::memcpy(v[i].tweak, units[i].tweak, 16);
+        v[i].first_block = units[i].first_block;
+        v[i].data = units[i].data;
+        v[i].len = units[i].len;
+    }
+    return v;
+}
+
+// the 1-bit WoP-PBS sets, key_bits and rounds of an XTS check that has no context
+tae::Params xts_params(int param_set, int key_bits, int rounds) {
+    const tae::Params p = params_of(param_set);
+    key_cts(key_bits);
+    if (p.model != 1) throw tae::ModelError{TAE_E_PARAM, "XTS runs on the 1-bit WoP-PBS parameter sets only"};
+    if (rounds < 1 || rounds > tae::aes_nr(key_bits))
+        throw tae::ModelError{TAE_E_PARAM, "rounds must be in 1..=" + std::to_string(tae::aes_nr(key_bits))};
+    return p;
+}
+}  // namespace
+}  // extern "C++"
+
+int tae_aesx_xts_row_weight(uint64_t block_index, int *weight) {
+    return guarded([&] {
+        require(weight != nullptr, "null");
+        *weight = tae::xts_row_weight(block_index);
+    });
+}
+
+int tae_aesx_xts_noise_schedule_check(int param_set, int key_bits, int rounds, uint64_t max_block_index) {
+    return guarded([&] {
+        const tae::Params p = xts_params(param_set, key_bits, rounds);
+        const int nk = tae::aes_nk(key_bits), nr = tae::aes_nr(key_bits);
+        auto fresh = [](size_t n) {
+            std::vector<tae::NoiseLevel> v(n);
+            for (auto &x : v) x = tae::NoiseLevel::with_noise_level(1, tae::next_ct_id());
+            return v;
+        };
+        // both keys from fresh key bits: the two expansions, the decryption key of the first, the tweak, the block
+        const std::vector<tae::NoiseLevel> rk1 = tae::aes_key_expand_noise_schedule(fresh((size_t)nk * 32), nk, p.max_noise_sq);
+        const std::vector<tae::NoiseLevel> rk2 = tae::aes_key_expand_noise_schedule(fresh((size_t)nk * 32), nk, p.max_noise_sq);
+        const std::vector<tae::NoiseLevel> dk1 = tae::aes_decrypt_key_noise_schedule(rk1, p.max_noise_sq, nr);
+        const std::vector<tae::NoiseLevel> tweak = tae::aes_xts_tweak_noise_schedule(rk2, rounds, p.max_noise_sq, nr);
+        tae::aes_xts_noise_schedule(dk1, tweak, max_block_index, rounds, p.max_noise_sq, nr);
+    });
+}
+
+int tae_aesx_xts_tweaks_raw(const tae_context *ctx, int key_bits, const uint64_t *rk2, const uint8_t *tweaks, size_t n,
+                            int rounds, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(rk2 && ((tweaks && out) || !n), "null");
+        key_cts(key_bits);
+        require_xts_server(ctx);
+        ctx->ctx->aes_xts_tweaks_raw(rk2, tweaks, n, rounds, out, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_stage_xts_masks(const tae_context *ctx, const uint64_t *tweaks_ct, size_t n_units, const int32_t *unit_of_block,
+                        const uint64_t *block_index, size_t nb, uint64_t *masks, int mem) {
+    return guarded([&] {
+        require((tweaks_ct && unit_of_block && block_index && masks) || !nb, "null");
+        require_xts_server(ctx);
+        ctx->ctx->xts_masks_raw(tweaks_ct, n_units, unit_of_block, block_index, nb, masks, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_aesx_xts_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *dk1, const uint64_t *rk2,
+                                 const tae_xts_unit *units, size_t n_units, int rounds, uint64_t *out, int mem) {
+    return guarded([&] {
+        require(dk1 && rk2 && (out || !n_units), "null");
+        key_cts(key_bits);
+        const std::vector<tae::Context::XtsUnitIn> in = xts_units_in(units, n_units);
+        require_xts_server(ctx);
+        ctx->ctx->aes_xts_transcipher_raw(dk1, rk2, in, rounds, out, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesx_xts_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *dk1, const tae_bit *const *ek2,
+                             const tae_xts_unit *units, size_t n_units, int rounds, tae_bit **out) {
+    return guarded([&] {
+        require(dk1 && ek2 && (out || !n_units), "null");
+        const size_t kw = key_cts(key_bits);
+        const std::vector<tae::Context::XtsUnitIn> in = xts_units_in(units, n_units);
+        require_xts_server(ctx);
+        emit(ctx->ctx->aes_xts_transcipher(unwrap(dk1, kw), unwrap(ek2, kw), in, rounds, key_bits), out);
+    });
+}
+
 /* ---- multi-key batches: key tables [n_keys][W*32][L] (no counterpart in the reference) ---- */
 extern "C++" {
 namespace {

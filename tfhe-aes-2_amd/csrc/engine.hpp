@@ -15,6 +15,7 @@
 
 #include "client.hpp"
 #include "cplx.hpp"
+#include "aes_xts.hpp"
 #include "ctr_plan.hpp"
 #include "kslots.hpp"
 #include "params.hpp"
@@ -155,6 +156,22 @@ class Engine {
     void aes_cbc_transcipher(const uint64_t *d_dk, const uint8_t *d_iv_data, size_t nb, int rounds, uint64_t *d_out,
                              int nr = 10);
 
+    // ---- XTS-AES decryption of a public ciphertext on the 1-bit model (aes_xts.hpp; the reference
+    // has no XTS).  `rounds` applies to both ciphers ----
+    // T = Enc_K2(tweak), refreshed by one identity bootstrap: rk2 [4 (nr + 1) * 32][K+1], d_tweaks [n][16] public
+    // bytes on the device -> [n][128][K+1] at noise^2 = 1
+    void aes_xts_tweaks(const uint64_t *d_rk2, const uint8_t *d_tweaks, size_t n, int rounds, uint64_t *d_out,
+                        int nr = 10);
+    // masks [nb][128][K+1] = alpha^j T of the plan's blocks (HOST plan) from tweak ciphertexts [n_units][128][K+1]
+    void aes_xts_masks(const uint64_t *d_tweak_cts, size_t n_units, const XtsPlan &plan, uint64_t *d_masks);
+    // out [nb][128][K+1] = Dec_K1(C_b + M_b) + M_b: the tweak pass over the n_tweaks distinct tweaks (device bytes),
+    // then per chunk of ctr_chunk_ blocks the masks, aes_decrypt_rounds on masks + public C and the last add.
+    // Block b is block block_index[b] of the unit with tweak tweak_of[b] (HOST arrays, the caller checks the
+    // range); d_data [nb][16] on the device
+    void aes_xts_transcipher(const uint64_t *d_dk1, const uint64_t *d_rk2, const uint8_t *d_tweaks, size_t n_tweaks,
+                             const int32_t *tweak_of, const uint64_t *block_index, const uint8_t *d_data, size_t nb,
+                             int rounds, uint64_t *d_out, int nr = 10);
+
     // ---- multi-key batches on the 1-bit model (the reference has one key).  A key table is
     // [n_keys][4 (nr + 1) * 32][K+1], slot s an expanded (or decryption) key in the layout above.  The bootstraps
     // are per ciphertext, so bits of different keys share their launches; the linear layer reads the round key of
@@ -252,7 +269,8 @@ class Engine {
     uint64_t *d_lut_inv32_ = nullptr, *d_lut_inv8_ = nullptr, *d_lut_mul32_ = nullptr, *d_lut_id1_ = nullptr;
     void require_inverse(int rounds, int nr) const;
     void aes_decrypt_rounds(const uint64_t *d_dk, const uint64_t *d_blocks, const uint8_t *d_cur, size_t nb, int rounds,
-                            const uint8_t *d_xor, uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride);
+                            const uint8_t *d_xor, uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride,
+                            bool keep_times = false);
     // the forward cipher's one round loop (aes_engine.hip): every forward entry point fills an AesRun
     struct AesRun;
     void aes_forward(const AesRun &run);
@@ -283,6 +301,15 @@ class Engine {
     const int32_t *upload_key_of(const int32_t *key_of, size_t nb);
     void aes_ctr_blocks_multi(const uint64_t *d_table, const CtrPlanMulti &plan, int rounds, const uint8_t *d_data,
                               uint64_t *d_out, int nr);
+    // XTS: the refreshed tweaks of the call, the masks of the chunk in flight, the plan arrays on the device and
+    // the host plans their pending uploads read
+    uint64_t *d_xts_tweaks_ = nullptr, *d_xts_masks_ = nullptr;
+    int16_t *d_xts_rows_ = nullptr;
+    int32_t *d_xts_unit_ = nullptr, *d_xts_set_ = nullptr;
+    size_t cap_xts_tweaks_ = 0, cap_xts_masks_ = 0, cap_xts_rows_ = 0, cap_xts_unit_ = 0, cap_xts_set_ = 0;
+    std::vector<XtsPlan> xts_plans_;
+    void xts_tweak_pass(const uint64_t *d_rk2, const uint8_t *d_tweaks, size_t n, int rounds, uint64_t *d_out, int nr);
+    void xts_mask_pass(const uint64_t *d_tweak_cts, size_t n_units, const XtsPlan &plan, uint64_t *d_masks);
     void copy_rows(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t rows,
                    size_t len);
     void copy_key_words(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t n_keys,

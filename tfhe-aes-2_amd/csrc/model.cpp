@@ -8,6 +8,7 @@
 
 #include "aes.hpp"
 #include "aes_inv.hpp"
+#include "aes_xts.hpp"
 #include "cplx.hpp"
 #include "glwe_pack.hpp"
 #include "../../include/tfhe_aes_gpu.h"
@@ -857,6 +858,211 @@ std::vector<BitCt> Context::aes_cbc_transcipher(const std::vector<const BitCt *>
         res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
         res[i].noise = out_noise[i / 128][i % 128];  // xor with a public bit adds no noise
         res[i].max_noise_sq = params().max_noise_sq;
+    }
+    return res;
+}
+
+// ---------------------------------------------------------------------------------------------
+// XTS-AES decryption of a public ciphertext (IEEE 1619; aes_xts.hpp).  The reference has no XTS.
+// ---------------------------------------------------------------------------------------------
+std::vector<NoiseLevel> aes_xts_tweak_noise_schedule(const std::vector<NoiseLevel> &rk2, int rounds, uint64_t max,
+                                                     int nr) {
+    // the cipher's output (8 + the last round key's bit) is validated by the schedule; the identity bootstrap
+    // then gives noise^2 = 1 with fresh ids, whatever went in
+    aes_noise_schedule(rk2, std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds, max, nr);
+    return fresh_levels(128);
+}
+
+std::vector<NoiseLevel> aes_xts_noise_schedule(const std::vector<NoiseLevel> &dk1, const std::vector<NoiseLevel> &tweak,
+                                               uint64_t j, int rounds, uint64_t max, int nr) {
+    std::vector<int16_t> rows[128];
+    xts_rows_of(j, rows);
+    std::vector<NoiseLevel> mask(128);
+    for (int o = 0; o < 128; o++) {
+        NoiseLevel v = tweak[rows[o][0]];  // x^(i + j) != 0 and A_j is invertible: no row is empty
+        for (size_t q = 1; q < rows[o].size(); q++) v.add_assign(tweak[rows[o][q]], max);
+        mask[o] = std::move(v);
+    }
+    std::vector<NoiseLevel> out = aes_decrypt_noise_schedule(dk1, mask, rounds, max, nr);
+    for (int o = 0; o < 128; o++) out[o].add_assign(mask[o], max);
+    return out;
+}
+
+namespace {
+// the blocks of the units in order, equal tweaks merged
+struct XtsFlat {
+    std::vector<uint8_t> tweaks, data;  // [n_tweaks][16], [nb][16]
+    std::vector<int32_t> tweak_of;      // [nb]
+    std::vector<uint64_t> block_index;  // [nb]
+};
+
+int32_t xts_tweak_slot(std::vector<uint8_t> &tweaks, const uint8_t tweak[16]) {
+    const size_t n = tweaks.size() / 16;
+    for (size_t i = 0; i < n; i++)
+        if (!std::memcmp(&tweaks[16 * i], tweak, 16)) return (int32_t)i;
+    tweaks.insert(tweaks.end(), tweak, tweak + 16);
+    return (int32_t)n;
+}
+
+XtsFlat xts_flatten(const std::vector<Context::XtsUnitIn> &units) {
+    XtsFlat f;
+    for (const Context::XtsUnitIn &u : units) {
+        if (!u.len || u.len % 16)
+            throw ModelError{TAE_E_PARAM, "an XTS data unit is a positive number of whole 16-byte blocks "
+                                          "(ciphertext stealing is not supported)"};
+        if (!u.data) throw ModelError{TAE_E_ARG, "null unit data"};
+        const uint64_t blocks = u.len / 16;
+        if (u.first_block + (blocks - 1) < u.first_block) throw ModelError{TAE_E_ARG, "block range wraps past 2^64 - 1"};
+        const int32_t slot = xts_tweak_slot(f.tweaks, u.tweak);
+        for (uint64_t b = 0; b < blocks; b++) {
+            f.tweak_of.push_back(slot);
+            f.block_index.push_back(u.first_block + b);
+        }
+        f.data.insert(f.data.end(), u.data, u.data + u.len);
+    }
+    return f;
+}
+
+// the block index of the call with the largest row weight (the first of them)
+uint64_t xts_heaviest_block(const std::vector<uint64_t> &block_index) {
+    std::vector<uint64_t> distinct = block_index;
+    std::sort(distinct.begin(), distinct.end());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    uint64_t at = distinct.front();
+    int w = 0;
+    for (uint64_t j : distinct) {
+        const int wj = xts_row_weight(j);
+        if (wj > w) {
+            w = wj;
+            at = j;
+        }
+    }
+    return at;
+}
+}  // namespace
+
+void Context::aes_xts_tweaks_raw(const uint64_t *rk2, const uint8_t *tweaks, size_t n, int rounds, uint64_t *out,
+                                 bool device_mem, int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32, S = bit_len(), block_len = 128 * S;
+    aes_xts_tweak_noise_schedule(fresh_levels(kw), rounds, params().max_noise_sq, nr);
+    if (!n) return;
+    std::vector<uint8_t> distinct;
+    std::vector<int32_t> slot(n);
+    for (size_t i = 0; i < n; i++) slot[i] = xts_tweak_slot(distinct, tweaks + 16 * i);
+    const size_t nd = distinct.size() / 16;
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    DevBuf d_bytes(distinct.size()), d_T(nd * block_len * 8);
+    DevBuf d_rk(device_mem ? 0 : kw * S * 8), d_out(device_mem ? 0 : n * block_len * 8);
+    hip_check(hipMemcpyAsync(d_bytes.p, distinct.data(), distinct.size(), hipMemcpyHostToDevice, engine_->stream()),
+              "upload tweaks");
+    if (device_mem)
+        engine_->order_after_caller();
+    else
+        hip_check(hipMemcpyAsync(d_rk.p, rk2, kw * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
+    uint64_t *dst = device_mem ? out : d_out.as<uint64_t>();
+    engine_->aes_xts_tweaks(device_mem ? rk2 : d_rk.as<uint64_t>(), d_bytes.as<uint8_t>(), nd, rounds,
+                            d_T.as<uint64_t>(), nr);
+    for (size_t i = 0; i < n; i++)
+        hip_check(hipMemcpyAsync(dst + i * block_len, d_T.as<uint64_t>() + (size_t)slot[i] * block_len, block_len * 8,
+                                 hipMemcpyDeviceToDevice, engine_->stream()),
+                  "place tweak");
+    if (!device_mem)
+        hip_check(hipMemcpyAsync(out, dst, n * block_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+void Context::xts_masks_raw(const uint64_t *tweak_cts, size_t n_units, const int32_t *unit_of_block,
+                            const uint64_t *block_index, size_t nb, uint64_t *masks, bool device_mem) {
+    if (params().model != 1) throw ModelError{TAE_E_PARAM, "XTS runs on the 1-bit WoP-PBS parameter sets only"};
+    for (size_t b = 0; b < nb; b++)
+        if (unit_of_block[b] < 0 || (size_t)unit_of_block[b] >= n_units)
+            throw ModelError{TAE_E_ARG, "a block's data unit is outside 0..n_units-1"};
+    if (!nb) return;
+    XtsPlan plan;
+    xts_plan(unit_of_block, block_index, nb, plan);
+    const size_t block_len = 128 * bit_len();
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    if (device_mem) {
+        engine_->order_after_caller();
+        engine_->aes_xts_masks(tweak_cts, n_units, plan, masks);
+        engine_->synchronize();
+        return;
+    }
+    DevBuf d_T(n_units * block_len * 8), d_M(nb * block_len * 8);
+    hip_check(hipMemcpyAsync(d_T.p, tweak_cts, n_units * block_len * 8, hipMemcpyHostToDevice, engine_->stream()),
+              "upload tweaks");
+    engine_->aes_xts_masks(d_T.as<uint64_t>(), n_units, plan, d_M.as<uint64_t>());
+    hip_check(hipMemcpyAsync(masks, d_M.p, nb * block_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+void Context::run_xts(const uint64_t *dk1, const uint64_t *rk2, size_t key_cts, const std::vector<uint8_t> &tweaks,
+                      const std::vector<int32_t> &tweak_of, const std::vector<uint64_t> &block_index,
+                      const std::vector<uint8_t> &data, int rounds, uint64_t *out, bool device_mem, int nr) {
+    const size_t S = bit_len(), nb = block_index.size(), out_bytes = nb * 128 * S * 8, key_bytes = key_cts * S * 8;
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    DevBuf d_tweaks(tweaks.size()), d_data(data.size());  // the public bytes are host arrays, always
+    DevBuf d_dk(device_mem ? 0 : key_bytes), d_rk(device_mem ? 0 : key_bytes), d_out(device_mem ? 0 : out_bytes);
+    hip_check(hipMemcpyAsync(d_tweaks.p, tweaks.data(), tweaks.size(), hipMemcpyHostToDevice, engine_->stream()),
+              "upload tweaks");
+    hip_check(hipMemcpyAsync(d_data.p, data.data(), data.size(), hipMemcpyHostToDevice, engine_->stream()), "upload data");
+    if (device_mem) {
+        engine_->order_after_caller();
+    } else {
+        hip_check(hipMemcpyAsync(d_dk.p, dk1, key_bytes, hipMemcpyHostToDevice, engine_->stream()), "upload key");
+        hip_check(hipMemcpyAsync(d_rk.p, rk2, key_bytes, hipMemcpyHostToDevice, engine_->stream()), "upload key");
+    }
+    engine_->aes_xts_transcipher(device_mem ? dk1 : d_dk.as<uint64_t>(), device_mem ? rk2 : d_rk.as<uint64_t>(),
+                                 d_tweaks.as<uint8_t>(), tweaks.size() / 16, tweak_of.data(), block_index.data(),
+                                 d_data.as<uint8_t>(), nb, rounds, device_mem ? out : d_out.as<uint64_t>(), nr);
+    if (!device_mem) hip_check(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+void Context::aes_xts_transcipher_raw(const uint64_t *dk1, const uint64_t *rk2, const std::vector<XtsUnitIn> &units,
+                                      int rounds, uint64_t *out, bool device_mem, int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    const XtsFlat f = xts_flatten(units);
+    const uint64_t max = params().max_noise_sq;
+    const std::vector<NoiseLevel> tweak = aes_xts_tweak_noise_schedule(fresh_levels(kw), rounds, max, nr);
+    if (f.block_index.empty()) return;
+    aes_xts_noise_schedule(fresh_levels(kw), tweak, xts_heaviest_block(f.block_index), rounds, max, nr);
+    run_xts(dk1, rk2, kw, f.tweaks, f.tweak_of, f.block_index, f.data, rounds, out, device_mem, nr);
+}
+
+std::vector<BitCt> Context::aes_xts_transcipher(const std::vector<const BitCt *> &dk1,
+                                                const std::vector<const BitCt *> &ek2,
+                                                const std::vector<XtsUnitIn> &units, int rounds, int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    require_key_words(dk1.size(), nr, "decryption key");
+    require_key_words(ek2.size(), nr, "tweak key");
+    const XtsFlat f = xts_flatten(units);
+    const size_t L = bit_len(), nb = f.block_index.size();
+    const std::vector<uint64_t> key1 = gather_bits(dk1, L), key2 = gather_bits(ek2, L);
+    std::vector<NoiseLevel> kdk(kw), krk(kw);
+    for (size_t i = 0; i < kw; i++) {
+        kdk[i] = dk1[i]->noise;
+        krk[i] = ek2[i]->noise;
+    }
+    const uint64_t max = params().max_noise_sq;
+    std::vector<std::vector<NoiseLevel>> tweak(f.tweaks.size() / 16), out_noise(nb);
+    for (auto &t : tweak) t = aes_xts_tweak_noise_schedule(krk, rounds, max, nr);
+    for (size_t b = 0; b < nb; b++)
+        out_noise[b] = aes_xts_noise_schedule(kdk, tweak[f.tweak_of[b]], f.block_index[b], rounds, max, nr);
+    if (!nb) return {};
+    std::vector<uint64_t> out(nb * 128 * L);
+    run_xts(key1.data(), key2.data(), kw, f.tweaks, f.tweak_of, f.block_index, f.data, rounds, out.data(), false, nr);
+    std::vector<BitCt> res(nb * 128);
+    for (size_t i = 0; i < res.size(); i++) {
+        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
+        res[i].noise = out_noise[i / 128][i % 128];  // xor with a public bit adds no noise
+        res[i].max_noise_sq = max;
     }
     return res;
 }

@@ -137,6 +137,32 @@ class Context {  // FheContext
     std::vector<BitCt> aes_cbc_transcipher(const std::vector<const BitCt *> &dk, const uint8_t iv[16],
                                            const uint8_t *data, size_t len, int rounds = 10, int key_bits = 128);
 
+    // ---- XTS-AES decryption of a public ciphertext (IEEE 1619; aes_xts.hpp; the reference has no
+    // XTS).  1-bit WoP-PBS sets, gal-mul driver, one key_bits for both keys (TAE_E_PARAM elsewhere).  Block j of a
+    // data unit: P_j = Dec_K1(C_j ^ M_j) ^ M_j, M_j = alpha^j Enc_K2(tweak).  `rounds` applies to both ciphers. ----
+    struct XtsUnitIn {
+        uint8_t tweak[16];
+        uint64_t first_block;  // data starts at this block of the unit
+        const uint8_t *data;
+        size_t len;  // a positive multiple of 16, or TAE_E_PARAM
+    };
+    // T = Enc_K2(tweak) after its identity bootstrap: rk2 [W*32], tweaks [n][16] host bytes -> [n][128][bit_len] at
+    // noise^2 = 1.  Equal tweaks are computed once and come out as identical words
+    void aes_xts_tweaks_raw(const uint64_t *rk2, const uint8_t *tweaks, size_t n, int rounds, uint64_t *out,
+                            bool device_mem, int key_bits);
+    // the mask stage alone: masks [nb][128][bit_len], block b = alpha^block_index[b] of tweak ciphertext
+    // unit_of_block[b] (host arrays; a unit outside 0..n_units-1 is TAE_E_ARG).  No noise rule: a stage call
+    void xts_masks_raw(const uint64_t *tweak_cts, size_t n_units, const int32_t *unit_of_block,
+                       const uint64_t *block_index, size_t nb, uint64_t *masks, bool device_mem);
+    // out [sum len][8][bit_len], units in order.  The schedule is validated statically for derived keys, at the
+    // block index of the call with the largest row weight: TAE_E_NOISE before any device work
+    void aes_xts_transcipher_raw(const uint64_t *dk1, const uint64_t *rk2, const std::vector<XtsUnitIn> &units,
+                                 int rounds, uint64_t *out, bool device_mem, int key_bits);
+    // BitCt variant: an output bit carries 8 + 1 + its row weight and the ids of the tweak bits in its row; units
+    // with equal tweaks share their tweak bits
+    std::vector<BitCt> aes_xts_transcipher(const std::vector<const BitCt *> &dk1, const std::vector<const BitCt *> &ek2,
+                                           const std::vector<XtsUnitIn> &units, int rounds, int key_bits);
+
     // ---- multi-key batches (the reference has one key): a key table is n_keys expanded (or
     // decryption) keys of one size, [n_keys][W*32][bit_len], slot s an expanded key as above.  1-bit model, gal-mul
     // driver (TAE_E_PARAM elsewhere).  Slots, streams and public bytes are host arrays; a slot outside
@@ -224,6 +250,11 @@ class Context {  // FheContext
                      uint64_t *out, size_t out_len, bool device_mem,
                      const std::function<void(const uint64_t *, const uint64_t *, const uint8_t *, uint64_t *)> &fn,
                      size_t key_cts);
+    // the flattened blocks of an XTS call through the engine: distinct tweaks [n][16], per block its tweak, its
+    // index in the unit and its 16 ciphertext bytes
+    void run_xts(const uint64_t *dk1, const uint64_t *rk2, size_t key_cts, const std::vector<uint8_t> &tweaks,
+                 const std::vector<int32_t> &tweak_of, const std::vector<uint64_t> &block_index,
+                 const std::vector<uint8_t> &data, int rounds, uint64_t *out, bool device_mem, int nr);
     void run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
                      const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem, int nr);
     void run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint64_t *d_in, size_t n_blocks, int rounds,
@@ -257,6 +288,16 @@ std::vector<NoiseLevel> aes_decrypt_key_noise_schedule(const std::vector<NoiseLe
 // before its identity bootstrap is rk[i-nk] + 8 on SubWord steps and rk[i-nk] + rk[i-1] otherwise (validated);
 // words below nk keep the key's levels and ids, every later word is noise^2 = 1 with fresh ids.
 std::vector<NoiseLevel> aes_key_expand_noise_schedule(const std::vector<NoiseLevel> &key, int nk, uint64_t max_noise_sq);
+
+// XTS (aes_xts.hpp) on metadata.  The tweak: the forward schedule of rk2 on a trivial block (output 8 + 1,
+// validated), then the identity bootstrap: [128] at noise^2 = 1 with fresh ids.
+std::vector<NoiseLevel> aes_xts_tweak_noise_schedule(const std::vector<NoiseLevel> &rk2, int rounds, uint64_t max_noise_sq,
+                                                     int nr = 10);
+// ONE block, index j of its unit: mask bit o = the sum of the tweak bits in row o of A_j (level = the row weight,
+// at most w(j)); round 0 = mask + dk1's last round key; output = 8 + the key bit + the mask bit, carrying the ids
+// of the tweak bits in its row.  dk1 [4 (nr + 1) * 32], tweak [128] -> [128]
+std::vector<NoiseLevel> aes_xts_noise_schedule(const std::vector<NoiseLevel> &dk1, const std::vector<NoiseLevel> &tweak,
+                                               uint64_t j, int rounds, uint64_t max_noise_sq, int nr = 10);
 
 // Counter mode on the 1-bit model: output noise [n_blocks][128] of the gal-mul schedule for trivial counter
 // blocks.  rounds >= 2: aes_noise_schedule per block.  rounds == 1: the final SubBytes runs on the plan's

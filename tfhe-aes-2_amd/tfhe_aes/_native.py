@@ -46,6 +46,8 @@ EXPORTED = [
     "tae_aesx_ctr_transcipher", "tae_aesx_decrypt_key", "tae_aesx_decrypt_key_raw", "tae_aesx_decrypt_blocks",
     "tae_aesx_decrypt_blocks_raw", "tae_aesx_cbc_transcipher", "tae_aesx_cbc_transcipher_raw",
     "tae_aesx_noise_schedule_check",
+    "tae_aesx_xts_row_weight", "tae_aesx_xts_noise_schedule_check", "tae_aesx_xts_tweaks_raw", "tae_stage_xts_masks",
+    "tae_aesx_xts_transcipher_raw", "tae_aesx_xts_transcipher",
     "tae_aesm_key_schedule_raw", "tae_aesm_decrypt_key_raw", "tae_aesm_encrypt_blocks_raw",
     "tae_aesm_decrypt_blocks_raw", "tae_aesm_ctr_plan", "tae_aesm_ctr_transcipher_raw",
     "tae_aesm_cbc_transcipher_raw", "tae_aesm_key_schedule", "tae_aesm_ctr_transcipher", "tae_aesm_cbc_transcipher",
@@ -77,6 +79,11 @@ class TaeCtrStream(C.Structure):
 class TaeCbcStream(C.Structure):
     """tae_cbc_stream: one CBC stream of a multi-key call."""
     _fields_ = [("key", C.c_int32), ("iv", C.c_uint8 * 16), ("data", C.c_void_p), ("len", C.c_size_t)]
+
+
+class TaeXtsUnit(C.Structure):
+    """tae_xts_unit: one XTS data unit, or a range of its blocks."""
+    _fields_ = [("tweak", C.c_uint8 * 16), ("first_block", C.c_uint64), ("data", C.c_void_p), ("len", C.c_size_t)]
 
 
 class TaeError(RuntimeError):
@@ -170,6 +177,12 @@ def lib() -> C.CDLL:
         "tae_aesx_cbc_transcipher": ([vp, C.c_int, vp, C.c_char_p, vp, sz, C.c_int, vp], C.c_int),
         "tae_aesx_cbc_transcipher_raw": ([vp, C.c_int, vp, C.c_char_p, vp, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_aesx_noise_schedule_check": ([C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
+        "tae_aesx_xts_row_weight": ([u64, C.POINTER(C.c_int)], C.c_int),
+        "tae_aesx_xts_noise_schedule_check": ([C.c_int, C.c_int, C.c_int, u64], C.c_int),
+        "tae_aesx_xts_tweaks_raw": ([vp, C.c_int, vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_stage_xts_masks": ([vp, vp, sz, vp, vp, sz, vp, C.c_int], C.c_int),
+        "tae_aesx_xts_transcipher_raw": ([vp, C.c_int, vp, vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesx_xts_transcipher": ([vp, C.c_int, vp, vp, vp, sz, C.c_int, vp], C.c_int),
         "tae_aesm_key_schedule_raw": ([vp, C.c_int, vp, sz, vp, C.c_int], C.c_int),
         "tae_aesm_decrypt_key_raw": ([vp, C.c_int, vp, sz, vp, C.c_int], C.c_int),
         "tae_aesm_encrypt_blocks_raw": ([vp, C.c_int, vp, sz, vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),

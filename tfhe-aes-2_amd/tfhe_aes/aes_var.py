@@ -137,6 +137,85 @@ def cbc_decrypt_plain(key: bytes, iv: bytes, data: bytes) -> bytes:
     return b"".join(out)
 
 
+def _xts_tweak16(tweak) -> bytes:
+    """16 tweak bytes, or a data-unit number (little-endian, IEEE 1619)."""
+    if isinstance(tweak, int):
+        return tweak.to_bytes(16, "little")
+    tweak = bytes(tweak)
+    if len(tweak) != 16:
+        raise ValueError("an XTS tweak is 16 bytes or a data-unit number")
+    return tweak
+
+
+def xts_alpha(t: bytes) -> bytes:
+    """IEEE 1619: multiplication by alpha, the byte-wise left shift with carry; 0x87 into byte 0 on carry out."""
+    out, carry = bytearray(16), 0
+    for i in range(16):
+        out[i] = ((t[i] << 1) & 0xff) | carry
+        carry = t[i] >> 7
+    if carry:
+        out[0] ^= 0x87
+    return bytes(out)
+
+
+def _xts_plain(key1: bytes, key2: bytes, tweak16, data: bytes, first_block: int, block_fn) -> bytes:
+    if len(key1) != len(key2) or len(key1) not in (16, 24, 32):
+        raise ValueError("XTS keys are two keys of one size: 16 or 32 bytes in IEEE 1619, 24 as for the other modes")
+    if not data or len(data) % 16:
+        raise ValueError("data must be a positive number of whole 16-byte blocks (no ciphertext stealing)")
+    ek1, ek2 = key_schedule_plain(key1), key_schedule_plain(key2)
+    mask = encrypt_block_plain(ek2, _xts_tweak16(tweak16))
+    for _ in range(first_block):
+        mask = xts_alpha(mask)
+    out = []
+    for i in range(0, len(data), 16):
+        x = block_fn(ek1, bytes(a ^ b for a, b in zip(data[i:i + 16], mask)))
+        out.append(bytes(a ^ b for a, b in zip(x, mask)))
+        mask = xts_alpha(mask)
+    return b"".join(out)
+
+
+def xts_encrypt_plain(key1: bytes, key2: bytes, tweak16, data: bytes, first_block: int = 0) -> bytes:
+    """Plain XTS-AES of whole blocks: C_j = Enc_K1(P_j ^ M_j) ^ M_j, M_j = alpha^j Enc_K2(tweak).  `data` starts at
+    block `first_block` of the data unit; tweak16 is 16 bytes or the unit number."""
+    return _xts_plain(key1, key2, tweak16, data, first_block, encrypt_block_plain)
+
+
+def xts_decrypt_plain(key1: bytes, key2: bytes, tweak16, data: bytes, first_block: int = 0) -> bytes:
+    """P_j = Dec_K1(C_j ^ M_j) ^ M_j."""
+    return _xts_plain(key1, key2, tweak16, data, first_block, decrypt_block_plain)
+
+
+def xts_row_weight(block_index: int) -> int:
+    """w(j): the largest row weight of the GF(2) matrix of alpha^j, the noise^2 of block j's mask."""
+    w = C.c_int(0)
+    check(lib().tae_aesx_xts_row_weight(block_index, C.byref(w)))
+    return w.value
+
+
+def xts_noise_schedule_check(param_set: int, key_bits: int, rounds: int, max_block_index: int) -> None:
+    """The noise bookkeeping of XTS decryption for fresh keys, without a context or device: both key expansions,
+    the decryption key, the refreshed tweak and block `max_block_index` of a unit."""
+    check(lib().tae_aesx_xts_noise_schedule_check(param_set, key_bits, rounds, max_block_index))
+
+
+def _xts_units(units):
+    """[(tweak, data) | (tweak, data, first_block)] -> a tae_xts_unit array, the buffers it points into and the
+    total length."""
+    arr = (N.TaeXtsUnit * max(len(units), 1))()
+    keep, total = [], 0
+    for i, u in enumerate(units):
+        tweak, data = u[0], u[1]
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        keep.append(buf)
+        arr[i].tweak[:] = list(_xts_tweak16(tweak))
+        arr[i].first_block = u[2] if len(u) > 2 else 0
+        arr[i].data = buf.ctypes.data if len(buf) else None
+        arr[i].len = len(buf)
+        total += len(buf)
+    return arr, keep, total
+
+
 def noise_schedule_check(param_set: int, key_bits: int, rounds: int, inverse: bool = False) -> None:
     """The noise bookkeeping for a fresh key and block, without a context or device: the key expansion, then
     `rounds` cipher rounds, or with `inverse` the decryption-key derivation and `rounds` inverse rounds."""
@@ -386,4 +465,70 @@ class GalMulAes:
         """Device pointers (ints) for dk and the output [len][8][L]; iv and data are host bytes."""
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
         check(lib().tae_aesx_cbc_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_dk), _iv16(iv), _p(buf), len(buf),
+                                                 rounds, C.c_void_p(d_out), N.TAE_MEM_DEVICE))
+
+    # ---- XTS-AES decryption of a public ciphertext (IEEE 1619; DESIGN.md 5.12) ----
+    # dk1 = decrypt_key of key 1, rk2 / ek2 = the expanded key 2, one key size for both.  A unit is (tweak, data)
+    # or (tweak, data, first_block): tweak = 16 bytes or the data-unit number, data = the unit's ciphertext from
+    # block first_block on, whole 16-byte blocks.
+    @staticmethod
+    def xts_tweaks_raw(ctx: FheContext, rk2: np.ndarray, tweaks, rounds: Optional[int] = None,
+                       key_bits: Optional[int] = None) -> np.ndarray:
+        """rk2 [W*32][L], n tweaks -> T = Enc_K2(tweak) after the identity bootstrap, [n][128][L]."""
+        rk2, kb = _raw_key(rk2, key_bits)
+        buf = np.frombuffer(b"".join(_xts_tweak16(t) for t in tweaks), dtype=np.uint8)
+        out = np.zeros((len(tweaks), 128, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_xts_tweaks_raw(ctx._h, kb, _p(rk2), _p(buf), len(tweaks), _nr(kb, rounds), _p(out),
+                                            N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def xts_masks_raw(ctx: FheContext, tweaks_ct: np.ndarray, unit_of_block, block_index) -> np.ndarray:
+        """The mask stage alone: tweaks_ct [n_units][128][L] -> masks [nb][128][L], block b = alpha^block_index[b]
+        of unit unit_of_block[b]."""
+        tweaks_ct = np.ascontiguousarray(tweaks_ct, dtype=np.uint64)
+        unit = np.ascontiguousarray(unit_of_block, dtype=np.int32)
+        index = np.ascontiguousarray(block_index, dtype=np.uint64)
+        out = np.zeros((len(index), 128, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_stage_xts_masks(ctx._h, _p(tweaks_ct), tweaks_ct.shape[0], _p(unit), _p(index), len(index),
+                                        _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def xts_masks_device(ctx: FheContext, d_tweaks_ct: int, n_units: int, unit_of_block, block_index, d_masks: int):
+        unit = np.ascontiguousarray(unit_of_block, dtype=np.int32)
+        index = np.ascontiguousarray(block_index, dtype=np.uint64)
+        check(lib().tae_stage_xts_masks(ctx._h, C.c_void_p(d_tweaks_ct), n_units, _p(unit), _p(index), len(index),
+                                        C.c_void_p(d_masks), N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def xts_transcipher(ctx: FheContext, dk1, ek2, units, rounds: Optional[int] = None,
+                        key_bits: Optional[int] = None):
+        """dk1, ek2: [W][4][8] BitCt (nested or flat) -> [sum len][8] BitCt of the plaintext bits, units in order."""
+        key1, kb = _bit_key(dk1, key_bits)
+        key2, _ = _bit_key(ek2, kb)
+        arr, keep, total = _xts_units(units)
+        outs = (C.c_void_p * (8 * total))()
+        check(lib().tae_aesx_xts_transcipher(ctx._h, kb, _handles(key1), _handles(key2), arr, len(units),
+                                             _nr(kb, rounds), outs))
+        bits = [BitCt(h, ctx) for h in outs]
+        return [bits[8 * i:8 * i + 8] for i in range(total)]
+
+    @staticmethod
+    def xts_transcipher_raw(ctx: FheContext, dk1: np.ndarray, rk2: np.ndarray, units, rounds: Optional[int] = None,
+                            key_bits: Optional[int] = None) -> np.ndarray:
+        """Host arrays: dk1, rk2 [W*32][L] -> [sum len][8][L] FHE encryptions of the plaintext bits."""
+        dk1, kb = _raw_key(dk1, key_bits)
+        rk2, _ = _raw_key(rk2, kb)
+        arr, keep, total = _xts_units(units)
+        out = np.zeros((total, 8, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_xts_transcipher_raw(ctx._h, kb, _p(dk1), _p(rk2), arr, len(units), _nr(kb, rounds),
+                                                 _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def xts_transcipher_device(ctx: FheContext, key_bits: int, d_dk1: int, d_rk2: int, units, rounds: int, d_out: int):
+        """Device pointers (ints) for the keys and the output [sum len][8][L]; the units are host bytes."""
+        arr, keep, _ = _xts_units(units)
+        check(lib().tae_aesx_xts_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_dk1), C.c_void_p(d_rk2), arr, len(units),
                                                  rounds, C.c_void_p(d_out), N.TAE_MEM_DEVICE))
