@@ -468,6 +468,71 @@ int tae_aesm_ctr_transcipher(const tae_context *ctx, int key_bits, const tae_bit
 int tae_aesm_cbc_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *dtable, size_t n_keys,
                              const tae_cbc_stream *streams, size_t n_streams, int rounds, tae_bit **out);
 
+/* ---- AES-CCM decryption of public frames (RFC 3610 / NIST SP 800-38C) ------------------
+ * The reference has no CCM and no counterpart of these functions.  The server holds the expanded key under FHE and
+ * the frame in the clear: a nonce of 7..13 bytes (L = 15 - nonce_len), associated data, and `data` = the
+ * encrypted payload followed by the tag_len-byte encrypted tag U.  With S_i = E(A_i), A_i = (L-1) || nonce || be_L(i),
+ * the payload is data ^ S_1 S_2 .., the CBC-MAC X runs over B_0 || encoded AAD || zero-padded payload through the
+ * forward cipher, and the frame is authentic iff the first tag_len bytes of X ^ S_0 ^ U are zero.  The server can
+ * see neither: it returns the payload bits and those 8 tag_len tag-difference bits under FHE, and the client
+ * decrypts both and accepts the payload iff every difference bit is 0.  There is no verdict bit.
+ * Every A_i and B_0 goes through the cipher as one batch of public blocks; the chain then takes one cipher call per
+ * MAC block, over all the frames of the call that still have one.  A payload bit has noise^2 = 8 + 1, a
+ * tag-difference bit 16 (it holds no key bit), the round 0 of a chain step 8 + 1 + 1 at a public byte and
+ * 8 + 8 + 1 at a payload byte.  Scope: TAE_PARAMS_SQRD_LVL_* (gal-mul driver), key_bits 128 / 192 / 256, decryption,
+ * whole frames; every other model is TAE_E_PARAM.  `rounds` applies to every cipher call and must be 2..=Nr.
+ * TAE_E_PARAM before any device work: a nonce outside 7..13 bytes, a tag_len outside 4, 6 .. 16, aad_len >= 0xFF00
+ * (only the two-byte AAD length form is supported), a payload length that does not fit L bytes, len < tag_len,
+ * rounds < 2.  A slot outside 0..n_keys-1 and null arrays are TAE_E_ARG.  The stream arrays and their bytes are
+ * host pointers under either `mem`. */
+/* one frame under slot `key` of a key table */
+typedef struct {
+    int32_t key;
+    const uint8_t *nonce;
+    size_t nonce_len;
+    const uint8_t *aad; /* may be NULL when aad_len == 0 */
+    size_t aad_len;
+    const uint8_t *data; /* payload ciphertext || encrypted tag */
+    size_t len;          /* >= tag_len */
+} tae_ccm_stream;
+/* the blocks of a frame (host only, no context; no reference counterpart): n_ctr = 1 + ceil(payload_len / 16)
+ * counter blocks A_0 .., n_mac MAC blocks B_0 ..; each of the three arrays may be NULL (a first call for the
+ * counts) or holds ctr_blocks [n_ctr][16], mac_blocks [n_mac][16] (0 where a payload byte goes) and mac_src
+ * [n_mac][16] (-1: the byte is public, else the index of the payload byte) */
+int tae_aesx_ccm_format(const uint8_t *nonce, size_t nonce_len, int tag_len, const uint8_t *aad, size_t aad_len,
+                        size_t payload_len, size_t *n_ctr, size_t *n_mac, uint8_t *ctr_blocks, uint8_t *mac_blocks,
+                        int64_t *mac_src);
+/* noise bookkeeping of CCM decryption for a fresh key (no reference counterpart; no GPU): the key expansion, then a
+ * frame with public, payload and padded MAC blocks.  TAE_OK, TAE_E_NOISE or TAE_E_INDEP; TAE_E_PARAM for other
+ * models than the 1-bit one and for rounds outside 2..=Nr */
+int tae_aesx_ccm_noise_schedule_check(int param_set, int key_bits, int rounds);
+/* the forward cipher over arbitrary public 16-byte blocks (no reference counterpart): blocks [n_blocks][16] and
+ * key_of_block are host pointers, out [n_blocks][128][L]; every word equals tae_aesm_encrypt_blocks_raw on trivial
+ * encryptions of the blocks, and round 1 runs once per distinct (slot, byte position, byte value).  Serves CCM's
+ * A_i and B_0, GCM-style iv12 || be32 counters and CFB decryption */
+int tae_aesm_pub_keystream_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys,
+                               const int32_t *key_of_block, const uint8_t *blocks, size_t n_blocks, int rounds,
+                               uint64_t *out, int mem);
+/* CCM decryption of several frames (no reference counterpart): out_plain [sum (len - tag_len)][8][L], frames in
+ * order (may be NULL when no frame has a payload); out_tag_diff [n_streams][8 tag_len][L] */
+int tae_aesm_ccm_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys,
+                                 const tae_ccm_stream *streams, size_t n_streams, int tag_len, int rounds,
+                                 uint64_t *out_plain, uint64_t *out_tag_diff, int mem);
+/* the same on handles (no reference counterpart): out_plain[sum (len - tag_len) * 8], out_tag_diff[n_streams * 8
+ * tag_len]; XORing two tag-difference bits of a frame, or one with a payload bit of another position, is legal */
+int tae_aesm_ccm_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *table, size_t n_keys,
+                             const tae_ccm_stream *streams, size_t n_streams, int tag_len, int rounds,
+                             tae_bit **out_plain, tae_bit **out_tag_diff);
+/* one frame under one expanded key rk [W*32][L] (no reference counterpart) */
+int tae_aesx_ccm_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint8_t *nonce,
+                                 size_t nonce_len, const uint8_t *aad, size_t aad_len, const uint8_t *data, size_t len,
+                                 int tag_len, int rounds, uint64_t *out_plain, uint64_t *out_tag_diff, int mem);
+/* one frame on handles (no reference counterpart): expanded_key [W*32] */
+int tae_aesx_ccm_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
+                             const uint8_t *nonce, size_t nonce_len, const uint8_t *aad, size_t aad_len,
+                             const uint8_t *data, size_t len, int tag_len, int rounds, tae_bit **out_plain,
+                             tae_bit **out_tag_diff);
+
 /* ---- Aes128Encrypt for the fhe_sbox_pbs driver (src/aes_128/fhe/fhe_sbox_pbs.rs:22-171) ------------
  * ShortintWoppbs1BitSboxPbsAesEncrypt on the 1-bit model (fhe_impls/shortint_woppbs_1bit.rs:47-81:
  * SubBytes = one 8 -> 8 circuit bootstrap per byte, MixColumns = gf_256_mul by BitCt XORs) and

@@ -1,12 +1,13 @@
 // The AES application layer of the Engine: the linear layers between the circuit bootstraps as HIP kernels
 // (ShiftRows / MixColumns / AddRoundKey as LWE additions: fhe_sbox_gal_mul_pbs.rs:61-132, data_model.rs:270-281;
 // the arithmetic of a word is in aes_linear.hpp and aes_inv.hpp) and the drivers of every mode: the forward
-// cipher on the three models, counter mode, the inverse cipher, CBC, multi-key batches and the two key
+// cipher on the three models, counter mode, the inverse cipher, CBC, XTS, CCM, multi-key batches and the two key
 // derivations.  The generic TFHE stages they call are in kernels.hip.
 #include <cstring>
 #include <stdexcept>
 
 #include "aes.hpp"
+#include "aes_ccm.hpp"
 #include "aes_linear.hpp"
 #include "aes_xts.hpp"
 #include "engine_detail.hpp"
@@ -87,6 +88,26 @@ __global__ void aes_xts_mask_kernel(const uint64_t *__restrict__ tweaks, const i
         masks[t] = xts_mask_word(tweaks, rows, width, unit_of, set_of, t, L);
 }
 
+// ---- CCM (aes_ccm.hpp): the round-0 state [n][128][L] of a chain step from the previous cipher output x, the
+// payload ciphertexts in the result buffer and the public bytes; the tag differences after the last step ----
+__global__ void aes_ccm_absorb_kernel(const uint64_t *__restrict__ x, const uint64_t *__restrict__ plain,
+                                      const uint64_t *__restrict__ rk, const int64_t *__restrict__ src,
+                                      uint64_t *__restrict__ state, size_t n, int L, const int32_t *__restrict__ key_of,
+                                      size_t key_stride, int nr) {
+    const size_t total = n * 128 * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+        state[t] = ccm_absorb_word(x, plain, rk, src, t, L, key_of, key_stride, nr);
+}
+
+__global__ void aes_ccm_tag_kernel(const uint64_t *__restrict__ x, const uint64_t *__restrict__ s0,
+                                   const uint64_t *__restrict__ rk, const uint8_t *__restrict__ tags, int M,
+                                   const int32_t *__restrict__ out_of, uint64_t *__restrict__ out, size_t n, int L,
+                                   const int32_t *__restrict__ key_of, size_t key_stride, int nr) {
+    const size_t total = n * 8 * (size_t)M * L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+        ccm_tag_word(x, s0, rk, tags, M, out_of, out, t, L, key_of, key_stride, nr);
+}
+
 // ---- key expansion (FIPS-197 5.2, figure 11): one word before its identity bootstrap ----
 // t = back + other (+ Rcon), whole ciphertexts: back = rk[i-Nk], other = rk[i-1] or SubWord(rk[i-1]), both
 // [4 bytes][8 bits][L].  SubWord works byte by byte, so RotWord is applied here, on the read of its output:
@@ -157,6 +178,12 @@ struct Engine::AesRun {
     const int64_t *blk_out = nullptr;
     const int32_t *blk_len = nullptr;
     uint64_t *out = nullptr;
+    // CCM.  state_ready: round 0 is in d_state_ already (a chain step's absorb kernel), nb blocks.  keep: the final
+    // kernel runs a second time and places the same outputs at keep_out / keep_len of `keep` (no public bytes)
+    bool state_ready = false;
+    const int64_t *keep_out = nullptr;
+    const int32_t *keep_len = nullptr;
+    uint64_t *keep = nullptr;
 };
 
 // fhe_sbox_gal_mul_pbs::encrypt_block_for_rounds / fhe_sbox_pbs::encrypt_block_for_rounds over nb blocks.  Round 0
@@ -167,7 +194,7 @@ void Engine::aes_forward(const AesRun &a) {
     const bool gal = a.sub == AesRun::GAL_MUL;
     const int L = (int)(gal ? p_.big_len() : p_.small_len());
     const size_t nb = a.nb, state_len = nb * 128 * (size_t)L, byte_stride = 8 * (size_t)L;
-    const bool plan = !a.blocks && !a.bytes;
+    const bool plan = !a.blocks && !a.bytes && !a.state_ready;
     size_t G = plan ? a.U : nb * 16;
     const int32_t *map = plan ? d_ctr_map_ : nullptr;
     // one round of a plan works on its U groups alone; the per-block state and the 24 SubBytes multiples of the
@@ -192,12 +219,13 @@ void Engine::aes_forward(const AesRun &a) {
         else
             s1_multivariate(d_state_, G, 8, d_s1_sbox_tv_, 8, d_muls_);
     };
-    linear([&] {
-        aes_round0_kernel<<<grid_for(G * byte_stride), kThreads, 0, stream_>>>(
-            a.rk, a.blocks, a.bytes, plan ? d_ctr_groups_ : nullptr, d_state_, G * 8, L, plan ? a.group_key : a.key_of,
-            a.key_stride);
-        HIPC(hipGetLastError());
-    });
+    if (!a.state_ready)
+        linear([&] {
+            aes_round0_kernel<<<grid_for(G * byte_stride), kThreads, 0, stream_>>>(
+                a.rk, a.blocks, a.bytes, plan ? d_ctr_groups_ : nullptr, d_state_, G * 8, L,
+                plan ? a.group_key : a.key_of, a.key_stride);
+            HIPC(hipGetLastError());
+        });
     for (int r = 1; r < a.rounds; r++) {
         sub_bytes(false);
         const uint64_t *rk_r = a.rk + (size_t)16 * r * byte_stride;
@@ -218,6 +246,13 @@ void Engine::aes_forward(const AesRun &a) {
             aes_final_kernel<<<grid_for(a.out_bytes * byte_stride), kThreads, 0, stream_>>>(
                 d_muls_, map, a.rk + (size_t)16 * a.nr * byte_stride, a.data, a.out, a.out_bytes, L, a.key_of, a.key_stride,
                 a.blk_out, a.blk_len, false);
+            HIPC(hipGetLastError());
+        });
+    if (a.out_bytes && a.keep)
+        linear([&] {
+            aes_final_kernel<<<grid_for(a.out_bytes * byte_stride), kThreads, 0, stream_>>>(
+                d_muls_, map, a.rk + (size_t)16 * a.nr * byte_stride, nullptr, a.keep, a.out_bytes, L, a.key_of,
+                a.key_stride, a.keep_out, a.keep_len, false);
             HIPC(hipGetLastError());
         });
     if (a.time_linear) collect_times();
@@ -350,14 +385,21 @@ void Engine::aes_ctr(const uint64_t *d_rk, const uint8_t iv[8], uint64_t first_c
 // One chunk of a multi-stream call: the round keys of every block and group are read from their slot of the key
 // table, and the final kernel writes each block's bytes at its place in the concatenated output
 void Engine::aes_ctr_blocks_multi(const uint64_t *d_table, const CtrPlanMulti &plan, int rounds, const uint8_t *d_data,
-                                  uint64_t *d_out, int nr) {
+                                  uint64_t *d_out, int nr, const std::vector<int64_t> *keep_out,
+                                  const std::vector<int32_t> *keep_len, uint64_t *d_keep) {
     const size_t nb = plan.block_slot.size(), U = plan.groups.size();
     if (!nb) return;
     if (plan.group_slot.size() != U || plan.block_out.size() != nb || plan.block_len.size() != nb)
         throw std::runtime_error("counter plan does not match the blocks");
+    if (d_keep && (!keep_out || !keep_len || keep_out->size() != nb || keep_len->size() != nb))
+        throw std::runtime_error("counter plan: the second placement does not match the blocks");
     check_ctr_plan(U, plan.map, nb);
-    for (int32_t n : plan.block_len)
-        if (n < 1 || n > 16) throw std::runtime_error("counter plan: block length out of range");
+    // a block that only the second placement takes has length 0 in the first
+    for (size_t i = 0; i < nb; i++) {
+        const int32_t n = plan.block_len[i], k = d_keep ? (*keep_len)[i] : 0;
+        if (n < (k ? 0 : 1) || n > 16 || (k != 0 && k != 16))
+            throw std::runtime_error("counter plan: block length out of range");
+    }
     upload(d_ctr_groups_, cap_ctr_groups_, plan.groups.data(), U);
     upload(d_ctr_map_, cap_ctr_map_, plan.map.data(), nb * 16);
     AesRun a{AesRun::GAL_MUL, d_table, nb, rounds, nr};
@@ -371,6 +413,11 @@ void Engine::aes_ctr_blocks_multi(const uint64_t *d_table, const CtrPlanMulti &p
     a.blk_out = upload(d_ctr_bout_, cap_ctr_bout_, plan.block_out.data(), nb);
     a.blk_len = upload(d_ctr_blen_, cap_ctr_blen_, plan.block_len.data(), nb);
     a.out = d_out;
+    if (d_keep) {
+        a.keep_out = upload(d_ccm_kout_, cap_ccm_kout_, keep_out->data(), nb);
+        a.keep_len = upload(d_ccm_klen_, cap_ccm_klen_, keep_len->data(), nb);
+        a.keep = d_keep;
+    }
     aes_forward(a);
 }
 
@@ -390,6 +437,152 @@ void Engine::aes_ctr_multi(const uint64_t *d_table, const std::vector<CtrBlock> 
         ctr_plan_multi(blocks.data() + b0, cn, ctr_mplans_.back());
         aes_ctr_blocks_multi(d_table, ctr_mplans_.back(), rounds, d_data, d_out, nr);
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// AES-CCM decryption of public frames (aes_ccm.hpp)
+// ---------------------------------------------------------------------------------------------
+void Engine::aes_pub_blocks_multi(const uint64_t *d_table, const std::vector<PubBlock> &blocks, int rounds,
+                                  uint64_t *d_out, int nr) {
+    if (blocks.empty()) return;
+    if (p_.model != 1) throw std::runtime_error("multi-key batches need the 1-bit model parameters");
+    require_rounds(rounds, nr);
+    times_ = StageTimes{};
+    // the uploads of a plan are asynchronous: every chunk's plan lives until the next call
+    ctr_mplans_.clear();
+    ctr_mplans_.reserve((blocks.size() + ctr_chunk_ - 1) / ctr_chunk_);
+    for (size_t b0 = 0; b0 < blocks.size(); b0 += ctr_chunk_) {
+        const size_t cn = std::min(ctr_chunk_, blocks.size() - b0);
+        ctr_mplans_.emplace_back();
+        pub_plan(blocks.data() + b0, cn, ctr_mplans_.back());
+        aes_ctr_blocks_multi(d_table, ctr_mplans_.back(), rounds, nullptr, d_out, nr);
+    }
+}
+
+void Engine::aes_ccm_transcipher(const uint64_t *d_table, const std::vector<CcmStreamIn> &streams, int rounds, int nr,
+                                 uint64_t *d_out_plain, uint64_t *d_out_tagdiff) {
+    const size_t n = streams.size();
+    if (!n) return;
+    if (p_.model != 1) throw std::runtime_error("CCM runs on the 1-bit model parameters");
+    require_rounds(rounds, nr);
+    // at one round the de-duplicated SubBytes outputs of B_0 and A_0 coincide at the nonce positions, and the tag
+    // difference would add a ciphertext to itself
+    if (rounds < 2) throw std::runtime_error("CCM needs rounds >= 2");
+    const int M = streams[0].frame->M, L = (int)p_.big_len();
+    const size_t block_len = 128 * (size_t)L, key_stride = (size_t)4 * (nr + 1) * 32 * L;
+    std::vector<int64_t> off(n);  // the first payload byte of every frame in the result
+    size_t total = 0;
+    for (size_t s = 0; s < n; s++) {
+        const CcmFrame &f = *streams[s].frame;
+        if (f.M != M || !f.n_mac() || f.n_ctr() != 1 + (f.payload_len + 15) / 16 || f.src.size() != f.mac.size())
+            throw std::runtime_error("CCM frames of one call have one tag length and a whole layout");
+        off[s] = (int64_t)total;
+        total += f.payload_len;
+    }
+    times_ = StageTimes{};
+    // the chain order: by decreasing MAC-block count, so the streams of a step are a prefix
+    ccm_order_.resize(n);
+    for (size_t s = 0; s < n; s++) ccm_order_[s] = (int32_t)s;
+    std::stable_sort(ccm_order_.begin(), ccm_order_.end(), [&](int32_t a, int32_t b) {
+        return streams[(size_t)a].frame->n_mac() > streams[(size_t)b].frame->n_mac();
+    });
+    std::vector<size_t> rank(n);
+    ccm_slot_.resize(n);
+    ccm_bytes_.assign(total + n * (size_t)M, 0);  // the payload ciphertexts in result order, then the tags in chain order
+    for (size_t j = 0; j < n; j++) {
+        const CcmStreamIn &st = streams[(size_t)ccm_order_[j]];
+        rank[(size_t)ccm_order_[j]] = j;
+        ccm_slot_[j] = st.slot;
+        if (st.frame->payload_len)
+            std::memcpy(&ccm_bytes_[(size_t)off[(size_t)ccm_order_[j]]], st.data, st.frame->payload_len);
+        std::memcpy(&ccm_bytes_[total + j * (size_t)M], st.tag, (size_t)M);
+    }
+    const uint8_t *d_bytes = upload(d_ccm_bytes_, cap_ccm_bytes_, ccm_bytes_.data(), ccm_bytes_.size());
+    const int32_t *d_slot = upload(d_ccm_slot_, cap_ccm_slot_, ccm_slot_.data(), n);
+    const int32_t *d_order = upload(d_ccm_order_, cap_ccm_order_, ccm_order_.data(), n);
+    grow(d_ccm_keep_, cap_ccm_keep_, 2 * n * block_len);
+    uint64_t *d_s0 = d_ccm_keep_, *d_x = d_ccm_keep_ + n * block_len;  // chain order, both
+
+    // ---- pass 1: A_1 .. A_n into the result, A_0 and B_0 into the kept blocks ----
+    std::vector<PubBlock> blocks;
+    std::vector<int64_t> kout;
+    std::vector<int32_t> klen;
+    auto add = [&](int32_t slot, const uint8_t *bytes, int64_t out_byte, int32_t len, int64_t keep_byte) {
+        PubBlock b;
+        b.slot = slot;
+        std::memcpy(b.bytes, bytes, 16);
+        b.out_byte = out_byte;
+        b.len = len;
+        blocks.push_back(b);
+        kout.push_back(keep_byte < 0 ? 0 : keep_byte);
+        klen.push_back(keep_byte < 0 ? 0 : 16);
+    };
+    for (size_t s = 0; s < n; s++) {
+        const CcmFrame &f = *streams[s].frame;
+        for (size_t i = 1; i < f.n_ctr(); i++)
+            add(streams[s].slot, &f.ctr[16 * i], off[s] + (int64_t)(16 * (i - 1)),
+                (int32_t)std::min<size_t>(16, f.payload_len - 16 * (i - 1)), -1);
+        add(streams[s].slot, &f.ctr[0], 0, 0, (int64_t)(16 * rank[s]));
+        add(streams[s].slot, &f.mac[0], 0, 0, (int64_t)(16 * (n + rank[s])));
+    }
+    const size_t n_chunks = (blocks.size() + ctr_chunk_ - 1) / ctr_chunk_;
+    ctr_mplans_.clear();
+    ccm_kout_.clear();
+    ccm_klen_.clear();
+    ctr_mplans_.reserve(n_chunks);
+    ccm_kout_.reserve(n_chunks);
+    ccm_klen_.reserve(n_chunks);
+    for (size_t b0 = 0; b0 < blocks.size(); b0 += ctr_chunk_) {
+        const size_t cn = std::min(ctr_chunk_, blocks.size() - b0);
+        ctr_mplans_.emplace_back();
+        pub_plan(blocks.data() + b0, cn, ctr_mplans_.back());
+        ccm_kout_.emplace_back(kout.begin() + b0, kout.begin() + b0 + cn);
+        ccm_klen_.emplace_back(klen.begin() + b0, klen.begin() + b0 + cn);
+        aes_ctr_blocks_multi(d_table, ctr_mplans_.back(), rounds, d_bytes, d_out_plain, nr, &ccm_kout_.back(),
+                             &ccm_klen_.back(), d_ccm_keep_);
+    }
+
+    // ---- the chain: step t absorbs MAC block t of the streams that have one ----
+    auto mac_blocks = [&](size_t j) { return streams[(size_t)ccm_order_[j]].frame->n_mac(); };
+    const size_t depth = mac_blocks(0);
+    std::vector<size_t> step_at(depth, 0), step_n(depth, 0);
+    ccm_src_.clear();
+    for (size_t t = 1; t < depth; t++) {
+        step_at[t] = ccm_src_.size();
+        for (size_t j = 0; j < n && mac_blocks(j) > t; j++) {
+            const size_t s = (size_t)ccm_order_[j];
+            const CcmFrame &f = *streams[s].frame;
+            for (int pos = 0; pos < 16; pos++) {
+                const int64_t q = f.src[t * 16 + pos];
+                ccm_src_.push_back(q >= 0 ? off[s] + q : ccm_src_public(f.mac[t * 16 + pos]));
+            }
+            step_n[t] = j + 1;
+        }
+    }
+    const int64_t *d_src = ccm_src_.empty() ? nullptr : upload(d_ccm_src_, cap_ccm_src_, ccm_src_.data(), ccm_src_.size());
+    if (depth > 1) grow(d_state_, cap_state_, step_n[1] * block_len);  // the largest step: aes_forward keeps the buffer
+    for (size_t t = 1; t < depth; t++) {
+        const size_t na = step_n[t];
+        timed(ST_LINEAR, [&] {
+            aes_ccm_absorb_kernel<<<grid_for(na * block_len), kThreads, 0, stream_>>>(
+                d_x, d_out_plain, d_table, d_src + step_at[t], d_state_, na, L, d_slot, key_stride, nr);
+            HIPC(hipGetLastError());
+        });
+        AesRun a{AesRun::GAL_MUL, d_table, na, rounds, nr};
+        a.state_ready = true;
+        a.key_of = d_slot;
+        a.key_stride = key_stride;
+        a.time_linear = true;
+        a.out_bytes = na * 16;
+        a.out = d_x;
+        aes_forward(a);
+    }
+    timed(ST_LINEAR, [&] {
+        aes_ccm_tag_kernel<<<grid_for(n * 8 * (size_t)M * L), kThreads, 0, stream_>>>(
+            d_x, d_s0, d_table, d_bytes + total, M, d_order, d_out_tagdiff, n, L, d_slot, key_stride, nr);
+        HIPC(hipGetLastError());
+    });
+    collect_times();
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1077,6 +1077,125 @@ int tae_aesm_cbc_transcipher(const tae_context *ctx, int key_bits, const tae_bit
     });
 }
 
+/* ---- AES-CCM decryption of public frames (RFC 3610; no counterpart in the reference) ---- */
+extern "C++" {
+namespace {
+std::vector<tae::Context::CcmStreamIn> ccm_streams_in(const tae_ccm_stream *streams, size_t n_streams) {
+    require(streams || !n_streams, "null");
+    std::vector<tae::Context::CcmStreamIn> v(n_streams);
+    for (size_t i = 0; i < n_streams; i++)
+        v[i] = {streams[i].key,  streams[i].nonce, streams[i].nonce_len, streams[i].aad,
+                streams[i].aad_len, streams[i].data,  streams[i].len};
+    return v;
+}
+
+void throw_ccm_format(tae::CcmFormat e) {
+    switch (e) {
+        case tae::CCM_FMT_NONCE: throw tae::ModelError{TAE_E_PARAM, "a CCM nonce is 7..13 bytes"};
+        case tae::CCM_FMT_TAG: throw tae::ModelError{TAE_E_PARAM, "a CCM tag is 4, 6 .. 16 bytes"};
+        case tae::CCM_FMT_AAD:
+            throw tae::ModelError{TAE_E_PARAM, "CCM associated data of 0xFF00 bytes or more is not supported"};
+        case tae::CCM_FMT_LEN:
+            throw tae::ModelError{TAE_E_PARAM, "the payload length does not fit the nonce's length field"};
+        default: break;
+    }
+}
+}  // namespace
+}  // extern "C++"
+
+int tae_aesx_ccm_format(const uint8_t *nonce, size_t nonce_len, int tag_len, const uint8_t *aad, size_t aad_len,
+                        size_t payload_len, size_t *n_ctr, size_t *n_mac, uint8_t *ctr_blocks, uint8_t *mac_blocks,
+                        int64_t *mac_src) {
+    return guarded([&] {
+        require(nonce && n_ctr && n_mac && (aad || !aad_len), "null");
+        tae::CcmFrame f;
+        throw_ccm_format(tae::ccm_format(nonce, nonce_len, tag_len, aad, aad_len, payload_len, f));
+        *n_ctr = f.n_ctr();
+        *n_mac = f.n_mac();
+        if (ctr_blocks) std::memcpy(ctr_blocks, f.ctr.data(), f.ctr.size());
+        if (mac_blocks) std::memcpy(mac_blocks, f.mac.data(), f.mac.size());
+        if (mac_src) std::memcpy(mac_src, f.src.data(), f.src.size() * sizeof(int64_t));
+    });
+}
+
+int tae_aesx_ccm_noise_schedule_check(int param_set, int key_bits, int rounds) {
+    return guarded([&] {
+        const tae::Params p = params_of(param_set);
+        const size_t kw = key_cts(key_bits);
+        const int nk = tae::aes_nk(key_bits), nr = tae::aes_nr(key_bits);
+        if (p.model != 1) throw tae::ModelError{TAE_E_PARAM, "CCM runs on the 1-bit WoP-PBS parameter sets only"};
+        std::vector<tae::NoiseLevel> key((size_t)nk * 32);
+        for (auto &x : key) x = tae::NoiseLevel::with_noise_level(1, tae::next_ct_id());
+        const std::vector<tae::NoiseLevel> rk = tae::aes_key_expand_noise_schedule(key, nk, p.max_noise_sq);
+        require(rk.size() == kw, "expanded key size");
+        // a frame with every kind of step: public AAD bytes, payload bytes and a padded last block
+        const uint8_t nonce[13] = {}, aad[8] = {};
+        tae::CcmFrame f;
+        throw_ccm_format(tae::ccm_format(nonce, sizeof(nonce), 16, aad, sizeof(aad), 17, f));
+        tae::aes_ccm_noise_schedule(rk, f, rounds, p.max_noise_sq, nr);
+    });
+}
+
+int tae_aesm_pub_keystream_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys,
+                               const int32_t *key_of_block, const uint8_t *blocks, size_t n_blocks, int rounds,
+                               uint64_t *out, int mem) {
+    return guarded([&] {
+        require(ctx && ((table && key_of_block && blocks && out) || !n_blocks), "null");
+        ctx->ctx->aes_pub_keystream_multi_raw(table, n_keys, key_of_block, blocks, n_blocks, rounds, out,
+                                              mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesm_ccm_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys,
+                                 const tae_ccm_stream *streams, size_t n_streams, int tag_len, int rounds,
+                                 uint64_t *out_plain, uint64_t *out_tag_diff, int mem) {
+    return guarded([&] {
+        require(ctx != nullptr, "null");
+        const std::vector<tae::Context::CcmStreamIn> in = ccm_streams_in(streams, n_streams);
+        require((table && out_tag_diff) || !n_streams, "null");
+        ctx->ctx->aes_ccm_multi_raw(table, n_keys, in, tag_len, rounds, out_plain, out_tag_diff, mem == TAE_MEM_DEVICE,
+                                    key_bits);
+    });
+}
+
+int tae_aesm_ccm_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *table, size_t n_keys,
+                             const tae_ccm_stream *streams, size_t n_streams, int tag_len, int rounds,
+                             tae_bit **out_plain, tae_bit **out_tag_diff) {
+    return guarded([&] {
+        require(ctx != nullptr, "null");
+        const std::vector<tae::Context::CcmStreamIn> in = ccm_streams_in(streams, n_streams);
+        require((table && out_tag_diff) || !n_streams, "null");
+        const tae::Context::CcmBits res = ctx->ctx->aes_ccm_multi(bit_at(table), n_keys, in, tag_len, rounds, key_bits);
+        require(out_plain || res.plain.empty(), "null");
+        emit(res.plain, out_plain);
+        emit(res.tag_diff, out_tag_diff);
+    });
+}
+
+int tae_aesx_ccm_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint8_t *nonce,
+                                 size_t nonce_len, const uint8_t *aad, size_t aad_len, const uint8_t *data, size_t len,
+                                 int tag_len, int rounds, uint64_t *out_plain, uint64_t *out_tag_diff, int mem) {
+    return guarded([&] {
+        require(ctx && rk && out_tag_diff, "null");
+        const std::vector<tae::Context::CcmStreamIn> in = {{0, nonce, nonce_len, aad, aad_len, data, len}};
+        ctx->ctx->aes_ccm_multi_raw(rk, 1, in, tag_len, rounds, out_plain, out_tag_diff, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesx_ccm_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
+                             const uint8_t *nonce, size_t nonce_len, const uint8_t *aad, size_t aad_len,
+                             const uint8_t *data, size_t len, int tag_len, int rounds, tae_bit **out_plain,
+                             tae_bit **out_tag_diff) {
+    return guarded([&] {
+        require(ctx && expanded_key && out_tag_diff, "null");
+        const std::vector<tae::Context::CcmStreamIn> in = {{0, nonce, nonce_len, aad, aad_len, data, len}};
+        const tae::Context::CcmBits res = ctx->ctx->aes_ccm_multi(bit_at(expanded_key), 1, in, tag_len, rounds, key_bits);
+        require(out_plain || res.plain.empty(), "null");
+        emit(res.plain, out_plain);
+        emit(res.tag_diff, out_tag_diff);
+    });
+}
+
 int tae_aes_sbox_pbs_encrypt_blocks(const tae_context *ctx, const tae_bit *const *expanded_key,
                                     const tae_bit *const *blocks, size_t n_blocks, int rounds, tae_bit **out) {
     return guarded([&] {

@@ -15,6 +15,7 @@
 
 #include "client.hpp"
 #include "cplx.hpp"
+#include "aes_ccm.hpp"
 #include "aes_xts.hpp"
 #include "ctr_plan.hpp"
 #include "kslots.hpp"
@@ -172,6 +173,27 @@ class Engine {
                              const int32_t *tweak_of, const uint64_t *block_index, const uint8_t *d_data, size_t nb,
                              int rounds, uint64_t *d_out, int nr = 10);
 
+    // ---- AES-CCM decryption of public frames on the 1-bit model (aes_ccm.hpp; the reference has no
+    // CCM).  `rounds` (>= 2) applies to every cipher call ----
+    // One frame under slot `slot` of a key table: `data` = the frame's payload_len ciphertext bytes, `tag` its M
+    // encrypted-tag bytes (HOST arrays, read during the call)
+    struct CcmStreamIn {
+        int32_t slot;
+        const CcmFrame *frame;
+        const uint8_t *data, *tag;
+    };
+    // The forward cipher over public blocks (HOST), block i under slot blocks[i].slot, in chunks of ctr_chunk_
+    // blocks with a pub_plan each; writes each block's len bytes at out_byte of d_out
+    void aes_pub_blocks_multi(const uint64_t *d_table, const std::vector<PubBlock> &blocks, int rounds, uint64_t *d_out,
+                              int nr);
+    // Pass 1: every stream's A_0, A_1 .. and B_0 as one batch of public blocks; the payload bits S_i + C go to
+    // d_out_plain [sum payload_len][8][K+1], frames in order.  Then the CBC-MAC chain, one forward cipher per step
+    // over the streams that still have a MAC block (the streams are ordered by decreasing block count inside the
+    // call, so they are a prefix), its round 0 from aes_ccm_absorb_kernel.  d_out_tagdiff [n_streams][8 M][K+1] =
+    // X_last + S_0 + U, frames in the caller's order; one M for the call
+    void aes_ccm_transcipher(const uint64_t *d_table, const std::vector<CcmStreamIn> &streams, int rounds, int nr,
+                             uint64_t *d_out_plain, uint64_t *d_out_tagdiff);
+
     // ---- multi-key batches on the 1-bit model (the reference has one key).  A key table is
     // [n_keys][4 (nr + 1) * 32][K+1], slot s an expanded (or decryption) key in the layout above.  The bootstraps
     // are per ciphertext, so bits of different keys share their launches; the linear layer reads the round key of
@@ -299,8 +321,23 @@ class Engine {
     std::vector<int32_t> key_of_host_;
     std::vector<CtrPlanMulti> ctr_mplans_;
     const int32_t *upload_key_of(const int32_t *key_of, size_t nb);
+    // keep_out / keep_len / d_keep (CCM): a second placement of the same cipher outputs, into d_keep
     void aes_ctr_blocks_multi(const uint64_t *d_table, const CtrPlanMulti &plan, int rounds, const uint8_t *d_data,
-                              uint64_t *d_out, int nr);
+                              uint64_t *d_out, int nr, const std::vector<int64_t> *keep_out = nullptr,
+                              const std::vector<int32_t> *keep_len = nullptr, uint64_t *d_keep = nullptr);
+    // CCM: S_0 and the chain value Xk of every stream [2 n][128][K+1], the arrays of the call on the device and
+    // the host copies their pending uploads read
+    uint64_t *d_ccm_keep_ = nullptr;
+    uint8_t *d_ccm_bytes_ = nullptr;
+    int64_t *d_ccm_src_ = nullptr, *d_ccm_kout_ = nullptr;
+    int32_t *d_ccm_slot_ = nullptr, *d_ccm_klen_ = nullptr, *d_ccm_order_ = nullptr;
+    size_t cap_ccm_keep_ = 0, cap_ccm_bytes_ = 0, cap_ccm_src_ = 0, cap_ccm_kout_ = 0, cap_ccm_slot_ = 0,
+           cap_ccm_klen_ = 0, cap_ccm_order_ = 0;
+    std::vector<uint8_t> ccm_bytes_;
+    std::vector<int64_t> ccm_src_;
+    std::vector<int32_t> ccm_slot_, ccm_order_;
+    std::vector<std::vector<int64_t>> ccm_kout_;
+    std::vector<std::vector<int32_t>> ccm_klen_;
     // XTS: the refreshed tweaks of the call, the masks of the chunk in flight, the plan arrays on the device and
     // the host plans their pending uploads read
     uint64_t *d_xts_tweaks_ = nullptr, *d_xts_masks_ = nullptr;

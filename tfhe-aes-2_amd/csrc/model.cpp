@@ -249,13 +249,21 @@ std::vector<BitCt> Context::circuit_bootstrap(const std::vector<const BitCt *> &
 // AES (fhe_sbox_gal_mul_pbs.rs)
 // ---------------------------------------------------------------------------------------------
 // Metadata-only replay of encrypt_block_for_rounds for ONE block: rk [4 (nr + 1) * 32], block [128].
+// The rounds after round 0: st [128] is the state with round key 0 added.  last_key == false leaves the last round
+// key out: the last SubBytes output after ShiftRows alone (CCM's X').
+static std::vector<NoiseLevel> aes_noise_rounds(const std::vector<NoiseLevel> &rk, std::vector<NoiseLevel> st, int rounds,
+                                                uint64_t max, int nr, bool last_key);
+
 std::vector<NoiseLevel> aes_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &block,
                                            int rounds, uint64_t max, int nr) {
-    auto key_bit = [&](int word, int byte, int bit) -> const NoiseLevel & { return rk[(word * 4 + byte) * 8 + bit]; };
     std::vector<NoiseLevel> st = block;  // index (4*col + row)*8 + bit
-    for (int c = 0; c < 4; c++)
-        for (int r = 0; r < 4; r++)
-            for (int b = 0; b < 8; b++) st[(4 * c + r) * 8 + b].add_assign(key_bit(c, r, b), max);
+    for (int i = 0; i < 128; i++) st[i].add_assign(rk[i], max);  // round key 0: words 0..3, the state's order
+    return aes_noise_rounds(rk, std::move(st), rounds, max, nr, true);
+}
+
+static std::vector<NoiseLevel> aes_noise_rounds(const std::vector<NoiseLevel> &rk, std::vector<NoiseLevel> st, int rounds,
+                                                uint64_t max, int nr, bool last_key) {
+    auto key_bit = [&](int word, int byte, int bit) -> const NoiseLevel & { return rk[(word * 4 + byte) * 8 + bit]; };
     auto cbs_outputs = [&](int n_out) {
         std::vector<NoiseLevel> o((size_t)16 * n_out);
         for (auto &x : o) x = NoiseLevel::with_noise_level(8, next_ct_id());
@@ -282,7 +290,7 @@ std::vector<NoiseLevel> aes_noise_schedule(const std::vector<NoiseLevel> &rk, co
         for (int r = 0; r < 4; r++)
             for (int b = 0; b < 8; b++) {
                 NoiseLevel v = sb[(4 * ((c + r) % 4) + r) * 8 + b];
-                v.add_assign(key_bit(4 * nr + c, r, b), max);
+                if (last_key) v.add_assign(key_bit(4 * nr + c, r, b), max);
                 st[(4 * c + r) * 8 + b] = std::move(v);
             }
     return st;
@@ -1687,6 +1695,194 @@ std::vector<BitCt> Context::aes_cbc_multi(const BitAt &dtable, size_t n_keys, co
         res[i].noise = std::move(noise[i]);  // xor with a public bit adds no noise
         res[i].max_noise_sq = params().max_noise_sq;
     }
+    return res;
+}
+
+// ---------------------------------------------------------------------------------------------
+// AES-CCM decryption of public frames (RFC 3610; aes_ccm.hpp).  The reference has no CCM.
+// ---------------------------------------------------------------------------------------------
+CcmNoise aes_ccm_noise_schedule(const std::vector<NoiseLevel> &rk, const CcmFrame &f, int rounds, uint64_t max, int nr) {
+    require_rounds(rounds, nr);
+    // at one round B_0 and A_0 share their de-duplicated SubBytes outputs at the nonce positions
+    if (rounds < 2) throw ModelError{TAE_E_PARAM, "CCM needs rounds >= 2"};
+    require_key_words(rk.size(), nr, "expanded key");
+    if (!f.n_mac() || !f.n_ctr()) throw ModelError{TAE_E_ARG, "empty CCM frame"};
+    auto last_key = [&](int i) -> const NoiseLevel & { return rk[(size_t)128 * nr + i]; };
+    // X' of a block: `in` is the round-0 state before round key 0
+    auto x_prime = [&](std::vector<NoiseLevel> in) {
+        for (int i = 0; i < 128; i++) in[i].add_assign(rk[i], max);
+        return aes_noise_rounds(rk, std::move(in), rounds, max, nr, false);
+    };
+    const std::vector<NoiseLevel> triv(128, NoiseLevel::trivial());
+    CcmNoise out;
+    std::vector<std::vector<NoiseLevel>> sp(f.n_ctr());  // S'_i
+    for (auto &s : sp) s = x_prime(triv);
+    out.plain.resize(f.payload_len * 8);
+    for (size_t q = 0; q < f.payload_len; q++)
+        for (int b = 0; b < 8; b++) {
+            const int i = (int)(q % 16) * 8 + b;
+            NoiseLevel v = sp[1 + q / 16][i];
+            v.add_assign(last_key(i), max);
+            out.plain[q * 8 + b] = std::move(v);
+        }
+    std::vector<NoiseLevel> x = x_prime(triv);  // B_0
+    for (size_t t = 1; t < f.n_mac(); t++) {
+        std::vector<NoiseLevel> in(128);
+        std::vector<uint64_t> levels(128);
+        for (int i = 0; i < 128; i++) {
+            const int64_t q = f.src[t * 16 + (size_t)(i >> 3)];
+            NoiseLevel v = x[i];
+            if (q >= 0)
+                v.add_assign(sp[1 + (size_t)q / 16][((size_t)q % 16) * 8 + (i & 7)], max);  // Xk + P - 2 rk_nr = X' + S'
+            else
+                v.add_assign(last_key(i), max);  // Xk = X' + rk_nr
+            levels[i] = v.noise_level_squared + rk[i].noise_level_squared;
+            in[i] = std::move(v);
+        }
+        out.step_round0.push_back(std::move(levels));
+        x = x_prime(std::move(in));
+    }
+    out.tag_diff.resize((size_t)8 * f.M);
+    for (int i = 0; i < 8 * f.M; i++) {
+        NoiseLevel v = x[i];
+        v.add_assign(sp[0][i], max);  // Xk_last + S_0 - 2 rk_nr = X'_last + S'_0
+        out.tag_diff[i] = std::move(v);
+    }
+    return out;
+}
+
+namespace {
+// the frames of the streams; every refusal of the format is TAE_E_PARAM, a bad slot or a null array TAE_E_ARG
+std::vector<CcmFrame> ccm_frames(const std::vector<Context::CcmStreamIn> &streams, int tag_len, size_t n_keys,
+                                 std::vector<int32_t> &slots) {
+    std::vector<CcmFrame> frames(streams.size());
+    slots.resize(streams.size());
+    for (size_t s = 0; s < streams.size(); s++) {
+        const Context::CcmStreamIn &st = streams[s];
+        if (!st.nonce || (!st.aad && st.aad_len) || (!st.data && st.len)) throw ModelError{TAE_E_ARG, "null frame array"};
+        const size_t M = tag_len > 0 ? (size_t)tag_len : 0;
+        switch (ccm_format(st.nonce, st.nonce_len, tag_len, st.aad, st.aad_len, st.len >= M ? st.len - M : 0, frames[s])) {
+            case CCM_FMT_NONCE: throw ModelError{TAE_E_PARAM, "a CCM nonce is 7..13 bytes"};
+            case CCM_FMT_TAG: throw ModelError{TAE_E_PARAM, "a CCM tag is 4, 6 .. 16 bytes"};
+            case CCM_FMT_AAD: throw ModelError{TAE_E_PARAM, "CCM associated data of 0xFF00 bytes or more is not supported"};
+            case CCM_FMT_LEN: throw ModelError{TAE_E_PARAM, "the payload length does not fit the nonce's length field"};
+            default: break;
+        }
+        if (st.len < M) throw ModelError{TAE_E_PARAM, "CCM data is shorter than the tag"};
+        if (st.slot < 0 || (uint64_t)st.slot >= n_keys)
+            throw ModelError{TAE_E_ARG, "a stream's key slot is outside 0..n_keys-1"};
+        slots[s] = st.slot;
+    }
+    return frames;
+}
+}  // namespace
+
+void Context::aes_pub_keystream_multi_raw(const uint64_t *table, size_t n_keys, const int32_t *slots,
+                                          const uint8_t *blocks, size_t n_blocks, int rounds, uint64_t *out,
+                                          bool device_mem, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    if (!n_blocks) return;
+    if (!n_keys) throw ModelError{TAE_E_ARG, "blocks but no keys"};
+    require_slots(slots, n_blocks, n_keys);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    aes_noise_schedule(fresh_levels(kw), std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds,
+                       params().max_noise_sq, nr);
+    std::vector<PubBlock> pb(n_blocks);
+    for (size_t i = 0; i < n_blocks; i++) {
+        std::memcpy(pb[i].bytes, blocks + 16 * i, 16);
+        pb[i].out_byte = (int64_t)(16 * i);
+        pb[i].len = 16;
+    }
+    run_multi(table, std::vector<int32_t>(slots, slots + n_blocks), device_mem, kw, nullptr, 0, nullptr, 0, out,
+              n_blocks * 128 * bit_len(),
+              [&](const uint64_t *t, const int32_t *ko, const uint64_t *, const uint8_t *, uint64_t *o) {
+                  for (size_t i = 0; i < n_blocks; i++) pb[i].slot = ko[i];
+                  engine_->aes_pub_blocks_multi(t, pb, rounds, o, nr);
+              });
+}
+
+void Context::run_ccm(const uint64_t *table, std::vector<int32_t> slots, const std::vector<CcmFrame> &frames,
+                      const std::vector<CcmStreamIn> &streams, int tag_len, int rounds, int nr, size_t key_cts,
+                      uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem) {
+    const size_t n = frames.size(), S = bit_len(), stride = key_cts * S;
+    size_t total = 0;
+    for (const CcmFrame &f : frames) total += f.payload_len;
+    const size_t plain_len = total * 8 * S, tag_len_w = n * 8 * (size_t)tag_len * S;
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    std::vector<int32_t> used;
+    if (!device_mem) used = compact_slots(slots);
+    std::vector<Engine::CcmStreamIn> in(n);
+    for (size_t s = 0; s < n; s++)
+        in[s] = {slots[s], &frames[s], streams[s].data, streams[s].data + frames[s].payload_len};
+    if (device_mem) {
+        engine_->order_after_caller();
+        engine_->aes_ccm_transcipher(table, in, rounds, nr, out_plain, out_tag_diff);
+        engine_->synchronize();
+        return;
+    }
+    DevBuf d_tab(used.size() * stride * 8), d_plain(plain_len * 8), d_tag(tag_len_w * 8);
+    for (size_t j = 0; j < used.size(); j++)
+        hip_check(hipMemcpyAsync(d_tab.as<uint64_t>() + j * stride, table + (size_t)used[j] * stride, stride * 8,
+                                 hipMemcpyHostToDevice, engine_->stream()),
+                  "upload key slot");
+    engine_->aes_ccm_transcipher(d_tab.as<uint64_t>(), in, rounds, nr, d_plain.as<uint64_t>(), d_tag.as<uint64_t>());
+    if (plain_len)
+        hip_check(hipMemcpyAsync(out_plain, d_plain.p, plain_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    hip_check(hipMemcpyAsync(out_tag_diff, d_tag.p, tag_len_w * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+void Context::aes_ccm_multi_raw(const uint64_t *table, size_t n_keys, const std::vector<CcmStreamIn> &streams,
+                                int tag_len, int rounds, uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem,
+                                int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    if (rounds < 2) throw ModelError{TAE_E_PARAM, "CCM needs rounds >= 2"};
+    std::vector<int32_t> slots;
+    const std::vector<CcmFrame> frames = ccm_frames(streams, tag_len, n_keys, slots);
+    if (frames.empty()) return;
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    // the levels depend on the layout alone: frames of one layout are replayed once
+    std::vector<const CcmFrame *> seen;
+    for (const CcmFrame &f : frames) {
+        bool dup = false;
+        for (const CcmFrame *o : seen) dup = dup || (o->M == f.M && o->src == f.src);
+        if (dup) continue;
+        seen.push_back(&f);
+        aes_ccm_noise_schedule(fresh_levels(kw), f, rounds, params().max_noise_sq, nr);
+    }
+    run_ccm(table, slots, frames, streams, tag_len, rounds, nr, kw, out_plain, out_tag_diff, device_mem);
+}
+
+Context::CcmBits Context::aes_ccm_multi(const BitAt &table, size_t n_keys, const std::vector<CcmStreamIn> &streams,
+                                        int tag_len, int rounds, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    if (rounds < 2) throw ModelError{TAE_E_PARAM, "CCM needs rounds >= 2"};
+    std::vector<int32_t> slots;
+    const std::vector<CcmFrame> frames = ccm_frames(streams, tag_len, n_keys, slots);
+    if (frames.empty()) return {};
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len(), n = frames.size();
+    std::vector<std::vector<NoiseLevel>> knoise;
+    const std::vector<uint64_t> tab = gather_slots(table, slots, kw, L, knoise);
+    std::vector<NoiseLevel> pn, tn;
+    for (size_t s = 0; s < n; s++) {
+        CcmNoise cn = aes_ccm_noise_schedule(knoise[(size_t)slots[s]], frames[s], rounds, params().max_noise_sq, nr);
+        for (NoiseLevel &x : cn.plain) pn.push_back(std::move(x));
+        for (NoiseLevel &x : cn.tag_diff) tn.push_back(std::move(x));
+    }
+    std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
+    run_ccm(tab.data(), slots, frames, streams, tag_len, rounds, nr, kw, plain.data(), tag.data(), false);
+    CcmBits res;
+    auto wrap_bits = [&](const std::vector<uint64_t> &w, std::vector<NoiseLevel> &noise, std::vector<BitCt> &bits) {
+        bits.resize(noise.size());
+        for (size_t i = 0; i < bits.size(); i++) {
+            bits[i].ct.assign(w.begin() + i * L, w.begin() + (i + 1) * L);
+            bits[i].noise = std::move(noise[i]);  // xor with a public bit adds no noise
+            bits[i].max_noise_sq = params().max_noise_sq;
+        }
+    };
+    wrap_bits(plain, pn, res.plain);
+    wrap_bits(tag, tn, res.tag_diff);
     return res;
 }
 

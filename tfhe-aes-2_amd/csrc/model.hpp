@@ -197,6 +197,34 @@ class Context {  // FheContext
     std::vector<BitCt> aes_cbc_multi(const BitAt &dtable, size_t n_keys, const std::vector<CbcStreamIn> &streams,
                                      int rounds, int key_bits);
 
+    // ---- AES-CCM decryption of public frames over a key table (RFC 3610; aes_ccm.hpp; the reference
+    // has no CCM).  The scope of the multi-key calls; a format refusal (nonce length, tag length, AAD >= 0xFF00, a
+    // payload length that does not fit L bytes, data shorter than the tag) and rounds < 2 are TAE_E_PARAM before
+    // any device work.  A single key is a table of one slot. ----
+    struct CcmStreamIn {
+        int32_t slot;
+        const uint8_t *nonce;
+        size_t nonce_len;
+        const uint8_t *aad;
+        size_t aad_len;
+        const uint8_t *data;  // the ciphertext and the encrypted tag: len >= tag_len bytes
+        size_t len;
+    };
+    struct CcmBits {
+        std::vector<BitCt> plain, tag_diff;  // [sum (len - tag_len) * 8], [n_streams * 8 tag_len]
+    };
+    // the forward cipher over arbitrary public blocks [n_blocks][16] (host), block i under slot slots[i]:
+    // out [n_blocks][128][bit_len], equal word for word to the cipher on trivial encryptions of the blocks
+    void aes_pub_keystream_multi_raw(const uint64_t *table, size_t n_keys, const int32_t *slots, const uint8_t *blocks,
+                                     size_t n_blocks, int rounds, uint64_t *out, bool device_mem, int key_bits);
+    // out_plain [sum (len - tag_len)][8][bit_len], frames in order; out_tag_diff [n_streams][8 tag_len][bit_len] =
+    // the recomputed tag xor the received one, all zero iff the frame is authentic
+    void aes_ccm_multi_raw(const uint64_t *table, size_t n_keys, const std::vector<CcmStreamIn> &streams, int tag_len,
+                           int rounds, uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem, int key_bits);
+    // BitCt variant: the bits carry the levels and ids of aes_ccm_noise_schedule
+    CcmBits aes_ccm_multi(const BitAt &table, size_t n_keys, const std::vector<CcmStreamIn> &streams, int tag_len,
+                          int rounds, int key_bits);
+
     // ---- 8-bit model (src/tfhe/shortint_woppbs_8bit.rs, fhe_impls/shortint_woppbs_8bit.rs) ----
     size_t bit_len() const { return params().bit_len(); }
     // FheContext::bootstrap_from_bits over G bytes: bits [G][8][n+1] -> int ciphertexts [G][K+1]
@@ -255,6 +283,10 @@ class Context {  // FheContext
     void run_xts(const uint64_t *dk1, const uint64_t *rk2, size_t key_cts, const std::vector<uint8_t> &tweaks,
                  const std::vector<int32_t> &tweak_of, const std::vector<uint64_t> &block_index,
                  const std::vector<uint8_t> &data, int rounds, uint64_t *out, bool device_mem, int nr);
+    // the frames of a CCM call through the engine; host memory uploads the referenced slots alone, as run_multi
+    void run_ccm(const uint64_t *table, std::vector<int32_t> slots, const std::vector<CcmFrame> &frames,
+                 const std::vector<CcmStreamIn> &streams, int tag_len, int rounds, int nr, size_t key_cts,
+                 uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem);
     void run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
                      const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem, int nr);
     void run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint64_t *d_in, size_t n_blocks, int rounds,
@@ -298,6 +330,18 @@ std::vector<NoiseLevel> aes_xts_tweak_noise_schedule(const std::vector<NoiseLeve
 // of the tweak bits in its row.  dk1 [4 (nr + 1) * 32], tweak [128] -> [128]
 std::vector<NoiseLevel> aes_xts_noise_schedule(const std::vector<NoiseLevel> &dk1, const std::vector<NoiseLevel> &tweak,
                                                uint64_t j, int rounds, uint64_t max_noise_sq, int nr = 10);
+
+// CCM (aes_ccm.hpp) on metadata, ONE frame under the expanded key rk [4 (nr + 1) * 32].  Squared levels per bit:
+// a circuit-bootstrap output is 8 with a fresh id; a plaintext bit is 8 + the last round key's bit; round 0 of a
+// chain step is X' + the last round key's bit + rk_0's (8 + 1 + 1) at a public byte and X' + S' + rk_0's
+// (8 + 8 + 1) at a payload byte, where the two last-round-key terms are removed, not added; a tag-difference bit
+// is X'_last + S'_0 = 16 and holds no key bit.  rounds < 2 is TAE_E_PARAM.
+struct CcmNoise {
+    std::vector<NoiseLevel> plain, tag_diff;           // [payload_len * 8], [8 M]
+    std::vector<std::vector<uint64_t>> step_round0;  // [n_mac - 1][128]: the squared levels of every step's round 0
+};
+CcmNoise aes_ccm_noise_schedule(const std::vector<NoiseLevel> &rk, const CcmFrame &frame, int rounds,
+                                uint64_t max_noise_sq, int nr = 10);
 
 // Counter mode on the 1-bit model: output noise [n_blocks][128] of the gal-mul schedule for trivial counter
 // blocks.  rounds >= 2: aes_noise_schedule per block.  rounds == 1: the final SubBytes runs on the plan's

@@ -51,6 +51,9 @@ EXPORTED = [
     "tae_aesm_key_schedule_raw", "tae_aesm_decrypt_key_raw", "tae_aesm_encrypt_blocks_raw",
     "tae_aesm_decrypt_blocks_raw", "tae_aesm_ctr_plan", "tae_aesm_ctr_transcipher_raw",
     "tae_aesm_cbc_transcipher_raw", "tae_aesm_key_schedule", "tae_aesm_ctr_transcipher", "tae_aesm_cbc_transcipher",
+    "tae_aesx_ccm_format", "tae_aesx_ccm_noise_schedule_check", "tae_aesm_pub_keystream_raw",
+    "tae_aesm_ccm_transcipher_raw", "tae_aesm_ccm_transcipher", "tae_aesx_ccm_transcipher_raw",
+    "tae_aesx_ccm_transcipher",
     "tae_last_pfks_kernel",
     "tae_packed_len", "tae_encrypt_packed_raw", "tae_decrypt_packed_raw", "tae_packed_narrow", "tae_packed_widen",
     "tae_unpack_bits_raw", "tae_pack_bits_raw", "tae_unpack_bits", "tae_pack_bits", "tae_last_pack_time",
@@ -84,6 +87,12 @@ class TaeCbcStream(C.Structure):
 class TaeXtsUnit(C.Structure):
     """tae_xts_unit: one XTS data unit, or a range of its blocks."""
     _fields_ = [("tweak", C.c_uint8 * 16), ("first_block", C.c_uint64), ("data", C.c_void_p), ("len", C.c_size_t)]
+
+
+class TaeCcmStream(C.Structure):
+    """tae_ccm_stream: one CCM frame of a multi-key call."""
+    _fields_ = [("key", C.c_int32), ("nonce", C.c_void_p), ("nonce_len", C.c_size_t), ("aad", C.c_void_p),
+                ("aad_len", C.c_size_t), ("data", C.c_void_p), ("len", C.c_size_t)]
 
 
 class TaeError(RuntimeError):
@@ -193,6 +202,14 @@ def lib() -> C.CDLL:
         "tae_aesm_key_schedule": ([vp, C.c_int, vp, sz, vp], C.c_int),
         "tae_aesm_ctr_transcipher": ([vp, C.c_int, vp, sz, vp, sz, C.c_int, vp], C.c_int),
         "tae_aesm_cbc_transcipher": ([vp, C.c_int, vp, sz, vp, sz, C.c_int, vp], C.c_int),
+        "tae_aesx_ccm_format": ([vp, sz, C.c_int, vp, sz, sz, C.POINTER(sz), C.POINTER(sz), vp, vp, vp], C.c_int),
+        "tae_aesx_ccm_noise_schedule_check": ([C.c_int, C.c_int, C.c_int], C.c_int),
+        "tae_aesm_pub_keystream_raw": ([vp, C.c_int, vp, sz, vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesm_ccm_transcipher_raw": ([vp, C.c_int, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp, C.c_int], C.c_int),
+        "tae_aesm_ccm_transcipher": ([vp, C.c_int, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp], C.c_int),
+        "tae_aesx_ccm_transcipher_raw": ([vp, C.c_int, vp, vp, sz, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp, C.c_int],
+                                         C.c_int),
+        "tae_aesx_ccm_transcipher": ([vp, C.c_int, vp, vp, sz, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp], C.c_int),
         "tae_stage_keyswitch": ([vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_pbs_shift_boolean": ([vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_stage_bootstrap": ([vp, vp, sz, vp, vp, C.c_int], C.c_int),

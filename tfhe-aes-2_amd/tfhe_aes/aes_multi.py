@@ -19,7 +19,7 @@ import numpy as np
 from . import _native as N
 from ._native import check, lib
 from .aes_128 import _flat_bits, _iv8, _iv16
-from .aes_var import KEY_BITS, _key_bits_of_words, _nr, _p, _words, expanded_words
+from .aes_var import KEY_BITS, _bytes_ptr, _key_bits_of_words, _nr, _p, _words, expanded_words
 from .tfhe import BitCt, FheContext, _handles
 
 
@@ -91,6 +91,24 @@ def _cbc_streams(streams):
         arr[i].data = buf.ctypes.data if len(buf) else None
         arr[i].len = len(buf)
         lens.append(len(buf))
+    return arr, keep, lens
+
+
+def _ccm_streams(streams, tag_len: int):
+    """(slot, nonce, aad, data) -> tae_ccm_stream array, the buffers it points into, and the payload lengths."""
+    arr = (N.TaeCcmStream * max(len(streams), 1))()
+    keep, lens = [], []
+    for i, (slot, nonce, aad, data) in enumerate(streams):
+        (nb, _), (ab, a_ptr), (db, d_ptr) = _bytes_ptr(nonce), _bytes_ptr(aad), _bytes_ptr(data)
+        keep += [nb, ab, db]
+        arr[i].key = slot
+        arr[i].nonce = nb.ctypes.data
+        arr[i].nonce_len = len(nb)
+        arr[i].aad = a_ptr.value if a_ptr else None
+        arr[i].aad_len = len(ab)
+        arr[i].data = d_ptr.value if d_ptr else None
+        arr[i].len = len(db)
+        lens.append(max(len(db) - tag_len, 0))
     return arr, keep, lens
 
 
@@ -257,3 +275,59 @@ class GalMulAesMulti:
         check(lib().tae_aesm_cbc_transcipher(ctx._h, kb, arr_t, n_keys, arr, len(streams), _nr(kb, rounds), outs))
         bits = [BitCt(h, ctx) for h in outs]
         return _split([bits[8 * i:8 * i + 8] for i in range(sum(lens))], lens)
+
+    # ---- AES-CCM decryption of public frames (RFC 3610) ----
+    # Frames are (slot, nonce, aad, data) with data = encrypted payload || encrypted tag, one tag_len for the call.
+    # Per frame the result is (payload bits [len - tag_len][8], tag-difference bits [tag_len][8]).
+    @staticmethod
+    def public_keystream_raw(ctx: FheContext, table: np.ndarray, key_of_block, blocks16,
+                             rounds: Optional[int] = None) -> np.ndarray:
+        """n public 16-byte blocks, block i under slot key_of_block[i] -> E(block) [n][128][L]."""
+        table, kb = _raw_table(table)
+        buf = np.ascontiguousarray(np.frombuffer(b"".join(bytes(b) for b in blocks16), dtype=np.uint8))
+        if len(buf) % 16:
+            raise N.TaeError(N.TAE_E_ARG, "public blocks are 16 bytes each")
+        n = len(buf) // 16
+        ko = _key_of(key_of_block, n)
+        out = np.zeros((n, 128, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesm_pub_keystream_raw(ctx._h, kb, _p(table), table.shape[0], _p(ko), _p(buf), n,
+                                               _nr(kb, rounds), _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def ccm_transcipher_raw(ctx: FheContext, table: np.ndarray, streams, tag_len: int,
+                            rounds: Optional[int] = None) -> list:
+        """Host arrays: per frame (bits [len - tag_len][8][L], tag_diff [tag_len][8][L]), in the caller's order."""
+        table, kb = _raw_table(table)
+        arr, _keep, lens = _ccm_streams(streams, tag_len)
+        out = np.zeros((sum(lens), 8, ctx.lwe_size), dtype=np.uint64)
+        diff = np.zeros((len(streams), max(tag_len, 0), 8, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesm_ccm_transcipher_raw(ctx._h, kb, _p(table), table.shape[0], arr, len(streams), tag_len,
+                                                 _nr(kb, rounds), _p(out), _p(diff), N.TAE_MEM_HOST))
+        return list(zip(_split(out, lens), diff))
+
+    @staticmethod
+    def ccm_transcipher_device(ctx: FheContext, key_bits: int, d_table: int, n_keys: int, streams, tag_len: int,
+                               rounds: int, d_out: int, d_tag_diff: int):
+        """Device pointers (ints) for the table, the payload bits [sum (len - tag_len)][8][L] and the tag
+        differences [n_streams][tag_len][8][L]; the frames are host data."""
+        arr, _keep, _ = _ccm_streams(streams, tag_len)
+        check(lib().tae_aesm_ccm_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_table), n_keys, arr, len(streams), tag_len,
+                                                 rounds, C.c_void_p(d_out), C.c_void_p(d_tag_diff), N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def ccm_transcipher(ctx: FheContext, table, streams, tag_len: int, rounds: Optional[int] = None) -> list:
+        """table: a list of expanded keys ([W][4][8] BitCt; None for a slot no frame uses) -> per frame
+        (bits [len - tag_len][8], tag_diff [tag_len][8]) BitCt."""
+        arr_t, n_keys, kb = _bit_table(table)
+        arr, _keep, lens = _ccm_streams(streams, tag_len)
+        outs = (C.c_void_p * max(8 * sum(lens), 1))()
+        tags = (C.c_void_p * max(8 * tag_len * len(streams), 1))()
+        check(lib().tae_aesm_ccm_transcipher(ctx._h, kb, arr_t, n_keys, arr, len(streams), tag_len, _nr(kb, rounds),
+                                             outs, tags))
+        bits = [BitCt(outs[i], ctx) for i in range(8 * sum(lens))]
+        diff = [BitCt(tags[i], ctx) for i in range(8 * tag_len * len(streams))]
+        plain = _split([bits[8 * i:8 * i + 8] for i in range(sum(lens))], lens)
+        per = 8 * tag_len
+        return [(plain[s], [diff[s * per + 8 * i:s * per + 8 * i + 8] for i in range(tag_len)])
+                for s in range(len(streams))]

@@ -216,6 +216,109 @@ def _xts_units(units):
     return arr, keep, total
 
 
+# ---------------------------------------------------------------- plain CCM, RFC 3610 ----
+def _ccm_blocks_plain(nonce: bytes, aad: bytes, payload: bytes, tag_len: int):
+    """RFC 3610 section 2: (L, the MAC blocks B_0 .., the counter blocks A_0 ..) of a frame."""
+    nonce, aad, payload = bytes(nonce), bytes(aad), bytes(payload)
+    if not 7 <= len(nonce) <= 13:
+        raise ValueError("a CCM nonce is 7..13 bytes")
+    if tag_len not in (4, 6, 8, 10, 12, 14, 16):
+        raise ValueError("a CCM tag is 4, 6 .. 16 bytes")
+    if len(aad) >= 0xFF00:
+        raise ValueError("associated data of 0xFF00 bytes or more is not supported")
+    ell = 15 - len(nonce)
+    if len(payload) >> (8 * ell):
+        raise ValueError("the payload length does not fit the nonce's length field")
+    flags = (64 if aad else 0) | (8 * ((tag_len - 2) // 2)) | (ell - 1)
+    mac = bytes([flags]) + nonce + len(payload).to_bytes(ell, "big")
+    if aad:
+        enc = len(aad).to_bytes(2, "big") + aad
+        mac += enc + bytes(-len(enc) % 16)
+    mac += payload + bytes(-len(payload) % 16)
+    n_blk = (len(payload) + 15) // 16
+    ctr = [bytes([ell - 1]) + nonce + i.to_bytes(ell, "big") for i in range(n_blk + 1)]
+    return ell, [mac[i:i + 16] for i in range(0, len(mac), 16)], ctr
+
+
+def ccm_mac_plain(key: bytes, nonce: bytes, aad: bytes, payload: bytes, tag_len: int,
+                  rounds: Optional[int] = None) -> bytes:
+    """The CBC-MAC of a frame before it is masked with S_0: the first tag_len bytes of X_last."""
+    ek = key_schedule_plain(key)
+    _, mac, _ = _ccm_blocks_plain(nonce, aad, payload, tag_len)
+    x = bytes(16)
+    for b in mac:
+        x = encrypt_block_plain(ek, bytes(p ^ q for p, q in zip(x, b)), rounds)
+    return x[:tag_len]
+
+
+def ccm_encrypt_plain(key: bytes, nonce: bytes, aad: bytes, plaintext: bytes, tag_len: int,
+                      rounds: Optional[int] = None) -> bytes:
+    """Plain AES-CCM: the encrypted payload followed by the encrypted tag U = T ^ S_0."""
+    ek = key_schedule_plain(key)
+    _, _, ctr = _ccm_blocks_plain(nonce, aad, plaintext, tag_len)
+    ks = [encrypt_block_plain(ek, a, rounds) for a in ctr]
+    tag = ccm_mac_plain(key, nonce, aad, plaintext, tag_len, rounds)
+    body = bytes(p ^ k for p, k in zip(plaintext, b"".join(ks[1:])))
+    return body + bytes(t ^ k for t, k in zip(tag, ks[0]))
+
+
+def ccm_decrypt_plain(key: bytes, nonce: bytes, aad: bytes, data: bytes, tag_len: int,
+                      rounds: Optional[int] = None):
+    """data = encrypted payload || encrypted tag -> (payload, tag difference): what the server computes under FHE.
+    The frame is authentic iff the tag_len difference bytes are zero; the payload is returned either way."""
+    data = bytes(data)
+    if len(data) < tag_len:
+        raise ValueError("data is shorter than the tag")
+    body, u = data[:len(data) - tag_len], data[len(data) - tag_len:]
+    ek = key_schedule_plain(key)
+    _, _, ctr = _ccm_blocks_plain(nonce, aad, body, tag_len)
+    ks = [encrypt_block_plain(ek, a, rounds) for a in ctr]
+    payload = bytes(c ^ k for c, k in zip(body, b"".join(ks[1:])))
+    tag = ccm_mac_plain(key, nonce, aad, payload, tag_len, rounds)
+    return payload, bytes(t ^ k ^ r for t, k, r in zip(tag, ks[0], u))
+
+
+def _bytes_ptr(b: bytes):
+    """(array, pointer or None) of host bytes; the array keeps the pointer alive."""
+    buf = np.frombuffer(bytes(b), dtype=np.uint8)
+    return buf, (C.c_void_p(buf.ctypes.data) if len(buf) else None)
+
+
+def ccm_format(nonce: bytes, aad: bytes, payload_len: int, tag_len: int):
+    """The library's frame layout (tae_aesx_ccm_format): (ctr [n_ctr][16], mac [n_mac][16], src [n_mac][16]) with
+    A_0 .. in ctr, the public bytes of B_0 .. in mac (0 where a payload byte goes) and src = -1 for a public byte,
+    else the index of the payload byte.  Refusals are TAE_E_PARAM."""
+    nb, _ = _bytes_ptr(nonce)
+    ab, a_ptr = _bytes_ptr(aad)
+    n_ctr, n_mac = C.c_size_t(0), C.c_size_t(0)
+    check(lib().tae_aesx_ccm_format(_p(nb), len(nb), tag_len, a_ptr, len(ab), payload_len, C.byref(n_ctr),
+                                    C.byref(n_mac), None, None, None))
+    ctr = np.zeros((n_ctr.value, 16), dtype=np.uint8)
+    mac = np.zeros((n_mac.value, 16), dtype=np.uint8)
+    src = np.zeros((n_mac.value, 16), dtype=np.int64)
+    check(lib().tae_aesx_ccm_format(_p(nb), len(nb), tag_len, a_ptr, len(ab), payload_len, C.byref(n_ctr),
+                                    C.byref(n_mac), _p(ctr), _p(mac), _p(src)))
+    return ctr, mac, src
+
+
+def ccm_noise_schedule_check(param_set: int, key_bits: int, rounds: int) -> None:
+    """The noise bookkeeping of CCM decryption for a fresh key, without a context or device."""
+    check(lib().tae_aesx_ccm_noise_schedule_check(param_set, key_bits, rounds))
+
+
+def ccm_tag_ok(client_key, tag_diff) -> bool:
+    """The client's check: decrypts the tag-difference bits ([tag_len][8] BitCt, a raw array [tag_len][8][L] or
+    FheContext.pack of either) and accepts iff all are zero."""
+    from .tfhe import PackedBits
+    if isinstance(tag_diff, PackedBits):
+        bits = client_key.decrypt_packed(tag_diff)
+    elif isinstance(tag_diff, np.ndarray):
+        bits = client_key.decrypt_bits_raw(tag_diff.reshape(-1, tag_diff.shape[-1]))
+    else:
+        bits = [client_key.decrypt(b).value for b in _flat_bits(tag_diff)]
+    return not any(int(b) for b in bits)
+
+
 def noise_schedule_check(param_set: int, key_bits: int, rounds: int, inverse: bool = False) -> None:
     """The noise bookkeeping for a fresh key and block, without a context or device: the key expansion, then
     `rounds` cipher rounds, or with `inverse` the decryption-key derivation and `rounds` inverse rounds."""
@@ -532,3 +635,59 @@ class GalMulAes:
         arr, keep, _ = _xts_units(units)
         check(lib().tae_aesx_xts_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_dk1), C.c_void_p(d_rk2), arr, len(units),
                                                  rounds, C.c_void_p(d_out), N.TAE_MEM_DEVICE))
+
+    # ---- AES-CCM decryption of a public frame (RFC 3610) ----
+    # data = the encrypted payload followed by the tag_len-byte encrypted tag.  The results are the payload bits
+    # [len - tag_len][8] and the tag-difference bits [tag_len][8]: the client decrypts both and accepts the payload
+    # iff ccm_tag_ok.  `rounds` applies to every cipher call and must be at least 2.
+    @staticmethod
+    def public_keystream_raw(ctx: FheContext, rk: np.ndarray, blocks16, rounds: Optional[int] = None,
+                             key_bits: Optional[int] = None) -> np.ndarray:
+        """rk [W*32][L], n public 16-byte blocks -> E(block) [n][128][L], equal word for word to encrypt_blocks_raw
+        on trivial encryptions of the blocks; round 1 runs once per distinct (position, byte value)."""
+        rk, kb = _raw_key(rk, key_bits)
+        buf = np.ascontiguousarray(np.frombuffer(b"".join(bytes(b) for b in blocks16), dtype=np.uint8))
+        if len(buf) % 16:
+            raise N.TaeError(N.TAE_E_ARG, "public blocks are 16 bytes each")
+        n = len(buf) // 16
+        ko = np.zeros(max(n, 1), dtype=np.int32)
+        out = np.zeros((n, 128, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesm_pub_keystream_raw(ctx._h, kb, _p(rk), 1, _p(ko), _p(buf), n, _nr(kb, rounds), _p(out),
+                                               N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def ccm_transcipher(ctx: FheContext, ek, nonce: bytes, aad: bytes, data: bytes, tag_len: int,
+                        rounds: Optional[int] = None, key_bits: Optional[int] = None):
+        """ek: [W][4][8] BitCt (nested or flat) -> (bits [len - tag_len][8], tag_diff [tag_len][8]) BitCt."""
+        key, kb = _bit_key(ek, key_bits)
+        (nb, _), (ab, a_ptr), (db, d_ptr) = _bytes_ptr(nonce), _bytes_ptr(aad), _bytes_ptr(data)
+        n_plain = max(len(db) - tag_len, 0)
+        outs, tags = (C.c_void_p * max(8 * n_plain, 1))(), (C.c_void_p * max(8 * tag_len, 1))()
+        check(lib().tae_aesx_ccm_transcipher(ctx._h, kb, _handles(key), _p(nb), len(nb), a_ptr, len(ab), d_ptr, len(db),
+                                             tag_len, _nr(kb, rounds), outs, tags))
+        bits = [BitCt(outs[i], ctx) for i in range(8 * n_plain)]
+        diff = [BitCt(tags[i], ctx) for i in range(8 * tag_len)]
+        return ([bits[8 * i:8 * i + 8] for i in range(n_plain)], [diff[8 * i:8 * i + 8] for i in range(tag_len)])
+
+    @staticmethod
+    def ccm_transcipher_raw(ctx: FheContext, rk: np.ndarray, nonce: bytes, aad: bytes, data: bytes, tag_len: int,
+                            rounds: Optional[int] = None, key_bits: Optional[int] = None):
+        """Host arrays: rk [W*32][L] -> (bits [len - tag_len][8][L], tag_diff [tag_len][8][L])."""
+        rk, kb = _raw_key(rk, key_bits)
+        (nb, _), (ab, a_ptr), (db, d_ptr) = _bytes_ptr(nonce), _bytes_ptr(aad), _bytes_ptr(data)
+        out = np.zeros((max(len(db) - tag_len, 0), 8, ctx.lwe_size), dtype=np.uint64)
+        diff = np.zeros((max(tag_len, 0), 8, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_ccm_transcipher_raw(ctx._h, kb, _p(rk), _p(nb), len(nb), a_ptr, len(ab), d_ptr, len(db),
+                                                 tag_len, _nr(kb, rounds), _p(out), _p(diff), N.TAE_MEM_HOST))
+        return out, diff
+
+    @staticmethod
+    def ccm_transcipher_device(ctx: FheContext, key_bits: int, d_rk: int, nonce: bytes, aad: bytes, data: bytes,
+                               tag_len: int, rounds: int, d_out: int, d_tag_diff: int):
+        """Device pointers (ints) for rk, the payload bits [len - tag_len][8][L] and the tag difference
+        [tag_len][8][L]; the frame is host bytes."""
+        (nb, _), (ab, a_ptr), (db, d_ptr) = _bytes_ptr(nonce), _bytes_ptr(aad), _bytes_ptr(data)
+        check(lib().tae_aesx_ccm_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_rk), _p(nb), len(nb), a_ptr, len(ab),
+                                                 d_ptr, len(db), tag_len, rounds, C.c_void_p(d_out),
+                                                 C.c_void_p(d_tag_diff), N.TAE_MEM_DEVICE))
