@@ -533,6 +533,70 @@ int tae_aesx_ccm_transcipher(const tae_context *ctx, int key_bits, const tae_bit
                              const uint8_t *data, size_t len, int tag_len, int rounds, tae_bit **out_plain,
                              tae_bit **out_tag_diff);
 
+/* ---- AES-GCM decryption of public frames (NIST SP 800-38D) ------------------------------
+ * The reference has no GCM and no counterpart of these functions.  The server holds the expanded key under FHE and
+ * the frame in the clear: a 12-byte IV, associated data, and `data` = the ciphertext followed by the tag_len-byte
+ * received tag.  With H = E(0^128) and J0 = iv || 00000001, payload block i is C_i ^ E(iv || be32(2 + i)) and the
+ * frame is authentic iff the first tag_len bytes of E(J0) ^ GHASH_H(aad, C) ^ tag are zero.  The hashed blocks
+ * X_1 .. X_m (padded AAD, padded ciphertext, the length block) are public, so GHASH = sum_i X_i H^(m+1-i) is a set
+ * of LWE row sums over the key's power table H^1 .. H^n, which tae_aesx_ghash_key makes once per key: an even power
+ * is a square (row sums and a refresh), an odd one a product of two encrypted elements (1024 nibble pairs through
+ * one 8 -> 7 circuit bootstrap, chunk sums, a refresh, the reduction, a refresh).  The server returns the payload
+ * bits and the 8 tag_len tag-difference bits under FHE; the client decrypts both and accepts the payload iff every
+ * difference bit is 0.  There is no verdict bit.  A table bit has noise^2 = 1, a payload bit 8 + 1, a
+ * tag-difference bit the number of refreshed chunks of its row (1 for up to 55 sources, one more per 64 beyond);
+ * it holds no key bit.  Scope: TAE_PARAMS_SQRD_LVL_* (gal-mul driver), key_bits 128 / 192 / 256, decryption,
+ * several frames under one key per call; every other model is TAE_E_PARAM.  `rounds` applies to every cipher call.
+ * TAE_E_PARAM before any device work: an IV that is not 12 bytes (other lengths need GHASH over the IV), a tag_len
+ * outside 4, 8, 12 .. 16, len < tag_len, rounds < 2 in the transcipher calls, n_powers outside 1..64 in tae_aesx_ghash_key*, a frame with
+ * more hashed blocks than n_powers.  TAE_E_NOISE before any device work: a row that needs more than 64 chunks
+ * (roughly m > 55).  Null arrays are TAE_E_ARG.  The frame arrays and their bytes are host pointers under either
+ * `mem`. */
+typedef struct {
+    const uint8_t *iv;
+    size_t iv_len;      /* 12 */
+    const uint8_t *aad; /* may be NULL when aad_len == 0 */
+    size_t aad_len;
+    const uint8_t *data; /* ciphertext || received tag */
+    size_t len;          /* >= tag_len */
+} tae_gcm_frame;
+/* the blocks of a frame (host only, no context): n_pub = 2 + ceil(data_len / 16) public cipher inputs 0^128, J0,
+ * iv || be32(2 + i) (the low 32 bits wrap modulo 2^32), n_hashed = m hashed blocks X_1 .. X_m; each array may be NULL
+ * (a first call for the counts) or holds pub_blocks [n_pub][16] and hashed_blocks [n_hashed][16].  `data` is the
+ * ciphertext alone */
+int tae_aesx_gcm_format(const uint8_t *iv, size_t iv_len, const uint8_t *aad, size_t aad_len, const uint8_t *data,
+                        size_t data_len, int tag_len, size_t *n_pub, size_t *n_hashed, uint8_t *pub_blocks,
+                        uint8_t *hashed_blocks);
+/* the tag rows of a frame against a table of n_powers (host only): row_sources[r] table bits and row_chunks[r]
+ * refreshed chunks for r < 8 tag_len, written before the refusals TAE_E_PARAM (m > n_powers) and TAE_E_NOISE */
+int tae_aesx_gcm_tag_rows(const uint8_t *iv, size_t iv_len, const uint8_t *aad, size_t aad_len, const uint8_t *data,
+                          size_t data_len, int tag_len, size_t n_powers, int32_t *row_sources, int32_t *row_chunks);
+/* noise bookkeeping for a fresh key (no GPU): the key expansion, the power table, then a frame of aad_len + data_len
+ * dense bytes with a 16-byte tag.  TAE_OK, TAE_E_NOISE, TAE_E_INDEP or TAE_E_PARAM */
+int tae_aesx_gcm_noise_schedule_check(int param_set, int key_bits, int rounds, int n_powers, size_t aad_len,
+                                      size_t data_len);
+/* the power table: rk [W*32][L] -> hk [n_powers][128][L], power k at block k - 1, coefficient i at ciphertext i */
+int tae_aesx_ghash_key_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, int n_powers, int rounds,
+                           uint64_t *hk, int mem);
+/* the same on handles: hk[n_powers * 128], every bit at noise^2 = 1 with a fresh id */
+int tae_aesx_ghash_key(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key, int n_powers, int rounds,
+                       tae_bit **hk);
+/* GCM decryption of n_frames frames under one key: out_plain [sum (len - tag_len)][8][L], frames in order (may be
+ * NULL when no frame has a payload); out_tag_diff [n_frames][8 tag_len][L] */
+int tae_aesx_gcm_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint64_t *hk,
+                                 size_t n_powers, const tae_gcm_frame *frames, size_t n_frames, int tag_len, int rounds,
+                                 uint64_t *out_plain, uint64_t *out_tag_diff, int mem);
+/* the same on handles: out_plain[sum (len - tag_len) * 8], out_tag_diff[n_frames * 8 tag_len]; XORing two
+ * tag-difference bits, or one with a payload bit, is legal */
+int tae_aesx_gcm_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
+                             const tae_bit *const *hk, size_t n_powers, const tae_gcm_frame *frames, size_t n_frames,
+                             int tag_len, int rounds, tae_bit **out_plain, tae_bit **out_tag_diff);
+/* stage entries for tests: the squares, and the products a_c b_c, of `count` field elements [count][128][L]
+ * (coefficient i of GCM's bit-reflected field at ciphertext i), every output bit refreshed to noise^2 = 1 */
+int tae_stage_gf128_square(const tae_context *ctx, const uint64_t *in, size_t count, uint64_t *out, int mem);
+int tae_stage_gf128_product(const tae_context *ctx, const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out,
+                            int mem);
+
 /* ---- Aes128Encrypt for the fhe_sbox_pbs driver (src/aes_128/fhe/fhe_sbox_pbs.rs:22-171) ------------
  * ShortintWoppbs1BitSboxPbsAesEncrypt on the 1-bit model (fhe_impls/shortint_woppbs_1bit.rs:47-81:
  * SubBytes = one 8 -> 8 circuit bootstrap per byte, MixColumns = gf_256_mul by BitCt XORs) and

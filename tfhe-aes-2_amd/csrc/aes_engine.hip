@@ -1,13 +1,14 @@
 // The AES application layer of the Engine: the linear layers between the circuit bootstraps as HIP kernels
 // (ShiftRows / MixColumns / AddRoundKey as LWE additions: fhe_sbox_gal_mul_pbs.rs:61-132, data_model.rs:270-281;
 // the arithmetic of a word is in aes_linear.hpp and aes_inv.hpp) and the drivers of every mode: the forward
-// cipher on the three models, counter mode, the inverse cipher, CBC, XTS, CCM, multi-key batches and the two key
+// cipher on the three models, counter mode, the inverse cipher, CBC, XTS, CCM, GCM, multi-key batches and the two key
 // derivations.  The generic TFHE stages they call are in kernels.hip.
 #include <cstring>
 #include <stdexcept>
 
 #include "aes.hpp"
 #include "aes_ccm.hpp"
+#include "aes_gcm.hpp"
 #include "aes_linear.hpp"
 #include "aes_xts.hpp"
 #include "engine_detail.hpp"
@@ -106,6 +107,29 @@ __global__ void aes_ccm_tag_kernel(const uint64_t *__restrict__ x, const uint64_
     const size_t total = n * 8 * (size_t)M * L;
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
         ccm_tag_word(x, s0, rk, tags, M, out_of, out, t, L, key_of, key_stride, nr);
+}
+
+// ---- GCM (aes_gcm.hpp): the row sums of a CSR plan, out [n_rows][L] from sources [n_src][L].  Consecutive lanes take
+// consecutive coefficients of one output ciphertext.  Serves the squares, a product's chunk sums and reduction, the
+// frames' chunks and the tag differences ----
+__global__ void gcm_rowsum_kernel(const uint64_t *__restrict__ sources, const int32_t *__restrict__ row_start,
+                                  const int32_t *__restrict__ src, const uint8_t *__restrict__ pub_bit,
+                                  uint64_t *__restrict__ out, size_t n_rows, int L) {
+    const size_t total = n_rows * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+        out[t] = gcm_rowsum_word(sources, row_start, src, pub_bit, t, L);
+}
+
+// The 1024 groups of `count` products from their keyswitched operand bits: small [count][256][S] (a's 128 bits, then
+// b's) -> pairs [count][1024][8][S], input `bit` of group g being operand bit gcm_pair_source(g, bit)
+__global__ void gcm_pairs_kernel(const uint64_t *__restrict__ small, uint64_t *__restrict__ pairs, size_t count, int S) {
+    const size_t total = count * kGcmGroups * 8 * (size_t)S;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t coef = t % S, ct = t / S;
+        const int bit = (int)(ct & 7), g = (int)((ct >> 3) & (kGcmGroups - 1));
+        const size_t c = ct >> 13;
+        pairs[t] = small[(c * 256 + (size_t)gcm_pair_source(g, bit)) * S + coef];
+    }
 }
 
 // ---- key expansion (FIPS-197 5.2, figure 11): one word before its identity bootstrap ----
@@ -582,6 +606,243 @@ void Engine::aes_ccm_transcipher(const uint64_t *d_table, const std::vector<CcmS
             d_x, d_s0, d_table, d_bytes + total, M, d_order, d_out_tagdiff, n, L, d_slot, key_stride, nr);
         HIPC(hipGetLastError());
     });
+    collect_times();
+}
+
+// ---------------------------------------------------------------------------------------------
+// AES-GCM decryption of public frames (aes_gcm.hpp)
+// ---------------------------------------------------------------------------------------------
+void Engine::require_gcm() const {
+    if (p_.model != 1 || !d_lut_gcm_ || !d_lut_id1_) throw std::runtime_error("GCM runs on the 1-bit model parameters");
+}
+
+// One launch.  The plan's arrays are uploaded asynchronously into buffers the stream's earlier launches may still
+// read, which the stream order allows; the host copy lives until the next call clears gcm_plans_.
+void Engine::gcm_rowsum_pass(const uint64_t *d_sources, size_t n_src, GcmRowPlan plan, uint64_t *d_out) {
+    if (!gcm_plan_ok(plan, n_src)) throw std::runtime_error("GCM row-sum plan: index out of range");
+    if (!plan.n_rows()) return;
+    gcm_plans_.push_back(std::move(plan));
+    const GcmRowPlan &p = gcm_plans_.back();
+    const int32_t *rs = upload(d_gcm_rs_, cap_gcm_rs_, p.row_start.data(), p.row_start.size());
+    const int32_t *ix = p.src.empty() ? nullptr : upload(d_gcm_ix_, cap_gcm_ix_, p.src.data(), p.src.size());
+    const uint8_t *pb = p.pub_bit.empty() ? nullptr : upload(d_gcm_pb_, cap_gcm_pb_, p.pub_bit.data(), p.pub_bit.size());
+    const int L = (int)p_.big_len();
+    const size_t n_rows = p.n_rows();
+    timed(ST_LINEAR, [&] {
+        gcm_rowsum_kernel<<<grid_for(n_rows * (size_t)L), kThreads, 0, stream_>>>(d_sources, rs, ix, pb, d_out, n_rows, L);
+        HIPC(hipGetLastError());
+    });
+}
+
+void Engine::gcm_rowsum(const uint64_t *d_sources, size_t n_src, const GcmRowPlan &plan, uint64_t *d_out) {
+    require_gcm();
+    times_ = StageTimes{};
+    gcm_plans_.clear();
+    gcm_rowsum_pass(d_sources, n_src, plan, d_out);
+    collect_times();
+}
+
+// Squares of blocks `blocks` of the source array [n_src / 128][128][L], square s written to outs[s]: one row-sum
+// launch and one identity bootstrap for all of them
+void Engine::gcm_square_pass(const uint64_t *d_src, size_t n_src, const std::vector<size_t> &blocks,
+                             const std::vector<uint64_t *> &outs) {
+    const size_t n = blocks.size(), block_len = 128 * p_.big_len();
+    if (!n) return;
+    GcmRowPlan plan;
+    for (size_t s = 0; s < n; s++) {
+        const GcmRowPlan one = gcm_square_plan(blocks[s]);
+        for (size_t r = 0; r < 128; r++) {
+            plan.src.insert(plan.src.end(), one.src.begin() + one.row_start[r], one.src.begin() + one.row_start[r + 1]);
+            plan.end_row();
+        }
+    }
+    grow(d_gcm_a_, cap_gcm_a_, n * block_len);
+    grow(d_gcm_b_, cap_gcm_b_, n * block_len);
+    gcm_rowsum_pass(d_src, n_src, std::move(plan), d_gcm_a_);
+    circuit_bootstrap(d_gcm_a_, n * 128, 1, d_lut_id1_, 1, d_gcm_b_);
+    for (size_t s = 0; s < n; s++)
+        HIPC(hipMemcpyAsync(outs[s], d_gcm_b_ + s * block_len, block_len * 8, hipMemcpyDeviceToDevice, stream_));
+}
+
+// Products a[c] b[c] -> outs[c], each [128][L].  Keyswitching after a gather of big ciphertexts would run 8192
+// keyswitches per product for the same words: the keyswitch is per ciphertext, so the 256 operand bits go through it
+// once and the small ciphertexts are gathered.
+void Engine::gcm_product_pass(const std::vector<const uint64_t *> &a, const std::vector<const uint64_t *> &b,
+                              const std::vector<uint64_t *> &outs) {
+    const size_t n = a.size(), L = p_.big_len(), S = p_.small_len(), block_len = 128 * L;
+    if (!n) return;
+    const GcmProductPlan one = gcm_product_plan();
+    const size_t n_chunks = one.chunks.n_rows();
+    grow(d_gcm_ops_, cap_gcm_ops_, n * 2 * block_len);
+    grow(d_gcm_ks_, cap_gcm_ks_, n * 256 * S);
+    grow(d_gcm_parts_, cap_gcm_parts_, n * kGcmParts * L);
+    grow(d_gcm_a_, cap_gcm_a_, n * n_chunks * L);
+    grow(d_gcm_b_, cap_gcm_b_, n * n_chunks * L);
+    for (size_t c = 0; c < n; c++) {
+        HIPC(hipMemcpyAsync(d_gcm_ops_ + 2 * c * block_len, a[c], block_len * 8, hipMemcpyDeviceToDevice, stream_));
+        HIPC(hipMemcpyAsync(d_gcm_ops_ + (2 * c + 1) * block_len, b[c], block_len * 8, hipMemcpyDeviceToDevice, stream_));
+    }
+    timed(ST_KS, [&] { keyswitch(d_gcm_ops_, d_gcm_ks_, n * 256); });
+    // the groups are written where cbs_vp's own reserve leaves its scratch: reserved first, so the buffer stays
+    reserve(n * kGcmGroups * 8, n * kGcmParts);
+    timed(ST_LINEAR, [&] {
+        gcm_pairs_kernel<<<grid_for(n * kGcmGroups * 8 * S), kThreads, 0, stream_>>>(d_gcm_ks_, d_small_, n, (int)S);
+        HIPC(hipGetLastError());
+    });
+    cbs_vp(d_small_, n * kGcmGroups, 8, d_lut_gcm_, kGcmPartBits, d_gcm_parts_);
+    gcm_rowsum_pass(d_gcm_parts_, n * kGcmParts, gcm_plan_repeat(one.chunks, n, kGcmParts), d_gcm_a_);
+    circuit_bootstrap(d_gcm_a_, n * n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
+    gcm_rowsum_pass(d_gcm_b_, n * n_chunks, gcm_plan_repeat(one.reduce, n, n_chunks), d_gcm_a_);
+    circuit_bootstrap(d_gcm_a_, n * 128, 1, d_lut_id1_, 1, d_gcm_b_);
+    for (size_t c = 0; c < n; c++)
+        HIPC(hipMemcpyAsync(outs[c], d_gcm_b_ + c * block_len, block_len * 8, hipMemcpyDeviceToDevice, stream_));
+}
+
+void Engine::gf128_square(const uint64_t *d_in, size_t count, uint64_t *d_out) {
+    require_gcm();
+    if (!count) return;
+    times_ = StageTimes{};
+    gcm_plans_.clear();
+    const size_t block_len = 128 * p_.big_len();
+    std::vector<size_t> blocks(count);
+    std::vector<uint64_t *> outs(count);
+    for (size_t c = 0; c < count; c++) {
+        blocks[c] = c;
+        outs[c] = d_out + c * block_len;
+    }
+    gcm_square_pass(d_in, count * 128, blocks, outs);
+    collect_times();
+}
+
+void Engine::gf128_product(const uint64_t *d_a, const uint64_t *d_b, size_t count, uint64_t *d_out) {
+    require_gcm();
+    if (!count) return;
+    times_ = StageTimes{};
+    gcm_plans_.clear();
+    const size_t block_len = 128 * p_.big_len();
+    std::vector<const uint64_t *> a(count), b(count);
+    std::vector<uint64_t *> outs(count);
+    for (size_t c = 0; c < count; c++) {
+        a[c] = d_a + c * block_len;
+        b[c] = d_b + c * block_len;
+        outs[c] = d_out + c * block_len;
+    }
+    gcm_product_pass(a, b, outs);
+    collect_times();
+}
+
+void Engine::ghash_key(const uint64_t *d_rk, int n_powers, int rounds, int nr, uint64_t *d_out) {
+    require_gcm();
+    require_rounds(rounds, nr);
+    if (n_powers < 1 || n_powers > kGcmMaxPowers) throw std::runtime_error("GCM: n_powers must be in 1..=64");
+    const size_t block_len = 128 * p_.big_len();
+    gcm_plans_.clear();
+    // H = E_K(0^128), then the identity bootstrap: H^1 at noise^2 = 1
+    PubBlock zero{};
+    zero.len = 16;
+    grow(d_gcm_a_, cap_gcm_a_, block_len);
+    aes_pub_blocks_multi(d_rk, std::vector<PubBlock>{zero}, rounds, d_gcm_a_, nr);  // resets the stage times
+    circuit_bootstrap(d_gcm_a_, 128, 1, d_lut_id1_, 1, d_out);
+    for (const GcmGeneration &gen : gcm_power_schedule(n_powers)) {
+        std::vector<size_t> blocks;
+        std::vector<const uint64_t *> a, b;
+        std::vector<uint64_t *> sq_out, pr_out;
+        for (int k : gen.squares) {
+            blocks.push_back((size_t)(k / 2 - 1));
+            sq_out.push_back(d_out + (size_t)(k - 1) * block_len);
+        }
+        for (int k : gen.products) {
+            a.push_back(d_out + (size_t)(k - 2) * block_len);
+            b.push_back(d_out);
+            pr_out.push_back(d_out + (size_t)(k - 1) * block_len);
+        }
+        gcm_square_pass(d_out, (size_t)n_powers * 128, blocks, sq_out);
+        gcm_product_pass(a, b, pr_out);
+    }
+    collect_times();
+}
+
+void Engine::aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers,
+                                 const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
+                                 uint64_t *d_out_tagdiff) {
+    const size_t n = frames.size();
+    if (!n) return;
+    require_gcm();
+    require_rounds(rounds, nr);
+    // at one round J0 and the counter blocks share their de-duplicated SubBytes outputs at the IV positions
+    if (rounds < 2) throw std::runtime_error("GCM needs rounds >= 2");
+    const int tag_len = frames[0].frame->tag_len;
+    const size_t L = p_.big_len(), block_len = 128 * L;
+    // ---- the plans, before any device work ----
+    size_t total = 0, table_blocks = 0;
+    std::vector<int64_t> off(n);
+    for (size_t s = 0; s < n; s++) {
+        const GcmFrame &f = *frames[s].frame;
+        if (f.tag_len != tag_len || !f.m() || f.n_pub() != 2 + (f.data_len + 15) / 16)
+            throw std::runtime_error("GCM frames of one call have one tag length and a whole layout");
+        off[s] = (int64_t)total;
+        total += f.data_len;
+        table_blocks = std::max(table_blocks, f.m());
+    }
+    GcmCallPlan plan;
+    std::vector<std::vector<int32_t>> rows;
+    for (size_t s = 0; s < n; s++) {
+        gcm_frame_rows(*frames[s].frame, rows);
+        if (gcm_frame_check(*frames[s].frame, n_powers, rows) != GCM_PLAN_OK)
+            throw std::runtime_error("GCM frame: more hashed blocks than the power table or the chunk sum takes");
+        gcm_call_plan_add(plan, rows, table_blocks, s, frames[s].tag);
+    }
+    const size_t n_src = (table_blocks + n) * 128, n_chunks = plan.chunks.n_rows();
+    times_ = StageTimes{};
+    gcm_plans_.clear();
+    gcm_bytes_.assign(std::max<size_t>(total, 1), 0);
+    for (size_t s = 0; s < n; s++)
+        if (frames[s].frame->data_len) std::memcpy(&gcm_bytes_[(size_t)off[s]], frames[s].data, frames[s].frame->data_len);
+    const uint8_t *d_bytes = upload(d_gcm_bytes_, cap_gcm_bytes_, gcm_bytes_.data(), gcm_bytes_.size());
+    grow(d_gcm_src_, cap_gcm_src_, n_src * L);
+    grow(d_gcm_a_, cap_gcm_a_, n_chunks * L);
+    grow(d_gcm_b_, cap_gcm_b_, n_chunks * L);
+    HIPC(hipMemcpyAsync(d_gcm_src_, d_hk, table_blocks * block_len * 8, hipMemcpyDeviceToDevice, stream_));
+    uint64_t *d_j0 = d_gcm_src_ + table_blocks * block_len;
+
+    // ---- the public blocks: the counters into the result, J0 into the kept blocks ----
+    std::vector<PubBlock> blocks;
+    std::vector<int64_t> kout;
+    std::vector<int32_t> klen;
+    for (size_t s = 0; s < n; s++) {
+        const GcmFrame &f = *frames[s].frame;
+        for (size_t i = 1; i < f.n_pub(); i++) {
+            PubBlock b{};
+            std::memcpy(b.bytes, &f.pub[16 * i], 16);
+            const bool j0 = i == 1;
+            b.out_byte = j0 ? 0 : off[s] + (int64_t)(16 * (i - 2));
+            b.len = j0 ? 0 : (int32_t)std::min<size_t>(16, f.data_len - 16 * (i - 2));
+            blocks.push_back(b);
+            kout.push_back(j0 ? (int64_t)(16 * s) : 0);
+            klen.push_back(j0 ? 16 : 0);
+        }
+    }
+    const size_t n_passes = (blocks.size() + ctr_chunk_ - 1) / ctr_chunk_;
+    ctr_mplans_.clear();
+    ccm_kout_.clear();
+    ccm_klen_.clear();
+    ctr_mplans_.reserve(n_passes);
+    ccm_kout_.reserve(n_passes);
+    ccm_klen_.reserve(n_passes);
+    for (size_t b0 = 0; b0 < blocks.size(); b0 += ctr_chunk_) {
+        const size_t cn = std::min(ctr_chunk_, blocks.size() - b0);
+        ctr_mplans_.emplace_back();
+        pub_plan(blocks.data() + b0, cn, ctr_mplans_.back());
+        ccm_kout_.emplace_back(kout.begin() + b0, kout.begin() + b0 + cn);
+        ccm_klen_.emplace_back(klen.begin() + b0, klen.begin() + b0 + cn);
+        aes_ctr_blocks_multi(d_rk, ctr_mplans_.back(), rounds, d_bytes, d_out_plain, nr, &ccm_kout_.back(),
+                             &ccm_klen_.back(), d_j0);
+    }
+
+    // ---- GHASH + E(J0) + the received tag: chunk sums, one refresh, the differences ----
+    gcm_rowsum_pass(d_gcm_src_, n_src, std::move(plan.chunks), d_gcm_a_);
+    circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
+    gcm_rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
     collect_times();
 }
 

@@ -1196,6 +1196,147 @@ int tae_aesx_ccm_transcipher(const tae_context *ctx, int key_bits, const tae_bit
     });
 }
 
+/* ---- AES-GCM decryption of public frames (SP 800-38D; no counterpart in the reference) ---- */
+extern "C++" {
+namespace {
+std::vector<tae::Context::GcmFrameIn> gcm_frames_in(const tae_gcm_frame *frames, size_t n_frames) {
+    require(frames || !n_frames, "null");
+    std::vector<tae::Context::GcmFrameIn> v(n_frames);
+    for (size_t i = 0; i < n_frames; i++)
+        v[i] = {frames[i].iv, frames[i].iv_len, frames[i].aad, frames[i].aad_len, frames[i].data, frames[i].len};
+    return v;
+}
+
+void throw_gcm_format(tae::GcmFormat e) {
+    if (e == tae::GCM_FMT_IV) throw tae::ModelError{TAE_E_PARAM, "only 12-byte GCM IVs are supported"};
+    if (e == tae::GCM_FMT_TAG) throw tae::ModelError{TAE_E_PARAM, "a GCM tag is 4, 8 or 12 .. 16 bytes"};
+}
+}  // namespace
+}  // extern "C++"
+
+int tae_aesx_gcm_format(const uint8_t *iv, size_t iv_len, const uint8_t *aad, size_t aad_len, const uint8_t *data,
+                        size_t data_len, int tag_len, size_t *n_pub, size_t *n_hashed, uint8_t *pub_blocks,
+                        uint8_t *hashed_blocks) {
+    return guarded([&] {
+        require(iv && n_pub && n_hashed && (aad || !aad_len) && (data || !data_len), "null");
+        tae::GcmFrame f;
+        throw_gcm_format(tae::gcm_format(iv, iv_len, aad, aad_len, data, data_len, tag_len, f));
+        *n_pub = f.n_pub();
+        *n_hashed = f.m();
+        if (pub_blocks) std::memcpy(pub_blocks, f.pub.data(), f.pub.size());
+        if (hashed_blocks) std::memcpy(hashed_blocks, f.hashed.data(), f.hashed.size());
+    });
+}
+
+int tae_aesx_gcm_tag_rows(const uint8_t *iv, size_t iv_len, const uint8_t *aad, size_t aad_len, const uint8_t *data,
+                          size_t data_len, int tag_len, size_t n_powers, int32_t *row_sources, int32_t *row_chunks) {
+    return guarded([&] {
+        require(iv && row_sources && row_chunks && (aad || !aad_len) && (data || !data_len), "null");
+        tae::GcmFrame f;
+        throw_gcm_format(tae::gcm_format(iv, iv_len, aad, aad_len, data, data_len, tag_len, f));
+        std::vector<std::vector<int32_t>> rows;
+        tae::gcm_frame_rows(f, rows);
+        for (size_t r = 0; r < rows.size(); r++) {
+            row_sources[r] = (int32_t)rows[r].size();
+            row_chunks[r] = (int32_t)tae::gcm_row_chunks(rows[r].size());
+        }
+        switch (tae::gcm_frame_check(f, n_powers, rows)) {
+            case tae::GCM_PLAN_POWERS:
+                throw tae::ModelError{TAE_E_PARAM, "the frame has more hashed blocks than the power table has powers"};
+            case tae::GCM_PLAN_NOISE: throw tae::ModelError{TAE_E_NOISE, "a tag row needs more than 64 refreshed chunks"};
+            default: break;
+        }
+    });
+}
+
+int tae_aesx_gcm_noise_schedule_check(int param_set, int key_bits, int rounds, int n_powers, size_t aad_len,
+                                      size_t data_len) {
+    return guarded([&] {
+        const tae::Params p = params_of(param_set);
+        const size_t kw = key_cts(key_bits);
+        const int nk = tae::aes_nk(key_bits), nr = tae::aes_nr(key_bits);
+        if (p.model != 1) throw tae::ModelError{TAE_E_PARAM, "GCM runs on the 1-bit WoP-PBS parameter sets only"};
+        std::vector<tae::NoiseLevel> key((size_t)nk * 32);
+        for (auto &x : key) x = tae::NoiseLevel::with_noise_level(1, tae::next_ct_id());
+        const std::vector<tae::NoiseLevel> rk = tae::aes_key_expand_noise_schedule(key, nk, p.max_noise_sq);
+        require(rk.size() == kw, "expanded key size");
+        const tae::GhashKeyNoise hk = tae::aes_ghash_key_noise_schedule(rk, n_powers, rounds, p.max_noise_sq, nr);
+        // a frame of the given sizes with dense blocks: every byte 0xA5
+        const uint8_t iv[12] = {};
+        const std::vector<uint8_t> aad(aad_len, 0xA5), data(data_len, 0xA5);
+        tae::GcmFrame f;
+        throw_gcm_format(tae::gcm_format(iv, 12, aad.data(), aad_len, data.data(), data_len, 16, f));
+        tae::aes_gcm_noise_schedule(rk, hk.table, f, rounds, p.max_noise_sq, nr);
+    });
+}
+
+int tae_aesx_ghash_key_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, int n_powers, int rounds,
+                           uint64_t *hk, int mem) {
+    return guarded([&] {
+        require(rk && hk, "null");
+        key_cts(key_bits);
+        require_xts_server(ctx);
+        ctx->ctx->aes_ghash_key_raw(rk, n_powers, rounds, hk, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesx_ghash_key(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key, int n_powers, int rounds,
+                       tae_bit **hk) {
+    return guarded([&] {
+        require(expanded_key && hk, "null");
+        const size_t kw = key_cts(key_bits);
+        require_xts_server(ctx);
+        emit(ctx->ctx->aes_ghash_key(unwrap(expanded_key, kw), n_powers, rounds, key_bits), hk);
+    });
+}
+
+int tae_aesx_gcm_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint64_t *hk,
+                                 size_t n_powers, const tae_gcm_frame *frames, size_t n_frames, int tag_len, int rounds,
+                                 uint64_t *out_plain, uint64_t *out_tag_diff, int mem) {
+    return guarded([&] {
+        require((rk && hk && out_tag_diff) || !n_frames, "null");
+        key_cts(key_bits);
+        const std::vector<tae::Context::GcmFrameIn> in = gcm_frames_in(frames, n_frames);
+        require_xts_server(ctx);
+        ctx->ctx->aes_gcm_raw(rk, hk, n_powers, in, tag_len, rounds, out_plain, out_tag_diff, mem == TAE_MEM_DEVICE,
+                              key_bits);
+    });
+}
+
+int tae_aesx_gcm_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
+                             const tae_bit *const *hk, size_t n_powers, const tae_gcm_frame *frames, size_t n_frames,
+                             int tag_len, int rounds, tae_bit **out_plain, tae_bit **out_tag_diff) {
+    return guarded([&] {
+        require((expanded_key && hk && out_tag_diff) || !n_frames, "null");
+        const size_t kw = key_cts(key_bits);
+        const std::vector<tae::Context::GcmFrameIn> in = gcm_frames_in(frames, n_frames);
+        require_xts_server(ctx);
+        if (!n_frames) return;
+        const tae::Context::GcmBits res =
+            ctx->ctx->aes_gcm(unwrap(expanded_key, kw), unwrap(hk, n_powers * 128), in, tag_len, rounds, key_bits);
+        require(out_plain || res.plain.empty(), "null");
+        emit(res.plain, out_plain);
+        emit(res.tag_diff, out_tag_diff);
+    });
+}
+
+int tae_stage_gf128_square(const tae_context *ctx, const uint64_t *in, size_t count, uint64_t *out, int mem) {
+    return guarded([&] {
+        require((in && out) || !count, "null");
+        require_xts_server(ctx);
+        ctx->ctx->gf128_square_raw(in, count, out, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_stage_gf128_product(const tae_context *ctx, const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out,
+                            int mem) {
+    return guarded([&] {
+        require((a && b && out) || !count, "null");
+        require_xts_server(ctx);
+        ctx->ctx->gf128_product_raw(a, b, count, out, mem == TAE_MEM_DEVICE);
+    });
+}
+
 int tae_aes_sbox_pbs_encrypt_blocks(const tae_context *ctx, const tae_bit *const *expanded_key,
                                     const tae_bit *const *blocks, size_t n_blocks, int rounds, tae_bit **out) {
     return guarded([&] {

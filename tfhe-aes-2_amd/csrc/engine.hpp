@@ -10,12 +10,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <deque>
 #include <string>
 #include <vector>
 
 #include "client.hpp"
 #include "cplx.hpp"
 #include "aes_ccm.hpp"
+#include "aes_gcm.hpp"
 #include "aes_xts.hpp"
 #include "ctr_plan.hpp"
 #include "kslots.hpp"
@@ -194,6 +196,32 @@ class Engine {
     void aes_ccm_transcipher(const uint64_t *d_table, const std::vector<CcmStreamIn> &streams, int rounds, int nr,
                              uint64_t *d_out_plain, uint64_t *d_out_tagdiff);
 
+    // ---- AES-GCM decryption of public frames on the 1-bit model (aes_gcm.hpp; the reference has no
+    // GCM).  One key per call ----
+    // row sums of a plan (HOST, validated against n_src before the launch): sources [n_src][K+1] -> [n_rows][K+1]
+    void gcm_rowsum(const uint64_t *d_sources, size_t n_src, const GcmRowPlan &plan, uint64_t *d_out);
+    // squares of `count` field elements [count][128][K+1]: row sums, then one identity bootstrap (noise^2 = 1)
+    void gf128_square(const uint64_t *d_in, size_t count, uint64_t *d_out);
+    // products a_c b_c of `count` pairs, a / b / out [count][128][K+1]: the 256 operand bits of a pair are keyswitched
+    // once and gathered as small ciphertexts into the 1024 groups of one 8 -> 7 cbs_vp call over all pairs; chunk
+    // sums, identity bootstrap, reduction, identity bootstrap
+    void gf128_product(const uint64_t *d_a, const uint64_t *d_b, size_t count, uint64_t *d_out);
+    // the power table H^1 .. H^n_powers [n_powers][128][K+1] of the expanded key rk, every bit at noise^2 = 1:
+    // E_K(0) through aes_pub_blocks_multi, one identity bootstrap, then the generations of gcm_power_schedule
+    void ghash_key(const uint64_t *d_rk, int n_powers, int rounds, int nr, uint64_t *d_out);
+    // One frame: `data` its data_len ciphertext bytes, `tag` its tag_len received-tag bytes (HOST, read during the call)
+    struct GcmFrameIn {
+        const GcmFrame *frame;
+        const uint8_t *data, *tag;
+    };
+    // One public-block batch over all frames' J0 and counter blocks: the payload bits E(ctr) + C go to d_out_plain
+    // [sum data_len][8][K+1], frames in order, and E(J0) is kept by the second placement.  Then one row-sum launch over
+    // all frames' chunks, one identity bootstrap of the chunk bits and one row-sum launch for the tag differences
+    // d_out_tagdiff [n_frames][8 tag_len][K+1].  d_hk [n_powers][128][K+1] (ghash_key); `rounds` >= 2
+    void aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers,
+                             const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
+                             uint64_t *d_out_tagdiff);
+
     // ---- multi-key batches on the 1-bit model (the reference has one key).  A key table is
     // [n_keys][4 (nr + 1) * 32][K+1], slot s an expanded (or decryption) key in the layout above.  The bootstraps
     // are per ciphertext, so bits of different keys share their launches; the linear layer reads the round key of
@@ -338,6 +366,24 @@ class Engine {
     std::vector<int32_t> ccm_slot_, ccm_order_;
     std::vector<std::vector<int64_t>> ccm_kout_;
     std::vector<std::vector<int32_t>> ccm_klen_;
+    // GCM: the 8 -> 7 nibble-product table; the source array of a call's chunk sums (power table, then E(J0) of every
+    // frame); two scratch arrays the row sums and the refreshes alternate between; the operand bits and the partial
+    // bits of a product batch; the plan arrays on the device and the host plans their pending uploads read
+    uint64_t *d_lut_gcm_ = nullptr;
+    uint64_t *d_gcm_src_ = nullptr, *d_gcm_a_ = nullptr, *d_gcm_b_ = nullptr, *d_gcm_ops_ = nullptr, *d_gcm_ks_ = nullptr,
+             *d_gcm_parts_ = nullptr;
+    int32_t *d_gcm_rs_ = nullptr, *d_gcm_ix_ = nullptr;
+    uint8_t *d_gcm_pb_ = nullptr, *d_gcm_bytes_ = nullptr;
+    size_t cap_gcm_src_ = 0, cap_gcm_a_ = 0, cap_gcm_b_ = 0, cap_gcm_ops_ = 0, cap_gcm_ks_ = 0, cap_gcm_parts_ = 0,
+           cap_gcm_rs_ = 0, cap_gcm_ix_ = 0, cap_gcm_pb_ = 0, cap_gcm_bytes_ = 0;
+    std::deque<GcmRowPlan> gcm_plans_;
+    std::vector<uint8_t> gcm_bytes_;
+    void require_gcm() const;
+    void gcm_rowsum_pass(const uint64_t *d_sources, size_t n_src, GcmRowPlan plan, uint64_t *d_out);
+    void gcm_square_pass(const uint64_t *d_src, size_t n_src, const std::vector<size_t> &blocks,
+                         const std::vector<uint64_t *> &outs);
+    void gcm_product_pass(const std::vector<const uint64_t *> &a, const std::vector<const uint64_t *> &b,
+                          const std::vector<uint64_t *> &outs);
     // XTS: the refreshed tweaks of the call, the masks of the chunk in flight, the plan arrays on the device and
     // the host plans their pending uploads read
     uint64_t *d_xts_tweaks_ = nullptr, *d_xts_masks_ = nullptr;

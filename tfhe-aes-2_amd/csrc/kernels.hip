@@ -708,6 +708,10 @@ void Engine::init_common() {
         d_lut_inv8_ = upload(8, 8, fi8);
         d_lut_mul32_ = upload(8, 32, fm32);
         d_lut_id1_ = upload(1, 1, fid);
+        // GCM (aes_gcm.hpp): the carry-less product of two nibbles, 8 -> 7
+        std::vector<uint64_t> fg(256);
+        for (unsigned x = 0; x < 256; x++) fg[x] = gcm_nibble_product(x);
+        d_lut_gcm_ = upload(8, 7, fg);
     }
     if (p_.model == 2) {
         // shortint_1bit ByteT (fhe_impls/shortint_1bit.rs:17-50): bootstrap_assign's identity test vector
@@ -1025,6 +1029,9 @@ Engine::~Engine() {
                     (void *)d_ccm_keep_, (void *)d_ccm_bytes_, (void *)d_ccm_src_, (void *)d_ccm_kout_, (void *)d_ccm_slot_,
                     (void *)d_ccm_klen_, (void *)d_ccm_order_,
                     (void *)d_xts_rows_, (void *)d_xts_unit_, (void *)d_xts_set_,
+                    (void *)d_lut_gcm_, (void *)d_gcm_src_, (void *)d_gcm_a_, (void *)d_gcm_b_, (void *)d_gcm_ops_,
+                    (void *)d_gcm_ks_, (void *)d_gcm_parts_, (void *)d_gcm_rs_, (void *)d_gcm_ix_, (void *)d_gcm_pb_,
+                    (void *)d_gcm_bytes_,
                     (void *)d_lut_inv32_, (void *)d_lut_inv8_, (void *)d_lut_mul32_, (void *)d_lut_id1_})
         if (q) hipFree(q);
     for (auto &e : ev_pool_) hipEventDestroy(e);

@@ -1887,6 +1887,245 @@ Context::CcmBits Context::aes_ccm_multi(const BitAt &table, size_t n_keys, const
 }
 
 // ---------------------------------------------------------------------------------------------
+// AES-GCM decryption of public frames (SP 800-38D; aes_gcm.hpp).  The reference has no GCM.
+// ---------------------------------------------------------------------------------------------
+namespace {
+// the sums of a row-sum plan on metadata, every one validated; the largest level met goes to *top
+std::vector<NoiseLevel> rowsum_noise(const std::vector<NoiseLevel> &src, const GcmRowPlan &p, uint64_t max, uint64_t *top) {
+    std::vector<NoiseLevel> out(p.n_rows());
+    for (size_t r = 0; r < p.n_rows(); r++) {
+        for (int32_t q = p.row_start[r]; q < p.row_start[r + 1]; q++) out[r].add_assign(src[(size_t)p.src[q]], max);
+        if (top && out[r].noise_level_squared > *top) *top = out[r].noise_level_squared;
+    }
+    return out;
+}
+
+void require_gcm_rounds(int rounds) {
+    // at one round J0 and the counter blocks share their de-duplicated SubBytes outputs at the IV positions
+    if (rounds < 2) throw ModelError{TAE_E_PARAM, "GCM needs rounds >= 2"};
+}
+
+void require_powers(int n_powers) {
+    if (n_powers < 1 || n_powers > kGcmMaxPowers) throw ModelError{TAE_E_PARAM, "n_powers must be in 1..=64"};
+}
+}  // namespace
+
+GhashKeyNoise aes_ghash_key_noise_schedule(const std::vector<NoiseLevel> &rk, int n_powers, int rounds, uint64_t max,
+                                           int nr) {
+    require_rounds(rounds, nr);
+    require_powers(n_powers);
+    require_key_words(rk.size(), nr, "expanded key");
+    GhashKeyNoise out;
+    out.table.resize((size_t)n_powers * 128);
+    auto put = [&](int k, std::vector<NoiseLevel> v) {
+        for (int i = 0; i < 128; i++) out.table[(size_t)(k - 1) * 128 + i] = std::move(v[i]);
+    };
+    // E_K(0) is validated by the cipher's schedule; the identity bootstrap gives noise^2 = 1 with fresh ids
+    aes_noise_schedule(rk, std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds, max, nr);
+    put(1, fresh_levels(128));
+    const GcmProductPlan pp = gcm_product_plan();
+    for (const GcmGeneration &gen : gcm_power_schedule(n_powers)) {
+        for (int k : gen.squares) {
+            rowsum_noise(out.table, gcm_square_plan((size_t)(k / 2 - 1)), max, &out.max_square);
+            put(k, fresh_levels(128));  // refreshed even at 5: table entries must not share ids with each other
+        }
+        for (int k : gen.products) {
+            (void)k;
+            std::vector<NoiseLevel> parts(kGcmParts);
+            for (auto &x : parts) x = NoiseLevel::with_noise_level(8, next_ct_id());
+            rowsum_noise(parts, pp.chunks, max, &out.max_chunk);
+            rowsum_noise(fresh_levels(pp.chunks.n_rows()), pp.reduce, max, &out.max_reduced);
+            put(k, fresh_levels(128));
+        }
+    }
+    return out;
+}
+
+GcmNoise aes_gcm_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &hk, const GcmFrame &f,
+                                int rounds, uint64_t max, int nr) {
+    require_rounds(rounds, nr);
+    require_gcm_rounds(rounds);
+    require_key_words(rk.size(), nr, "expanded key");
+    if (!f.m() || f.n_pub() < 2 || hk.size() % 128) throw ModelError{TAE_E_ARG, "empty GCM frame or a broken power table"};
+    std::vector<std::vector<int32_t>> rows;
+    gcm_frame_rows(f, rows);
+    switch (gcm_frame_check(f, hk.size() / 128, rows)) {
+        case GCM_PLAN_POWERS: throw ModelError{TAE_E_PARAM, "the frame has more hashed blocks than the power table has powers"};
+        case GCM_PLAN_NOISE: throw ModelError{TAE_E_NOISE, "a tag row needs more than 64 refreshed chunks"};
+        default: break;
+    }
+    const std::vector<NoiseLevel> triv(128, NoiseLevel::trivial());
+    GcmNoise out;
+    out.plain.resize(f.data_len * 8);
+    for (size_t b = 0; b * 16 < f.data_len; b++) {
+        const std::vector<NoiseLevel> ks = aes_noise_schedule(rk, triv, rounds, max, nr);
+        for (size_t i = 0; i < 128 && (b * 16 + i / 8) < f.data_len; i++) out.plain[b * 128 + i] = ks[i];
+    }
+    // the chunk source array of a one-frame call: the table's first m blocks, then E(J0)
+    std::vector<NoiseLevel> src(hk.begin(), hk.begin() + (std::ptrdiff_t)(f.m() * 128));
+    const std::vector<NoiseLevel> j0 = aes_noise_schedule(rk, triv, rounds, max, nr);
+    src.insert(src.end(), j0.begin(), j0.end());
+    GcmCallPlan plan;
+    const std::vector<uint8_t> no_tag((size_t)f.tag_len, 0);
+    gcm_call_plan_add(plan, rows, f.m(), 0, no_tag.data());
+    rowsum_noise(src, plan.chunks, max, &out.max_chunk);
+    out.tag_diff = rowsum_noise(fresh_levels(plan.chunks.n_rows()), plan.diff, max, nullptr);
+    return out;
+}
+
+namespace {
+std::vector<GcmFrame> gcm_frames(const std::vector<Context::GcmFrameIn> &in, int tag_len) {
+    std::vector<GcmFrame> frames(in.size());
+    const size_t T = tag_len > 0 ? (size_t)tag_len : 0;
+    for (size_t s = 0; s < in.size(); s++) {
+        const Context::GcmFrameIn &st = in[s];
+        if (!st.iv || (!st.aad && st.aad_len) || (!st.data && st.len)) throw ModelError{TAE_E_ARG, "null frame array"};
+        switch (gcm_format(st.iv, st.iv_len, st.aad, st.aad_len, st.data, st.len >= T ? st.len - T : 0, tag_len, frames[s])) {
+            case GCM_FMT_IV: throw ModelError{TAE_E_PARAM, "only 12-byte GCM IVs are supported"};
+            case GCM_FMT_TAG: throw ModelError{TAE_E_PARAM, "a GCM tag is 4, 8 or 12 .. 16 bytes"};
+            default: break;
+        }
+        if (st.len < T) throw ModelError{TAE_E_PARAM, "GCM data is shorter than the tag"};
+    }
+    return frames;
+}
+}  // namespace
+
+void Context::aes_ghash_key_raw(const uint64_t *rk, int n_powers, int rounds, uint64_t *out, bool device_mem, int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    aes_ghash_key_noise_schedule(fresh_levels(kw), n_powers, rounds, params().max_noise_sq, nr);
+    run_inverse(rk, nullptr, 0, nullptr, 0, out, (size_t)n_powers * 128 * bit_len(), device_mem,
+                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) {
+                    engine_->ghash_key(k, n_powers, rounds, nr, o);
+                },
+                kw);
+}
+
+std::vector<BitCt> Context::aes_ghash_key(const std::vector<const BitCt *> &expanded_key, int n_powers, int rounds,
+                                          int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
+    require_key_words(expanded_key.size(), nr, "expanded key");
+    const std::vector<uint64_t> rk = gather_bits(expanded_key, L);
+    std::vector<NoiseLevel> krk(kw);
+    for (size_t i = 0; i < kw; i++) krk[i] = expanded_key[i]->noise;
+    GhashKeyNoise kn = aes_ghash_key_noise_schedule(krk, n_powers, rounds, params().max_noise_sq, nr);
+    std::vector<uint64_t> hk(kn.table.size() * L);
+    run_inverse(rk.data(), nullptr, 0, nullptr, 0, hk.data(), hk.size(), false,
+                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) {
+                    engine_->ghash_key(k, n_powers, rounds, nr, o);
+                },
+                kw);
+    std::vector<BitCt> res(kn.table.size());
+    for (size_t i = 0; i < res.size(); i++) {
+        res[i].ct.assign(hk.begin() + i * L, hk.begin() + (i + 1) * L);
+        res[i].noise = std::move(kn.table[i]);
+        res[i].max_noise_sq = params().max_noise_sq;
+    }
+    return res;
+}
+
+void Context::run_gcm(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrame> &frames,
+                      const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int nr, size_t key_cts,
+                      uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem) {
+    const size_t n = frames.size(), S = bit_len();
+    size_t total = 0;
+    for (const GcmFrame &f : frames) total += f.data_len;
+    const size_t plain_len = total * 8 * S, tag_w = n * 8 * (size_t)tag_len * S, hk_len = n_powers * 128 * S;
+    std::vector<Engine::GcmFrameIn> ein(n);
+    for (size_t s = 0; s < n; s++) ein[s] = {&frames[s], in[s].data, in[s].data + frames[s].data_len};
+    std::lock_guard<std::mutex> g(mu_);
+    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
+    if (device_mem) {
+        engine_->order_after_caller();
+        engine_->aes_gcm_transcipher(rk, hk, n_powers, ein, rounds, nr, out_plain, out_tag_diff);
+        engine_->synchronize();
+        return;
+    }
+    DevBuf d_rk(key_cts * S * 8), d_hk(hk_len * 8), d_plain(plain_len * 8), d_tag(tag_w * 8);
+    hip_check(hipMemcpyAsync(d_rk.p, rk, key_cts * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
+    hip_check(hipMemcpyAsync(d_hk.p, hk, hk_len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload power table");
+    engine_->aes_gcm_transcipher(d_rk.as<uint64_t>(), d_hk.as<uint64_t>(), n_powers, ein, rounds, nr, d_plain.as<uint64_t>(),
+                                 d_tag.as<uint64_t>());
+    if (plain_len)
+        hip_check(hipMemcpyAsync(out_plain, d_plain.p, plain_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    hip_check(hipMemcpyAsync(out_tag_diff, d_tag.p, tag_w * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+    engine_->synchronize();
+}
+
+void Context::aes_gcm_raw(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrameIn> &in,
+                          int tag_len, int rounds, uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem,
+                          int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    require_gcm_rounds(rounds);
+    if (!n_powers) throw ModelError{TAE_E_PARAM, "the power table is empty"};
+    const std::vector<GcmFrame> frames = gcm_frames(in, tag_len);
+    if (frames.empty()) return;
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    const std::vector<NoiseLevel> krk = fresh_levels(kw), khk = fresh_levels(n_powers * 128);
+    for (const GcmFrame &f : frames) aes_gcm_noise_schedule(krk, khk, f, rounds, params().max_noise_sq, nr);
+    run_gcm(rk, hk, n_powers, frames, in, tag_len, rounds, nr, kw, out_plain, out_tag_diff, device_mem);
+}
+
+Context::GcmBits Context::aes_gcm(const std::vector<const BitCt *> &expanded_key, const std::vector<const BitCt *> &hk,
+                                  const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    require_gcm_rounds(rounds);
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
+    require_key_words(expanded_key.size(), nr, "expanded key");
+    if (hk.empty() || hk.size() % 128) throw ModelError{TAE_E_ARG, "the power table is n_powers * 128 bits"};
+    const size_t n_powers = hk.size() / 128;
+    if (!n_powers) throw ModelError{TAE_E_PARAM, "the power table is empty"};
+    const std::vector<GcmFrame> frames = gcm_frames(in, tag_len);
+    if (frames.empty()) return {};
+    std::vector<NoiseLevel> krk(kw), khk(hk.size()), pn, tn;
+    for (size_t i = 0; i < kw; i++) krk[i] = expanded_key[i]->noise;
+    for (size_t i = 0; i < hk.size(); i++) khk[i] = hk[i]->noise;
+    for (const GcmFrame &f : frames) {
+        GcmNoise gn = aes_gcm_noise_schedule(krk, khk, f, rounds, params().max_noise_sq, nr);
+        for (NoiseLevel &x : gn.plain) pn.push_back(std::move(x));
+        for (NoiseLevel &x : gn.tag_diff) tn.push_back(std::move(x));
+    }
+    const std::vector<uint64_t> rk = gather_bits(expanded_key, L), table = gather_bits(hk, L);
+    std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
+    run_gcm(rk.data(), table.data(), n_powers, frames, in, tag_len, rounds, nr, kw, plain.data(), tag.data(), false);
+    GcmBits res;
+    auto wrap_bits = [&](const std::vector<uint64_t> &w, std::vector<NoiseLevel> &noise, std::vector<BitCt> &bits) {
+        bits.resize(noise.size());
+        for (size_t i = 0; i < bits.size(); i++) {
+            bits[i].ct.assign(w.begin() + i * L, w.begin() + (i + 1) * L);
+            bits[i].noise = std::move(noise[i]);  // xor with a public bit adds no noise
+            bits[i].max_noise_sq = params().max_noise_sq;
+        }
+    };
+    wrap_bits(plain, pn, res.plain);
+    wrap_bits(tag, tn, res.tag_diff);
+    return res;
+}
+
+void Context::gf128_square_raw(const uint64_t *in, size_t count, uint64_t *out, bool device_mem) {
+    if (params().model != 1) throw ModelError{TAE_E_PARAM, "GCM runs on the 1-bit WoP-PBS parameter sets only"};
+    if (!count) return;
+    const size_t len = count * 128 * bit_len();
+    run_inverse(nullptr, in, len, nullptr, 0, out, len, device_mem,
+                [&](const uint64_t *, const uint64_t *i, const uint8_t *, uint64_t *o) { engine_->gf128_square(i, count, o); },
+                0);
+}
+
+void Context::gf128_product_raw(const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out, bool device_mem) {
+    if (params().model != 1) throw ModelError{TAE_E_PARAM, "GCM runs on the 1-bit WoP-PBS parameter sets only"};
+    if (!count) return;
+    const size_t len = count * 128 * bit_len();
+    // the second operand travels as run_inverse's key
+    run_inverse(b, a, len, nullptr, 0, out, len, device_mem,
+                [&](const uint64_t *kb, const uint64_t *ia, const uint8_t *, uint64_t *o) {
+                    engine_->gf128_product(ia, kb, count, o);
+                },
+                count * 128);
+}
+
+// ---------------------------------------------------------------------------------------------
 // shortint_1bit model (src/tfhe/shortint_1bit.rs)
 // ---------------------------------------------------------------------------------------------
 void Context::require_s1() const {

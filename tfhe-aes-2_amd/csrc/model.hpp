@@ -225,6 +225,36 @@ class Context {  // FheContext
     CcmBits aes_ccm_multi(const BitAt &table, size_t n_keys, const std::vector<CcmStreamIn> &streams, int tag_len,
                           int rounds, int key_bits);
 
+    // ---- AES-GCM decryption of public frames under one key (SP 800-38D; aes_gcm.hpp; the reference
+    // has no GCM).  1-bit WoP-PBS sets, gal-mul driver, 96-bit IVs, decryption (TAE_E_PARAM elsewhere).  Refusals
+    // before any device work: an IV that is not 12 bytes, a tag_len outside 4, 8, 12 .. 16, rounds < 2, more hashed
+    // blocks than n_powers (all TAE_E_PARAM); a row beyond the two-level chunk sum (TAE_E_NOISE). ----
+    struct GcmFrameIn {
+        const uint8_t *iv;
+        size_t iv_len;
+        const uint8_t *aad;
+        size_t aad_len;
+        const uint8_t *data;  // the ciphertext and the received tag: len >= tag_len bytes
+        size_t len;
+    };
+    struct GcmBits {
+        std::vector<BitCt> plain, tag_diff;  // [sum (len - tag_len) * 8], [n_frames * 8 tag_len]
+    };
+    // the power table H^1 .. H^n_powers [n_powers][128][bit_len] of the expanded key rk [W*32], n_powers in 1..=64
+    void aes_ghash_key_raw(const uint64_t *rk, int n_powers, int rounds, uint64_t *out, bool device_mem, int key_bits);
+    // BitCt variant: every table bit at noise^2 = 1 with a fresh id
+    std::vector<BitCt> aes_ghash_key(const std::vector<const BitCt *> &expanded_key, int n_powers, int rounds, int key_bits);
+    // out_plain [sum (len - tag_len)][8][bit_len], frames in order; out_tag_diff [n_frames][8 tag_len][bit_len] = the
+    // recomputed tag xor the received one, all zero iff the frame is authentic
+    void aes_gcm_raw(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrameIn> &frames,
+                     int tag_len, int rounds, uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem, int key_bits);
+    // BitCt variant: the bits carry the levels and ids of aes_gcm_noise_schedule
+    GcmBits aes_gcm(const std::vector<const BitCt *> &expanded_key, const std::vector<const BitCt *> &hk,
+                    const std::vector<GcmFrameIn> &frames, int tag_len, int rounds, int key_bits);
+    // stage calls, no noise rule: squares / products of `count` field elements [count][128][bit_len]
+    void gf128_square_raw(const uint64_t *in, size_t count, uint64_t *out, bool device_mem);
+    void gf128_product_raw(const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out, bool device_mem);
+
     // ---- 8-bit model (src/tfhe/shortint_woppbs_8bit.rs, fhe_impls/shortint_woppbs_8bit.rs) ----
     size_t bit_len() const { return params().bit_len(); }
     // FheContext::bootstrap_from_bits over G bytes: bits [G][8][n+1] -> int ciphertexts [G][K+1]
@@ -287,6 +317,10 @@ class Context {  // FheContext
     void run_ccm(const uint64_t *table, std::vector<int32_t> slots, const std::vector<CcmFrame> &frames,
                  const std::vector<CcmStreamIn> &streams, int tag_len, int rounds, int nr, size_t key_cts,
                  uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem);
+    // the frames of a GCM call through the engine
+    void run_gcm(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrame> &frames,
+                 const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int nr, size_t key_cts, uint64_t *out_plain,
+                 uint64_t *out_tag_diff, bool device_mem);
     void run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
                      const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem, int nr);
     void run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint64_t *d_in, size_t n_blocks, int rounds,
@@ -342,6 +376,27 @@ struct CcmNoise {
 };
 CcmNoise aes_ccm_noise_schedule(const std::vector<NoiseLevel> &rk, const CcmFrame &frame, int rounds,
                                 uint64_t max_noise_sq, int nr = 10);
+
+// GCM (aes_gcm.hpp) on metadata.  The power table of rk [4 (nr + 1) * 32]: E_K(0) (8 + 1, validated) and its refresh;
+// a square is the row sum of its operand's bits (at most 5) and a refresh; a product is 7168 partial bits at 8 with
+// fresh ids, chunk sums of at most 7 (56), a refresh, the reduction (at most 34) and a refresh.  Every sum is
+// validated; every table bit comes out at noise^2 = 1 with a fresh id.  The largest level of each kind is recorded.
+struct GhashKeyNoise {
+    std::vector<NoiseLevel> table;  // [n_powers * 128]
+    uint64_t max_chunk = 0, max_reduced = 0, max_square = 0;
+};
+GhashKeyNoise aes_ghash_key_noise_schedule(const std::vector<NoiseLevel> &rk, int n_powers, int rounds,
+                                           uint64_t max_noise_sq, int nr = 10);
+// ONE frame under rk and the table hk [n_powers * 128]: a payload bit is 8 + the last round key's bit; a chunk is the
+// E(J0) bit (8 + 1) plus at most 55 table bits, or at most 64 table bits; a tag-difference bit is the sum of its
+// row's refreshed chunks: its level is their number, its ids are fresh, it holds no key bit.  m > n_powers and
+// rounds < 2 are TAE_E_PARAM, a row of more than 64 chunks TAE_E_NOISE.
+struct GcmNoise {
+    std::vector<NoiseLevel> plain, tag_diff;  // [data_len * 8], [8 tag_len]
+    uint64_t max_chunk = 0;
+};
+GcmNoise aes_gcm_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &hk, const GcmFrame &frame,
+                                int rounds, uint64_t max_noise_sq, int nr = 10);
 
 // Counter mode on the 1-bit model: output noise [n_blocks][128] of the gal-mul schedule for trivial counter
 // blocks.  rounds >= 2: aes_noise_schedule per block.  rounds == 1: the final SubBytes runs on the plan's

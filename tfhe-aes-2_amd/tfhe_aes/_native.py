@@ -54,6 +54,9 @@ EXPORTED = [
     "tae_aesx_ccm_format", "tae_aesx_ccm_noise_schedule_check", "tae_aesm_pub_keystream_raw",
     "tae_aesm_ccm_transcipher_raw", "tae_aesm_ccm_transcipher", "tae_aesx_ccm_transcipher_raw",
     "tae_aesx_ccm_transcipher",
+    "tae_aesx_gcm_format", "tae_aesx_gcm_tag_rows", "tae_aesx_gcm_noise_schedule_check", "tae_aesx_ghash_key_raw",
+    "tae_aesx_ghash_key", "tae_aesx_gcm_transcipher_raw", "tae_aesx_gcm_transcipher", "tae_stage_gf128_square",
+    "tae_stage_gf128_product",
     "tae_last_pfks_kernel",
     "tae_packed_len", "tae_encrypt_packed_raw", "tae_decrypt_packed_raw", "tae_packed_narrow", "tae_packed_widen",
     "tae_unpack_bits_raw", "tae_pack_bits_raw", "tae_unpack_bits", "tae_pack_bits", "tae_last_pack_time",
@@ -93,6 +96,12 @@ class TaeCcmStream(C.Structure):
     """tae_ccm_stream: one CCM frame of a multi-key call."""
     _fields_ = [("key", C.c_int32), ("nonce", C.c_void_p), ("nonce_len", C.c_size_t), ("aad", C.c_void_p),
                 ("aad_len", C.c_size_t), ("data", C.c_void_p), ("len", C.c_size_t)]
+
+
+class TaeGcmFrame(C.Structure):
+    """tae_gcm_frame: one GCM frame of a call."""
+    _fields_ = [("iv", C.c_void_p), ("iv_len", C.c_size_t), ("aad", C.c_void_p), ("aad_len", C.c_size_t),
+                ("data", C.c_void_p), ("len", C.c_size_t)]
 
 
 class TaeError(RuntimeError):
@@ -210,6 +219,15 @@ def lib() -> C.CDLL:
         "tae_aesx_ccm_transcipher_raw": ([vp, C.c_int, vp, vp, sz, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp, C.c_int],
                                          C.c_int),
         "tae_aesx_ccm_transcipher": ([vp, C.c_int, vp, vp, sz, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp], C.c_int),
+        "tae_aesx_gcm_format": ([vp, sz, vp, sz, vp, sz, C.c_int, C.POINTER(sz), C.POINTER(sz), vp, vp], C.c_int),
+        "tae_aesx_gcm_tag_rows": ([vp, sz, vp, sz, vp, sz, C.c_int, sz, vp, vp], C.c_int),
+        "tae_aesx_gcm_noise_schedule_check": ([C.c_int, C.c_int, C.c_int, C.c_int, sz, sz], C.c_int),
+        "tae_aesx_ghash_key_raw": ([vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesx_ghash_key": ([vp, C.c_int, vp, C.c_int, C.c_int, vp], C.c_int),
+        "tae_aesx_gcm_transcipher_raw": ([vp, C.c_int, vp, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp, C.c_int], C.c_int),
+        "tae_aesx_gcm_transcipher": ([vp, C.c_int, vp, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp], C.c_int),
+        "tae_stage_gf128_square": ([vp, vp, sz, vp, C.c_int], C.c_int),
+        "tae_stage_gf128_product": ([vp, vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_keyswitch": ([vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_pbs_shift_boolean": ([vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_stage_bootstrap": ([vp, vp, sz, vp, vp, C.c_int], C.c_int),

@@ -319,6 +319,130 @@ def ccm_tag_ok(client_key, tag_diff) -> bool:
     return not any(int(b) for b in bits)
 
 
+# ---------------------------------------------------------------- plain GCM, SP 800-38D ----
+GCM_TAG_LENGTHS = (4, 8, 12, 13, 14, 15, 16)
+
+
+def gf128_mul_plain(x: bytes, y: bytes) -> bytes:
+    """SP 800-38D algorithm 1 on 16-byte blocks: the coefficient of x^k is bit k from the MSB of byte 0."""
+    xi, v, z = int.from_bytes(x, "big"), int.from_bytes(y, "big"), 0
+    for i in range(128):
+        if (xi >> (127 - i)) & 1:
+            z ^= v
+        v = (v >> 1) ^ (0xE1 << 120 if v & 1 else 0)
+    return z.to_bytes(16, "big")
+
+
+def _gcm_hashed_blocks(aad: bytes, ciphertext: bytes) -> List[bytes]:
+    buf = (aad + bytes(-len(aad) % 16) + ciphertext + bytes(-len(ciphertext) % 16)
+           + (8 * len(aad)).to_bytes(8, "big") + (8 * len(ciphertext)).to_bytes(8, "big"))
+    return [buf[i:i + 16] for i in range(0, len(buf), 16)]
+
+
+def ghash_plain(h: bytes, aad: bytes, ciphertext: bytes) -> bytes:
+    """GHASH_H over the padded AAD, the padded ciphertext and the length block: Y_i = (Y_{i-1} ^ X_i) H."""
+    y = bytes(16)
+    for x in _gcm_hashed_blocks(bytes(aad), bytes(ciphertext)):
+        y = gf128_mul_plain(bytes(a ^ b for a, b in zip(y, x)), h)
+    return y
+
+
+def _gcm_check_plain(iv: bytes, tag_len: int) -> None:
+    if len(iv) != 12:
+        raise ValueError("only 12-byte GCM IVs are supported")
+    if tag_len not in GCM_TAG_LENGTHS:
+        raise ValueError("a GCM tag is 4, 8 or 12 .. 16 bytes")
+
+
+def _gcm_counter_block(iv: bytes, i: int) -> bytes:
+    """The cipher input of payload block i: the low 32 bits wrap modulo 2^32 and never carry into the IV."""
+    return iv + ((2 + i) & 0xFFFFFFFF).to_bytes(4, "big")
+
+
+def _gcm_keystream_plain(ek, iv: bytes, n: int, rounds) -> bytes:
+    return b"".join(encrypt_block_plain(ek, _gcm_counter_block(iv, i), rounds) for i in range(n))
+
+
+def gcm_encrypt_plain(key: bytes, iv: bytes, aad: bytes, plaintext: bytes, tag_len: int = 16,
+                      rounds: Optional[int] = None) -> bytes:
+    """Plain AES-GCM with a 96-bit IV: the ciphertext followed by the tag_len-byte tag."""
+    iv, aad, plaintext = bytes(iv), bytes(aad), bytes(plaintext)
+    _gcm_check_plain(iv, tag_len)
+    ek = key_schedule_plain(key)
+    ks = _gcm_keystream_plain(ek, iv, (len(plaintext) + 15) // 16, rounds)
+    c = bytes(p ^ k for p, k in zip(plaintext, ks))
+    h = encrypt_block_plain(ek, bytes(16), rounds)
+    s = encrypt_block_plain(ek, iv + b"\x00\x00\x00\x01", rounds)
+    return c + bytes(a ^ b for a, b in zip(ghash_plain(h, aad, c), s))[:tag_len]
+
+
+def gcm_decrypt_plain(key: bytes, iv: bytes, aad: bytes, data: bytes, tag_len: int = 16,
+                      rounds: Optional[int] = None):
+    """data = ciphertext || received tag -> (payload, tag difference): what the server computes under FHE.  The frame
+    is authentic iff the tag_len difference bytes are zero; the payload is returned either way."""
+    iv, aad, data = bytes(iv), bytes(aad), bytes(data)
+    _gcm_check_plain(iv, tag_len)
+    if len(data) < tag_len:
+        raise ValueError("data is shorter than the tag")
+    c, t = data[:len(data) - tag_len], data[len(data) - tag_len:]
+    ek = key_schedule_plain(key)
+    ks = _gcm_keystream_plain(ek, iv, (len(c) + 15) // 16, rounds)
+    h = encrypt_block_plain(ek, bytes(16), rounds)
+    s = encrypt_block_plain(ek, iv + b"\x00\x00\x00\x01", rounds)
+    diff = bytes(a ^ b ^ r for a, b, r in zip(ghash_plain(h, aad, c), s, t))
+    return bytes(p ^ k for p, k in zip(c, ks)), diff
+
+
+def gcm_format(iv: bytes, aad: bytes, data: bytes, tag_len: int):
+    """The library's frame layout (tae_aesx_gcm_format) of the ciphertext `data`: (pub [n_pub][16], hashed [m][16])
+    with 0^128, J0 and the counter blocks in pub and X_1 .. X_m in hashed.  Refusals are TAE_E_PARAM."""
+    (ib, _), (ab, a_ptr), (db, d_ptr) = _bytes_ptr(iv), _bytes_ptr(aad), _bytes_ptr(data)
+    n_pub, m = C.c_size_t(0), C.c_size_t(0)
+    args = (_p(ib), len(ib), a_ptr, len(ab), d_ptr, len(db), tag_len, C.byref(n_pub), C.byref(m))
+    check(lib().tae_aesx_gcm_format(*args, None, None))
+    pub = np.zeros((n_pub.value, 16), dtype=np.uint8)
+    hashed = np.zeros((m.value, 16), dtype=np.uint8)
+    check(lib().tae_aesx_gcm_format(*args, _p(pub), _p(hashed)))
+    return pub, hashed
+
+
+def gcm_tag_rows(iv: bytes, aad: bytes, data: bytes, tag_len: int, n_powers: int):
+    """(sources [8 tag_len], chunks [8 tag_len]) of the frame's tag rows: the table bits a row sums and the refreshed
+    chunks it takes, which is the level of its tag-difference bit.  m > n_powers is TAE_E_PARAM, a row of more than 64
+    chunks TAE_E_NOISE."""
+    (ib, _), (ab, a_ptr), (db, d_ptr) = _bytes_ptr(iv), _bytes_ptr(aad), _bytes_ptr(data)
+    src = np.zeros(max(8 * tag_len, 1), dtype=np.int32)
+    chunks = np.zeros(max(8 * tag_len, 1), dtype=np.int32)
+    check(lib().tae_aesx_gcm_tag_rows(_p(ib), len(ib), a_ptr, len(ab), d_ptr, len(db), tag_len, n_powers, _p(src),
+                                      _p(chunks)))
+    return src[:8 * tag_len], chunks[:8 * tag_len]
+
+
+def gcm_noise_schedule_check(param_set: int, key_bits: int, rounds: int, n_powers: int, aad_len: int = 8,
+                             data_len: int = 17) -> None:
+    """The noise bookkeeping of the power table and of one dense frame for a fresh key, without a context or device."""
+    check(lib().tae_aesx_gcm_noise_schedule_check(param_set, key_bits, rounds, n_powers, aad_len, data_len))
+
+
+def gcm_tag_ok(client_key, tag_diff) -> bool:
+    """The client's check, with the semantics of ccm_tag_ok: accepts iff every tag-difference bit decrypts to zero."""
+    return ccm_tag_ok(client_key, tag_diff)
+
+
+def _gcm_frames(frames, tag_len: int):
+    """[(iv12, aad, data || tag), ..] -> (tae_gcm_frame array, the byte arrays it points into, the payload lengths)."""
+    arr = (N.TaeGcmFrame * max(len(frames), 1))()
+    keep, lens = [], []
+    for i, (iv, aad, data) in enumerate(frames):
+        (ib, i_ptr), (ab, a_ptr), (db, d_ptr) = _bytes_ptr(iv), _bytes_ptr(aad), _bytes_ptr(data)
+        keep += [ib, ab, db]
+        arr[i].iv, arr[i].iv_len = (i_ptr.value if i_ptr else None), len(ib)
+        arr[i].aad, arr[i].aad_len = (a_ptr.value if a_ptr else None), len(ab)
+        arr[i].data, arr[i].len = (d_ptr.value if d_ptr else None), len(db)
+        lens.append(max(len(db) - tag_len, 0))
+    return arr, keep, lens
+
+
 def noise_schedule_check(param_set: int, key_bits: int, rounds: int, inverse: bool = False) -> None:
     """The noise bookkeeping for a fresh key and block, without a context or device: the key expansion, then
     `rounds` cipher rounds, or with `inverse` the decryption-key derivation and `rounds` inverse rounds."""
@@ -691,3 +815,97 @@ class GalMulAes:
         check(lib().tae_aesx_ccm_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_rk), _p(nb), len(nb), a_ptr, len(ab),
                                                  d_ptr, len(db), tag_len, rounds, C.c_void_p(d_out),
                                                  C.c_void_p(d_tag_diff), N.TAE_MEM_DEVICE))
+
+    # ---- AES-GCM decryption of public frames (SP 800-38D) ----
+    # ghash_key makes the power table H^1 .. H^n_powers once per key; gcm_transcipher then takes frames
+    # (iv12, aad, ciphertext || received tag) under that key and returns, per frame and in caller order, the payload
+    # bits [len - tag_len][8] and the tag-difference bits [tag_len][8]: the client accepts a payload iff gcm_tag_ok.
+    # A frame of m hashed blocks (padded AAD, padded ciphertext, one length block) needs n_powers >= m.
+    @staticmethod
+    def ghash_key(ctx: FheContext, ek, n_powers: int, rounds: Optional[int] = None, key_bits: Optional[int] = None):
+        """ek: [W][4][8] BitCt (nested or flat) -> the table as a flat list of n_powers * 128 BitCt."""
+        key, kb = _bit_key(ek, key_bits)
+        outs = (C.c_void_p * max(128 * n_powers, 1))()
+        check(lib().tae_aesx_ghash_key(ctx._h, kb, _handles(key), n_powers, _nr(kb, rounds), outs))
+        return [BitCt(outs[i], ctx) for i in range(128 * n_powers)]
+
+    @staticmethod
+    def ghash_key_raw(ctx: FheContext, rk: np.ndarray, n_powers: int, rounds: Optional[int] = None,
+                      key_bits: Optional[int] = None) -> np.ndarray:
+        """Host arrays: rk [W*32][L] -> hk [n_powers][128][L]."""
+        rk, kb = _raw_key(rk, key_bits)
+        hk = np.zeros((max(n_powers, 1), 128, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_ghash_key_raw(ctx._h, kb, _p(rk), n_powers, _nr(kb, rounds), _p(hk), N.TAE_MEM_HOST))
+        return hk[:max(n_powers, 0)]
+
+    @staticmethod
+    def ghash_key_device(ctx: FheContext, key_bits: int, d_rk: int, n_powers: int, rounds: int, d_hk: int):
+        check(lib().tae_aesx_ghash_key_raw(ctx._h, key_bits, C.c_void_p(d_rk), n_powers, rounds, C.c_void_p(d_hk),
+                                           N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def gcm_transcipher(ctx: FheContext, ek, hk, frames, tag_len: int, rounds: Optional[int] = None,
+                        key_bits: Optional[int] = None):
+        """ek / hk BitCt (nested or flat) -> [(bits [len - tag_len][8], tag_diff [tag_len][8]), ..] BitCt."""
+        key, kb = _bit_key(ek, key_bits)
+        table = _flat_bits(hk)
+        arr, _keep, lens = _gcm_frames(frames, tag_len)
+        n, total = len(frames), sum(lens)
+        outs, tags = (C.c_void_p * max(8 * total, 1))(), (C.c_void_p * max(8 * tag_len * n, 1))()
+        check(lib().tae_aesx_gcm_transcipher(ctx._h, kb, _handles(key), _handles(table), len(table) // 128, arr, n,
+                                             tag_len, _nr(kb, rounds), outs, tags))
+        res, at = [], 0
+        for f in range(n):
+            bits = [BitCt(outs[8 * at + i], ctx) for i in range(8 * lens[f])]
+            diff = [BitCt(tags[8 * tag_len * f + i], ctx) for i in range(8 * tag_len)]
+            res.append(([bits[8 * i:8 * i + 8] for i in range(lens[f])], [diff[8 * i:8 * i + 8] for i in range(tag_len)]))
+            at += lens[f]
+        return res
+
+    @staticmethod
+    def gcm_transcipher_raw(ctx: FheContext, rk: np.ndarray, hk: np.ndarray, frames, tag_len: int,
+                            rounds: Optional[int] = None, key_bits: Optional[int] = None):
+        """Host arrays: rk [W*32][L], hk [n_powers][128][L] -> [(bits [len - tag_len][8][L], tag_diff [tag_len][8][L]), ..]."""
+        rk, kb = _raw_key(rk, key_bits)
+        hk = np.ascontiguousarray(hk, dtype=np.uint64)
+        if hk.ndim != 3 or hk.shape[1] != 128:
+            raise N.TaeError(N.TAE_E_ARG, "a power table is an array [n_powers][128][L]")
+        arr, _keep, lens = _gcm_frames(frames, tag_len)
+        n, total = len(frames), sum(lens)
+        out = np.zeros((total, 8, ctx.lwe_size), dtype=np.uint64)
+        diff = np.zeros((n, max(tag_len, 0), 8, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_gcm_transcipher_raw(ctx._h, kb, _p(rk), _p(hk), hk.shape[0], arr, n, tag_len,
+                                                 _nr(kb, rounds), _p(out), _p(diff), N.TAE_MEM_HOST))
+        res, at = [], 0
+        for f in range(n):
+            res.append((out[at:at + lens[f]], diff[f]))
+            at += lens[f]
+        return res
+
+    @staticmethod
+    def gcm_transcipher_device(ctx: FheContext, key_bits: int, d_rk: int, d_hk: int, n_powers: int, frames, tag_len: int,
+                               rounds: int, d_out: int, d_tag_diff: int):
+        """Device pointers (ints) for rk, hk, the payload bits [sum (len - tag_len)][8][L] and the tag differences
+        [n_frames][tag_len][8][L]; the frames are host bytes."""
+        arr, _keep, _ = _gcm_frames(frames, tag_len)
+        check(lib().tae_aesx_gcm_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_rk), C.c_void_p(d_hk), n_powers, arr,
+                                                 len(frames), tag_len, rounds, C.c_void_p(d_out),
+                                                 C.c_void_p(d_tag_diff), N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def gf128_square_raw(ctx: FheContext, elems: np.ndarray) -> np.ndarray:
+        """Stage call (tae_stage_gf128_square): [count][128][L] -> the refreshed squares."""
+        elems = np.ascontiguousarray(elems, dtype=np.uint64)
+        out = np.zeros_like(elems)
+        check(lib().tae_stage_gf128_square(ctx._h, _p(elems), elems.shape[0], _p(out), N.TAE_MEM_HOST))
+        return out
+
+    @staticmethod
+    def gf128_product_raw(ctx: FheContext, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+        """Stage call (tae_stage_gf128_product): a, b [count][128][L] -> the refreshed products a_c b_c."""
+        a, b = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(b, dtype=np.uint64)
+        if a.shape != b.shape:
+            raise N.TaeError(N.TAE_E_ARG, "the operands have one shape")
+        out = np.zeros_like(a)
+        check(lib().tae_stage_gf128_product(ctx._h, _p(a), _p(b), a.shape[0], _p(out), N.TAE_MEM_HOST))
+        return out
