@@ -1,5 +1,5 @@
 // The GCM host layer (csrc/aes_gcm.hpp) compiled stand-alone, on PLAIN BIT VALUES: a "ciphertext" is L = 3 words
-// whose body word holds the bit at 1 << 63, sums are the u64 additions gcm_rowsum_word does, a refresh is the identity
+// whose body word holds the bit at 1 << 63, sums are the u64 additions rowsum_word does, a refresh is the identity
 // on the bit (the body's top bit) and the 8 -> 7 table is evaluated directly.  Checked against the bitwise product of
 // SP 800-38D algorithm 1: the power schedule H^1 .. H^5 of test case 2's H, products with 0, 1, x^127 and all-ones,
 // the tag difference of test case 4 and of a one-bit-flipped tag.  Built and run by tests/test_aes_gcm.py, also under
@@ -41,13 +41,18 @@ static GcmElem decode(const uint64_t *c) {
     return a;
 }
 
-static Cts rowsum(const Cts &src, const GcmRowPlan &p) {
-    CHECK(gcm_plan_ok(p, src.size() / L));
+static Cts rowsum(const Cts &src, const RowPlan &p) {
+    CHECK(rowplan_ok(p, src.size() / L));
     Cts out(p.n_rows() * L);
-    for (size_t t = 0; t < out.size(); t++)
-        out[t] = gcm_rowsum_word(src.data(), p.row_start.data(), p.src.data(), p.pub_bit.empty() ? nullptr : p.pub_bit.data(),
-                                 t, L);
+    for (size_t t = 0; t < out.size(); t++) out[t] = rowsum_word(src.data(), p, t, L);
     return out;
+}
+
+// the square plan reading block `block` of the source array
+static RowPlan square_of(size_t block) {
+    RowPlan p = gcm_square_plan();
+    p.base_of.assign(128, (int32_t)(block * 128));
+    return p;
 }
 
 // the identity bootstrap: the bit survives, the rest is new
@@ -117,9 +122,6 @@ int main() {
     const GcmElem ops[] = {zero, one, top, ones, H};
     for (const GcmElem &a : ops)
         for (const GcmElem &b : ops) CHECK(eq(product(a, b, P), gcm_mul(a, b)));
-    // `count` copies read their own sources
-    const GcmRowPlan rep = gcm_plan_repeat(P.reduce, 2, P.chunks.n_rows());
-    CHECK(rep.n_rows() == 256 && rep.src[P.reduce.src.size()] == P.reduce.src[0] + 1135);
 
     // ---- the power schedule on plain bits: H^1 .. H^5 ----
     const std::vector<GcmGeneration> gens = gcm_power_schedule(5);
@@ -129,7 +131,7 @@ int main() {
     auto put = [&](int k, const Cts &c) { std::memcpy(&table[(size_t)(k - 1) * 128 * L], c.data(), c.size() * 8); };
     put(1, refresh(encode(H)));
     for (const GcmGeneration &g : gens) {
-        for (int k : g.squares) put(k, refresh(rowsum(table, gcm_square_plan((size_t)(k / 2 - 1)))));
+        for (int k : g.squares) put(k, refresh(rowsum(table, square_of((size_t)(k / 2 - 1)))));
         for (int k : g.products)
             put(k, encode(product(decode(&table[(size_t)(k - 2) * 128 * L]), decode(table.data()), P)));
     }
@@ -191,9 +193,9 @@ int main() {
     CHECK(gcm_format(iv.data(), 16, nullptr, 0, nullptr, 0, 16, e) == GCM_FMT_IV);
     CHECK(gcm_format(iv.data(), 12, nullptr, 0, nullptr, 0, 5, e) == GCM_FMT_TAG);
     // a broken plan is refused before a launch
-    GcmRowPlan bad = P.reduce;
+    RowPlan bad = P.reduce;
     bad.src[3] = 1135;
-    CHECK(!gcm_plan_ok(bad, 1135) && gcm_plan_ok(P.reduce, 1135));
+    CHECK(!rowplan_ok(bad, 1135) && rowplan_ok(P.reduce, 1135));
     if (fails) return 1;
     std::printf("OK\n");
     return 0;

@@ -1,6 +1,6 @@
 // Host check of the XTS mask layer (csrc/aes_xts.hpp), following the data flow of the device kernel with bit values
 // in place of ciphertexts (L = 1: a "ciphertext" is one word holding a bit, and an LWE sum is a sum whose parity is
-// the XOR): xts_mask_word over the row lists against the byte-wise alpha procedure of IEEE 1619 on random 16-byte
+// the XOR): rowsum_word over the RowPlan of xts_plan against the byte-wise alpha procedure of IEEE 1619 on random 16-byte
 // values, the row weights, and the full decrypt data flow (mask, plain inverse cipher, mask) on IEEE 1619 vector 2.
 // Stand-alone: built plain and with -fsanitize=address,undefined by tests/test_aes_xts.py.
 #include <cstdio>
@@ -40,11 +40,10 @@ static void from_bits(const uint64_t *bits, size_t n, uint8_t *bytes) {
 }
 
 // the mask kernel on the host: nb blocks from n_units tweaks
-static std::vector<uint64_t> masks_of(const std::vector<uint64_t> &tweaks, const tae::XtsPlan &plan) {
-    const size_t nb = plan.unit_of.size();
-    std::vector<uint64_t> m(nb * 128);
-    for (size_t t = 0; t < m.size(); t++)
-        m[t] = tae::xts_mask_word(tweaks.data(), plan.rows.data(), plan.width, plan.unit_of.data(), plan.set_of.data(), t, 1);
+static std::vector<uint64_t> masks_of(const std::vector<uint64_t> &tweaks, const tae::RowPlan &plan) {
+    CHECK(tae::rowplan_ok(plan, tweaks.size()));
+    std::vector<uint64_t> m(plan.n_rows());
+    for (size_t t = 0; t < m.size(); t++) m[t] = tae::rowsum_word(tweaks.data(), plan, t, 1);
     return m;
 }
 
@@ -112,7 +111,7 @@ int main() {
                    {244, 8}, {255, 9}, {256, 9}, {511, 11}, {1023, 13}, {4095, 14}, {65535, 81}};
     for (const auto &e : weights) CHECK(tae::xts_row_weight(e.j) == e.w);
 
-    // xts_mask_word against the byte-wise procedure: 3 units of random tweaks, every index under every unit
+    // the row sums of xts_plan against the byte-wise procedure: 3 units of random tweaks, every index under every unit
     static const uint64_t index[] = {0, 1, 7, 8, 121, 122, 127, 128, 255, 300, 4095};
     const size_t n_idx = sizeof(index) / sizeof(index[0]), n_units = 3;
     uint8_t T[n_units][16];
@@ -131,10 +130,16 @@ int main() {
             unit_of.push_back((int32_t)((u + i) % n_units));
             block_index.push_back(index[i]);
         }
-    tae::XtsPlan plan;
-    tae::xts_plan(unit_of.data(), block_index.data(), block_index.size(), plan);
-    CHECK(plan.n_sets() == n_idx && plan.width == 14);  // distinct indices share a set; 4095 is the heaviest
-    CHECK(plan.rows.size() == n_idx * 128 * 14);
+    const tae::RowPlan plan = tae::xts_plan(unit_of.data(), block_index.data(), block_index.size());
+    CHECK(plan.n_lists() == n_idx * 128 && plan.max_width() == 14);  // distinct indices share a set; 4095 is the heaviest
+    CHECK(plan.n_rows() == block_index.size() * 128 && plan.base_of.size() == plan.n_rows());
+    size_t listed = 0;  // every distinct index is listed once, whole: the sum of its 128 row weights
+    for (size_t i = 0; i < n_idx; i++) {
+        std::vector<int16_t> rows[128];
+        tae::xts_rows_of(index[i], rows);
+        for (const auto &r : rows) listed += r.size();
+    }
+    CHECK(plan.src.size() == listed);
     const std::vector<uint64_t> masks = masks_of(tweaks, plan);
     for (size_t b = 0; b < block_index.size(); b++) {
         uint8_t want[16], got[16];
@@ -159,9 +164,8 @@ int main() {
     std::vector<uint64_t> t_bits(128);
     to_bits(t_enc, 16, t_bits.data());
     const uint64_t two[2] = {0, 1};
-    tae::XtsPlan p2;
-    tae::xts_plan(nullptr, two, 2, p2);
-    CHECK(p2.width == 2 && p2.n_sets() == 2 && p2.unit_of[1] == 0);
+    const tae::RowPlan p2 = tae::xts_plan(nullptr, two, 2);
+    CHECK(p2.max_width() == 2 && p2.n_lists() == 2 * 128 && p2.base_of[128] == 0 && p2.list_of[128] == 128);
     const std::vector<uint64_t> m2 = masks_of(t_bits, p2);
     for (int b = 0; b < 2; b++) {
         uint8_t m[16], x[16], y[16];

@@ -177,6 +177,20 @@ def test_single_frame_equals_composition(gpu_context, client, lut_id, rk2, hk2):
     assert np.array_equal(d_diff.cpu().numpy().view(np.uint64), diff)
 
 
+def test_chunked_pass_gives_the_same_words(gpu_context, product_raw, rk2, hk2, monkeypatch):
+    """The frame of test_single_frame_equals_composition with its three public blocks in chunks of 2: J0 and the first
+    counter fall in one chunk, the last counter in the next.  The chunk size is read when the context is created."""
+    aad, msg = bytes(range(8)), bytes((13 * i + 7) & 255 for i in range(20))
+    data = aes_var.gcm_encrypt_plain(R.KEY3, R.IV3, aad, msg, 12, rounds=2)
+    (want_plain, want_diff), = V.gcm_transcipher_raw(gpu_context, rk2, hk2, [(R.IV3, aad, data)], 12, rounds=2)
+    monkeypatch.setenv("TAE_CTR_CHUNK_BLOCKS", "2")
+    ctx2 = tfhe_aes.context_from_raw(tfhe_aes.PARAMS_SQRD_LVL_64, product_raw[1], device=0)
+    monkeypatch.delenv("TAE_CTR_CHUNK_BLOCKS")
+    (plain, diff), = V.gcm_transcipher_raw(ctx2, rk2, hk2, [(R.IV3, aad, data)], 12, rounds=2)
+    assert np.array_equal(plain, want_plain) and np.array_equal(diff, want_diff)
+    del ctx2
+
+
 def test_ragged_batch_equals_single_frames(gpu_context, client, rk2, hk2):
     iv_b = bytes(range(0x20, 0x2C))
     shapes = [(R.IV3, b"", b""), (iv_b, bytes(range(15)), b""), (R.IV3[::-1], b"", bytes((7 * i + 3) & 255 for i in range(17)))]

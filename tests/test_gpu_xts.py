@@ -139,6 +139,46 @@ def test_transcipher_equals_composition(gpu_context, client, keys128, tweaks2):
     assert np.array_equal(got.reshape(3, 128, BIG), want)
 
 
+def test_masks_shared_lists(gpu_context, tweaks2):
+    """The lists of index 5 are read under two bases and twice under one; beside them index 0, whose lists all have
+    width 1."""
+    torch = pytest.importorskip("torch")
+    unit_of, index = [0, 1, 0, 1, 1], [5, 5, 5, 0, 5]
+    got = V.xts_masks_raw(gpu_context, tweaks2, unit_of, index)
+    assert np.array_equal(got, _masks_np(tweaks2, unit_of, index))
+    d_t = torch.from_numpy(tweaks2.view(np.int64)).to("cuda:0")
+    d_m = torch.full((len(index), 128, BIG), -1, dtype=torch.int64, device="cuda:0")
+    V.xts_masks_device(gpu_context, d_t.data_ptr(), 2, unit_of, index, d_m.data_ptr())
+    assert np.array_equal(d_m.cpu().numpy().view(np.uint64), got)
+
+
+@pytest.fixture(scope="module")
+def three_blocks(gpu_context, keys128):
+    """The units of test_transcipher_equals_composition and their words from host arrays."""
+    units = [(UNIT, bytes((29 * i + 5) & 255 for i in range(32))), (7, bytes((13 * i + 1) & 255 for i in range(16)), 127)]
+    return units, V.xts_transcipher_raw(gpu_context, keys128[0], keys128[1], units, rounds=2)
+
+
+def test_chunked_transcipher_gives_the_same_words(product_raw, keys128, three_blocks, monkeypatch):
+    """Three blocks in chunks of 2: two mask plans are alive in one call, and the first unit's tweak is shared across
+    the boundary.  The chunk size is read when the context is created."""
+    monkeypatch.setenv("TAE_CTR_CHUNK_BLOCKS", "2")
+    ctx2 = tfhe_aes.context_from_raw(tfhe_aes.PARAMS_SQRD_LVL_64, product_raw[1], device=0)
+    monkeypatch.delenv("TAE_CTR_CHUNK_BLOCKS")
+    units, want = three_blocks
+    assert np.array_equal(V.xts_transcipher_raw(ctx2, keys128[0], keys128[1], units, rounds=2), want)
+    del ctx2
+
+
+def test_transcipher_device_memory(gpu_context, keys128, three_blocks):
+    torch = pytest.importorskip("torch")
+    units, want = three_blocks
+    d_dk1, d_rk2 = (torch.from_numpy(k.view(np.int64)).to("cuda:0") for k in keys128)
+    d_out = torch.full((48, 8, BIG), -1, dtype=torch.int64, device="cuda:0")
+    V.xts_transcipher_device(gpu_context, 128, d_dk1.data_ptr(), d_rk2.data_ptr(), units, 2, d_out.data_ptr())
+    assert np.array_equal(d_out.cpu().numpy().view(np.uint64), want)
+
+
 def test_ieee_vector_ten_rounds(gpu_context, client):
     """Vector 2 with both key schedules and the decryption key made under FHE; raw arrays, then handles and pack."""
     k1 = client.encrypt_bits_raw(_bits(KEY1), start_index=7_020_000)

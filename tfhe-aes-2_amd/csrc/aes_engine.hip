@@ -12,6 +12,7 @@
 #include "aes_linear.hpp"
 #include "aes_xts.hpp"
 #include "engine_detail.hpp"
+#include "rowsum.hpp"
 
 namespace tae {
 
@@ -79,14 +80,16 @@ __global__ void aes_inv_mix_kernel(const uint64_t *__restrict__ muls, const uint
     }
 }
 
-// ---- XTS (aes_xts.hpp): masks [nb][128][L] = the row sums of the tweaks [n_units][128][L], block blk reading data
-// unit unit_of[blk] through row-list set set_of[blk] of rows [n_sets][128][width] ----
-__global__ void aes_xts_mask_kernel(const uint64_t *__restrict__ tweaks, const int16_t *__restrict__ rows, int width,
-                                    const int32_t *__restrict__ unit_of, const int32_t *__restrict__ set_of,
-                                    uint64_t *__restrict__ masks, size_t nb, int L) {
-    const size_t total = nb * 128 * (size_t)L;
+// ---- row sums (rowsum.hpp): out [n_rows][L] from sources [n_src][L].  Consecutive lanes take consecutive
+// coefficients of one output ciphertext.  Serves XTS's masks and GCM's squares, chunk sums, reductions and tag
+// differences ----
+__global__ void rowsum_kernel(const uint64_t *__restrict__ sources, const int32_t *__restrict__ row_start,
+                              const int32_t *__restrict__ src, const int32_t *__restrict__ list_of,
+                              const int32_t *__restrict__ base_of, const uint8_t *__restrict__ pub_bit,
+                              uint64_t *__restrict__ out, size_t n_rows, int L) {
+    const size_t total = n_rows * (size_t)L;
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
-        masks[t] = xts_mask_word(tweaks, rows, width, unit_of, set_of, t, L);
+        out[t] = rowsum_word(sources, row_start, src, list_of, base_of, pub_bit, t, L);
 }
 
 // ---- CCM (aes_ccm.hpp): the round-0 state [n][128][L] of a chain step from the previous cipher output x, the
@@ -109,18 +112,7 @@ __global__ void aes_ccm_tag_kernel(const uint64_t *__restrict__ x, const uint64_
         ccm_tag_word(x, s0, rk, tags, M, out_of, out, t, L, key_of, key_stride, nr);
 }
 
-// ---- GCM (aes_gcm.hpp): the row sums of a CSR plan, out [n_rows][L] from sources [n_src][L].  Consecutive lanes take
-// consecutive coefficients of one output ciphertext.  Serves the squares, a product's chunk sums and reduction, the
-// frames' chunks and the tag differences ----
-__global__ void gcm_rowsum_kernel(const uint64_t *__restrict__ sources, const int32_t *__restrict__ row_start,
-                                  const int32_t *__restrict__ src, const uint8_t *__restrict__ pub_bit,
-                                  uint64_t *__restrict__ out, size_t n_rows, int L) {
-    const size_t total = n_rows * (size_t)L;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
-        out[t] = gcm_rowsum_word(sources, row_start, src, pub_bit, t, L);
-}
-
-// The 1024 groups of `count` products from their keyswitched operand bits: small [count][256][S] (a's 128 bits, then
+// ---- GCM (aes_gcm.hpp): the 1024 groups of `count` products from their keyswitched operand bits: small [count][256][S] (a's 128 bits, then
 // b's) -> pairs [count][1024][8][S], input `bit` of group g being operand bit gcm_pair_source(g, bit)
 __global__ void gcm_pairs_kernel(const uint64_t *__restrict__ small, uint64_t *__restrict__ pairs, size_t count, int S) {
     const size_t total = count * kGcmGroups * 8 * (size_t)S;
@@ -438,8 +430,8 @@ void Engine::aes_ctr_blocks_multi(const uint64_t *d_table, const CtrPlanMulti &p
     a.blk_len = upload(d_ctr_blen_, cap_ctr_blen_, plan.block_len.data(), nb);
     a.out = d_out;
     if (d_keep) {
-        a.keep_out = upload(d_ccm_kout_, cap_ccm_kout_, keep_out->data(), nb);
-        a.keep_len = upload(d_ccm_klen_, cap_ccm_klen_, keep_len->data(), nb);
+        a.keep_out = upload(d_pub_kout_, cap_pub_kout_, keep_out->data(), nb);
+        a.keep_len = upload(d_pub_klen_, cap_pub_klen_, keep_len->data(), nb);
         a.keep = d_keep;
     }
     aes_forward(a);
@@ -466,21 +458,39 @@ void Engine::aes_ctr_multi(const uint64_t *d_table, const std::vector<CtrBlock> 
 // ---------------------------------------------------------------------------------------------
 // AES-CCM decryption of public frames (aes_ccm.hpp)
 // ---------------------------------------------------------------------------------------------
+void Engine::pub_pass(const uint64_t *d_table, const std::vector<PubBlock> &blocks, int rounds, const uint8_t *d_data,
+                      uint64_t *d_out, int nr, const std::vector<int64_t> *keep_out, const std::vector<int32_t> *keep_len,
+                      uint64_t *d_keep) {
+    // the uploads of a plan are asynchronous: every chunk's plan and lists live until the next pass
+    const size_t n_chunks = (blocks.size() + ctr_chunk_ - 1) / ctr_chunk_;
+    ctr_mplans_.clear();
+    pub_kout_.clear();
+    pub_klen_.clear();
+    ctr_mplans_.reserve(n_chunks);
+    pub_kout_.reserve(n_chunks);
+    pub_klen_.reserve(n_chunks);
+    for (size_t b0 = 0; b0 < blocks.size(); b0 += ctr_chunk_) {
+        const size_t cn = std::min(ctr_chunk_, blocks.size() - b0);
+        ctr_mplans_.emplace_back();
+        pub_plan(blocks.data() + b0, cn, ctr_mplans_.back());
+        if (!d_keep) {
+            aes_ctr_blocks_multi(d_table, ctr_mplans_.back(), rounds, d_data, d_out, nr);
+            continue;
+        }
+        pub_kout_.emplace_back(keep_out->begin() + b0, keep_out->begin() + b0 + cn);
+        pub_klen_.emplace_back(keep_len->begin() + b0, keep_len->begin() + b0 + cn);
+        aes_ctr_blocks_multi(d_table, ctr_mplans_.back(), rounds, d_data, d_out, nr, &pub_kout_.back(), &pub_klen_.back(),
+                             d_keep);
+    }
+}
+
 void Engine::aes_pub_blocks_multi(const uint64_t *d_table, const std::vector<PubBlock> &blocks, int rounds,
                                   uint64_t *d_out, int nr) {
     if (blocks.empty()) return;
     if (p_.model != 1) throw std::runtime_error("multi-key batches need the 1-bit model parameters");
     require_rounds(rounds, nr);
     times_ = StageTimes{};
-    // the uploads of a plan are asynchronous: every chunk's plan lives until the next call
-    ctr_mplans_.clear();
-    ctr_mplans_.reserve((blocks.size() + ctr_chunk_ - 1) / ctr_chunk_);
-    for (size_t b0 = 0; b0 < blocks.size(); b0 += ctr_chunk_) {
-        const size_t cn = std::min(ctr_chunk_, blocks.size() - b0);
-        ctr_mplans_.emplace_back();
-        pub_plan(blocks.data() + b0, cn, ctr_mplans_.back());
-        aes_ctr_blocks_multi(d_table, ctr_mplans_.back(), rounds, nullptr, d_out, nr);
-    }
+    pub_pass(d_table, blocks, rounds, nullptr, d_out, nr);
 }
 
 void Engine::aes_ccm_transcipher(const uint64_t *d_table, const std::vector<CcmStreamIn> &streams, int rounds, int nr,
@@ -549,22 +559,7 @@ void Engine::aes_ccm_transcipher(const uint64_t *d_table, const std::vector<CcmS
         add(streams[s].slot, &f.ctr[0], 0, 0, (int64_t)(16 * rank[s]));
         add(streams[s].slot, &f.mac[0], 0, 0, (int64_t)(16 * (n + rank[s])));
     }
-    const size_t n_chunks = (blocks.size() + ctr_chunk_ - 1) / ctr_chunk_;
-    ctr_mplans_.clear();
-    ccm_kout_.clear();
-    ccm_klen_.clear();
-    ctr_mplans_.reserve(n_chunks);
-    ccm_kout_.reserve(n_chunks);
-    ccm_klen_.reserve(n_chunks);
-    for (size_t b0 = 0; b0 < blocks.size(); b0 += ctr_chunk_) {
-        const size_t cn = std::min(ctr_chunk_, blocks.size() - b0);
-        ctr_mplans_.emplace_back();
-        pub_plan(blocks.data() + b0, cn, ctr_mplans_.back());
-        ccm_kout_.emplace_back(kout.begin() + b0, kout.begin() + b0 + cn);
-        ccm_klen_.emplace_back(klen.begin() + b0, klen.begin() + b0 + cn);
-        aes_ctr_blocks_multi(d_table, ctr_mplans_.back(), rounds, d_bytes, d_out_plain, nr, &ccm_kout_.back(),
-                             &ccm_klen_.back(), d_ccm_keep_);
-    }
+    pub_pass(d_table, blocks, rounds, d_bytes, d_out_plain, nr, &kout, &klen, d_ccm_keep_);
 
     // ---- the chain: step t absorbs MAC block t of the streams that have one ----
     auto mac_blocks = [&](size_t j) { return streams[(size_t)ccm_order_[j]].frame->n_mac(); };
@@ -616,30 +611,26 @@ void Engine::require_gcm() const {
     if (p_.model != 1 || !d_lut_gcm_ || !d_lut_id1_) throw std::runtime_error("GCM runs on the 1-bit model parameters");
 }
 
-// One launch.  The plan's arrays are uploaded asynchronously into buffers the stream's earlier launches may still
-// read, which the stream order allows; the host copy lives until the next call clears gcm_plans_.
-void Engine::gcm_rowsum_pass(const uint64_t *d_sources, size_t n_src, GcmRowPlan plan, uint64_t *d_out) {
-    if (!gcm_plan_ok(plan, n_src)) throw std::runtime_error("GCM row-sum plan: index out of range");
+// Row sums (rowsum.hpp) for GCM and XTS: one launch.  The plan's arrays are uploaded asynchronously into buffers the
+// stream's earlier launches may still read, which the stream order allows; the host copy lives until the next call
+// clears rowsum_plans_.
+void Engine::rowsum_pass(const uint64_t *d_sources, size_t n_src, RowPlan plan, uint64_t *d_out) {
+    if (!rowplan_ok(plan, n_src)) throw std::runtime_error("row-sum plan: index out of range");
     if (!plan.n_rows()) return;
-    gcm_plans_.push_back(std::move(plan));
-    const GcmRowPlan &p = gcm_plans_.back();
-    const int32_t *rs = upload(d_gcm_rs_, cap_gcm_rs_, p.row_start.data(), p.row_start.size());
-    const int32_t *ix = p.src.empty() ? nullptr : upload(d_gcm_ix_, cap_gcm_ix_, p.src.data(), p.src.size());
-    const uint8_t *pb = p.pub_bit.empty() ? nullptr : upload(d_gcm_pb_, cap_gcm_pb_, p.pub_bit.data(), p.pub_bit.size());
+    rowsum_plans_.push_back(std::move(plan));
+    const RowPlan &p = rowsum_plans_.back();
+    auto up = [&](auto *&d_buf, size_t &cap, const auto &v) {  // an empty array is a null argument
+        return v.empty() ? nullptr : upload(d_buf, cap, v.data(), v.size());
+    };
+    const int32_t *rs = up(d_rs_start_, cap_rs_start_, p.row_start), *ix = up(d_rs_src_, cap_rs_src_, p.src);
+    const int32_t *lo = up(d_rs_list_, cap_rs_list_, p.list_of), *bo = up(d_rs_base_, cap_rs_base_, p.base_of);
+    const uint8_t *pb = up(d_rs_pub_, cap_rs_pub_, p.pub_bit);
     const int L = (int)p_.big_len();
     const size_t n_rows = p.n_rows();
     timed(ST_LINEAR, [&] {
-        gcm_rowsum_kernel<<<grid_for(n_rows * (size_t)L), kThreads, 0, stream_>>>(d_sources, rs, ix, pb, d_out, n_rows, L);
+        rowsum_kernel<<<grid_for(n_rows * (size_t)L), kThreads, 0, stream_>>>(d_sources, rs, ix, lo, bo, pb, d_out, n_rows, L);
         HIPC(hipGetLastError());
     });
-}
-
-void Engine::gcm_rowsum(const uint64_t *d_sources, size_t n_src, const GcmRowPlan &plan, uint64_t *d_out) {
-    require_gcm();
-    times_ = StageTimes{};
-    gcm_plans_.clear();
-    gcm_rowsum_pass(d_sources, n_src, plan, d_out);
-    collect_times();
 }
 
 // Squares of blocks `blocks` of the source array [n_src / 128][128][L], square s written to outs[s]: one row-sum
@@ -648,17 +639,15 @@ void Engine::gcm_square_pass(const uint64_t *d_src, size_t n_src, const std::vec
                              const std::vector<uint64_t *> &outs) {
     const size_t n = blocks.size(), block_len = 128 * p_.big_len();
     if (!n) return;
-    GcmRowPlan plan;
-    for (size_t s = 0; s < n; s++) {
-        const GcmRowPlan one = gcm_square_plan(blocks[s]);
-        for (size_t r = 0; r < 128; r++) {
-            plan.src.insert(plan.src.end(), one.src.begin() + one.row_start[r], one.src.begin() + one.row_start[r + 1]);
-            plan.end_row();
+    RowPlan plan = gcm_square_plan();  // the one list set, read at every operand's base
+    for (size_t s = 0; s < n; s++)
+        for (int32_t r = 0; r < 128; r++) {
+            plan.list_of.push_back(r);
+            plan.base_of.push_back((int32_t)(blocks[s] * 128));
         }
-    }
     grow(d_gcm_a_, cap_gcm_a_, n * block_len);
     grow(d_gcm_b_, cap_gcm_b_, n * block_len);
-    gcm_rowsum_pass(d_src, n_src, std::move(plan), d_gcm_a_);
+    rowsum_pass(d_src, n_src, std::move(plan), d_gcm_a_);
     circuit_bootstrap(d_gcm_a_, n * 128, 1, d_lut_id1_, 1, d_gcm_b_);
     for (size_t s = 0; s < n; s++)
         HIPC(hipMemcpyAsync(outs[s], d_gcm_b_ + s * block_len, block_len * 8, hipMemcpyDeviceToDevice, stream_));
@@ -673,6 +662,15 @@ void Engine::gcm_product_pass(const std::vector<const uint64_t *> &a, const std:
     if (!n) return;
     const GcmProductPlan one = gcm_product_plan();
     const size_t n_chunks = one.chunks.n_rows();
+    // a product's plan once, product c reading its sources at c * stride
+    auto per_product = [n](RowPlan p, size_t stride) {
+        const size_t n_lists = p.n_lists();
+        for (size_t r = 0; r < n * n_lists; r++) {
+            p.list_of.push_back((int32_t)(r % n_lists));
+            p.base_of.push_back((int32_t)(r / n_lists * stride));
+        }
+        return p;
+    };
     grow(d_gcm_ops_, cap_gcm_ops_, n * 2 * block_len);
     grow(d_gcm_ks_, cap_gcm_ks_, n * 256 * S);
     grow(d_gcm_parts_, cap_gcm_parts_, n * kGcmParts * L);
@@ -690,9 +688,9 @@ void Engine::gcm_product_pass(const std::vector<const uint64_t *> &a, const std:
         HIPC(hipGetLastError());
     });
     cbs_vp(d_small_, n * kGcmGroups, 8, d_lut_gcm_, kGcmPartBits, d_gcm_parts_);
-    gcm_rowsum_pass(d_gcm_parts_, n * kGcmParts, gcm_plan_repeat(one.chunks, n, kGcmParts), d_gcm_a_);
+    rowsum_pass(d_gcm_parts_, n * kGcmParts, per_product(one.chunks, kGcmParts), d_gcm_a_);
     circuit_bootstrap(d_gcm_a_, n * n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
-    gcm_rowsum_pass(d_gcm_b_, n * n_chunks, gcm_plan_repeat(one.reduce, n, n_chunks), d_gcm_a_);
+    rowsum_pass(d_gcm_b_, n * n_chunks, per_product(one.reduce, n_chunks), d_gcm_a_);
     circuit_bootstrap(d_gcm_a_, n * 128, 1, d_lut_id1_, 1, d_gcm_b_);
     for (size_t c = 0; c < n; c++)
         HIPC(hipMemcpyAsync(outs[c], d_gcm_b_ + c * block_len, block_len * 8, hipMemcpyDeviceToDevice, stream_));
@@ -702,7 +700,7 @@ void Engine::gf128_square(const uint64_t *d_in, size_t count, uint64_t *d_out) {
     require_gcm();
     if (!count) return;
     times_ = StageTimes{};
-    gcm_plans_.clear();
+    rowsum_plans_.clear();
     const size_t block_len = 128 * p_.big_len();
     std::vector<size_t> blocks(count);
     std::vector<uint64_t *> outs(count);
@@ -718,7 +716,7 @@ void Engine::gf128_product(const uint64_t *d_a, const uint64_t *d_b, size_t coun
     require_gcm();
     if (!count) return;
     times_ = StageTimes{};
-    gcm_plans_.clear();
+    rowsum_plans_.clear();
     const size_t block_len = 128 * p_.big_len();
     std::vector<const uint64_t *> a(count), b(count);
     std::vector<uint64_t *> outs(count);
@@ -736,7 +734,7 @@ void Engine::ghash_key(const uint64_t *d_rk, int n_powers, int rounds, int nr, u
     require_rounds(rounds, nr);
     if (n_powers < 1 || n_powers > kGcmMaxPowers) throw std::runtime_error("GCM: n_powers must be in 1..=64");
     const size_t block_len = 128 * p_.big_len();
-    gcm_plans_.clear();
+    rowsum_plans_.clear();
     // H = E_K(0^128), then the identity bootstrap: H^1 at noise^2 = 1
     PubBlock zero{};
     zero.len = 16;
@@ -794,7 +792,7 @@ void Engine::aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, siz
     }
     const size_t n_src = (table_blocks + n) * 128, n_chunks = plan.chunks.n_rows();
     times_ = StageTimes{};
-    gcm_plans_.clear();
+    rowsum_plans_.clear();
     gcm_bytes_.assign(std::max<size_t>(total, 1), 0);
     for (size_t s = 0; s < n; s++)
         if (frames[s].frame->data_len) std::memcpy(&gcm_bytes_[(size_t)off[s]], frames[s].data, frames[s].frame->data_len);
@@ -822,27 +820,12 @@ void Engine::aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, siz
             klen.push_back(j0 ? 16 : 0);
         }
     }
-    const size_t n_passes = (blocks.size() + ctr_chunk_ - 1) / ctr_chunk_;
-    ctr_mplans_.clear();
-    ccm_kout_.clear();
-    ccm_klen_.clear();
-    ctr_mplans_.reserve(n_passes);
-    ccm_kout_.reserve(n_passes);
-    ccm_klen_.reserve(n_passes);
-    for (size_t b0 = 0; b0 < blocks.size(); b0 += ctr_chunk_) {
-        const size_t cn = std::min(ctr_chunk_, blocks.size() - b0);
-        ctr_mplans_.emplace_back();
-        pub_plan(blocks.data() + b0, cn, ctr_mplans_.back());
-        ccm_kout_.emplace_back(kout.begin() + b0, kout.begin() + b0 + cn);
-        ccm_klen_.emplace_back(klen.begin() + b0, klen.begin() + b0 + cn);
-        aes_ctr_blocks_multi(d_rk, ctr_mplans_.back(), rounds, d_bytes, d_out_plain, nr, &ccm_kout_.back(),
-                             &ccm_klen_.back(), d_j0);
-    }
+    pub_pass(d_rk, blocks, rounds, d_bytes, d_out_plain, nr, &kout, &klen, d_j0);
 
     // ---- GHASH + E(J0) + the received tag: chunk sums, one refresh, the differences ----
-    gcm_rowsum_pass(d_gcm_src_, n_src, std::move(plan.chunks), d_gcm_a_);
+    rowsum_pass(d_gcm_src_, n_src, std::move(plan.chunks), d_gcm_a_);
     circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
-    gcm_rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
+    rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
     collect_times();
 }
 
@@ -945,35 +928,18 @@ void Engine::aes_xts_tweaks(const uint64_t *d_rk2, const uint8_t *d_tweaks, size
     xts_tweak_pass(d_rk2, d_tweaks, n, rounds, d_out, nr);
 }
 
-// the plan's arrays are uploaded asynchronously: it lives until the next call
-void Engine::xts_mask_pass(const uint64_t *d_tweak_cts, size_t n_units, const XtsPlan &plan, uint64_t *d_masks) {
-    const size_t nb = plan.unit_of.size();
-    if (plan.set_of.size() != nb || plan.width < 1 || plan.rows.size() % (128 * (size_t)plan.width))
-        throw std::runtime_error("XTS plan does not match the blocks");
-    for (size_t b = 0; b < nb; b++)
-        if (plan.unit_of[b] < 0 || (size_t)plan.unit_of[b] >= n_units || plan.set_of[b] < 0 ||
-            (size_t)plan.set_of[b] >= plan.n_sets())
-            throw std::runtime_error("XTS plan: unit or row-list index out of range");
-    for (int16_t src : plan.rows)
-        if (src < -1 || src > 127) throw std::runtime_error("XTS plan: source ciphertext out of range");
-    const int16_t *rows = upload(d_xts_rows_, cap_xts_rows_, plan.rows.data(), plan.rows.size());
-    const int32_t *unit_of = upload(d_xts_unit_, cap_xts_unit_, plan.unit_of.data(), nb);
-    const int32_t *set_of = upload(d_xts_set_, cap_xts_set_, plan.set_of.data(), nb);
-    const int L = (int)p_.big_len();
-    timed(ST_LINEAR, [&] {
-        aes_xts_mask_kernel<<<grid_for(nb * 128 * (size_t)L), kThreads, 0, stream_>>>(d_tweak_cts, rows, plan.width,
-                                                                                       unit_of, set_of, d_masks, nb, L);
-        HIPC(hipGetLastError());
-    });
-}
-
-void Engine::aes_xts_masks(const uint64_t *d_tweak_cts, size_t n_units, const XtsPlan &plan, uint64_t *d_masks) {
-    if (plan.unit_of.empty()) return;
+void Engine::aes_xts_masks(const uint64_t *d_tweak_cts, size_t n_units, const RowPlan &plan, uint64_t *d_masks) {
+    if (!plan.n_rows()) return;
     if (p_.model != 1) throw std::runtime_error("XTS runs on the 1-bit model parameters");
+    // a mask sums bits of its own unit's tweak: rowsum_pass bounds base + src, which alone would let a row reach
+    // into the next unit
+    for (int32_t s : plan.src)
+        if (s > 127) throw std::runtime_error("XTS plan: source ciphertext out of range");
+    for (int32_t b : plan.base_of)
+        if (b % 128) throw std::runtime_error("XTS plan: unit or row-list index out of range");
     times_ = StageTimes{};
-    xts_plans_.clear();
-    xts_plans_.push_back(plan);
-    xts_mask_pass(d_tweak_cts, n_units, xts_plans_.back(), d_masks);
+    rowsum_plans_.clear();
+    rowsum_pass(d_tweak_cts, n_units * 128, plan, d_masks);
     collect_times();
 }
 
@@ -987,15 +953,12 @@ void Engine::aes_xts_transcipher(const uint64_t *d_dk1, const uint64_t *d_rk2, c
     grow(d_xts_tweaks_, cap_xts_tweaks_, n_tweaks * block_len);
     xts_tweak_pass(d_rk2, d_tweaks, n_tweaks, rounds, d_xts_tweaks_, nr);
     // the tweaks stay resident across the chunks; every chunk's plan lives until the next call
-    xts_plans_.clear();
-    xts_plans_.reserve((nb + ctr_chunk_ - 1) / ctr_chunk_);
+    rowsum_plans_.clear();
     grow(d_xts_masks_, cap_xts_masks_, std::min(ctr_chunk_, nb) * block_len);
     for (size_t b0 = 0; b0 < nb; b0 += ctr_chunk_) {
         const size_t cn = std::min(ctr_chunk_, nb - b0);
         uint64_t *out = d_out + b0 * block_len;
-        xts_plans_.emplace_back();
-        xts_plan(tweak_of + b0, block_index + b0, cn, xts_plans_.back());
-        xts_mask_pass(d_xts_tweaks_, n_tweaks, xts_plans_.back(), d_xts_masks_);
+        rowsum_pass(d_xts_tweaks_, n_tweaks * 128, xts_plan(tweak_of + b0, block_index + b0, cn), d_xts_masks_);
         aes_decrypt_rounds(d_dk1, d_xts_masks_, d_data + b0 * 16, cn, rounds, nullptr, out, nr, nullptr, 0, true);
         timed(ST_LINEAR, [&] { lwe_add(out, d_xts_masks_, cn * block_len); });
     }

@@ -1,6 +1,6 @@
 // AES-GCM (NIST SP 800-38D) decryption of a public frame under FHE: the field, the row-sum plans and the frame
 // layout.  Plain C++ in the style of aes_xts.hpp and aes_ccm.hpp: the plans have no device code and
-// gcm_rowsum_word is host/device, so a stand-alone program runs the whole algorithm on plain bits
+// the row sums are rowsum.hpp's, host/device, so a stand-alone program runs the whole algorithm on plain bits
 // (tests/native/aes_gcm_test.cpp).
 //
 //   H = E_K(0^128)    J0 = iv || 00000001    P_i = C_i ^ E_K(iv || be32(2 + i))
@@ -18,6 +18,8 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+
+#include "rowsum.hpp"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define TAE_GCM_HD __host__ __device__ inline
@@ -75,68 +77,15 @@ inline void gcm_mul_cols(GcmElem X, GcmElem cols[128]) {
     for (int i = 0; i < 128; i++, X = gcm_times_x(X)) cols[i] = X;
 }
 
-// ---- row-sum plans, CSR: row r sums the ciphertexts src[row_start[r] .. row_start[r + 1]) of one source array
-// [n_src][L] and adds its public bit, if the plan has any, as a trivial encryption.  The widths range from 1 to 64,
-// so no table padded to the largest ----
-struct GcmRowPlan {
-    std::vector<int32_t> row_start{0};
-    std::vector<int32_t> src;
-    std::vector<uint8_t> pub_bit;  // empty, or one 0 / 1 per row
-    size_t n_rows() const { return row_start.size() - 1; }
-    void end_row() { row_start.push_back((int32_t)src.size()); }
-    int width(size_t r) const { return row_start[r + 1] - row_start[r]; }
-    int max_width() const {
-        int w = 0;
-        for (size_t r = 0; r < n_rows(); r++) w = width(r) > w ? width(r) : w;
-        return w;
-    }
-};
-
-// what a launch relies on: whole rows, every index inside the n_src sources, one public bit per row or none
-inline bool gcm_plan_ok(const GcmRowPlan &p, size_t n_src) {
-    if (p.row_start.empty() || p.row_start[0] != 0 || (size_t)p.row_start.back() != p.src.size()) return false;
-    for (size_t r = 0; r < p.n_rows(); r++)
-        if (p.row_start[r + 1] < p.row_start[r]) return false;
-    for (int32_t s : p.src)
-        if (s < 0 || (size_t)s >= n_src) return false;
-    if (!p.pub_bit.empty() && p.pub_bit.size() != p.n_rows()) return false;
-    for (uint8_t b : p.pub_bit)
-        if (b > 1) return false;
-    return true;
-}
-
-// `count` copies of a plan, copy c reading its sources at + c * src_stride
-inline GcmRowPlan gcm_plan_repeat(const GcmRowPlan &p, size_t count, size_t src_stride) {
-    GcmRowPlan out;
-    for (size_t c = 0; c < count; c++)
-        for (size_t r = 0; r < p.n_rows(); r++) {
-            for (int32_t q = p.row_start[r]; q < p.row_start[r + 1]; q++)
-                out.src.push_back(p.src[q] + (int32_t)(c * src_stride));
-            out.end_row();
-        }
-    return out;
-}
-
-// Word t of the row sums [n_rows][L]: coefficient t % L of row t / L, plus pub_bit << 63 in the body word.  Every
-// read is a contiguous run of L words over the lanes of a row.
-TAE_GCM_HD uint64_t gcm_rowsum_word(const uint64_t *sources, const int32_t *row_start, const int32_t *src,
-                                    const uint8_t *pub_bit, size_t t, int L) {
-    const size_t coef = t % L, row = t / L;
-    uint64_t acc = 0;
-    for (int32_t q = row_start[row]; q < row_start[row + 1]; q++) acc += sources[(size_t)src[q] * L + coef];
-    if (pub_bit && coef == (size_t)L - 1) acc += (uint64_t)pub_bit[row] << 63;
-    return acc;
-}
-
 // ---- squaring: linear over GF(2).  Row r lists the bits i of the operand with x^(2 i) mod p containing x^r; the
-// operand is block `block` of the source array ----
-inline GcmRowPlan gcm_square_plan(size_t block = 0) {
-    GcmRowPlan p;
+// operand is block 0 of the source array (another block: base_of = 128 block) ----
+inline RowPlan gcm_square_plan() {
+    RowPlan p;
     GcmElem sq[128];
     for (int i = 0; i < 128; i++) sq[i] = gcm_x_pow(2 * i);
     for (int r = 0; r < 128; r++) {
         for (int i = 0; i < 128; i++)
-            if (gcm_coef(sq[i], r)) p.src.push_back((int32_t)(block * 128 + i));
+            if (gcm_coef(sq[i], r)) p.src.push_back((int32_t)i);
         p.end_row();
     }
     return p;
@@ -165,9 +114,9 @@ TAE_GCM_HD int gcm_pair_source(int g, int bit) {
 }
 
 struct GcmProductPlan {
-    GcmRowPlan chunks;           // over the partial bits [1024][7]: greedy chunks of at most 7 per coefficient t
-    std::vector<int> chunk_t;    // the unreduced coefficient (0 .. 254) of every chunk
-    GcmRowPlan reduce;           // over the refreshed chunks: bit r sums the chunks of every t with x^t mod p containing x^r
+    RowPlan chunks;            // over the partial bits [1024][7]: greedy chunks of at most 7 per coefficient t
+    std::vector<int> chunk_t;  // the unreduced coefficient (0 .. 254) of every chunk
+    RowPlan reduce;            // over the refreshed chunks: bit r sums the chunks of every t with x^t mod p containing x^r
 };
 
 inline GcmProductPlan gcm_product_plan() {
@@ -300,7 +249,7 @@ inline GcmPlanStatus gcm_frame_check(const GcmFrame &f, size_t n_powers,
 // The plans of a call.  Source array of `chunks`: the power table's first table_blocks blocks, then E(J0) of every
 // frame, [table_blocks + n_frames][128].  `diff` sums a row's refreshed chunks and adds the received tag bit.
 struct GcmCallPlan {
-    GcmRowPlan chunks, diff;
+    RowPlan chunks, diff;
     std::vector<int32_t> chunks_of_row;  // [n_frames * 8 tag_len]
 };
 

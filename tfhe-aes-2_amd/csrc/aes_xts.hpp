@@ -8,22 +8,17 @@
 // MSB first, so coefficient k is ciphertext xts_ct_of_coef(k) = 8 (k >> 3) + 7 - (k & 7) of a block.
 //
 // Over GF(2) the mask is M_j = A_j T, column i of A_j being x^(i + j) mod p.  On ciphertexts, output bit k of the
-// mask is the LWE sum (u64 addition) of the tweak ciphertexts i with A_j[k][i] = 1: the row list of k.  The row
-// lists of a set of distinct j form a fixed-width table [n_sets][128][width] of source ciphertext indices in the
-// project's bit order, padded with -1 up to the set's largest row weight.  The device kernel
-// (aes_xts_mask_kernel in aes_engine.hip) is a grid-stride loop around xts_mask_word, so a host program runs the
-// same arithmetic (tests/native/aes_xts_test.cpp).
+// mask is the LWE sum (u64 addition) of the tweak ciphertexts i with A_j[k][i] = 1: the row list of k, in the
+// project's bit order.  xts_plan turns the blocks of a call into a RowPlan (rowsum.hpp): the 128 lists of every
+// distinct block index once, and per mask ciphertext its list and the first tweak ciphertext of its data unit, so the
+// shared row-sum kernel computes the masks and a host program the same words (tests/native/aes_xts_test.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <map>
 #include <vector>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define TAE_XTS_HD __host__ __device__ inline
-#else
-#define TAE_XTS_HD inline
-#endif
+#include "rowsum.hpp"
 
 namespace tae {
 
@@ -90,55 +85,31 @@ inline int xts_row_weight(uint64_t j) {
     return (int)w;
 }
 
-// The row lists of the distinct block indices of a call and, per block, its data unit and its row-list set
-struct XtsPlan {
-    int width = 0;               // the largest row weight of the sets
-    std::vector<int16_t> rows;   // [n_sets][128][width], -1 padded
-    std::vector<int32_t> unit_of, set_of;  // [nb]
-    size_t n_sets() const { return width ? rows.size() / (128 * (size_t)width) : 0; }
-};
-
-// block b of the call is block block_index[b] of data unit unit_of[b] (unit_of == nullptr: unit 0)
-inline void xts_plan(const int32_t *unit_of, const uint64_t *block_index, size_t nb, XtsPlan &plan) {
+// The masks [nb][128] of a call as row sums over the tweak ciphertexts [n_units][128]: block b of the call is block
+// block_index[b] of data unit unit_of[b] (unit_of == nullptr: unit 0).  The lists of the distinct block indices
+// once, set s at lists 128 s ..; mask ciphertext o of block b sums list 128 set(b) + o at base 128 unit_of[b]
+inline RowPlan xts_plan(const int32_t *unit_of, const uint64_t *block_index, size_t nb) {
+    RowPlan plan;
     std::map<uint64_t, int32_t> sets;
-    std::vector<std::vector<int16_t>> lists;  // [set * 128 + o]
-    plan.unit_of.resize(nb);
-    plan.set_of.resize(nb);
-    plan.width = 0;
+    plan.list_of.reserve(nb * 128);
+    plan.base_of.reserve(nb * 128);
     for (size_t b = 0; b < nb; b++) {
-        plan.unit_of[b] = unit_of ? unit_of[b] : 0;
         auto it = sets.find(block_index[b]);
         if (it == sets.end()) {
             it = sets.emplace(block_index[b], (int32_t)sets.size()).first;
             std::vector<int16_t> rows[128];
             xts_rows_of(block_index[b], rows);
-            for (auto &r : rows) {
-                plan.width = (int)r.size() > plan.width ? (int)r.size() : plan.width;
-                lists.push_back(std::move(r));
+            for (const auto &r : rows) {
+                plan.src.insert(plan.src.end(), r.begin(), r.end());
+                plan.end_row();
             }
         }
-        plan.set_of[b] = it->second;
+        for (int32_t o = 0; o < 128; o++) {
+            plan.list_of.push_back(it->second * 128 + o);
+            plan.base_of.push_back((unit_of ? unit_of[b] : 0) * 128);
+        }
     }
-    plan.rows.assign(lists.size() * (size_t)plan.width, -1);
-    for (size_t r = 0; r < lists.size(); r++)
-        for (size_t q = 0; q < lists[r].size(); q++) plan.rows[r * plan.width + q] = lists[r][q];
-}
-
-// Word t of the masks [nb][128][L]: coefficient t % L of ciphertext o = (t / L) & 127 of block (t / L) >> 7, the
-// sum of that coefficient of the tweak ciphertexts in row o of the block's set.  tweaks [n_units][128][L].  The
-// unit and the set are uniform over the L coefficients of a ciphertext, so every read is a contiguous run.
-TAE_XTS_HD uint64_t xts_mask_word(const uint64_t *tweaks, const int16_t *rows, int width, const int32_t *unit_of,
-                                  const int32_t *set_of, size_t t, int L) {
-    const size_t coef = t % L, ct = t / L, blk = ct >> 7;
-    const int16_t *row = rows + ((size_t)set_of[blk] * 128 + (ct & 127)) * width;
-    const uint64_t *T = tweaks + (size_t)unit_of[blk] * 128 * L + coef;
-    uint64_t acc = 0;
-    for (int q = 0; q < width; q++) {
-        const int src = row[q];
-        if (src < 0) break;
-        acc += T[(size_t)src * L];
-    }
-    return acc;
+    return plan;
 }
 
 }  // namespace tae

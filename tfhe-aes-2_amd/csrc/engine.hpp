@@ -22,6 +22,7 @@
 #include "ctr_plan.hpp"
 #include "kslots.hpp"
 #include "params.hpp"
+#include "rowsum.hpp"
 
 namespace tae {
 
@@ -165,8 +166,9 @@ class Engine {
     // bytes on the device -> [n][128][K+1] at noise^2 = 1
     void aes_xts_tweaks(const uint64_t *d_rk2, const uint8_t *d_tweaks, size_t n, int rounds, uint64_t *d_out,
                         int nr = 10);
-    // masks [nb][128][K+1] = alpha^j T of the plan's blocks (HOST plan) from tweak ciphertexts [n_units][128][K+1]
-    void aes_xts_masks(const uint64_t *d_tweak_cts, size_t n_units, const XtsPlan &plan, uint64_t *d_masks);
+    // masks [nb][128][K+1] = alpha^j T of the blocks of an xts_plan (HOST, validated against n_units before the
+    // launch) from tweak ciphertexts [n_units][128][K+1]: one row-sum launch
+    void aes_xts_masks(const uint64_t *d_tweak_cts, size_t n_units, const RowPlan &plan, uint64_t *d_masks);
     // out [nb][128][K+1] = Dec_K1(C_b + M_b) + M_b: the tweak pass over the n_tweaks distinct tweaks (device bytes),
     // then per chunk of ctr_chunk_ blocks the masks, aes_decrypt_rounds on masks + public C and the last add.
     // Block b is block block_index[b] of the unit with tweak tweak_of[b] (HOST arrays, the caller checks the
@@ -185,7 +187,7 @@ class Engine {
         const uint8_t *data, *tag;
     };
     // The forward cipher over public blocks (HOST), block i under slot blocks[i].slot, in chunks of ctr_chunk_
-    // blocks with a pub_plan each; writes each block's len bytes at out_byte of d_out
+    // blocks (pub_pass); writes each block's len bytes at out_byte of d_out
     void aes_pub_blocks_multi(const uint64_t *d_table, const std::vector<PubBlock> &blocks, int rounds, uint64_t *d_out,
                               int nr);
     // Pass 1: every stream's A_0, A_1 .. and B_0 as one batch of public blocks; the payload bits S_i + C go to
@@ -198,8 +200,6 @@ class Engine {
 
     // ---- AES-GCM decryption of public frames on the 1-bit model (aes_gcm.hpp; the reference has no
     // GCM).  One key per call ----
-    // row sums of a plan (HOST, validated against n_src before the launch): sources [n_src][K+1] -> [n_rows][K+1]
-    void gcm_rowsum(const uint64_t *d_sources, size_t n_src, const GcmRowPlan &plan, uint64_t *d_out);
     // squares of `count` field elements [count][128][K+1]: row sums, then one identity bootstrap (noise^2 = 1)
     void gf128_square(const uint64_t *d_in, size_t count, uint64_t *d_out);
     // products a_c b_c of `count` pairs, a / b / out [count][128][K+1]: the 256 operand bits of a pair are keyswitched
@@ -349,50 +349,58 @@ class Engine {
     std::vector<int32_t> key_of_host_;
     std::vector<CtrPlanMulti> ctr_mplans_;
     const int32_t *upload_key_of(const int32_t *key_of, size_t nb);
-    // keep_out / keep_len / d_keep (CCM): a second placement of the same cipher outputs, into d_keep
+    // keep_out / keep_len / d_keep (CCM, GCM): a second placement of the same cipher outputs, into d_keep
     void aes_ctr_blocks_multi(const uint64_t *d_table, const CtrPlanMulti &plan, int rounds, const uint8_t *d_data,
                               uint64_t *d_out, int nr, const std::vector<int64_t> *keep_out = nullptr,
                               const std::vector<int32_t> *keep_len = nullptr, uint64_t *d_keep = nullptr);
+    // The chunked public-block pass: a pub_plan and one aes_ctr_blocks_multi per chunk of ctr_chunk_ blocks, with
+    // the chunk's part of the second placement if there is one.  The plans and the placement's per-chunk lists
+    // live until the next pass; its arrays on the device
+    void pub_pass(const uint64_t *d_table, const std::vector<PubBlock> &blocks, int rounds, const uint8_t *d_data,
+                  uint64_t *d_out, int nr, const std::vector<int64_t> *keep_out = nullptr,
+                  const std::vector<int32_t> *keep_len = nullptr, uint64_t *d_keep = nullptr);
+    int64_t *d_pub_kout_ = nullptr;
+    int32_t *d_pub_klen_ = nullptr;
+    size_t cap_pub_kout_ = 0, cap_pub_klen_ = 0;
+    std::vector<std::vector<int64_t>> pub_kout_;
+    std::vector<std::vector<int32_t>> pub_klen_;
+    // Row sums (rowsum.hpp): validates the plan against the n_src sources [n_src][K+1], keeps it alive until the next
+    // call (the uploads are asynchronous) and launches once under ST_LINEAR: -> d_out [n_rows][K+1].  The plan's
+    // arrays on the device and the host plans their pending uploads read
+    void rowsum_pass(const uint64_t *d_sources, size_t n_src, RowPlan plan, uint64_t *d_out);
+    int32_t *d_rs_start_ = nullptr, *d_rs_src_ = nullptr, *d_rs_list_ = nullptr, *d_rs_base_ = nullptr;
+    uint8_t *d_rs_pub_ = nullptr;
+    size_t cap_rs_start_ = 0, cap_rs_src_ = 0, cap_rs_list_ = 0, cap_rs_base_ = 0, cap_rs_pub_ = 0;
+    std::deque<RowPlan> rowsum_plans_;
     // CCM: S_0 and the chain value Xk of every stream [2 n][128][K+1], the arrays of the call on the device and
     // the host copies their pending uploads read
     uint64_t *d_ccm_keep_ = nullptr;
     uint8_t *d_ccm_bytes_ = nullptr;
-    int64_t *d_ccm_src_ = nullptr, *d_ccm_kout_ = nullptr;
-    int32_t *d_ccm_slot_ = nullptr, *d_ccm_klen_ = nullptr, *d_ccm_order_ = nullptr;
-    size_t cap_ccm_keep_ = 0, cap_ccm_bytes_ = 0, cap_ccm_src_ = 0, cap_ccm_kout_ = 0, cap_ccm_slot_ = 0,
-           cap_ccm_klen_ = 0, cap_ccm_order_ = 0;
+    int64_t *d_ccm_src_ = nullptr;
+    int32_t *d_ccm_slot_ = nullptr, *d_ccm_order_ = nullptr;
+    size_t cap_ccm_keep_ = 0, cap_ccm_bytes_ = 0, cap_ccm_src_ = 0, cap_ccm_slot_ = 0, cap_ccm_order_ = 0;
     std::vector<uint8_t> ccm_bytes_;
     std::vector<int64_t> ccm_src_;
     std::vector<int32_t> ccm_slot_, ccm_order_;
-    std::vector<std::vector<int64_t>> ccm_kout_;
-    std::vector<std::vector<int32_t>> ccm_klen_;
     // GCM: the 8 -> 7 nibble-product table; the source array of a call's chunk sums (power table, then E(J0) of every
     // frame); two scratch arrays the row sums and the refreshes alternate between; the operand bits and the partial
-    // bits of a product batch; the plan arrays on the device and the host plans their pending uploads read
+    // bits of a product batch; the public bytes of a call and the host copy their pending upload reads
     uint64_t *d_lut_gcm_ = nullptr;
     uint64_t *d_gcm_src_ = nullptr, *d_gcm_a_ = nullptr, *d_gcm_b_ = nullptr, *d_gcm_ops_ = nullptr, *d_gcm_ks_ = nullptr,
              *d_gcm_parts_ = nullptr;
-    int32_t *d_gcm_rs_ = nullptr, *d_gcm_ix_ = nullptr;
-    uint8_t *d_gcm_pb_ = nullptr, *d_gcm_bytes_ = nullptr;
+    uint8_t *d_gcm_bytes_ = nullptr;
     size_t cap_gcm_src_ = 0, cap_gcm_a_ = 0, cap_gcm_b_ = 0, cap_gcm_ops_ = 0, cap_gcm_ks_ = 0, cap_gcm_parts_ = 0,
-           cap_gcm_rs_ = 0, cap_gcm_ix_ = 0, cap_gcm_pb_ = 0, cap_gcm_bytes_ = 0;
-    std::deque<GcmRowPlan> gcm_plans_;
+           cap_gcm_bytes_ = 0;
     std::vector<uint8_t> gcm_bytes_;
     void require_gcm() const;
-    void gcm_rowsum_pass(const uint64_t *d_sources, size_t n_src, GcmRowPlan plan, uint64_t *d_out);
     void gcm_square_pass(const uint64_t *d_src, size_t n_src, const std::vector<size_t> &blocks,
                          const std::vector<uint64_t *> &outs);
     void gcm_product_pass(const std::vector<const uint64_t *> &a, const std::vector<const uint64_t *> &b,
                           const std::vector<uint64_t *> &outs);
-    // XTS: the refreshed tweaks of the call, the masks of the chunk in flight, the plan arrays on the device and
-    // the host plans their pending uploads read
+    // XTS: the refreshed tweaks of the call and the masks of the chunk in flight
     uint64_t *d_xts_tweaks_ = nullptr, *d_xts_masks_ = nullptr;
-    int16_t *d_xts_rows_ = nullptr;
-    int32_t *d_xts_unit_ = nullptr, *d_xts_set_ = nullptr;
-    size_t cap_xts_tweaks_ = 0, cap_xts_masks_ = 0, cap_xts_rows_ = 0, cap_xts_unit_ = 0, cap_xts_set_ = 0;
-    std::vector<XtsPlan> xts_plans_;
+    size_t cap_xts_tweaks_ = 0, cap_xts_masks_ = 0;
     void xts_tweak_pass(const uint64_t *d_rk2, const uint8_t *d_tweaks, size_t n, int rounds, uint64_t *d_out, int nr);
-    void xts_mask_pass(const uint64_t *d_tweak_cts, size_t n_units, const XtsPlan &plan, uint64_t *d_masks);
     void copy_rows(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t rows,
                    size_t len);
     void copy_key_words(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t n_keys,

@@ -1026,11 +1026,11 @@ Engine::~Engine() {
                     (void *)d_s1_id_tv_, (void *)d_s1_in_, (void *)d_s1_out_, (void *)d_s1_pks_, (void *)d_s1_tv_, (void *)d_pf_flags_, (void *)d_clk_, (void *)d_lf_, (void *)d_acc_w_,
                     (void *)d_ctr_groups_, (void *)d_ctr_map_, (void *)d_key_of_, (void *)d_ctr_gslot_,
                     (void *)d_ctr_blen_, (void *)d_ctr_bout_, (void *)d_pack_, (void *)d_xts_tweaks_, (void *)d_xts_masks_,
-                    (void *)d_ccm_keep_, (void *)d_ccm_bytes_, (void *)d_ccm_src_, (void *)d_ccm_kout_, (void *)d_ccm_slot_,
-                    (void *)d_ccm_klen_, (void *)d_ccm_order_,
-                    (void *)d_xts_rows_, (void *)d_xts_unit_, (void *)d_xts_set_,
+                    (void *)d_ccm_keep_, (void *)d_ccm_bytes_, (void *)d_ccm_src_, (void *)d_pub_kout_, (void *)d_ccm_slot_,
+                    (void *)d_pub_klen_, (void *)d_ccm_order_,
+                    (void *)d_rs_start_, (void *)d_rs_src_, (void *)d_rs_list_, (void *)d_rs_base_, (void *)d_rs_pub_,
                     (void *)d_lut_gcm_, (void *)d_gcm_src_, (void *)d_gcm_a_, (void *)d_gcm_b_, (void *)d_gcm_ops_,
-                    (void *)d_gcm_ks_, (void *)d_gcm_parts_, (void *)d_gcm_rs_, (void *)d_gcm_ix_, (void *)d_gcm_pb_,
+                    (void *)d_gcm_ks_, (void *)d_gcm_parts_,
                     (void *)d_gcm_bytes_,
                     (void *)d_lut_inv32_, (void *)d_lut_inv8_, (void *)d_lut_mul32_, (void *)d_lut_id1_})
         if (q) hipFree(q);

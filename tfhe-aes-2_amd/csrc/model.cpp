@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <array>
 #include <cstring>
+#include <deque>
 
 #include "aes.hpp"
 #include "aes_inv.hpp"
@@ -144,79 +145,122 @@ struct DevBuf {
 };
 }  // namespace
 
-// Run fn(d_in, d_out, d_lut) on the engine stream with host staging unless device_mem.
-template <class F>
-void Context::run8(const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len, bool device_mem, F fn,
-                   const Lut *lut) {
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    std::unique_ptr<DevBuf> d_lut;
-    if (lut) {
-        d_lut = std::make_unique<DevBuf>(lut->data.size() * 8);
-        hip_check(hipMemcpyAsync(d_lut->p, lut->data.data(), lut->data.size() * 8, hipMemcpyHostToDevice,
-                                 engine_->stream()),
-                  "lut upload");
+// The staging scope of one entry point: it holds the context's lock, sets its device and hands the engine the arrays
+// of the call.  Device memory (TAE_MEM_DEVICE) passes through, ordered after the caller's work; host memory is
+// uploaded into buffers the scope owns (one hipMalloc per array) and the outputs are downloaded by finish().  The
+// destructor only frees: an exception before finish() leaves the caller's outputs untouched.
+class Context::Staged {
+  public:
+    Staged(Context &c, bool device_mem) : lock_(c.mu_), e_(*c.engine_), dev_(device_mem) {
+        hip_check(hipSetDevice(e_.device()), "hipSetDevice");
+        if (dev_) e_.order_after_caller();
     }
-    const uint64_t *dl = d_lut ? d_lut->as<uint64_t>() : nullptr;
-    if (device_mem) {
-        engine_->order_after_caller();
-        fn(in, out, dl);
-        engine_->synchronize();
-        return;
+    // n elements the engine reads: the caller's array, or its upload
+    template <class T>
+    const T *in(const T *p, size_t n) {
+        return dev_ ? p : upload(p, n);
     }
-    DevBuf d_in(in_len * 8), d_out(out_len * 8);
-    hip_check(hipMemcpyAsync(d_in.p, in, in_len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload");
-    fn(d_in.as<uint64_t>(), d_out.as<uint64_t>(), dl);
-    hip_check(hipMemcpyAsync(out, d_out.p, out_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    // public bytes, lookup tables, test vectors: host arrays, always; null or empty stays null
+    template <class T>
+    const T *pub(const T *p, size_t n) {
+        return p && n ? upload(p, n) : nullptr;
+    }
+    // n elements the engine writes: the caller's array, or a buffer that finish() downloads into it
+    template <class T>
+    T *out(T *p, size_t n) {
+        if (dev_) return p;
+        T *d = alloc<T>(n);
+        downloads_.push_back({p, d, n * sizeof(T)});
+        return d;
+    }
+    // a key table [..][stride]: the caller's, or a compact upload of only the slots that `slots` refers to, which is
+    // rewritten to index it, so a slot that nothing refers to is not read in either case
+    const uint64_t *table(const uint64_t *table, std::vector<int32_t> &slots, size_t stride);
+    // the downloads, in the order of their out() calls, then the engine's synchronize
+    void finish() {
+        for (const Download &d : downloads_)
+            if (d.bytes) hip_check(hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, e_.stream()), "download");
+        e_.synchronize();
+    }
+
+  private:
+    struct Download {
+        void *host;
+        const void *dev;
+        size_t bytes;
+    };
+    template <class T>
+    T *alloc(size_t n) {
+        bufs_.emplace_back(n * sizeof(T));
+        return bufs_.back().as<T>();
+    }
+    template <class T>
+    const T *upload(const T *p, size_t n) {
+        T *d = alloc<T>(n);
+        if (n) hip_check(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyHostToDevice, e_.stream()), "upload");
+        return d;
+    }
+    std::lock_guard<std::mutex> lock_;
+    Engine &e_;
+    const bool dev_;
+    std::deque<DevBuf> bufs_;  // freed before the lock is released
+    std::vector<Download> downloads_;
+};
+
+// words [n][L] as n bits carrying noise[i]
+static std::vector<BitCt> wrap_bits(const std::vector<uint64_t> &words, std::vector<NoiseLevel> noise, size_t L,
+                                    uint64_t max_noise_sq) {
+    std::vector<BitCt> bits(noise.size());
+    for (size_t i = 0; i < bits.size(); i++) {
+        bits[i].ct.assign(words.begin() + i * L, words.begin() + (i + 1) * L);
+        bits[i].noise = std::move(noise[i]);
+        bits[i].max_noise_sq = max_noise_sq;
+    }
+    return bits;
+}
+
+// the levels of whole blocks [n][128] as one list, cut to n_bits
+static std::vector<NoiseLevel> flat_noise(std::vector<std::vector<NoiseLevel>> blocks, size_t n_bits) {
+    std::vector<NoiseLevel> flat;
+    flat.reserve(blocks.size() * 128);
+    for (auto &b : blocks)
+        for (NoiseLevel &x : b) flat.push_back(std::move(x));
+    flat.resize(n_bits);
+    return flat;
 }
 
 void Context::bootstrap_from_bits_raw(const uint64_t *bits, size_t groups, const Lut &lut, uint64_t *out,
                                       bool device_mem) {
     if (params().model != 8) throw ModelError{TAE_E_PARAM, "bootstrap_from_bits belongs to the 8-bit model"};
     if (lut.input_bits != 8) throw ModelError{TAE_E_ARG, "bootstrap_from_bits needs an 8-bit LUT"};
-    run8(bits, groups * 8 * bit_len(), out, groups * params().big_len(), device_mem,
-         [&](const uint64_t *in, uint64_t *o, const uint64_t *d_lut) { engine_->cbs_vp(in, groups, 8, d_lut, 1, o); },
-         &lut);
+    Staged st(*this, device_mem);
+    engine_->cbs_vp(st.in(bits, groups * 8 * bit_len()), groups, 8, st.pub(lut.data.data(), lut.data.size()), 1,
+                    st.out(out, groups * params().big_len()));
+    st.finish();
 }
 
 void Context::extract_bits_raw(const uint64_t *ints, size_t groups, uint64_t *out, bool device_mem) {
     if (params().model != 8) throw ModelError{TAE_E_PARAM, "extract_bits_from_ciphertext belongs to the 8-bit model"};
-    run8(ints, groups * params().big_len(), out, groups * 8 * bit_len(), device_mem,
-         [&](const uint64_t *in, uint64_t *o, const uint64_t *) { engine_->extract_bits(in, groups, 56, 8, o); },
-         nullptr);
+    Staged st(*this, device_mem);
+    engine_->extract_bits(st.in(ints, groups * params().big_len()), groups, 56, 8, st.out(out, groups * 8 * bit_len()));
+    st.finish();
 }
 
 void Context::circuit_bootstrap_raw(const uint64_t *bits, size_t groups, int n_in, const Lut &lut, uint64_t *out,
                                     bool device_mem) {
     if (n_in != lut.input_bits) throw ModelError{TAE_E_ARG, "number of input bits does not match the LUT"};
+    Staged st(*this, device_mem);
+    const uint64_t *d_lut = st.pub(lut.data.data(), lut.data.size());
     if (params().model == 8) {
         // Byte::bootstrap_with_lut (fhe_impls/shortint_woppbs_8bit.rs:37-42): bits [G][8][n+1] -> [G][8][n+1]
-        run8(bits, groups * 8 * bit_len(), out, groups * 8 * bit_len(), device_mem,
-             [&](const uint64_t *in, uint64_t *o, const uint64_t *d_lut) { engine_->bootstrap_bytes8(in, groups, d_lut, o); },
-             &lut);
-        return;
+        const size_t len = groups * 8 * bit_len();
+        engine_->bootstrap_bytes8(st.in(bits, len), groups, d_lut, st.out(out, len));
+    } else {
+        const size_t L = params().big_len();
+        engine_->circuit_bootstrap(st.in(bits, groups * n_in * L), groups, n_in, d_lut, lut.output_bits,
+                                   st.out(out, groups * lut.output_bits * L));
     }
-    std::lock_guard<std::mutex> g(mu_);
-    const size_t L = params().big_len();
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    DevBuf d_lut(lut.data.size() * 8);
-    hip_check(hipMemcpyAsync(d_lut.p, lut.data.data(), lut.data.size() * 8, hipMemcpyHostToDevice,
-                             engine_->stream()),
-              "lut upload");
-    if (device_mem) {
-        engine_->order_after_caller();
-        engine_->circuit_bootstrap(bits, groups, n_in, d_lut.as<uint64_t>(), lut.output_bits, out);
-        engine_->synchronize();
-        return;
-    }
-    DevBuf d_in(groups * n_in * L * 8), d_out(groups * lut.output_bits * L * 8);
-    hip_check(hipMemcpyAsync(d_in.p, bits, groups * n_in * L * 8, hipMemcpyHostToDevice, engine_->stream()), "upload");
-    engine_->circuit_bootstrap(d_in.as<uint64_t>(), groups, n_in, d_lut.as<uint64_t>(), lut.output_bits,
-                               d_out.as<uint64_t>());
-    hip_check(hipMemcpyAsync(out, d_out.p, groups * lut.output_bits * L * 8, hipMemcpyDeviceToHost, engine_->stream()),
-              "download");
-    engine_->synchronize();
+    st.finish();
 }
 
 // FheContext::circuit_bootstrap (shortint_woppbs_1bit.rs:292-336)
@@ -454,23 +498,10 @@ void Context::aes_encrypt_blocks_raw(const uint64_t *rk, const uint64_t *blocks,
         for (auto &x : kbl) x = params().model != 1 ? NoiseLevel{1, {}} : NoiseLevel::with_noise_level(1, next_ct_id());
         block_noise_schedule(driver, krk, kbl, rounds, nr);
     }
-    const size_t S = bit_len();
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    if (device_mem) {
-        engine_->order_after_caller();
-        run_aes_blocks(driver, rk, blocks, n_blocks, rounds, out, nr);
-        engine_->synchronize();
-        return;
-    }
-    DevBuf d_rk(kw * S * 8), d_in(n_blocks * 128 * S * 8), d_out(n_blocks * 128 * S * 8);
-    hip_check(hipMemcpyAsync(d_rk.p, rk, kw * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload rk");
-    hip_check(hipMemcpyAsync(d_in.p, blocks, n_blocks * 128 * S * 8, hipMemcpyHostToDevice, engine_->stream()),
-              "upload blocks");
-    run_aes_blocks(driver, d_rk.as<uint64_t>(), d_in.as<uint64_t>(), n_blocks, rounds, d_out.as<uint64_t>(), nr);
-    hip_check(hipMemcpyAsync(out, d_out.p, n_blocks * 128 * S * 8, hipMemcpyDeviceToHost, engine_->stream()),
-              "download");
-    engine_->synchronize();
+    const size_t S = bit_len(), len = n_blocks * 128 * S;
+    Staged st(*this, device_mem);
+    run_aes_blocks(driver, st.in(rk, kw * S), st.in(blocks, len), n_blocks, rounds, st.out(out, len), nr);
+    st.finish();
 }
 
 std::vector<BitCt> Context::aes_encrypt_blocks(const std::vector<const BitCt *> &expanded_key,
@@ -498,22 +529,12 @@ std::vector<BitCt> Context::aes_encrypt_blocks(const std::vector<const BitCt *> 
     for (size_t i = 0; i < kw; i++) std::memcpy(&rk[i * L], expanded_key[i]->ct.data(), L * 8);
     for (size_t i = 0; i < n_blocks * 128; i++) std::memcpy(&in[i * L], blocks[i]->ct.data(), L * 8);
     {
-        std::lock_guard<std::mutex> g(mu_);
-        hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-        DevBuf d_rk(rk.size() * 8), d_in(in.size() * 8), d_out(out.size() * 8);
-        hip_check(hipMemcpyAsync(d_rk.p, rk.data(), rk.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
-        hip_check(hipMemcpyAsync(d_in.p, in.data(), in.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
-        run_aes_blocks(driver, d_rk.as<uint64_t>(), d_in.as<uint64_t>(), n_blocks, rounds, d_out.as<uint64_t>(), nr);
-        hip_check(hipMemcpyAsync(out.data(), d_out.p, out.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
-        engine_->synchronize();
+        Staged st(*this, false);
+        run_aes_blocks(driver, st.in(rk.data(), rk.size()), st.in(in.data(), in.size()), n_blocks, rounds,
+                       st.out(out.data(), out.size()), nr);
+        st.finish();
     }
-    std::vector<BitCt> res(n_blocks * 128);
-    for (size_t i = 0; i < n_blocks * 128; i++) {
-        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
-        res[i].noise = out_noise[i / 128][i % 128];
-        res[i].max_noise_sq = params().max_noise_sq;
-    }
-    return res;
+    return wrap_bits(out, flat_noise(std::move(out_noise), n_blocks * 128), L, params().max_noise_sq);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -560,23 +581,10 @@ int Context::check_ctr(uint64_t first_counter, size_t n_blocks, int rounds, int 
 void Context::run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
                           const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem, int nr) {
     const size_t S = bit_len(), kw = (size_t)4 * (nr + 1) * 32;
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    DevBuf d_data(data ? out_bytes : 0);  // the public bytes are a host array, always
-    if (data)
-        hip_check(hipMemcpyAsync(d_data.p, data, out_bytes, hipMemcpyHostToDevice, engine_->stream()), "upload data");
-    const uint8_t *dd = data ? d_data.as<uint8_t>() : nullptr;
-    if (device_mem) {
-        engine_->order_after_caller();
-        engine_->aes_ctr(rk, iv, first_counter, n_blocks, rounds, dd, out_bytes, out, nr);
-        engine_->synchronize();
-        return;
-    }
-    DevBuf d_rk(kw * S * 8), d_out(out_bytes * 8 * S * 8);
-    hip_check(hipMemcpyAsync(d_rk.p, rk, kw * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload rk");
-    engine_->aes_ctr(d_rk.as<uint64_t>(), iv, first_counter, n_blocks, rounds, dd, out_bytes, d_out.as<uint64_t>(), nr);
-    hip_check(hipMemcpyAsync(out, d_out.p, out_bytes * 8 * S * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    Staged st(*this, device_mem);
+    engine_->aes_ctr(st.in(rk, kw * S), iv, first_counter, n_blocks, rounds, st.pub(data, out_bytes), out_bytes,
+                     st.out(out, out_bytes * 8 * S), nr);
+    st.finish();
 }
 
 void Context::aes_ctr_keystream_raw(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks,
@@ -621,13 +629,8 @@ std::vector<BitCt> Context::aes_ctr_transcipher(const std::vector<const BitCt *>
     std::vector<uint64_t> rk(kw * L), out(len * 8 * L);
     for (size_t i = 0; i < kw; i++) std::memcpy(&rk[i * L], expanded_key[i]->ct.data(), L * 8);
     run_aes_ctr(rk.data(), iv, first_counter, n_blocks, rounds, data, len, out.data(), false, nr);
-    std::vector<BitCt> res(len * 8);
-    for (size_t i = 0; i < res.size(); i++) {
-        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
-        res[i].noise = out_noise[i / 128][i % 128];  // xor with a public bit adds no noise
-        res[i].max_noise_sq = params().max_noise_sq;
-    }
-    return res;
+    // xor with a public bit adds no noise
+    return wrap_bits(out, flat_noise(std::move(out_noise), len * 8), L, params().max_noise_sq);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -710,39 +713,14 @@ static std::vector<uint64_t> gather_bits(const std::vector<const BitCt *> &bits,
     return a;
 }
 
-// host or device arrays through the engine: in (in_len words, may be null), the key (key_cts ciphertexts), out
-void Context::run_inverse(const uint64_t *key, const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes,
-                          uint64_t *out, size_t out_len, bool device_mem,
-                          const std::function<void(const uint64_t *, const uint64_t *, const uint8_t *, uint64_t *)> &fn,
-                          size_t key_cts) {
-    const size_t S = bit_len();
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    DevBuf d_bytes(n_bytes);  // the public bytes are a host array, always
-    if (n_bytes)
-        hip_check(hipMemcpyAsync(d_bytes.p, bytes, n_bytes, hipMemcpyHostToDevice, engine_->stream()), "upload data");
-    if (device_mem) {
-        engine_->order_after_caller();
-        fn(key, in, d_bytes.as<uint8_t>(), out);
-        engine_->synchronize();
-        return;
-    }
-    DevBuf d_key(key_cts * S * 8), d_in(in_len * 8), d_out(out_len * 8);
-    hip_check(hipMemcpyAsync(d_key.p, key, key_cts * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
-    if (in_len) hip_check(hipMemcpyAsync(d_in.p, in, in_len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload");
-    fn(d_key.as<uint64_t>(), d_in.as<uint64_t>(), d_bytes.as<uint8_t>(), d_out.as<uint64_t>());
-    hip_check(hipMemcpyAsync(out, d_out.p, out_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
-}
-
 void Context::aes_decrypt_key_raw(const uint64_t *rk, uint64_t *dk, bool device_mem, int key_bits) {
     const int nr = require_inverse(-1, key_bits);
     const size_t kw = (size_t)aes_words(key_bits) * 32;
     aes_decrypt_key_noise_schedule(fresh_levels(kw), params().max_noise_sq, nr);
     if (device_mem && rk == dk) throw ModelError{TAE_E_ARG, "the decryption key cannot be derived in place"};
-    run_inverse(rk, nullptr, 0, nullptr, 0, dk, kw * bit_len(), device_mem,
-                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) { engine_->aes_decrypt_key(k, o, nr); },
-                kw);
+    Staged st(*this, device_mem);
+    engine_->aes_decrypt_key(st.in(rk, kw * bit_len()), st.out(dk, kw * bit_len()), nr);
+    st.finish();
 }
 
 std::vector<BitCt> Context::aes_decrypt_key(const std::vector<const BitCt *> &expanded_key, int key_bits) {
@@ -755,16 +733,12 @@ std::vector<BitCt> Context::aes_decrypt_key(const std::vector<const BitCt *> &ex
     for (size_t i = 0; i < krk.size(); i++) krk[i] = expanded_key[i]->noise;
     const std::vector<NoiseLevel> kdk = aes_decrypt_key_noise_schedule(krk, params().max_noise_sq, nr);
     std::vector<uint64_t> dk(rk.size());
-    run_inverse(rk.data(), nullptr, 0, nullptr, 0, dk.data(), dk.size(), false,
-                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) { engine_->aes_decrypt_key(k, o, nr); },
-                kw);
-    std::vector<BitCt> res(kw);
-    for (size_t i = 0; i < res.size(); i++) {
-        res[i].ct.assign(dk.begin() + i * L, dk.begin() + (i + 1) * L);
-        res[i].noise = kdk[i];
-        res[i].max_noise_sq = params().max_noise_sq;
+    {
+        Staged st(*this, false);
+        engine_->aes_decrypt_key(st.in(rk.data(), rk.size()), st.out(dk.data(), dk.size()), nr);
+        st.finish();
     }
-    return res;
+    return wrap_bits(dk, kdk, L, params().max_noise_sq);
 }
 
 void Context::aes_decrypt_blocks_raw(const uint64_t *dk, const uint64_t *blocks, size_t n_blocks, int rounds,
@@ -775,11 +749,9 @@ void Context::aes_decrypt_blocks_raw(const uint64_t *dk, const uint64_t *blocks,
     aes_decrypt_noise_schedule(fresh_levels(kw), fresh_levels(128), rounds, params().max_noise_sq, nr);
     if (!n_blocks) return;
     const size_t len = n_blocks * 128 * bit_len();
-    run_inverse(dk, blocks, len, nullptr, 0, out, len, device_mem,
-                [&](const uint64_t *k, const uint64_t *i, const uint8_t *, uint64_t *o) {
-                    engine_->aes_decrypt_blocks(k, i, n_blocks, rounds, o, nr);
-                },
-                kw);
+    Staged st(*this, device_mem);
+    engine_->aes_decrypt_blocks(st.in(dk, kw * bit_len()), st.in(blocks, len), n_blocks, rounds, st.out(out, len), nr);
+    st.finish();
 }
 
 std::vector<BitCt> Context::aes_decrypt_blocks(const std::vector<const BitCt *> &dk,
@@ -800,19 +772,13 @@ std::vector<BitCt> Context::aes_decrypt_blocks(const std::vector<const BitCt *> 
         out_noise[blk] = aes_decrypt_noise_schedule(kdk, kb, rounds, params().max_noise_sq, nr);
     }
     std::vector<uint64_t> out(in.size());
-    if (n_blocks)
-        run_inverse(key.data(), in.data(), in.size(), nullptr, 0, out.data(), out.size(), false,
-                    [&](const uint64_t *k, const uint64_t *i, const uint8_t *, uint64_t *o) {
-                        engine_->aes_decrypt_blocks(k, i, n_blocks, rounds, o, nr);
-                    },
-                    kw);
-    std::vector<BitCt> res(n_blocks * 128);
-    for (size_t i = 0; i < res.size(); i++) {
-        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
-        res[i].noise = out_noise[i / 128][i % 128];
-        res[i].max_noise_sq = params().max_noise_sq;
+    if (n_blocks) {
+        Staged st(*this, false);
+        engine_->aes_decrypt_blocks(st.in(key.data(), key.size()), st.in(in.data(), in.size()), n_blocks, rounds,
+                                    st.out(out.data(), out.size()), nr);
+        st.finish();
     }
-    return res;
+    return wrap_bits(out, flat_noise(std::move(out_noise), n_blocks * 128), L, params().max_noise_sq);
 }
 
 // iv || data, the public bytes both ends of the CBC pass read
@@ -832,12 +798,10 @@ void Context::aes_cbc_transcipher_raw(const uint64_t *dk, const uint8_t iv[16], 
     aes_decrypt_noise_schedule(fresh_levels(kw), std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds,
                                params().max_noise_sq, nr);
     if (!len) return;
-    const size_t n_blocks = len / 16;
-    run_inverse(dk, nullptr, 0, pub.data(), pub.size(), out, len * 8 * bit_len(), device_mem,
-                [&](const uint64_t *k, const uint64_t *, const uint8_t *b, uint64_t *o) {
-                    engine_->aes_cbc_transcipher(k, b, n_blocks, rounds, o, nr);
-                },
-                kw);
+    Staged st(*this, device_mem);
+    engine_->aes_cbc_transcipher(st.in(dk, kw * bit_len()), st.pub(pub.data(), pub.size()), len / 16, rounds,
+                                 st.out(out, len * 8 * bit_len()), nr);
+    st.finish();
 }
 
 std::vector<BitCt> Context::aes_cbc_transcipher(const std::vector<const BitCt *> &dk, const uint8_t iv[16],
@@ -856,18 +820,14 @@ std::vector<BitCt> Context::aes_cbc_transcipher(const std::vector<const BitCt *>
     for (auto &o : out_noise) o = aes_decrypt_noise_schedule(kdk, triv, rounds, params().max_noise_sq, nr);
     if (!len) return {};
     std::vector<uint64_t> out(len * 8 * L);
-    run_inverse(key.data(), nullptr, 0, pub.data(), pub.size(), out.data(), out.size(), false,
-                [&](const uint64_t *k, const uint64_t *, const uint8_t *b, uint64_t *o) {
-                    engine_->aes_cbc_transcipher(k, b, n_blocks, rounds, o, nr);
-                },
-                kw);
-    std::vector<BitCt> res(len * 8);
-    for (size_t i = 0; i < res.size(); i++) {
-        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
-        res[i].noise = out_noise[i / 128][i % 128];  // xor with a public bit adds no noise
-        res[i].max_noise_sq = params().max_noise_sq;
+    {
+        Staged st(*this, false);
+        engine_->aes_cbc_transcipher(st.in(key.data(), key.size()), st.pub(pub.data(), pub.size()), n_blocks, rounds,
+                                     st.out(out.data(), out.size()), nr);
+        st.finish();
     }
-    return res;
+    // xor with a public bit adds no noise
+    return wrap_bits(out, flat_noise(std::move(out_noise), len * 8), L, params().max_noise_sq);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -959,26 +919,16 @@ void Context::aes_xts_tweaks_raw(const uint64_t *rk2, const uint8_t *tweaks, siz
     std::vector<int32_t> slot(n);
     for (size_t i = 0; i < n; i++) slot[i] = xts_tweak_slot(distinct, tweaks + 16 * i);
     const size_t nd = distinct.size() / 16;
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    DevBuf d_bytes(distinct.size()), d_T(nd * block_len * 8);
-    DevBuf d_rk(device_mem ? 0 : kw * S * 8), d_out(device_mem ? 0 : n * block_len * 8);
-    hip_check(hipMemcpyAsync(d_bytes.p, distinct.data(), distinct.size(), hipMemcpyHostToDevice, engine_->stream()),
-              "upload tweaks");
-    if (device_mem)
-        engine_->order_after_caller();
-    else
-        hip_check(hipMemcpyAsync(d_rk.p, rk2, kw * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
-    uint64_t *dst = device_mem ? out : d_out.as<uint64_t>();
-    engine_->aes_xts_tweaks(device_mem ? rk2 : d_rk.as<uint64_t>(), d_bytes.as<uint8_t>(), nd, rounds,
-                            d_T.as<uint64_t>(), nr);
+    Staged st(*this, device_mem);
+    DevBuf d_T(nd * block_len * 8);  // the distinct tweaks, each copied to its places in the result
+    uint64_t *dst = st.out(out, n * block_len);
+    engine_->aes_xts_tweaks(st.in(rk2, kw * S), st.pub(distinct.data(), distinct.size()), nd, rounds, d_T.as<uint64_t>(),
+                            nr);
     for (size_t i = 0; i < n; i++)
         hip_check(hipMemcpyAsync(dst + i * block_len, d_T.as<uint64_t>() + (size_t)slot[i] * block_len, block_len * 8,
                                  hipMemcpyDeviceToDevice, engine_->stream()),
                   "place tweak");
-    if (!device_mem)
-        hip_check(hipMemcpyAsync(out, dst, n * block_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    st.finish();
 }
 
 void Context::xts_masks_raw(const uint64_t *tweak_cts, size_t n_units, const int32_t *unit_of_block,
@@ -988,47 +938,18 @@ void Context::xts_masks_raw(const uint64_t *tweak_cts, size_t n_units, const int
         if (unit_of_block[b] < 0 || (size_t)unit_of_block[b] >= n_units)
             throw ModelError{TAE_E_ARG, "a block's data unit is outside 0..n_units-1"};
     if (!nb) return;
-    XtsPlan plan;
-    xts_plan(unit_of_block, block_index, nb, plan);
+    const RowPlan plan = xts_plan(unit_of_block, block_index, nb);
     const size_t block_len = 128 * bit_len();
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    if (device_mem) {
-        engine_->order_after_caller();
-        engine_->aes_xts_masks(tweak_cts, n_units, plan, masks);
-        engine_->synchronize();
-        return;
-    }
-    DevBuf d_T(n_units * block_len * 8), d_M(nb * block_len * 8);
-    hip_check(hipMemcpyAsync(d_T.p, tweak_cts, n_units * block_len * 8, hipMemcpyHostToDevice, engine_->stream()),
-              "upload tweaks");
-    engine_->aes_xts_masks(d_T.as<uint64_t>(), n_units, plan, d_M.as<uint64_t>());
-    hip_check(hipMemcpyAsync(masks, d_M.p, nb * block_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    Staged st(*this, device_mem);
+    engine_->aes_xts_masks(st.in(tweak_cts, n_units * block_len), n_units, plan, st.out(masks, nb * block_len));
+    st.finish();
 }
 
-void Context::run_xts(const uint64_t *dk1, const uint64_t *rk2, size_t key_cts, const std::vector<uint8_t> &tweaks,
-                      const std::vector<int32_t> &tweak_of, const std::vector<uint64_t> &block_index,
-                      const std::vector<uint8_t> &data, int rounds, uint64_t *out, bool device_mem, int nr) {
-    const size_t S = bit_len(), nb = block_index.size(), out_bytes = nb * 128 * S * 8, key_bytes = key_cts * S * 8;
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    DevBuf d_tweaks(tweaks.size()), d_data(data.size());  // the public bytes are host arrays, always
-    DevBuf d_dk(device_mem ? 0 : key_bytes), d_rk(device_mem ? 0 : key_bytes), d_out(device_mem ? 0 : out_bytes);
-    hip_check(hipMemcpyAsync(d_tweaks.p, tweaks.data(), tweaks.size(), hipMemcpyHostToDevice, engine_->stream()),
-              "upload tweaks");
-    hip_check(hipMemcpyAsync(d_data.p, data.data(), data.size(), hipMemcpyHostToDevice, engine_->stream()), "upload data");
-    if (device_mem) {
-        engine_->order_after_caller();
-    } else {
-        hip_check(hipMemcpyAsync(d_dk.p, dk1, key_bytes, hipMemcpyHostToDevice, engine_->stream()), "upload key");
-        hip_check(hipMemcpyAsync(d_rk.p, rk2, key_bytes, hipMemcpyHostToDevice, engine_->stream()), "upload key");
-    }
-    engine_->aes_xts_transcipher(device_mem ? dk1 : d_dk.as<uint64_t>(), device_mem ? rk2 : d_rk.as<uint64_t>(),
-                                 d_tweaks.as<uint8_t>(), tweaks.size() / 16, tweak_of.data(), block_index.data(),
-                                 d_data.as<uint8_t>(), nb, rounds, device_mem ? out : d_out.as<uint64_t>(), nr);
-    if (!device_mem) hip_check(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+// the flattened blocks of an XTS call through the engine, on arrays a staging scope has placed
+static void xts_engine_call(Engine &e, const uint64_t *d_dk1, const uint64_t *d_rk2, const uint8_t *d_tweaks,
+                            const uint8_t *d_data, const XtsFlat &f, int rounds, uint64_t *d_out, int nr) {
+    e.aes_xts_transcipher(d_dk1, d_rk2, d_tweaks, f.tweaks.size() / 16, f.tweak_of.data(), f.block_index.data(), d_data,
+                          f.block_index.size(), rounds, d_out, nr);
 }
 
 void Context::aes_xts_transcipher_raw(const uint64_t *dk1, const uint64_t *rk2, const std::vector<XtsUnitIn> &units,
@@ -1040,7 +961,11 @@ void Context::aes_xts_transcipher_raw(const uint64_t *dk1, const uint64_t *rk2, 
     const std::vector<NoiseLevel> tweak = aes_xts_tweak_noise_schedule(fresh_levels(kw), rounds, max, nr);
     if (f.block_index.empty()) return;
     aes_xts_noise_schedule(fresh_levels(kw), tweak, xts_heaviest_block(f.block_index), rounds, max, nr);
-    run_xts(dk1, rk2, kw, f.tweaks, f.tweak_of, f.block_index, f.data, rounds, out, device_mem, nr);
+    const size_t S = bit_len();
+    Staged st(*this, device_mem);
+    xts_engine_call(*engine_, st.in(dk1, kw * S), st.in(rk2, kw * S), st.pub(f.tweaks.data(), f.tweaks.size()),
+                    st.pub(f.data.data(), f.data.size()), f, rounds, st.out(out, f.block_index.size() * 128 * S), nr);
+    st.finish();
 }
 
 std::vector<BitCt> Context::aes_xts_transcipher(const std::vector<const BitCt *> &dk1,
@@ -1065,14 +990,15 @@ std::vector<BitCt> Context::aes_xts_transcipher(const std::vector<const BitCt *>
         out_noise[b] = aes_xts_noise_schedule(kdk, tweak[f.tweak_of[b]], f.block_index[b], rounds, max, nr);
     if (!nb) return {};
     std::vector<uint64_t> out(nb * 128 * L);
-    run_xts(key1.data(), key2.data(), kw, f.tweaks, f.tweak_of, f.block_index, f.data, rounds, out.data(), false, nr);
-    std::vector<BitCt> res(nb * 128);
-    for (size_t i = 0; i < res.size(); i++) {
-        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
-        res[i].noise = out_noise[i / 128][i % 128];  // xor with a public bit adds no noise
-        res[i].max_noise_sq = max;
+    {
+        Staged st(*this, false);
+        xts_engine_call(*engine_, st.in(key1.data(), key1.size()), st.in(key2.data(), key2.size()),
+                        st.pub(f.tweaks.data(), f.tweaks.size()), st.pub(f.data.data(), f.data.size()), f, rounds,
+                        st.out(out.data(), out.size()), nr);
+        st.finish();
     }
-    return res;
+    // xor with a public bit adds no noise
+    return wrap_bits(out, flat_noise(std::move(out_noise), nb * 128), L, max);
 }
 
 // fhe_sbox_gal_mul_pbs::key_schedule (:134-164) with ByteT::{sbox_substitute, bootstrap_assign}
@@ -1155,16 +1081,16 @@ std::vector<BitCt> Context::sbox_pbs_key_schedule(const std::vector<const BitCt 
             const size_t nbits = bits.size();
             std::vector<uint64_t> in(nbits * L), out(nbits * L);
             for (size_t t = 0; t < nbits; t++) std::memcpy(&in[t * L], bits[t]->ct.data(), L * 8);
-            std::lock_guard<std::mutex> g(mu_);
-            hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-            DevBuf d_in(in.size() * 8), d_out(out.size() * 8);
-            hip_check(hipMemcpyAsync(d_in.p, in.data(), in.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
-            if (sbox)
-                engine_->s1_multivariate(d_in.as<uint64_t>(), nbits / 8, 8, e.s1_sbox_tvs(), 8, d_out.as<uint64_t>());
-            else
-                engine_->s1_bootstrap(d_in.as<uint64_t>(), e.s1_identity_tv(), 1, d_out.as<uint64_t>(), nbits);
-            hip_check(hipMemcpyAsync(out.data(), d_out.p, out.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
-            engine_->synchronize();
+            {
+                Staged st(*this, false);
+                const uint64_t *d_in = st.in(in.data(), in.size());
+                uint64_t *d_out = st.out(out.data(), out.size());
+                if (sbox)
+                    engine_->s1_multivariate(d_in, nbits / 8, 8, e.s1_sbox_tvs(), 8, d_out);
+                else
+                    engine_->s1_bootstrap(d_in, e.s1_identity_tv(), 1, d_out, nbits);
+                st.finish();
+            }
             for (size_t t = 0; t < nbits; t++) *bits[t] = wrap(std::vector<uint64_t>(out.begin() + t * L, out.begin() + (t + 1) * L), 0);
         };
         auto bit_at = [&](int word, int byte, int bit) -> BitCt & { return ek[(word * 4 + byte) * 8 + bit]; };
@@ -1305,19 +1231,14 @@ void Context::aes_key_expand_raw(const uint64_t *key, uint64_t *expanded, bool d
     const int nk = require_key_expand(key_bits);
     const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
     aes_key_expand_noise_schedule(fresh_levels((size_t)nk * 32), nk, params().max_noise_sq);
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    if (device_mem) {
-        engine_->order_after_caller();
-        engine_->aes_key_expand(key, nk, expanded);
-        engine_->synchronize();
-        return;
+    Staged st(*this, device_mem);
+    uint64_t *d_rk = st.out(expanded, kw * L);
+    if (!device_mem) {  // the key is uploaded into its place, words 0 .. nk - 1, and expanded there
+        hip_check(hipMemcpyAsync(d_rk, key, (size_t)nk * 32 * L * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
+        key = d_rk;
     }
-    DevBuf d_rk(kw * L * 8);  // the key is uploaded into its place, words 0 .. nk - 1
-    hip_check(hipMemcpyAsync(d_rk.p, key, (size_t)nk * 32 * L * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
-    engine_->aes_key_expand(d_rk.as<uint64_t>(), nk, d_rk.as<uint64_t>());
-    hip_check(hipMemcpyAsync(expanded, d_rk.p, kw * L * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    engine_->aes_key_expand(key, nk, d_rk);
+    st.finish();
 }
 
 std::vector<BitCt> Context::aes_key_expand(const std::vector<const BitCt *> &key, int key_bits) {
@@ -1331,21 +1252,13 @@ std::vector<BitCt> Context::aes_key_expand(const std::vector<const BitCt *> &key
     const std::vector<NoiseLevel> krk = aes_key_expand_noise_schedule(kn, nk, params().max_noise_sq);
     std::vector<uint64_t> rk(kw * L);
     {
-        std::lock_guard<std::mutex> g(mu_);
-        hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-        DevBuf d_rk(rk.size() * 8);
-        hip_check(hipMemcpyAsync(d_rk.p, hk.data(), hk.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
-        engine_->aes_key_expand(d_rk.as<uint64_t>(), nk, d_rk.as<uint64_t>());
-        hip_check(hipMemcpyAsync(rk.data(), d_rk.p, rk.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
-        engine_->synchronize();
+        Staged st(*this, false);
+        uint64_t *d_rk = st.out(rk.data(), rk.size());  // the key in its place, as in aes_key_expand_raw
+        hip_check(hipMemcpyAsync(d_rk, hk.data(), hk.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
+        engine_->aes_key_expand(d_rk, nk, d_rk);
+        st.finish();
     }
-    std::vector<BitCt> res(kw);
-    for (size_t i = 0; i < res.size(); i++) {
-        res[i].ct.assign(rk.begin() + i * L, rk.begin() + (i + 1) * L);
-        res[i].noise = krk[i];
-        res[i].max_noise_sq = params().max_noise_sq;
-    }
-    return res;
+    return wrap_bits(rk, krk, L, params().max_noise_sq);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1376,38 +1289,15 @@ static std::vector<int32_t> compact_slots(std::vector<int32_t> &slots) {
     return used;
 }
 
-// fn(d_table, slots, d_in, d_bytes, d_out) on the engine stream.  Device memory: the caller's table and slots as
-// they are.  Host memory: only the referenced slots of the table are uploaded, into a compact table, and fn gets
-// the slots renumbered to it, so a slot that nothing refers to is not read in either case.
-void Context::run_multi(const uint64_t *table, const std::vector<int32_t> &slots, bool device_mem, size_t key_cts,
-                        const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes, uint64_t *out,
-                        size_t out_len,
-                        const std::function<void(const uint64_t *, const int32_t *, const uint64_t *, const uint8_t *,
-                                                 uint64_t *)> &fn) {
-    const size_t stride = key_cts * bit_len();
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    DevBuf d_bytes(n_bytes);  // the public bytes are a host array, always
-    if (n_bytes)
-        hip_check(hipMemcpyAsync(d_bytes.p, bytes, n_bytes, hipMemcpyHostToDevice, engine_->stream()), "upload data");
-    const uint8_t *db = n_bytes ? d_bytes.as<uint8_t>() : nullptr;
-    if (device_mem) {
-        engine_->order_after_caller();
-        fn(table, slots.data(), in, db, out);
-        engine_->synchronize();
-        return;
-    }
-    std::vector<int32_t> local(slots);
-    const std::vector<int32_t> used = compact_slots(local);
-    DevBuf d_tab(used.size() * stride * 8), d_in(in_len * 8), d_out(out_len * 8);
+const uint64_t *Context::Staged::table(const uint64_t *table, std::vector<int32_t> &slots, size_t stride) {
+    if (dev_) return table;
+    const std::vector<int32_t> used = compact_slots(slots);
+    uint64_t *d_tab = alloc<uint64_t>(used.size() * stride);
     for (size_t j = 0; j < used.size(); j++)
-        hip_check(hipMemcpyAsync(d_tab.as<uint64_t>() + j * stride, table + (size_t)used[j] * stride, stride * 8,
-                                 hipMemcpyHostToDevice, engine_->stream()),
+        hip_check(hipMemcpyAsync(d_tab + j * stride, table + (size_t)used[j] * stride, stride * 8, hipMemcpyHostToDevice,
+                                 e_.stream()),
                   "upload key slot");
-    if (in_len) hip_check(hipMemcpyAsync(d_in.p, in, in_len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload");
-    fn(d_tab.as<uint64_t>(), local.data(), d_in.as<uint64_t>(), db, d_out.as<uint64_t>());
-    hip_check(hipMemcpyAsync(out, d_out.p, out_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    return d_tab;
 }
 
 void Context::aes_key_expand_multi_raw(const uint64_t *keys, size_t n_keys, uint64_t *table, bool device_mem,
@@ -1417,20 +1307,9 @@ void Context::aes_key_expand_multi_raw(const uint64_t *keys, size_t n_keys, uint
     if (!n_keys) return;
     const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
     aes_key_expand_noise_schedule(fresh_levels((size_t)nk * 32), nk, params().max_noise_sq);
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    if (device_mem) {
-        engine_->order_after_caller();
-        engine_->aes_key_expand_multi(keys, nk, n_keys, table);
-        engine_->synchronize();
-        return;
-    }
-    const size_t key_len = n_keys * (size_t)nk * 32 * L, tab_len = n_keys * kw * L;
-    DevBuf d_keys(key_len * 8), d_tab(tab_len * 8);
-    hip_check(hipMemcpyAsync(d_keys.p, keys, key_len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload keys");
-    engine_->aes_key_expand_multi(d_keys.as<uint64_t>(), nk, n_keys, d_tab.as<uint64_t>());
-    hip_check(hipMemcpyAsync(table, d_tab.p, tab_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    Staged st(*this, device_mem);
+    engine_->aes_key_expand_multi(st.in(keys, n_keys * (size_t)nk * 32 * L), nk, n_keys, st.out(table, n_keys * kw * L));
+    st.finish();
 }
 
 std::vector<BitCt> Context::aes_key_expand_multi(const std::vector<const BitCt *> &keys, size_t n_keys, int key_bits) {
@@ -1449,21 +1328,11 @@ std::vector<BitCt> Context::aes_key_expand_multi(const std::vector<const BitCt *
     }
     std::vector<uint64_t> tab(n_keys * kw * L);
     {
-        std::lock_guard<std::mutex> g(mu_);
-        hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-        DevBuf d_keys(hk.size() * 8), d_tab(tab.size() * 8);
-        hip_check(hipMemcpyAsync(d_keys.p, hk.data(), hk.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
-        engine_->aes_key_expand_multi(d_keys.as<uint64_t>(), nk, n_keys, d_tab.as<uint64_t>());
-        hip_check(hipMemcpyAsync(tab.data(), d_tab.p, tab.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
-        engine_->synchronize();
+        Staged st(*this, false);
+        engine_->aes_key_expand_multi(st.in(hk.data(), hk.size()), nk, n_keys, st.out(tab.data(), tab.size()));
+        st.finish();
     }
-    std::vector<BitCt> res(n_keys * kw);
-    for (size_t i = 0; i < res.size(); i++) {
-        res[i].ct.assign(tab.begin() + i * L, tab.begin() + (i + 1) * L);
-        res[i].noise = std::move(noise[i]);
-        res[i].max_noise_sq = params().max_noise_sq;
-    }
-    return res;
+    return wrap_bits(tab, std::move(noise), L, params().max_noise_sq);
 }
 
 void Context::aes_decrypt_key_multi_raw(const uint64_t *table, size_t n_keys, uint64_t *dtable, bool device_mem,
@@ -1473,19 +1342,9 @@ void Context::aes_decrypt_key_multi_raw(const uint64_t *table, size_t n_keys, ui
     const size_t kw = (size_t)aes_words(key_bits) * 32, len = n_keys * kw * bit_len();
     aes_decrypt_key_noise_schedule(fresh_levels(kw), params().max_noise_sq, nr);
     if (table == dtable) throw ModelError{TAE_E_ARG, "the decryption keys cannot be derived in place"};
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    if (device_mem) {
-        engine_->order_after_caller();
-        engine_->aes_decrypt_key_multi(table, n_keys, dtable, nr);
-        engine_->synchronize();
-        return;
-    }
-    DevBuf d_tab(len * 8), d_dtab(len * 8);
-    hip_check(hipMemcpyAsync(d_tab.p, table, len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload table");
-    engine_->aes_decrypt_key_multi(d_tab.as<uint64_t>(), n_keys, d_dtab.as<uint64_t>(), nr);
-    hip_check(hipMemcpyAsync(dtable, d_dtab.p, len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    Staged st(*this, device_mem);
+    engine_->aes_decrypt_key_multi(st.in(table, len), n_keys, st.out(dtable, len), nr);
+    st.finish();
 }
 
 void Context::aes_blocks_multi_raw(bool inverse, const uint64_t *table, size_t n_keys, const int32_t *key_of,
@@ -1502,13 +1361,15 @@ void Context::aes_blocks_multi_raw(bool inverse, const uint64_t *table, size_t n
     else
         aes_noise_schedule(fresh_levels(kw), fresh_levels(128), rounds, params().max_noise_sq, nr);
     const size_t len = n_blocks * 128 * bit_len();
-    run_multi(table, std::vector<int32_t>(key_of, key_of + n_blocks), device_mem, kw, blocks, len, nullptr, 0, out, len,
-              [&](const uint64_t *t, const int32_t *ko, const uint64_t *in, const uint8_t *, uint64_t *o) {
-                  if (inverse)
-                      engine_->aes_decrypt_blocks_multi(t, ko, in, n_blocks, rounds, o, nr);
-                  else
-                      engine_->aes_encrypt_blocks_multi(t, ko, in, n_blocks, rounds, o, nr);
-              });
+    std::vector<int32_t> slots(key_of, key_of + n_blocks);
+    Staged st(*this, device_mem);
+    const uint64_t *d_tab = st.table(table, slots, kw * bit_len()), *d_in = st.in(blocks, len);
+    uint64_t *d_out = st.out(out, len);
+    if (inverse)
+        engine_->aes_decrypt_blocks_multi(d_tab, slots.data(), d_in, n_blocks, rounds, d_out, nr);
+    else
+        engine_->aes_encrypt_blocks_multi(d_tab, slots.data(), d_in, n_blocks, rounds, d_out, nr);
+    st.finish();
 }
 
 // the flattened blocks of the streams and their public bytes in output order (empty: every stream asks for the
@@ -1551,11 +1412,11 @@ void Context::aes_ctr_multi_raw(const uint64_t *table, size_t n_keys, const std:
                        params().max_noise_sq, nr);
     std::vector<int32_t> slots(blocks.size());
     for (size_t i = 0; i < blocks.size(); i++) slots[i] = blocks[i].slot;
-    run_multi(table, slots, device_mem, kw, nullptr, 0, pub.data(), pub.size(), out, total * 8 * bit_len(),
-              [&](const uint64_t *t, const int32_t *ko, const uint64_t *, const uint8_t *b, uint64_t *o) {
-                  for (size_t i = 0; i < blocks.size(); i++) blocks[i].slot = ko[i];
-                  engine_->aes_ctr_multi(t, blocks, rounds, b, o, nr);
-              });
+    Staged st(*this, device_mem);
+    const uint64_t *d_tab = st.table(table, slots, kw * bit_len());
+    for (size_t i = 0; i < blocks.size(); i++) blocks[i].slot = slots[i];
+    engine_->aes_ctr_multi(d_tab, blocks, rounds, st.pub(pub.data(), pub.size()), st.out(out, total * 8 * bit_len()), nr);
+    st.finish();
 }
 
 // the referenced slots of a handle table as a compact host table, with the noise of every bit; `slots` is renumbered
@@ -1604,24 +1465,13 @@ std::vector<BitCt> Context::aes_ctr_multi(const BitAt &table, size_t n_keys, con
     for (size_t i = 0; i < blocks.size(); i++) blocks[i].slot = slots[i];
     std::vector<uint64_t> out(total * 8 * L);
     {
-        std::lock_guard<std::mutex> g(mu_);
-        hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-        DevBuf d_tab(tab.size() * 8), d_pub(pub.size()), d_out(out.size() * 8);
-        hip_check(hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
-        if (!pub.empty())
-            hip_check(hipMemcpyAsync(d_pub.p, pub.data(), pub.size(), hipMemcpyHostToDevice, engine_->stream()), "up");
-        engine_->aes_ctr_multi(d_tab.as<uint64_t>(), blocks, rounds, pub.empty() ? nullptr : d_pub.as<uint8_t>(),
-                               d_out.as<uint64_t>(), nr);
-        hip_check(hipMemcpyAsync(out.data(), d_out.p, out.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
-        engine_->synchronize();
+        Staged st(*this, false);
+        engine_->aes_ctr_multi(st.in(tab.data(), tab.size()), blocks, rounds, st.pub(pub.data(), pub.size()),
+                               st.out(out.data(), out.size()), nr);
+        st.finish();
     }
-    std::vector<BitCt> res(total * 8);
-    for (size_t i = 0; i < res.size(); i++) {
-        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
-        res[i].noise = std::move(noise[i]);  // xor with a public bit adds no noise
-        res[i].max_noise_sq = params().max_noise_sq;
-    }
-    return res;
+    // xor with a public bit adds no noise
+    return wrap_bits(out, std::move(noise), L, params().max_noise_sq);
 }
 
 // per block of the flattened streams: slot, the ciphertext block and the block before it (the iv first)
@@ -1655,10 +1505,12 @@ void Context::aes_cbc_multi_raw(const uint64_t *dtable, size_t n_keys, const std
     if (!nb) return;
     aes_decrypt_noise_schedule(fresh_levels(kw), std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds,
                                params().max_noise_sq, nr);
-    run_multi(dtable, slots, device_mem, kw, nullptr, 0, pub.data(), pub.size(), out, nb * 128 * bit_len(),
-              [&](const uint64_t *t, const int32_t *ko, const uint64_t *, const uint8_t *b, uint64_t *o) {
-                  engine_->aes_cbc_transcipher_multi(t, ko, b, b + nb * 16, nb, rounds, o, nr);
-              });
+    Staged st(*this, device_mem);
+    const uint64_t *d_tab = st.table(dtable, slots, kw * bit_len());
+    const uint8_t *d_pub = st.pub(pub.data(), pub.size());
+    engine_->aes_cbc_transcipher_multi(d_tab, slots.data(), d_pub, d_pub + nb * 16, nb, rounds,
+                                       st.out(out, nb * 128 * bit_len()), nr);
+    st.finish();
 }
 
 std::vector<BitCt> Context::aes_cbc_multi(const BitAt &dtable, size_t n_keys, const std::vector<CbcStreamIn> &streams,
@@ -1679,23 +1531,14 @@ std::vector<BitCt> Context::aes_cbc_multi(const BitAt &dtable, size_t n_keys, co
             noise.push_back(std::move(x));
     std::vector<uint64_t> out(nb * 128 * L);
     {
-        std::lock_guard<std::mutex> g(mu_);
-        hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-        DevBuf d_tab(tab.size() * 8), d_pub(pub.size()), d_out(out.size() * 8);
-        hip_check(hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "up");
-        hip_check(hipMemcpyAsync(d_pub.p, pub.data(), pub.size(), hipMemcpyHostToDevice, engine_->stream()), "up");
-        engine_->aes_cbc_transcipher_multi(d_tab.as<uint64_t>(), slots.data(), d_pub.as<uint8_t>(),
-                                           d_pub.as<uint8_t>() + nb * 16, nb, rounds, d_out.as<uint64_t>(), nr);
-        hip_check(hipMemcpyAsync(out.data(), d_out.p, out.size() * 8, hipMemcpyDeviceToHost, engine_->stream()), "dn");
-        engine_->synchronize();
+        Staged st(*this, false);
+        const uint8_t *d_pub = st.pub(pub.data(), pub.size());
+        engine_->aes_cbc_transcipher_multi(st.in(tab.data(), tab.size()), slots.data(), d_pub, d_pub + nb * 16, nb, rounds,
+                                           st.out(out.data(), out.size()), nr);
+        st.finish();
     }
-    std::vector<BitCt> res(nb * 128);
-    for (size_t i = 0; i < res.size(); i++) {
-        res[i].ct.assign(out.begin() + i * L, out.begin() + (i + 1) * L);
-        res[i].noise = std::move(noise[i]);  // xor with a public bit adds no noise
-        res[i].max_noise_sq = params().max_noise_sq;
-    }
-    return res;
+    // xor with a public bit adds no noise
+    return wrap_bits(out, std::move(noise), L, params().max_noise_sq);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1793,44 +1636,29 @@ void Context::aes_pub_keystream_multi_raw(const uint64_t *table, size_t n_keys, 
         pb[i].out_byte = (int64_t)(16 * i);
         pb[i].len = 16;
     }
-    run_multi(table, std::vector<int32_t>(slots, slots + n_blocks), device_mem, kw, nullptr, 0, nullptr, 0, out,
-              n_blocks * 128 * bit_len(),
-              [&](const uint64_t *t, const int32_t *ko, const uint64_t *, const uint8_t *, uint64_t *o) {
-                  for (size_t i = 0; i < n_blocks; i++) pb[i].slot = ko[i];
-                  engine_->aes_pub_blocks_multi(t, pb, rounds, o, nr);
-              });
+    std::vector<int32_t> ko(slots, slots + n_blocks);
+    Staged st(*this, device_mem);
+    const uint64_t *d_tab = st.table(table, ko, kw * bit_len());
+    for (size_t i = 0; i < n_blocks; i++) pb[i].slot = ko[i];
+    engine_->aes_pub_blocks_multi(d_tab, pb, rounds, st.out(out, n_blocks * 128 * bit_len()), nr);
+    st.finish();
 }
 
-void Context::run_ccm(const uint64_t *table, std::vector<int32_t> slots, const std::vector<CcmFrame> &frames,
-                      const std::vector<CcmStreamIn> &streams, int tag_len, int rounds, int nr, size_t key_cts,
-                      uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem) {
-    const size_t n = frames.size(), S = bit_len(), stride = key_cts * S;
+// the frames of a CCM call through the engine; host memory uploads the referenced slots alone
+void Context::ccm_call(const uint64_t *table, std::vector<int32_t> slots, const std::vector<CcmFrame> &frames,
+                       const std::vector<CcmStreamIn> &streams, int tag_len, int rounds, int nr, size_t key_cts,
+                       uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem) {
+    const size_t n = frames.size(), S = bit_len();
     size_t total = 0;
     for (const CcmFrame &f : frames) total += f.payload_len;
-    const size_t plain_len = total * 8 * S, tag_len_w = n * 8 * (size_t)tag_len * S;
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    std::vector<int32_t> used;
-    if (!device_mem) used = compact_slots(slots);
+    Staged st(*this, device_mem);
+    const uint64_t *d_tab = st.table(table, slots, key_cts * S);
     std::vector<Engine::CcmStreamIn> in(n);
     for (size_t s = 0; s < n; s++)
         in[s] = {slots[s], &frames[s], streams[s].data, streams[s].data + frames[s].payload_len};
-    if (device_mem) {
-        engine_->order_after_caller();
-        engine_->aes_ccm_transcipher(table, in, rounds, nr, out_plain, out_tag_diff);
-        engine_->synchronize();
-        return;
-    }
-    DevBuf d_tab(used.size() * stride * 8), d_plain(plain_len * 8), d_tag(tag_len_w * 8);
-    for (size_t j = 0; j < used.size(); j++)
-        hip_check(hipMemcpyAsync(d_tab.as<uint64_t>() + j * stride, table + (size_t)used[j] * stride, stride * 8,
-                                 hipMemcpyHostToDevice, engine_->stream()),
-                  "upload key slot");
-    engine_->aes_ccm_transcipher(d_tab.as<uint64_t>(), in, rounds, nr, d_plain.as<uint64_t>(), d_tag.as<uint64_t>());
-    if (plain_len)
-        hip_check(hipMemcpyAsync(out_plain, d_plain.p, plain_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    hip_check(hipMemcpyAsync(out_tag_diff, d_tag.p, tag_len_w * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    uint64_t *d_plain = st.out(out_plain, total * 8 * S), *d_tag = st.out(out_tag_diff, n * 8 * (size_t)tag_len * S);
+    engine_->aes_ccm_transcipher(d_tab, in, rounds, nr, d_plain, d_tag);
+    st.finish();
 }
 
 void Context::aes_ccm_multi_raw(const uint64_t *table, size_t n_keys, const std::vector<CcmStreamIn> &streams,
@@ -1851,7 +1679,7 @@ void Context::aes_ccm_multi_raw(const uint64_t *table, size_t n_keys, const std:
         seen.push_back(&f);
         aes_ccm_noise_schedule(fresh_levels(kw), f, rounds, params().max_noise_sq, nr);
     }
-    run_ccm(table, slots, frames, streams, tag_len, rounds, nr, kw, out_plain, out_tag_diff, device_mem);
+    ccm_call(table, slots, frames, streams, tag_len, rounds, nr, kw, out_plain, out_tag_diff, device_mem);
 }
 
 Context::CcmBits Context::aes_ccm_multi(const BitAt &table, size_t n_keys, const std::vector<CcmStreamIn> &streams,
@@ -1871,19 +1699,9 @@ Context::CcmBits Context::aes_ccm_multi(const BitAt &table, size_t n_keys, const
         for (NoiseLevel &x : cn.tag_diff) tn.push_back(std::move(x));
     }
     std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
-    run_ccm(tab.data(), slots, frames, streams, tag_len, rounds, nr, kw, plain.data(), tag.data(), false);
-    CcmBits res;
-    auto wrap_bits = [&](const std::vector<uint64_t> &w, std::vector<NoiseLevel> &noise, std::vector<BitCt> &bits) {
-        bits.resize(noise.size());
-        for (size_t i = 0; i < bits.size(); i++) {
-            bits[i].ct.assign(w.begin() + i * L, w.begin() + (i + 1) * L);
-            bits[i].noise = std::move(noise[i]);  // xor with a public bit adds no noise
-            bits[i].max_noise_sq = params().max_noise_sq;
-        }
-    };
-    wrap_bits(plain, pn, res.plain);
-    wrap_bits(tag, tn, res.tag_diff);
-    return res;
+    ccm_call(tab.data(), slots, frames, streams, tag_len, rounds, nr, kw, plain.data(), tag.data(), false);
+    // xor with a public bit adds no noise
+    return {wrap_bits(plain, std::move(pn), L, params().max_noise_sq), wrap_bits(tag, std::move(tn), L, params().max_noise_sq)};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1891,10 +1709,11 @@ Context::CcmBits Context::aes_ccm_multi(const BitAt &table, size_t n_keys, const
 // ---------------------------------------------------------------------------------------------
 namespace {
 // the sums of a row-sum plan on metadata, every one validated; the largest level met goes to *top
-std::vector<NoiseLevel> rowsum_noise(const std::vector<NoiseLevel> &src, const GcmRowPlan &p, uint64_t max, uint64_t *top) {
+std::vector<NoiseLevel> rowsum_noise(const std::vector<NoiseLevel> &src, const RowPlan &p, uint64_t max, uint64_t *top) {
     std::vector<NoiseLevel> out(p.n_rows());
     for (size_t r = 0; r < p.n_rows(); r++) {
-        for (int32_t q = p.row_start[r]; q < p.row_start[r + 1]; q++) out[r].add_assign(src[(size_t)p.src[q]], max);
+        const size_t l = p.list_of.empty() ? r : (size_t)p.list_of[r], base = p.base_of.empty() ? 0 : (size_t)p.base_of[r];
+        for (int32_t q = p.row_start[l]; q < p.row_start[l + 1]; q++) out[r].add_assign(src[base + (size_t)p.src[q]], max);
         if (top && out[r].noise_level_squared > *top) *top = out[r].noise_level_squared;
     }
     return out;
@@ -1924,9 +1743,11 @@ GhashKeyNoise aes_ghash_key_noise_schedule(const std::vector<NoiseLevel> &rk, in
     aes_noise_schedule(rk, std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds, max, nr);
     put(1, fresh_levels(128));
     const GcmProductPlan pp = gcm_product_plan();
+    RowPlan sq = gcm_square_plan();
     for (const GcmGeneration &gen : gcm_power_schedule(n_powers)) {
         for (int k : gen.squares) {
-            rowsum_noise(out.table, gcm_square_plan((size_t)(k / 2 - 1)), max, &out.max_square);
+            sq.base_of.assign(128, (k / 2 - 1) * 128);  // the operand: H^(k/2)
+            rowsum_noise(out.table, sq, max, &out.max_square);
             put(k, fresh_levels(128));  // refreshed even at 5: table entries must not share ids with each other
         }
         for (int k : gen.products) {
@@ -1995,11 +1816,9 @@ void Context::aes_ghash_key_raw(const uint64_t *rk, int n_powers, int rounds, ui
     const int nr = require_inverse(rounds, key_bits);
     const size_t kw = (size_t)aes_words(key_bits) * 32;
     aes_ghash_key_noise_schedule(fresh_levels(kw), n_powers, rounds, params().max_noise_sq, nr);
-    run_inverse(rk, nullptr, 0, nullptr, 0, out, (size_t)n_powers * 128 * bit_len(), device_mem,
-                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) {
-                    engine_->ghash_key(k, n_powers, rounds, nr, o);
-                },
-                kw);
+    Staged st(*this, device_mem);
+    engine_->ghash_key(st.in(rk, kw * bit_len()), n_powers, rounds, nr, st.out(out, (size_t)n_powers * 128 * bit_len()));
+    st.finish();
 }
 
 std::vector<BitCt> Context::aes_ghash_key(const std::vector<const BitCt *> &expanded_key, int n_powers, int rounds,
@@ -2012,46 +1831,28 @@ std::vector<BitCt> Context::aes_ghash_key(const std::vector<const BitCt *> &expa
     for (size_t i = 0; i < kw; i++) krk[i] = expanded_key[i]->noise;
     GhashKeyNoise kn = aes_ghash_key_noise_schedule(krk, n_powers, rounds, params().max_noise_sq, nr);
     std::vector<uint64_t> hk(kn.table.size() * L);
-    run_inverse(rk.data(), nullptr, 0, nullptr, 0, hk.data(), hk.size(), false,
-                [&](const uint64_t *k, const uint64_t *, const uint8_t *, uint64_t *o) {
-                    engine_->ghash_key(k, n_powers, rounds, nr, o);
-                },
-                kw);
-    std::vector<BitCt> res(kn.table.size());
-    for (size_t i = 0; i < res.size(); i++) {
-        res[i].ct.assign(hk.begin() + i * L, hk.begin() + (i + 1) * L);
-        res[i].noise = std::move(kn.table[i]);
-        res[i].max_noise_sq = params().max_noise_sq;
+    {
+        Staged st(*this, false);
+        engine_->ghash_key(st.in(rk.data(), rk.size()), n_powers, rounds, nr, st.out(hk.data(), hk.size()));
+        st.finish();
     }
-    return res;
+    return wrap_bits(hk, std::move(kn.table), L, params().max_noise_sq);
 }
 
-void Context::run_gcm(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrame> &frames,
-                      const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int nr, size_t key_cts,
-                      uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem) {
+// the frames of a GCM call through the engine
+void Context::gcm_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrame> &frames,
+                       const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int nr, size_t key_cts,
+                       uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem) {
     const size_t n = frames.size(), S = bit_len();
     size_t total = 0;
     for (const GcmFrame &f : frames) total += f.data_len;
-    const size_t plain_len = total * 8 * S, tag_w = n * 8 * (size_t)tag_len * S, hk_len = n_powers * 128 * S;
     std::vector<Engine::GcmFrameIn> ein(n);
     for (size_t s = 0; s < n; s++) ein[s] = {&frames[s], in[s].data, in[s].data + frames[s].data_len};
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    if (device_mem) {
-        engine_->order_after_caller();
-        engine_->aes_gcm_transcipher(rk, hk, n_powers, ein, rounds, nr, out_plain, out_tag_diff);
-        engine_->synchronize();
-        return;
-    }
-    DevBuf d_rk(key_cts * S * 8), d_hk(hk_len * 8), d_plain(plain_len * 8), d_tag(tag_w * 8);
-    hip_check(hipMemcpyAsync(d_rk.p, rk, key_cts * S * 8, hipMemcpyHostToDevice, engine_->stream()), "upload key");
-    hip_check(hipMemcpyAsync(d_hk.p, hk, hk_len * 8, hipMemcpyHostToDevice, engine_->stream()), "upload power table");
-    engine_->aes_gcm_transcipher(d_rk.as<uint64_t>(), d_hk.as<uint64_t>(), n_powers, ein, rounds, nr, d_plain.as<uint64_t>(),
-                                 d_tag.as<uint64_t>());
-    if (plain_len)
-        hip_check(hipMemcpyAsync(out_plain, d_plain.p, plain_len * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    hip_check(hipMemcpyAsync(out_tag_diff, d_tag.p, tag_w * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    Staged st(*this, device_mem);
+    const uint64_t *d_rk = st.in(rk, key_cts * S), *d_hk = st.in(hk, n_powers * 128 * S);
+    uint64_t *d_plain = st.out(out_plain, total * 8 * S), *d_tag = st.out(out_tag_diff, n * 8 * (size_t)tag_len * S);
+    engine_->aes_gcm_transcipher(d_rk, d_hk, n_powers, ein, rounds, nr, d_plain, d_tag);
+    st.finish();
 }
 
 void Context::aes_gcm_raw(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrameIn> &in,
@@ -2065,7 +1866,7 @@ void Context::aes_gcm_raw(const uint64_t *rk, const uint64_t *hk, size_t n_power
     const size_t kw = (size_t)aes_words(key_bits) * 32;
     const std::vector<NoiseLevel> krk = fresh_levels(kw), khk = fresh_levels(n_powers * 128);
     for (const GcmFrame &f : frames) aes_gcm_noise_schedule(krk, khk, f, rounds, params().max_noise_sq, nr);
-    run_gcm(rk, hk, n_powers, frames, in, tag_len, rounds, nr, kw, out_plain, out_tag_diff, device_mem);
+    gcm_call(rk, hk, n_powers, frames, in, tag_len, rounds, nr, kw, out_plain, out_tag_diff, device_mem);
 }
 
 Context::GcmBits Context::aes_gcm(const std::vector<const BitCt *> &expanded_key, const std::vector<const BitCt *> &hk,
@@ -2089,40 +1890,27 @@ Context::GcmBits Context::aes_gcm(const std::vector<const BitCt *> &expanded_key
     }
     const std::vector<uint64_t> rk = gather_bits(expanded_key, L), table = gather_bits(hk, L);
     std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
-    run_gcm(rk.data(), table.data(), n_powers, frames, in, tag_len, rounds, nr, kw, plain.data(), tag.data(), false);
-    GcmBits res;
-    auto wrap_bits = [&](const std::vector<uint64_t> &w, std::vector<NoiseLevel> &noise, std::vector<BitCt> &bits) {
-        bits.resize(noise.size());
-        for (size_t i = 0; i < bits.size(); i++) {
-            bits[i].ct.assign(w.begin() + i * L, w.begin() + (i + 1) * L);
-            bits[i].noise = std::move(noise[i]);  // xor with a public bit adds no noise
-            bits[i].max_noise_sq = params().max_noise_sq;
-        }
-    };
-    wrap_bits(plain, pn, res.plain);
-    wrap_bits(tag, tn, res.tag_diff);
-    return res;
+    gcm_call(rk.data(), table.data(), n_powers, frames, in, tag_len, rounds, nr, kw, plain.data(), tag.data(), false);
+    // xor with a public bit adds no noise
+    return {wrap_bits(plain, std::move(pn), L, params().max_noise_sq), wrap_bits(tag, std::move(tn), L, params().max_noise_sq)};
 }
 
 void Context::gf128_square_raw(const uint64_t *in, size_t count, uint64_t *out, bool device_mem) {
     if (params().model != 1) throw ModelError{TAE_E_PARAM, "GCM runs on the 1-bit WoP-PBS parameter sets only"};
     if (!count) return;
     const size_t len = count * 128 * bit_len();
-    run_inverse(nullptr, in, len, nullptr, 0, out, len, device_mem,
-                [&](const uint64_t *, const uint64_t *i, const uint8_t *, uint64_t *o) { engine_->gf128_square(i, count, o); },
-                0);
+    Staged st(*this, device_mem);
+    engine_->gf128_square(st.in(in, len), count, st.out(out, len));
+    st.finish();
 }
 
 void Context::gf128_product_raw(const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out, bool device_mem) {
     if (params().model != 1) throw ModelError{TAE_E_PARAM, "GCM runs on the 1-bit WoP-PBS parameter sets only"};
     if (!count) return;
     const size_t len = count * 128 * bit_len();
-    // the second operand travels as run_inverse's key
-    run_inverse(b, a, len, nullptr, 0, out, len, device_mem,
-                [&](const uint64_t *kb, const uint64_t *ia, const uint8_t *, uint64_t *o) {
-                    engine_->gf128_product(ia, kb, count, o);
-                },
-                count * 128);
+    Staged st(*this, device_mem);
+    engine_->gf128_product(st.in(a, len), st.in(b, len), count, st.out(out, len));
+    st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2137,22 +1925,9 @@ void Context::s1_bootstrap_raw(const uint64_t *in, size_t B, const uint64_t *tvs
     require_s1();
     if (n_tv < 1) throw ModelError{TAE_E_ARG, "at least one test vector"};
     const size_t L = bit_len(), G = params().glwe_len();
-    // the test vectors are host arrays, always (like the LUTs of the other models)
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    DevBuf d_tv(n_tv * G * 8);
-    hip_check(hipMemcpyAsync(d_tv.p, tvs, n_tv * G * 8, hipMemcpyHostToDevice, engine_->stream()), "tv upload");
-    if (device_mem) {
-        engine_->order_after_caller();
-        engine_->s1_bootstrap(in, d_tv.as<uint64_t>(), n_tv, out, B);
-        engine_->synchronize();
-        return;
-    }
-    DevBuf d_in(B * L * 8), d_out(B * L * 8);
-    hip_check(hipMemcpyAsync(d_in.p, in, B * L * 8, hipMemcpyHostToDevice, engine_->stream()), "upload");
-    engine_->s1_bootstrap(d_in.as<uint64_t>(), d_tv.as<uint64_t>(), n_tv, d_out.as<uint64_t>(), B);
-    hip_check(hipMemcpyAsync(out, d_out.p, B * L * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    Staged st(*this, device_mem);
+    engine_->s1_bootstrap(st.in(in, B * L), st.pub(tvs, n_tv * G), n_tv, st.out(out, B * L), B);
+    st.finish();
 }
 
 // ---- packed ciphertext I/O (glwe_pack.hpp) ----
@@ -2165,8 +1940,9 @@ void Context::require_pack(size_t count) const {
 void Context::unpack_bits_raw(const uint64_t *glwes, size_t count, uint64_t *bits, bool device_mem) {
     require_pack(count);
     const size_t G = glwe_pack::glwe_count(count, params().N);
-    run8(glwes, G * params().glwe_len(), bits, count * bit_len(), device_mem,
-         [&](const uint64_t *i, uint64_t *o, const uint64_t *) { engine_->unpack_bits(i, count, o); }, nullptr);
+    Staged st(*this, device_mem);
+    engine_->unpack_bits(st.in(glwes, G * params().glwe_len()), count, st.out(bits, count * bit_len()));
+    st.finish();
 }
 
 std::vector<BitCt> Context::unpack_bits(const uint64_t *glwes, size_t count) {
@@ -2183,8 +1959,9 @@ std::vector<BitCt> Context::unpack_bits(const uint64_t *glwes, size_t count) {
 void Context::pack_bits_raw(const uint64_t *bits, size_t count, uint64_t *glwes, bool device_mem) {
     require_pack(count);
     const size_t G = glwe_pack::glwe_count(count, params().N);
-    run8(bits, count * bit_len(), glwes, G * params().glwe_len(), device_mem,
-         [&](const uint64_t *i, uint64_t *o, const uint64_t *) { engine_->pack_bits(i, count, o); }, nullptr);
+    Staged st(*this, device_mem);
+    engine_->pack_bits(st.in(bits, count * bit_len()), count, st.out(glwes, G * params().glwe_len()));
+    st.finish();
 }
 
 void Context::pack_bits(const std::vector<const BitCt *> &bits, uint64_t *glwes) {
@@ -2200,15 +1977,17 @@ void Context::pack_bits(const std::vector<const BitCt *> &bits, uint64_t *glwes)
 
 void Context::pack_pfks_raw(const uint64_t *bits, size_t count, uint64_t *glwes, bool device_mem) {
     require_pack(count);
-    run8(bits, count * bit_len(), glwes, count * params().glwe_len(), device_mem,
-         [&](const uint64_t *i, uint64_t *o, const uint64_t *) { engine_->pack_pfks(i, count, o); }, nullptr);
+    Staged st(*this, device_mem);
+    engine_->pack_pfks(st.in(bits, count * bit_len()), count, st.out(glwes, count * params().glwe_len()));
+    st.finish();
 }
 
 void Context::s1_packing_keyswitch_raw(const uint64_t *cts, size_t count, uint64_t *glwe, bool device_mem) {
     require_s1();
     if (count < 1 || count > (size_t)params().N) throw ModelError{TAE_E_ARG, "packing keyswitch takes 1..N ciphertexts"};
-    run8(cts, count * bit_len(), glwe, params().glwe_len(), device_mem,
-         [&](const uint64_t *i, uint64_t *o, const uint64_t *) { engine_->s1_pack(i, (int)count, o); }, nullptr);
+    Staged st(*this, device_mem);
+    engine_->s1_pack(st.in(cts, count * bit_len()), (int)count, st.out(glwe, params().glwe_len()));
+    st.finish();
 }
 
 void Context::s1_test_vectors_from_ciphertexts_raw(const uint64_t *ct0, const uint64_t *ct1, size_t B, uint64_t *tvs,
@@ -2251,21 +2030,10 @@ void Context::s1_multivariate_raw(const uint64_t *bits, size_t G, int nbits, con
             if (tab[2 * v] > 1 || tab[2 * v + 1] > 1) throw ModelError{TAE_E_ARG, "function values must be 0 or 1"};
             s1_test_vector(params(), tab[2 * v], tab[2 * v + 1], &tvs[((size_t)f * V + v) * GL]);
         }
-    std::lock_guard<std::mutex> g(mu_);
-    hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
-    DevBuf d_tv(tvs.size() * 8);
-    hip_check(hipMemcpyAsync(d_tv.p, tvs.data(), tvs.size() * 8, hipMemcpyHostToDevice, engine_->stream()), "tv upload");
-    if (device_mem) {
-        engine_->order_after_caller();
-        engine_->s1_multivariate(bits, G, nbits, d_tv.as<uint64_t>(), n_fn, out);
-        engine_->synchronize();
-        return;
-    }
-    DevBuf d_in(G * nbits * L * 8), d_out(G * n_fn * L * 8);
-    hip_check(hipMemcpyAsync(d_in.p, bits, G * nbits * L * 8, hipMemcpyHostToDevice, engine_->stream()), "upload");
-    engine_->s1_multivariate(d_in.as<uint64_t>(), G, nbits, d_tv.as<uint64_t>(), n_fn, d_out.as<uint64_t>());
-    hip_check(hipMemcpyAsync(out, d_out.p, G * n_fn * L * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
-    engine_->synchronize();
+    Staged st(*this, device_mem);
+    engine_->s1_multivariate(st.in(bits, G * nbits * L), G, nbits, st.pub(tvs.data(), tvs.size()), n_fn,
+                             st.out(out, G * n_fn * L));
+    st.finish();
 }
 
 }  // namespace tae

@@ -290,8 +290,7 @@ class Context {  // FheContext
 
   private:
     void require_s1() const;
-    template <class F>
-    void run8(const uint64_t *in, size_t in_len, uint64_t *out, size_t out_len, bool device_mem, F fn, const Lut *lut);
+    class Staged;  // the staging scope of an entry point (model.cpp)
     std::vector<BitCt> sbox_pbs_key_schedule(const std::vector<const BitCt *> &key);
     std::vector<NoiseLevel> block_noise_schedule(AesDriver driver, const std::vector<NoiseLevel> &rk,
                                                  const std::vector<NoiseLevel> &block, int rounds, int nr = 10) const;
@@ -300,27 +299,13 @@ class Context {  // FheContext
     int check_ctr(uint64_t first_counter, size_t n_blocks, int rounds, int key_bits) const;
     int require_inverse(int rounds, int key_bits) const;
     int require_multi(int key_bits, int rounds) const;
-    void run_multi(const uint64_t *table, const std::vector<int32_t> &slots, bool device_mem, size_t key_cts,
-                   const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes, uint64_t *out, size_t out_len,
-                   const std::function<void(const uint64_t *, const int32_t *, const uint64_t *, const uint8_t *,
-                                            uint64_t *)> &fn);
-    void run_inverse(const uint64_t *key, const uint64_t *in, size_t in_len, const uint8_t *bytes, size_t n_bytes,
-                     uint64_t *out, size_t out_len, bool device_mem,
-                     const std::function<void(const uint64_t *, const uint64_t *, const uint8_t *, uint64_t *)> &fn,
-                     size_t key_cts);
-    // the flattened blocks of an XTS call through the engine: distinct tweaks [n][16], per block its tweak, its
-    // index in the unit and its 16 ciphertext bytes
-    void run_xts(const uint64_t *dk1, const uint64_t *rk2, size_t key_cts, const std::vector<uint8_t> &tweaks,
-                 const std::vector<int32_t> &tweak_of, const std::vector<uint64_t> &block_index,
-                 const std::vector<uint8_t> &data, int rounds, uint64_t *out, bool device_mem, int nr);
-    // the frames of a CCM call through the engine; host memory uploads the referenced slots alone, as run_multi
-    void run_ccm(const uint64_t *table, std::vector<int32_t> slots, const std::vector<CcmFrame> &frames,
-                 const std::vector<CcmStreamIn> &streams, int tag_len, int rounds, int nr, size_t key_cts,
-                 uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem);
-    // the frames of a GCM call through the engine
-    void run_gcm(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrame> &frames,
-                 const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int nr, size_t key_cts, uint64_t *out_plain,
-                 uint64_t *out_tag_diff, bool device_mem);
+    // the frames of a CCM / GCM call through the engine, host or device arrays
+    void ccm_call(const uint64_t *table, std::vector<int32_t> slots, const std::vector<CcmFrame> &frames,
+                  const std::vector<CcmStreamIn> &streams, int tag_len, int rounds, int nr, size_t key_cts,
+                  uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem);
+    void gcm_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrame> &frames,
+                  const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int nr, size_t key_cts, uint64_t *out_plain,
+                  uint64_t *out_tag_diff, bool device_mem);
     void run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
                      const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem, int nr);
     void run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint64_t *d_in, size_t n_blocks, int rounds,
