@@ -168,13 +168,14 @@ def test_context_shared_across_host_threads(gpu_context, client):
 
 def _pbs_main_cts(B):
     """The ciphertexts Engine::bootstrap gives the throughput kernel for a batch of B (kernels.hip): whole
-    rounds of 3 x CUs, a remainder of at most min(TAE_BR_LAT_MAX, CUs) going to br512lat."""
+    rounds of cpw x CUs (cpw = 3 ciphertexts per workgroup on br512x4, 2 with TAE_PBS_KERNEL=p16), a remainder of
+    at most min(TAE_BR_LAT_MAX, CUs) going to br512lat."""
     import torch
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     lat_max = int(os.environ.get("TAE_BR_LAT_MAX", "256"))
     if B <= lat_max:
         return 0
-    per_round = 3 * cus
+    per_round = (2 if os.environ.get("TAE_PBS_KERNEL") == "p16" else 3) * cus
     rest = B % per_round
     return B - rest if (B > per_round and 0 < rest <= min(lat_max, cus)) else B
 

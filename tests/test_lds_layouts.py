@@ -39,6 +39,18 @@ def test_br512x4_spectrum_layout_is_conflict_free():
     assert all(c == 0 for c in costs.values()), costs
 
 
+def test_br512p16_job_layout_is_conflict_free(monkeypatch):
+    """br512p16's XOR-swizzled job regions, digit slots and MAC accesses; its MAC stores go through br512x4's
+    sidx layout, so the model takes the SF / SG tables the header ships, not the script's own copy."""
+    import p16_banks
+    src = _header("br512x4.hpp")
+    monkeypatch.setattr(p16_banks, "X4_TABLES", (_table(src, "SF"), _table(src, "SG1"), _table(src, "SG3")))
+    assert p16_banks.bijective()
+    costs = p16_banks.cost()
+    assert any(name.startswith("mac_st") for name in costs) and len(costs) == 16 + 32 + 4 + 1 + 8
+    assert all(c == 0 for c in costs.values()), {k: v for k, v in costs.items() if v}
+
+
 def test_br1024_mac_positions():
     src = _header("br1024.hpp")
     body = re.search(r"int mac_pos\(int tid\) \{(.*?)\n\}", src, re.S).group(1)

@@ -106,7 +106,12 @@ void staged(tae_context const *ctx, const TI *in, size_t in_bytes, TO *out, size
         tae::hip_check(hipMemcpyAsync(daux.p, aux, aux_bytes, hipMemcpyHostToDevice, e.stream()), "upload aux");
         aux = static_cast<const uint64_t *>(daux.p);
     }
-    auto call = [&](const TI *a, TO *b) { fn(a, b, aux); };
+    // a stage call owns the stage times (Engine::begin_call): bootstrap() records the throughput kernel's span
+    auto call = [&](const TI *a, TO *b) {
+        e.begin_call();
+        fn(a, b, aux);
+        e.end_call();
+    };
     if (mem == TAE_MEM_DEVICE) {
         e.order_after_caller();
         call(in, out);

@@ -278,6 +278,12 @@ class Engine {
     // waits on an event recorded on this caller stream (no host sync, other streams not waited for)
     void set_caller_stream(hipStream_t s) { caller_stream_ = s; }
     const StageTimes &last_times() const { return times_; }
+    // The AES and mode drivers restart the stage times themselves.  A public call that reaches a stage directly (the
+    // circuit bootstrap, the 8-bit and shortint_1bit entry points, unpack, the stage calls) brackets it with these: the
+    // times and launch counts are that call's alone, and the spans it recorded are summed and their events returned
+    // to the pool before the next call.  pack_bits does neither: its callers read the last batched call's slots
+    void begin_call() { times_ = StageTimes{}; }
+    void end_call() { collect_times(); }
     // the kernel of the last pfks_into_ggsw launch: "g6", "s16", "w32" or "w16" (K-layout GEMMs, TAE_PFKS_GEMM),
     // "rows" (6-bit row-tile GEMM), "u64" (scalar kernel), "none" before the first
     const char *last_pfks_kernel() const { return last_pfks_kernel_; }

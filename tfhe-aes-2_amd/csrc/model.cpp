@@ -176,8 +176,15 @@ class Context::Staged {
     // a key table [..][stride]: the caller's, or a compact upload of only the slots that `slots` refers to, which is
     // rewritten to index it, so a slot that nothing refers to is not read in either case
     const uint64_t *table(const uint64_t *table, std::vector<int32_t> &slots, size_t stride);
+    // a call outside the engine's AES and mode drivers (Engine::begin_call): the stage times restart here, after
+    // the call's own checks, and finish() sums what it recorded
+    void own_times() {
+        e_.begin_call();
+        own_times_ = true;
+    }
     // the downloads, in the order of their out() calls, then the engine's synchronize
     void finish() {
+        if (own_times_) e_.end_call();
         for (const Download &d : downloads_)
             if (d.bytes) hip_check(hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, e_.stream()), "download");
         e_.synchronize();
@@ -203,6 +210,7 @@ class Context::Staged {
     std::lock_guard<std::mutex> lock_;
     Engine &e_;
     const bool dev_;
+    bool own_times_ = false;
     std::deque<DevBuf> bufs_;  // freed before the lock is released
     std::vector<Download> downloads_;
 };
@@ -234,6 +242,7 @@ void Context::bootstrap_from_bits_raw(const uint64_t *bits, size_t groups, const
     if (params().model != 8) throw ModelError{TAE_E_PARAM, "bootstrap_from_bits belongs to the 8-bit model"};
     if (lut.input_bits != 8) throw ModelError{TAE_E_ARG, "bootstrap_from_bits needs an 8-bit LUT"};
     Staged st(*this, device_mem);
+    st.own_times();
     engine_->cbs_vp(st.in(bits, groups * 8 * bit_len()), groups, 8, st.pub(lut.data.data(), lut.data.size()), 1,
                     st.out(out, groups * params().big_len()));
     st.finish();
@@ -242,6 +251,7 @@ void Context::bootstrap_from_bits_raw(const uint64_t *bits, size_t groups, const
 void Context::extract_bits_raw(const uint64_t *ints, size_t groups, uint64_t *out, bool device_mem) {
     if (params().model != 8) throw ModelError{TAE_E_PARAM, "extract_bits_from_ciphertext belongs to the 8-bit model"};
     Staged st(*this, device_mem);
+    st.own_times();
     engine_->extract_bits(st.in(ints, groups * params().big_len()), groups, 56, 8, st.out(out, groups * 8 * bit_len()));
     st.finish();
 }
@@ -250,6 +260,7 @@ void Context::circuit_bootstrap_raw(const uint64_t *bits, size_t groups, int n_i
                                     bool device_mem) {
     if (n_in != lut.input_bits) throw ModelError{TAE_E_ARG, "number of input bits does not match the LUT"};
     Staged st(*this, device_mem);
+    st.own_times();
     const uint64_t *d_lut = st.pub(lut.data.data(), lut.data.size());
     if (params().model == 8) {
         // Byte::bootstrap_with_lut (fhe_impls/shortint_woppbs_8bit.rs:37-42): bits [G][8][n+1] -> [G][8][n+1]
@@ -1926,6 +1937,7 @@ void Context::s1_bootstrap_raw(const uint64_t *in, size_t B, const uint64_t *tvs
     if (n_tv < 1) throw ModelError{TAE_E_ARG, "at least one test vector"};
     const size_t L = bit_len(), G = params().glwe_len();
     Staged st(*this, device_mem);
+    st.own_times();
     engine_->s1_bootstrap(st.in(in, B * L), st.pub(tvs, n_tv * G), n_tv, st.out(out, B * L), B);
     st.finish();
 }
@@ -1941,6 +1953,7 @@ void Context::unpack_bits_raw(const uint64_t *glwes, size_t count, uint64_t *bit
     require_pack(count);
     const size_t G = glwe_pack::glwe_count(count, params().N);
     Staged st(*this, device_mem);
+    st.own_times();
     engine_->unpack_bits(st.in(glwes, G * params().glwe_len()), count, st.out(bits, count * bit_len()));
     st.finish();
 }
@@ -1978,6 +1991,7 @@ void Context::pack_bits(const std::vector<const BitCt *> &bits, uint64_t *glwes)
 void Context::pack_pfks_raw(const uint64_t *bits, size_t count, uint64_t *glwes, bool device_mem) {
     require_pack(count);
     Staged st(*this, device_mem);
+    st.own_times();
     engine_->pack_pfks(st.in(bits, count * bit_len()), count, st.out(glwes, count * params().glwe_len()));
     st.finish();
 }
@@ -1986,6 +2000,7 @@ void Context::s1_packing_keyswitch_raw(const uint64_t *cts, size_t count, uint64
     require_s1();
     if (count < 1 || count > (size_t)params().N) throw ModelError{TAE_E_ARG, "packing keyswitch takes 1..N ciphertexts"};
     Staged st(*this, device_mem);
+    st.own_times();
     engine_->s1_pack(st.in(cts, count * bit_len()), (int)count, st.out(glwe, params().glwe_len()));
     st.finish();
 }
@@ -2003,6 +2018,7 @@ void Context::s1_test_vectors_from_ciphertexts_raw(const uint64_t *ct0, const ui
     hip_check(hipMemcpy2DAsync(d_pairs.p, 2 * L * 8, ct0, L * 8, L * 8, B, kind, engine_->stream()), "pairs");
     hip_check(hipMemcpy2DAsync(d_pairs.as<uint64_t>() + L, 2 * L * 8, ct1, L * 8, L * 8, B, kind, engine_->stream()),
               "pairs");
+    engine_->begin_call();
     engine_->s1_pks(d_pairs.as<uint64_t>(), 2 * B, d_pks.as<uint64_t>());
     if (device_mem) {
         engine_->s1_tv_from_pks(d_pks.as<uint64_t>(), B, tvs);
@@ -2031,6 +2047,7 @@ void Context::s1_multivariate_raw(const uint64_t *bits, size_t G, int nbits, con
             s1_test_vector(params(), tab[2 * v], tab[2 * v + 1], &tvs[((size_t)f * V + v) * GL]);
         }
     Staged st(*this, device_mem);
+    st.own_times();
     engine_->s1_multivariate(st.in(bits, G * nbits * L), G, nbits, st.pub(tvs.data(), tvs.size()), n_fn,
                              st.out(out, G * n_fn * L));
     st.finish();
