@@ -591,6 +591,47 @@ int tae_aesx_gcm_transcipher_raw(const tae_context *ctx, int key_bits, const uin
 int tae_aesx_gcm_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
                              const tae_bit *const *hk, size_t n_powers, const tae_gcm_frame *frames, size_t n_frames,
                              int tag_len, int rounds, tae_bit **out_plain, tae_bit **out_tag_diff);
+/* ---- frames beyond one table: segmented GHASH ------------------------------------------
+ * tae_aesx_gcm_transcipher* stops at about 55 hashed blocks.  These calls split GHASH into C = ceil(m / seg) segments
+ * of seg hashed blocks.  With e = m + 1 - i the exponent of X_i, c = (e - 1) / seg and k = (e - 1) % seg + 1:
+ *   GHASH = S_0 + sum_{c >= 1} S_c H^(seg c),   S_c = sum_k X_(c,k) H^k
+ * so every segment is row sums over the table's first seg powers, and each inner segment (c >= 1) is lifted by one
+ * product with a stride power H^(seg c).  The stride key holds H^(seg j) at entry j - 1 and is made once per key and
+ * seg from the power table; a frame takes up to (n_strides + 1) seg hashed blocks.  Inputs and outputs are those of
+ * tae_aesx_gcm_transcipher*; a frame of at most seg hashed blocks gives the same words as that call.  Levels: an
+ * inner chunk sums at most 64 table bits, an inner row its refreshed chunks (at most 64) and is refreshed to 1, the
+ * product bits are 1 with fresh ids and enter the final rows like table bits; a tag-difference bit is the number of
+ * refreshed chunks of its final row.  TAE_E_PARAM before any device work, beside the conditions above: seg outside
+ * 1 .. min(n_powers, 64), n_strides outside 1 .. 64, a frame with C - 1 > n_strides.  TAE_E_NOISE before any device work: an
+ * inner or a final row of more than 64 chunks.  A hashed block puts at most 128 sources into a row, so seg <= 31 is
+ * never refused for noise (31 * 128 + 64 <= 55 + 63 * 64); longer segments depend on the data (about 50 chunks a row
+ * at seg = 48 on random blocks). */
+/* the rows of a frame (host only): row_sources / row_chunks [C][128], C = ceil(n_hashed / seg).  Segment 0 holds the
+ * final rows r < 8 tag_len (table bits and one bit per product; the rest of its 128 entries is 0), segment c >= 1 the
+ * 128 inner rows of S_c.  For seg >= 1 they are written before the refusals */
+int tae_aesx_gcm_long_rows(const uint8_t *iv, size_t iv_len, const uint8_t *aad, size_t aad_len, const uint8_t *data,
+                           size_t data_len, int tag_len, size_t n_powers, size_t seg, size_t n_strides,
+                           int32_t *row_sources, int32_t *row_chunks);
+/* noise bookkeeping for a fresh key (no GPU): the key expansion, the power table, the stride key, then a frame of
+ * aad_len + data_len dense bytes with a 16-byte tag */
+int tae_aesx_gcm_long_noise_schedule_check(int param_set, int key_bits, int rounds, int n_powers, size_t seg,
+                                           int n_strides, size_t aad_len, size_t data_len);
+/* the stride key: hk [n_powers][128][L] -> sk [n_strides][128][L], entry 0 a copy of hk's block seg - 1, an even
+ * stride a square, an odd one a product with entry 0 */
+int tae_aesx_ghash_stride_key_raw(const tae_context *ctx, const uint64_t *hk, size_t n_powers, size_t seg, int n_strides,
+                                  uint64_t *sk, int mem);
+/* the same on handles: sk[n_strides * 128]; entry 0 clones the table's bits and shares their ids, every later bit is
+ * noise^2 = 1 with a fresh id */
+int tae_aesx_ghash_stride_key(const tae_context *ctx, const tae_bit *const *hk, size_t n_powers, size_t seg, int n_strides,
+                              tae_bit **sk);
+int tae_aesx_gcm_long_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint64_t *hk,
+                                      size_t n_powers, const uint64_t *sk, size_t n_strides, size_t seg,
+                                      const tae_gcm_frame *frames, size_t n_frames, int tag_len, int rounds,
+                                      uint64_t *out_plain, uint64_t *out_tag_diff, int mem);
+int tae_aesx_gcm_long_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
+                                  const tae_bit *const *hk, size_t n_powers, const tae_bit *const *sk, size_t n_strides,
+                                  size_t seg, const tae_gcm_frame *frames, size_t n_frames, int tag_len, int rounds,
+                                  tae_bit **out_plain, tae_bit **out_tag_diff);
 /* stage entries for tests: the squares, and the products a_c b_c, of `count` field elements [count][128][L]
  * (coefficient i of GCM's bit-reflected field at ciphertext i), every output bit refreshed to noise^2 = 1 */
 int tae_stage_gf128_square(const tae_context *ctx, const uint64_t *in, size_t count, uint64_t *out, int mem);

@@ -1,0 +1,237 @@
+// The segmented GHASH plans (csrc/aes_gcm.hpp) compiled stand-alone, on PLAIN BIT VALUES as
+// aes_gcm_test.cpp does: a "ciphertext" is L = 3 words whose body word holds the bit at 1 << 63, sums are the u64
+// additions rowsum_word does and a refresh is the identity on the bit.  The whole plan (inner chunk sums, refresh, row
+// sums, refresh, the product by gcm_mul, the final chunk sums, refresh, the differences) must give
+// E(J0) ^ GHASH ^ tag with GHASH by Horner's rule; the stride schedule must give H^(seg j); at C = 1 the plan is the
+// single-table plan, array for array; and the refusals.  Built and run by tests/test_aes_gcm_long.py, also under
+// -fsanitize=address,undefined.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <set>
+#include <vector>
+
+#include "../../tfhe-aes-2_amd/csrc/aes_gcm.hpp"
+
+using namespace tae;
+
+static int fails = 0;
+#define CHECK(c)                                                    \
+    do {                                                            \
+        if (!(c)) {                                                 \
+            std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); \
+            fails++;                                                \
+        }                                                           \
+    } while (0)
+
+static const int L = 3;
+using Cts = std::vector<uint64_t>;  // [n][L]
+
+static Cts encode(const GcmElem &a) {
+    Cts c((size_t)128 * L, 0);
+    for (int k = 0; k < 128; k++) {
+        c[(size_t)k * L] = 0x1111 * (uint64_t)(k + 1);  // mask words: the sums must carry them along untouched
+        c[(size_t)k * L + L - 1] = (uint64_t)gcm_coef(a, k) << 63;
+    }
+    return c;
+}
+
+static GcmElem decode(const uint64_t *c) {
+    GcmElem a{{0, 0}};
+    for (int k = 0; k < 128; k++)
+        if (c[(size_t)k * L + L - 1] >> 63) a.w[k >> 6] |= 1ull << (63 - (k & 63));
+    return a;
+}
+
+static Cts rowsum(const Cts &src, const RowPlan &p) {
+    CHECK(rowplan_ok(p, src.size() / L));
+    Cts out(p.n_rows() * L);
+    for (size_t t = 0; t < out.size(); t++) out[t] = rowsum_word(src.data(), p, t, L);
+    return out;
+}
+
+// the identity bootstrap: the bit survives, the rest is new
+static Cts refresh(const Cts &in) {
+    Cts out(in.size(), 0);
+    for (size_t i = 0; i < in.size() / L; i++) out[i * L + L - 1] = in[i * L + L - 1] & (1ull << 63);
+    return out;
+}
+
+static bool eq(const GcmElem &a, const GcmElem &b) { return a.w[0] == b.w[0] && a.w[1] == b.w[1]; }
+static GcmElem add(const GcmElem &a, const GcmElem &b) { return GcmElem{{a.w[0] ^ b.w[0], a.w[1] ^ b.w[1]}}; }
+
+static GcmElem pow_of(const GcmElem &h, size_t e) {
+    GcmElem r = gcm_x_pow(0);
+    for (size_t i = 0; i < e; i++) r = gcm_mul(r, h);
+    return r;
+}
+
+// GHASH by Horner's rule: Y_i = (Y_(i-1) ^ X_i) H
+static GcmElem ghash_plain(const GcmFrame &f, const GcmElem &h) {
+    GcmElem y{{0, 0}};
+    for (size_t i = 0; i < f.m(); i++) y = gcm_mul(add(y, gcm_from_bytes(&f.hashed[16 * i])), h);
+    return y;
+}
+
+static GcmFrame frame_of(size_t m, uint8_t fill, bool random, int tag_len = 16) {
+    const uint8_t iv[12] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12};
+    std::vector<uint8_t> data((m - 1) * 16, fill);
+    uint32_t x = 12345u + (uint32_t)m;
+    if (random)
+        for (auto &b : data) b = (uint8_t)((x = x * 1664525u + 1013904223u) >> 24);
+    GcmFrame f;
+    CHECK(gcm_format(iv, 12, nullptr, 0, data.data(), data.size(), tag_len, f) == GCM_FMT_OK);
+    CHECK(f.m() == m);
+    return f;
+}
+
+static const uint8_t kTag[16] = {0x5b, 0xc9, 0x4f, 0xbc, 0x32, 0x21, 0xa5, 0xdb, 0x94, 0xfa, 0xe9, 0x5a, 0xe7, 0x12, 0x1a, 0x47};
+
+// the whole plan of one frame on plain bits; all inner segments of the frame share one GcmInnerPlan, as a batch does
+static void whole_plan(size_t seg, size_t m, const GcmElem &H, const GcmElem &EJ0, bool random) {
+    const GcmFrame f = frame_of(m, 0x00, random);
+    const size_t C = gcm_long_segments(m, seg), tb = seg < m ? seg : m;
+    Cts src;
+    for (size_t k = 1; k <= tb; k++) {
+        const Cts e = refresh(encode(pow_of(H, k)));
+        src.insert(src.end(), e.begin(), e.end());
+    }
+    const Cts table = src;
+    const Cts ej = encode(EJ0);
+    src.insert(src.end(), ej.begin(), ej.end());
+    std::vector<std::vector<int32_t>> rows;
+    GcmInnerPlan ip;
+    for (size_t c = 1; c < C; c++) {
+        gcm_segment_rows(f, seg, c, 128, rows);
+        CHECK(gcm_inner_rows_ok(rows));
+        gcm_inner_plan_add(ip, rows);
+    }
+    CHECK(ip.rows.n_rows() == (C - 1) * 128 && ip.chunks_of_row.size() == (C - 1) * 128);
+    CHECK(ip.chunks.max_width() <= kGcmInnerChunk && ip.rows.max_width() <= kGcmMaxChunks);
+    if (C > 1) {
+        const Cts S = refresh(rowsum(refresh(rowsum(table, ip.chunks)), ip.rows));
+        for (size_t c = 1; c < C; c++) {
+            GcmElem want{{0, 0}};  // S_c = sum_k X_(c,k) H^k, X_(c,k) the block of exponent seg c + k
+            for (size_t k = 1; k <= seg && seg * c + k <= m; k++)
+                want = add(want, gcm_mul(gcm_from_bytes(&f.hashed[(m - (seg * c + k)) * 16]), pow_of(H, k)));
+            const GcmElem Sc = decode(&S[(c - 1) * 128 * L]);
+            CHECK(eq(Sc, want));
+            const Cts prod = refresh(encode(gcm_mul(Sc, pow_of(H, seg * c))));
+            src.insert(src.end(), prod.begin(), prod.end());
+        }
+    }
+    gcm_long_final_rows(f, seg, tb + 1, rows);
+    CHECK(rows.size() == 128 && gcm_final_rows_ok(rows));
+    GcmCallPlan plan;
+    gcm_call_plan_add(plan, rows, tb, 0, kTag);
+    CHECK(plan.chunks.max_width() <= 64 && plan.diff.n_rows() == 128);
+    const Cts diff = rowsum(refresh(rowsum(src, plan.chunks)), plan.diff);
+    const GcmElem want = add(add(EJ0, ghash_plain(f, H)), gcm_from_bytes(kTag));
+    CHECK(eq(decode(diff.data()), want));
+    if (C == 1) {  // the single-table plan, array for array
+        std::vector<std::vector<int32_t>> old_rows;
+        gcm_frame_rows(f, old_rows);
+        CHECK(old_rows == rows);
+        GcmCallPlan old;
+        gcm_call_plan_add(old, old_rows, m, 0, kTag);
+        CHECK(old.chunks.row_start == plan.chunks.row_start && old.chunks.src == plan.chunks.src);
+        CHECK(old.diff.row_start == plan.diff.row_start && old.diff.src == plan.diff.src && old.diff.pub_bit == plan.diff.pub_bit);
+        CHECK(old.chunks_of_row == plan.chunks_of_row);
+    }
+}
+
+// one product through the product plan, as aes_gcm_test.cpp
+static GcmElem product(const GcmElem &a, const GcmElem &b, const GcmProductPlan &P) {
+    Cts parts((size_t)kGcmParts * L, 0);
+    for (int g = 0; g < kGcmGroups; g++) {
+        unsigned v = 0;
+        for (int bit = 0; bit < 8; bit++) {
+            const int s = gcm_pair_source(g, bit);
+            v = (v << 1) | (unsigned)(s < 128 ? gcm_coef(a, s) : gcm_coef(b, s - 128));
+        }
+        const uint64_t fv = gcm_nibble_product(v);
+        for (int d = 0; d < kGcmPartBits; d++)
+            parts[((size_t)g * kGcmPartBits + d) * L + L - 1] = ((fv >> (kGcmPartBits - 1 - d)) & 1) << 63;
+    }
+    return decode(refresh(rowsum(refresh(rowsum(parts, P.chunks)), P.reduce)).data());
+}
+
+int main() {
+    uint8_t hb[16] = {0x66, 0xe9, 0x4b, 0xd4, 0xef, 0x8a, 0x2c, 0x3b, 0x88, 0x4c, 0xfa, 0x59, 0xca, 0x34, 0x2b, 0x2e};
+    uint8_t jb[16] = {0x32, 0x47, 0x18, 0x4b, 0x3c, 0x4f, 0x69, 0xa4, 0x4d, 0xbc, 0xd2, 0x28, 0x87, 0xbb, 0xb4, 0x18};
+    const GcmElem H = gcm_from_bytes(hb), EJ0 = gcm_from_bytes(jb);
+
+    // ---- the whole plan: seg in {1, 2, 31}, m in {1, seg, seg + 1, 2 seg, 2 seg + 1, 100} ----
+    for (size_t seg : {(size_t)1, (size_t)2, (size_t)31}) {
+        const std::set<size_t> ms = {1, seg, seg + 1, 2 * seg, 2 * seg + 1, 100};
+        for (size_t m : ms) whole_plan(seg, m, H, EJ0, true);
+    }
+    whole_plan(1, 3, H, EJ0, false);  // all-zero blocks: every inner row is one empty chunk
+    {
+        const GcmFrame z = frame_of(3, 0x00, false);
+        std::vector<std::vector<int32_t>> rows;
+        gcm_segment_rows(z, 1, 1, 128, rows);
+        GcmInnerPlan ip;
+        gcm_inner_plan_add(ip, rows);
+        CHECK(ip.chunks.src.empty() && ip.chunks.n_rows() == 128 && ip.rows.src.size() == 128);
+        for (int32_t n : ip.chunks_of_row) CHECK(n == 1);
+        CHECK(gcm_inner_chunks(0) == 1 && gcm_inner_chunks(64) == 1 && gcm_inner_chunks(65) == 2);
+    }
+
+    // ---- the stride schedule on plain bits: base G_1 = H^2, strides 1 .. 5 -> H^2, H^4 .. H^10 ----
+    {
+        const GcmProductPlan P = gcm_product_plan();
+        const size_t seg = 2, ns = 5;
+        Cts sk(ns * 128 * L, 0);
+        auto put = [&](int j, const Cts &c) { std::memcpy(&sk[(size_t)(j - 1) * 128 * L], c.data(), c.size() * 8); };
+        put(1, refresh(encode(pow_of(H, seg))));
+        for (const GcmGeneration &g : gcm_power_schedule((int)ns)) {
+            for (int j : g.squares) {
+                RowPlan p = gcm_square_plan();
+                p.base_of.assign(128, (int32_t)((j / 2 - 1) * 128));
+                put(j, refresh(rowsum(sk, p)));
+            }
+            for (int j : g.products)
+                put(j, encode(product(decode(&sk[(size_t)(j - 2) * 128 * L]), decode(sk.data()), P)));
+        }
+        for (size_t j = 1; j <= ns; j++) CHECK(eq(decode(&sk[(j - 1) * 128 * L]), pow_of(H, seg * j)));
+    }
+
+    // ---- refusals ----
+    CHECK(gcm_long_segments(1, 31) == 1 && gcm_long_segments(31, 31) == 1 && gcm_long_segments(32, 31) == 2 &&
+          gcm_long_segments(100, 31) == 4);
+    CHECK(gcm_long_shape_check(100, 0, 31, 64) == GCM_LONG_SEG && gcm_long_shape_check(100, 32, 31, 64) == GCM_LONG_SEG);
+    CHECK(gcm_long_shape_check(100, 31, 31, 0) == GCM_LONG_STRIDES && gcm_long_shape_check(100, 31, 31, 65) == GCM_LONG_STRIDES);
+    CHECK(gcm_long_shape_check(100, 31, 31, 2) == GCM_LONG_STRIDES && gcm_long_shape_check(100, 31, 31, 3) == GCM_LONG_OK);
+    CHECK(gcm_long_shape_check(100, 1, 1, 64) == GCM_LONG_STRIDES && gcm_long_shape_check(65, 1, 1, 64) == GCM_LONG_OK);
+    // 100 blocks of 0xFF at seg = 31: accepted, and no row can pass 31 * 128 + 64 sources
+    const GcmFrame ff = frame_of(101, 0xFF, false);
+    CHECK(gcm_long_frame_check(ff, 31, 31, 64) == GCM_LONG_OK);
+    CHECK(31 * 128 + 64 <= kGcmFirstChunk + (kGcmMaxChunks - 1) * kGcmNextChunk);
+    {
+        std::vector<std::vector<int32_t>> rows;
+        size_t most = 0;
+        gcm_segment_rows(ff, 31, 1, 128, rows);
+        for (const auto &r : rows) most = r.size() > most ? r.size() : most;
+        CHECK(most <= 31 * 128 && most > 31 * 100);  // an all-ones block reaches 126 of 128
+    }
+    // 99 blocks of 0xA5 at seg = 48: rows of 48 * 93 = 4464 > 4087 sources
+    const GcmFrame fa = frame_of(100, 0xA5, false);
+    CHECK(gcm_long_frame_check(fa, 48, 48, 64) == GCM_LONG_NOISE);
+    CHECK(gcm_long_frame_check(fa, 31, 31, 3) == GCM_LONG_OK);
+    CHECK(gcm_long_frame_check(fa, 31, 31, 2) == GCM_LONG_STRIDES);  // the shape before the rows
+    {
+        std::vector<std::vector<int32_t>> rows;
+        size_t most = 0;
+        gcm_segment_rows(fa, 48, 1, 128, rows);
+        for (const auto &r : rows) most = r.size() > most ? r.size() : most;
+        CHECK(most == 48 * 93 && !gcm_inner_rows_ok(rows));
+        gcm_long_final_rows(fa, 31, 0, rows);  // the issue's bound for seg = 31: at most 31 * 93 + 3 sources, 46 chunks
+        most = 0;
+        for (const auto &r : rows) most = r.size() > most ? r.size() : most;
+        CHECK(most <= 31 * 93 + 3 && gcm_row_chunks(31 * 93 + 3) == 46);
+    }
+    if (fails) return 1;
+    std::printf("OK\n");
+    return 0;
+}

@@ -741,69 +741,66 @@ void Engine::ghash_key(const uint64_t *d_rk, int n_powers, int rounds, int nr, u
     grow(d_gcm_a_, cap_gcm_a_, block_len);
     aes_pub_blocks_multi(d_rk, std::vector<PubBlock>{zero}, rounds, d_gcm_a_, nr);  // resets the stage times
     circuit_bootstrap(d_gcm_a_, 128, 1, d_lut_id1_, 1, d_out);
-    for (const GcmGeneration &gen : gcm_power_schedule(n_powers)) {
+    gcm_power_generations(d_out, n_powers);
+    collect_times();
+}
+
+// Power k of the base at entry k - 1: a generation's squares in one launch sequence, its products in another
+void Engine::gcm_power_generations(uint64_t *d_tab, int n) {
+    const size_t block_len = 128 * p_.big_len();
+    for (const GcmGeneration &gen : gcm_power_schedule(n)) {
         std::vector<size_t> blocks;
         std::vector<const uint64_t *> a, b;
         std::vector<uint64_t *> sq_out, pr_out;
         for (int k : gen.squares) {
             blocks.push_back((size_t)(k / 2 - 1));
-            sq_out.push_back(d_out + (size_t)(k - 1) * block_len);
+            sq_out.push_back(d_tab + (size_t)(k - 1) * block_len);
         }
         for (int k : gen.products) {
-            a.push_back(d_out + (size_t)(k - 2) * block_len);
-            b.push_back(d_out);
-            pr_out.push_back(d_out + (size_t)(k - 1) * block_len);
+            a.push_back(d_tab + (size_t)(k - 2) * block_len);
+            b.push_back(d_tab);
+            pr_out.push_back(d_tab + (size_t)(k - 1) * block_len);
         }
-        gcm_square_pass(d_out, (size_t)n_powers * 128, blocks, sq_out);
+        gcm_square_pass(d_tab, (size_t)n * 128, blocks, sq_out);
         gcm_product_pass(a, b, pr_out);
     }
+}
+
+void Engine::ghash_stride_key(const uint64_t *d_hk, size_t n_powers, size_t seg, int n_strides, uint64_t *d_out) {
+    require_gcm();
+    if (seg < 1 || seg > n_powers || seg > (size_t)kGcmMaxPowers)
+        throw std::runtime_error("GCM: seg must be in 1..=min(n_powers, 64)");
+    if (n_strides < 1 || n_strides > kGcmMaxStrides) throw std::runtime_error("GCM: n_strides must be in 1..=64");
+    const size_t block_len = 128 * p_.big_len();
+    times_ = StageTimes{};
+    rowsum_plans_.clear();
+    HIPC(hipMemcpyAsync(d_out, d_hk + (seg - 1) * block_len, block_len * 8, hipMemcpyDeviceToDevice, stream_));
+    gcm_power_generations(d_out, n_strides);
     collect_times();
 }
 
-void Engine::aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers,
-                                 const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
-                                 uint64_t *d_out_tagdiff) {
-    const size_t n = frames.size();
-    if (!n) return;
-    require_gcm();
-    require_rounds(rounds, nr);
-    // at one round J0 and the counter blocks share their de-duplicated SubBytes outputs at the IV positions
-    if (rounds < 2) throw std::runtime_error("GCM needs rounds >= 2");
+size_t Engine::gcm_frame_offsets(const std::vector<GcmFrameIn> &frames, std::vector<int64_t> &off) const {
     const int tag_len = frames[0].frame->tag_len;
-    const size_t L = p_.big_len(), block_len = 128 * L;
-    // ---- the plans, before any device work ----
-    size_t total = 0, table_blocks = 0;
-    std::vector<int64_t> off(n);
-    for (size_t s = 0; s < n; s++) {
+    size_t total = 0;
+    off.resize(frames.size());
+    for (size_t s = 0; s < frames.size(); s++) {
         const GcmFrame &f = *frames[s].frame;
         if (f.tag_len != tag_len || !f.m() || f.n_pub() != 2 + (f.data_len + 15) / 16)
             throw std::runtime_error("GCM frames of one call have one tag length and a whole layout");
         off[s] = (int64_t)total;
         total += f.data_len;
-        table_blocks = std::max(table_blocks, f.m());
     }
-    GcmCallPlan plan;
-    std::vector<std::vector<int32_t>> rows;
-    for (size_t s = 0; s < n; s++) {
-        gcm_frame_rows(*frames[s].frame, rows);
-        if (gcm_frame_check(*frames[s].frame, n_powers, rows) != GCM_PLAN_OK)
-            throw std::runtime_error("GCM frame: more hashed blocks than the power table or the chunk sum takes");
-        gcm_call_plan_add(plan, rows, table_blocks, s, frames[s].tag);
-    }
-    const size_t n_src = (table_blocks + n) * 128, n_chunks = plan.chunks.n_rows();
-    times_ = StageTimes{};
-    rowsum_plans_.clear();
+    return total;
+}
+
+void Engine::gcm_public_pass(const uint64_t *d_rk, const std::vector<GcmFrameIn> &frames, const std::vector<int64_t> &off,
+                             size_t total, int rounds, int nr, uint64_t *d_out_plain, uint64_t *d_j0) {
+    const size_t n = frames.size();
     gcm_bytes_.assign(std::max<size_t>(total, 1), 0);
     for (size_t s = 0; s < n; s++)
         if (frames[s].frame->data_len) std::memcpy(&gcm_bytes_[(size_t)off[s]], frames[s].data, frames[s].frame->data_len);
     const uint8_t *d_bytes = upload(d_gcm_bytes_, cap_gcm_bytes_, gcm_bytes_.data(), gcm_bytes_.size());
-    grow(d_gcm_src_, cap_gcm_src_, n_src * L);
-    grow(d_gcm_a_, cap_gcm_a_, n_chunks * L);
-    grow(d_gcm_b_, cap_gcm_b_, n_chunks * L);
-    HIPC(hipMemcpyAsync(d_gcm_src_, d_hk, table_blocks * block_len * 8, hipMemcpyDeviceToDevice, stream_));
-    uint64_t *d_j0 = d_gcm_src_ + table_blocks * block_len;
-
-    // ---- the public blocks: the counters into the result, J0 into the kept blocks ----
+    // the counters into the result, J0 into the kept blocks
     std::vector<PubBlock> blocks;
     std::vector<int64_t> kout;
     std::vector<int32_t> klen;
@@ -821,8 +818,120 @@ void Engine::aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, siz
         }
     }
     pub_pass(d_rk, blocks, rounds, d_bytes, d_out_plain, nr, &kout, &klen, d_j0);
+}
+
+void Engine::aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers,
+                                 const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
+                                 uint64_t *d_out_tagdiff) {
+    const size_t n = frames.size();
+    if (!n) return;
+    require_gcm();
+    require_rounds(rounds, nr);
+    // at one round J0 and the counter blocks share their de-duplicated SubBytes outputs at the IV positions
+    if (rounds < 2) throw std::runtime_error("GCM needs rounds >= 2");
+    const size_t L = p_.big_len(), block_len = 128 * L;
+    // ---- the plans, before any device work ----
+    size_t table_blocks = 0;
+    std::vector<int64_t> off;
+    const size_t total = gcm_frame_offsets(frames, off);
+    for (size_t s = 0; s < n; s++) table_blocks = std::max(table_blocks, frames[s].frame->m());
+    GcmCallPlan plan;
+    std::vector<std::vector<int32_t>> rows;
+    for (size_t s = 0; s < n; s++) {
+        gcm_frame_rows(*frames[s].frame, rows);
+        if (gcm_frame_check(*frames[s].frame, n_powers, rows) != GCM_PLAN_OK)
+            throw std::runtime_error("GCM frame: more hashed blocks than the power table or the chunk sum takes");
+        gcm_call_plan_add(plan, rows, table_blocks, s, frames[s].tag);
+    }
+    const size_t n_src = (table_blocks + n) * 128, n_chunks = plan.chunks.n_rows();
+    times_ = StageTimes{};
+    rowsum_plans_.clear();
+    grow(d_gcm_src_, cap_gcm_src_, n_src * L);
+    grow(d_gcm_a_, cap_gcm_a_, n_chunks * L);
+    grow(d_gcm_b_, cap_gcm_b_, n_chunks * L);
+    HIPC(hipMemcpyAsync(d_gcm_src_, d_hk, table_blocks * block_len * 8, hipMemcpyDeviceToDevice, stream_));
+    gcm_public_pass(d_rk, frames, off, total, rounds, nr, d_out_plain, d_gcm_src_ + table_blocks * block_len);
 
     // ---- GHASH + E(J0) + the received tag: chunk sums, one refresh, the differences ----
+    rowsum_pass(d_gcm_src_, n_src, std::move(plan.chunks), d_gcm_a_);
+    circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
+    rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
+    collect_times();
+}
+
+// Segmented GHASH (aes_gcm.hpp).  d_gcm_src_ is sized once and holds, in blocks of [128][K+1]: the
+// table's first table_blocks powers, E(J0) of every frame, every product S_c G_c, and one batch of S_c operands.
+// gcm_product_pass grows d_gcm_a_ / d_gcm_b_ / d_gcm_ops_ before it copies its operands, so no operand lives in those:
+// S_c is written into d_gcm_src_ and the stride operands are read from the caller's d_sk.
+void Engine::aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers, const uint64_t *d_sk,
+                                      size_t n_strides, size_t seg, const std::vector<GcmFrameIn> &frames, int rounds,
+                                      int nr, uint64_t *d_out_plain, uint64_t *d_out_tagdiff) {
+    const size_t n = frames.size();
+    if (!n) return;
+    require_gcm();
+    require_rounds(rounds, nr);
+    if (rounds < 2) throw std::runtime_error("GCM needs rounds >= 2");
+    const size_t L = p_.big_len(), block_len = 128 * L, B = gcm_seg_batch_;
+    // ---- the plans, before any device work ----
+    std::vector<int64_t> off;
+    const size_t total = gcm_frame_offsets(frames, off);
+    size_t table_blocks = 0, n_products = 0;
+    std::vector<size_t> first_product(n);
+    for (size_t s = 0; s < n; s++) {
+        const size_t m = frames[s].frame->m();
+        if (gcm_long_shape_check(m, seg, n_powers, n_strides) != GCM_LONG_OK)
+            throw std::runtime_error("GCM: seg must be in 1..=n_powers and a frame's segments need a stride power each");
+        table_blocks = std::max(table_blocks, std::min(seg, m));
+        first_product[s] = n_products;
+        n_products += gcm_long_segments(m, seg) - 1;
+    }
+    const size_t prod_block0 = table_blocks + n, s_block0 = prod_block0 + n_products;
+    std::vector<GcmInnerPlan> inner((n_products + B - 1) / B);
+    std::vector<size_t> stride_of;  // [n_products]: the stride power (c - 1) of every inner segment, in call order
+    GcmCallPlan plan;
+    std::vector<std::vector<int32_t>> rows;
+    for (size_t s = 0; s < n; s++) {
+        const GcmFrame &f = *frames[s].frame;
+        for (size_t c = 1; c < gcm_long_segments(f.m(), seg); c++) {
+            gcm_segment_rows(f, seg, c, 128, rows);
+            if (!gcm_inner_rows_ok(rows)) throw std::runtime_error("GCM frame: an inner row needs more than 64 chunks");
+            gcm_inner_plan_add(inner[stride_of.size() / B], rows);
+            stride_of.push_back(c - 1);
+        }
+        gcm_long_final_rows(f, seg, prod_block0 + first_product[s], rows);
+        if (!gcm_final_rows_ok(rows)) throw std::runtime_error("GCM frame: a tag row needs more than 64 chunks");
+        gcm_call_plan_add(plan, rows, table_blocks, s, frames[s].tag);
+    }
+    const size_t n_src = s_block0 * 128, n_chunks = plan.chunks.n_rows(), batch = std::min(B, n_products);
+    size_t scratch = std::max(n_chunks, batch * gcm_product_plan().chunks.n_rows());
+    for (const GcmInnerPlan &ip : inner) scratch = std::max(scratch, ip.chunks.n_rows());
+    times_ = StageTimes{};
+    rowsum_plans_.clear();
+    grow(d_gcm_src_, cap_gcm_src_, (s_block0 + batch) * block_len);
+    grow(d_gcm_a_, cap_gcm_a_, scratch * L);
+    grow(d_gcm_b_, cap_gcm_b_, scratch * L);
+    HIPC(hipMemcpyAsync(d_gcm_src_, d_hk, table_blocks * block_len * 8, hipMemcpyDeviceToDevice, stream_));
+    gcm_public_pass(d_rk, frames, off, total, rounds, nr, d_out_plain, d_gcm_src_ + table_blocks * block_len);
+
+    // ---- the inner segments: S_c at level 1 with fresh ids, then S_c G_c into the final source array ----
+    uint64_t *d_prod = d_gcm_src_ + prod_block0 * block_len, *d_s = d_gcm_src_ + s_block0 * block_len;
+    for (size_t bi = 0; bi < inner.size(); bi++) {
+        const size_t at = bi * B, nb = std::min(B, n_products - at), nck = inner[bi].chunks.n_rows();
+        rowsum_pass(d_gcm_src_, table_blocks * 128, std::move(inner[bi].chunks), d_gcm_a_);
+        circuit_bootstrap(d_gcm_a_, nck, 1, d_lut_id1_, 1, d_gcm_b_);
+        rowsum_pass(d_gcm_b_, nck, std::move(inner[bi].rows), d_gcm_a_);
+        circuit_bootstrap(d_gcm_a_, nb * 128, 1, d_lut_id1_, 1, d_s);
+        std::vector<const uint64_t *> a(nb), b(nb);
+        std::vector<uint64_t *> outs(nb);
+        for (size_t j = 0; j < nb; j++) {
+            a[j] = d_s + j * block_len;
+            b[j] = d_sk + stride_of[at + j] * block_len;
+            outs[j] = d_prod + (at + j) * block_len;
+        }
+        gcm_product_pass(a, b, outs);
+    }
+
+    // ---- GHASH + E(J0) + the received tag, as aes_gcm_transcipher: the products are sources like the table's ----
     rowsum_pass(d_gcm_src_, n_src, std::move(plan.chunks), d_gcm_a_);
     circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
     rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);

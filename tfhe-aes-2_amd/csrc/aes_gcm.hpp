@@ -279,4 +279,106 @@ inline void gcm_call_plan_add(GcmCallPlan &P, const std::vector<std::vector<int3
     }
 }
 
+// ---- segmented GHASH: frames beyond one table ----
+// With e = m + 1 - i the exponent of X_i, c = (e - 1) / seg and k = (e - 1) % seg + 1:
+//   GHASH = S_0 + sum_{c >= 1} S_c G_c,   S_c = sum_k X_(c,k) H^k,   G_c = H^(seg c)
+// Every S_c is row sums over the table's first seg powers; an inner segment (c >= 1) is refreshed to a table-like
+// element and lifted by one product with the stride power G_c (the stride key: H^(seg j) at entry j - 1, made by
+// gcm_power_schedule on the base G_1).  C = ceil(m / seg) segments, C - 1 products.
+//
+// A hashed block puts at most 128 sources into a row, so an inner row holds at most 128 seg sources in chunks of 64
+// and a final row 128 seg + (C - 1) <= 128 seg + 64 in chunks of 55 / 64.  For seg <= 31 that is at most
+// 31 * 128 + 64 = 4032 <= 55 + 63 * 64 = 4087: no frame is refused for noise.  Beyond 31 it depends on the data.
+constexpr int kGcmMaxStrides = 64;
+constexpr int kGcmInnerChunk = 64;  // level-1 table bits per refreshed chunk of an inner row
+
+inline size_t gcm_long_segments(size_t m, size_t seg) { return (m + seg - 1) / seg; }
+
+// Segment c of a frame, rows r < n_rows: the sources (k, i), as 128 (k - 1) + i into the power table, for which
+// coefficient r of X_(c,k) x^i is 1; ascending (k, i).  X_(c,k) is the hashed block of exponent seg c + k.  Segment 0
+// with seg >= m is gcm_frame_rows.
+inline void gcm_segment_rows(const GcmFrame &f, size_t seg, size_t c, size_t n_rows,
+                             std::vector<std::vector<int32_t>> &rows) {
+    rows.assign(n_rows, {});
+    const size_t m = f.m(), kc = m - seg * c < seg ? m - seg * c : seg;
+    GcmElem cols[128];
+    for (size_t k = 1; k <= kc; k++) {
+        gcm_mul_cols(gcm_from_bytes(&f.hashed[(m - (seg * c + k)) * 16]), cols);
+        for (int i = 0; i < 128; i++)
+            for (size_t r = 0; r < n_rows; r++)
+                if (gcm_coef(cols[i], (int)r)) rows[r].push_back((int32_t)(128 * (k - 1) + i));
+    }
+}
+
+// chunks of an inner row of n sources: no E(J0) bit; a row without a source is one empty chunk, the zero ciphertext
+inline size_t gcm_inner_chunks(size_t n) { return n ? (n + kGcmInnerChunk - 1) / kGcmInnerChunk : 1; }
+
+// The plans of a batch of inner segments.  `chunks` reads the power table's first seg blocks; `rows` sums a row's
+// refreshed chunks: segment j of the batch is output rows 128 j .. 128 j + 127, refreshed once more into S_c.
+struct GcmInnerPlan {
+    RowPlan chunks, rows;
+    std::vector<int32_t> chunks_of_row;  // [n_segments * 128]
+};
+
+inline void gcm_inner_plan_add(GcmInnerPlan &P, const std::vector<std::vector<int32_t>> &rows) {
+    for (const std::vector<int32_t> &row : rows) {
+        const size_t n_chunks = gcm_inner_chunks(row.size());
+        for (size_t q = 0; q < n_chunks; q++) {
+            const size_t a = q * kGcmInnerChunk, b = a + kGcmInnerChunk < row.size() ? a + kGcmInnerChunk : row.size();
+            P.chunks.src.insert(P.chunks.src.end(), row.begin() + (std::ptrdiff_t)a, row.begin() + (std::ptrdiff_t)b);
+            P.chunks.end_row();
+            P.rows.src.push_back((int32_t)P.chunks.n_rows() - 1);
+        }
+        P.rows.end_row();
+        P.chunks_of_row.push_back((int32_t)n_chunks);
+    }
+}
+
+// The final rows of a frame: segment 0's sources, then bit r of every product S_c G_c, c ascending; product c - 1 of
+// the frame is block first_product_block + c - 1 of the final source array.  Level-1 sources like any other.
+inline void gcm_long_final_rows(const GcmFrame &f, size_t seg, size_t first_product_block,
+                                std::vector<std::vector<int32_t>> &rows) {
+    gcm_segment_rows(f, seg, 0, (size_t)8 * f.tag_len, rows);
+    const size_t C = gcm_long_segments(f.m(), seg);
+    for (size_t r = 0; r < rows.size(); r++)
+        for (size_t c = 1; c < C; c++) rows[r].push_back((int32_t)((first_product_block + c - 1) * 128 + r));
+}
+
+enum GcmLongStatus { GCM_LONG_OK = 0, GCM_LONG_SEG, GCM_LONG_STRIDES, GCM_LONG_NOISE };
+
+// seg in 1 .. min(n_powers, 64) (so the table holds min(seg, m) powers; ghash_key makes at most 64, and a caller's
+// n_powers bounds nothing by itself), n_strides in 1 .. 64 and at least C - 1
+inline GcmLongStatus gcm_long_shape_check(size_t m, size_t seg, size_t n_powers, size_t n_strides) {
+    if (seg < 1 || seg > n_powers || seg > (size_t)kGcmMaxPowers) return GCM_LONG_SEG;
+    if (n_strides < 1 || n_strides > (size_t)kGcmMaxStrides || gcm_long_segments(m, seg) - 1 > n_strides)
+        return GCM_LONG_STRIDES;
+    return GCM_LONG_OK;
+}
+
+inline bool gcm_inner_rows_ok(const std::vector<std::vector<int32_t>> &rows) {
+    for (const auto &r : rows)
+        if (gcm_inner_chunks(r.size()) > (size_t)kGcmMaxChunks) return false;
+    return true;
+}
+
+inline bool gcm_final_rows_ok(const std::vector<std::vector<int32_t>> &rows) {
+    for (const auto &r : rows)
+        if (gcm_row_chunks(r.size()) > (size_t)kGcmMaxChunks) return false;
+    return true;
+}
+
+// Every row of a frame, before any device work.  The shape comes first: rows are not walked for a refused shape.
+inline GcmLongStatus gcm_long_frame_check(const GcmFrame &f, size_t seg, size_t n_powers, size_t n_strides) {
+    const GcmLongStatus st = gcm_long_shape_check(f.m(), seg, n_powers, n_strides);
+    if (st != GCM_LONG_OK) return st;
+    std::vector<std::vector<int32_t>> rows;
+    const size_t C = gcm_long_segments(f.m(), seg);
+    for (size_t c = 1; c < C; c++) {
+        gcm_segment_rows(f, seg, c, 128, rows);
+        if (!gcm_inner_rows_ok(rows)) return GCM_LONG_NOISE;
+    }
+    gcm_long_final_rows(f, seg, 0, rows);
+    return gcm_final_rows_ok(rows) ? GCM_LONG_OK : GCM_LONG_NOISE;
+}
+
 }  // namespace tae

@@ -1325,6 +1325,112 @@ int tae_aesx_gcm_transcipher(const tae_context *ctx, int key_bits, const tae_bit
     });
 }
 
+/* ---- frames beyond one table: segmented GHASH ---- */
+int tae_aesx_gcm_long_rows(const uint8_t *iv, size_t iv_len, const uint8_t *aad, size_t aad_len, const uint8_t *data,
+                           size_t data_len, int tag_len, size_t n_powers, size_t seg, size_t n_strides,
+                           int32_t *row_sources, int32_t *row_chunks) {
+    return guarded([&] {
+        require(iv && row_sources && row_chunks && (aad || !aad_len) && (data || !data_len), "null");
+        tae::GcmFrame f;
+        throw_gcm_format(tae::gcm_format(iv, iv_len, aad, aad_len, data, data_len, tag_len, f));
+        if (seg < 1) throw tae::ModelError{TAE_E_PARAM, "seg must be in 1..=n_powers"};
+        const size_t C = tae::gcm_long_segments(f.m(), seg);
+        std::vector<std::vector<int32_t>> rows;
+        bool noise = false;
+        for (size_t c = 0; c < C; c++) {
+            if (c) tae::gcm_segment_rows(f, seg, c, 128, rows);
+            else tae::gcm_long_final_rows(f, seg, 0, rows);
+            noise = noise || !(c ? tae::gcm_inner_rows_ok(rows) : tae::gcm_final_rows_ok(rows));
+            for (size_t r = 0; r < 128; r++) {
+                const bool in = r < rows.size();
+                row_sources[c * 128 + r] = in ? (int32_t)rows[r].size() : 0;
+                row_chunks[c * 128 + r] =
+                    !in ? 0 : (int32_t)(c ? tae::gcm_inner_chunks(rows[r].size()) : tae::gcm_row_chunks(rows[r].size()));
+            }
+        }
+        switch (tae::gcm_long_shape_check(f.m(), seg, n_powers, n_strides)) {
+            case tae::GCM_LONG_SEG: throw tae::ModelError{TAE_E_PARAM, "seg must be in 1..=n_powers"};
+            case tae::GCM_LONG_STRIDES:
+                throw tae::ModelError{TAE_E_PARAM, "n_strides must be in 1..=64 and at least the frame's segments less one"};
+            default: break;
+        }
+        if (noise) throw tae::ModelError{TAE_E_NOISE, "a row needs more than 64 refreshed chunks"};
+    });
+}
+
+int tae_aesx_gcm_long_noise_schedule_check(int param_set, int key_bits, int rounds, int n_powers, size_t seg,
+                                           int n_strides, size_t aad_len, size_t data_len) {
+    return guarded([&] {
+        const tae::Params p = params_of(param_set);
+        const size_t kw = key_cts(key_bits);
+        const int nk = tae::aes_nk(key_bits), nr = tae::aes_nr(key_bits);
+        if (p.model != 1) throw tae::ModelError{TAE_E_PARAM, "GCM runs on the 1-bit WoP-PBS parameter sets only"};
+        std::vector<tae::NoiseLevel> key((size_t)nk * 32);
+        for (auto &x : key) x = tae::NoiseLevel::with_noise_level(1, tae::next_ct_id());
+        const std::vector<tae::NoiseLevel> rk = tae::aes_key_expand_noise_schedule(key, nk, p.max_noise_sq);
+        require(rk.size() == kw, "expanded key size");
+        const tae::GhashKeyNoise hk = tae::aes_ghash_key_noise_schedule(rk, n_powers, rounds, p.max_noise_sq, nr);
+        const tae::GhashKeyNoise sk = tae::aes_ghash_stride_key_noise_schedule(hk.table, seg, n_strides, p.max_noise_sq);
+        // a frame of the given sizes with dense blocks: every byte 0xA5
+        const uint8_t iv[12] = {};
+        const std::vector<uint8_t> aad(aad_len, 0xA5), data(data_len, 0xA5);
+        tae::GcmFrame f;
+        throw_gcm_format(tae::gcm_format(iv, 12, aad.data(), aad_len, data.data(), data_len, 16, f));
+        tae::aes_gcm_long_noise_schedule(rk, hk.table, sk.table, seg, f, rounds, p.max_noise_sq, nr);
+    });
+}
+
+int tae_aesx_ghash_stride_key_raw(const tae_context *ctx, const uint64_t *hk, size_t n_powers, size_t seg, int n_strides,
+                                  uint64_t *sk, int mem) {
+    return guarded([&] {
+        require(hk && sk, "null");
+        require_xts_server(ctx);
+        ctx->ctx->aes_ghash_stride_key_raw(hk, n_powers, seg, n_strides, sk, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_aesx_ghash_stride_key(const tae_context *ctx, const tae_bit *const *hk, size_t n_powers, size_t seg, int n_strides,
+                              tae_bit **sk) {
+    return guarded([&] {
+        require(hk && sk, "null");
+        require_xts_server(ctx);
+        emit(ctx->ctx->aes_ghash_stride_key(unwrap(hk, n_powers * 128), seg, n_strides), sk);
+    });
+}
+
+int tae_aesx_gcm_long_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *rk, const uint64_t *hk,
+                                      size_t n_powers, const uint64_t *sk, size_t n_strides, size_t seg,
+                                      const tae_gcm_frame *frames, size_t n_frames, int tag_len, int rounds,
+                                      uint64_t *out_plain, uint64_t *out_tag_diff, int mem) {
+    return guarded([&] {
+        require((rk && hk && sk && out_tag_diff) || !n_frames, "null");
+        key_cts(key_bits);
+        const std::vector<tae::Context::GcmFrameIn> in = gcm_frames_in(frames, n_frames);
+        require_xts_server(ctx);
+        ctx->ctx->aes_gcm_long_raw(rk, hk, n_powers, sk, n_strides, seg, in, tag_len, rounds, out_plain, out_tag_diff,
+                                   mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesx_gcm_long_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
+                                  const tae_bit *const *hk, size_t n_powers, const tae_bit *const *sk, size_t n_strides,
+                                  size_t seg, const tae_gcm_frame *frames, size_t n_frames, int tag_len, int rounds,
+                                  tae_bit **out_plain, tae_bit **out_tag_diff) {
+    return guarded([&] {
+        require((expanded_key && hk && sk && out_tag_diff) || !n_frames, "null");
+        const size_t kw = key_cts(key_bits);
+        const std::vector<tae::Context::GcmFrameIn> in = gcm_frames_in(frames, n_frames);
+        require_xts_server(ctx);
+        if (!n_frames) return;
+        const tae::Context::GcmBits res =
+            ctx->ctx->aes_gcm_long(unwrap(expanded_key, kw), unwrap(hk, n_powers * 128), unwrap(sk, n_strides * 128), seg,
+                                   in, tag_len, rounds, key_bits);
+        require(out_plain || res.plain.empty(), "null");
+        emit(res.plain, out_plain);
+        emit(res.tag_diff, out_tag_diff);
+    });
+}
+
 int tae_stage_gf128_square(const tae_context *ctx, const uint64_t *in, size_t count, uint64_t *out, int mem) {
     return guarded([&] {
         require((in && out) || !count, "null");

@@ -221,6 +221,17 @@ class Engine {
     void aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers,
                              const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
                              uint64_t *d_out_tagdiff);
+    // ---- frames beyond one table: segmented GHASH (aes_gcm.hpp) ----
+    // the stride key H^seg, H^(2 seg) .. H^(n_strides seg) [n_strides][128][K+1] of the table d_hk: entry 0 a copy of
+    // d_hk's block seg - 1, the rest the generations of gcm_power_schedule(n_strides) on that base
+    void ghash_stride_key(const uint64_t *d_hk, size_t n_powers, size_t seg, int n_strides, uint64_t *d_out);
+    // aes_gcm_transcipher's public pass, then the inner segments of all frames in batches of gcm_seg_batch_ (chunk
+    // sums over the table's first seg powers, identity bootstrap, row sums, identity bootstrap, one product with the
+    // segment's stride power from d_sk), then the final chunk sums over the table, E(J0) and the products, one
+    // identity bootstrap and the differences.  A frame of at most seg hashed blocks runs aes_gcm_transcipher's launches
+    void aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers, const uint64_t *d_sk,
+                                  size_t n_strides, size_t seg, const std::vector<GcmFrameIn> &frames, int rounds, int nr,
+                                  uint64_t *d_out_plain, uint64_t *d_out_tagdiff);
 
     // ---- multi-key batches on the 1-bit model (the reference has one key).  A key table is
     // [n_keys][4 (nr + 1) * 32][K+1], slot s an expanded (or decryption) key in the layout above.  The bootstraps
@@ -398,7 +409,18 @@ class Engine {
     size_t cap_gcm_src_ = 0, cap_gcm_a_ = 0, cap_gcm_b_ = 0, cap_gcm_ops_ = 0, cap_gcm_ks_ = 0, cap_gcm_parts_ = 0,
            cap_gcm_bytes_ = 0;
     std::vector<uint8_t> gcm_bytes_;
+    // segmented GHASH: inner segments per batch (TAE_GCM_SEG_BATCH, 1 .. 64; 16 products are the largest cbs_vp launch
+    // the tests pin)
+    size_t gcm_seg_batch_ = 16;
     void require_gcm() const;
+    // the generations of gcm_power_schedule(n) on the table d_tab [n][128][K+1], whose entry 0 is the base
+    void gcm_power_generations(uint64_t *d_tab, int n);
+    // the layout checks and payload offsets of a call's frames; returns the payload bytes
+    size_t gcm_frame_offsets(const std::vector<GcmFrameIn> &frames, std::vector<int64_t> &off) const;
+    // the public blocks of a call: the ciphertext bytes up, the counters into d_out_plain, E(J0) of frame s into block
+    // s of d_j0
+    void gcm_public_pass(const uint64_t *d_rk, const std::vector<GcmFrameIn> &frames, const std::vector<int64_t> &off,
+                         size_t total, int rounds, int nr, uint64_t *d_out_plain, uint64_t *d_j0);
     void gcm_square_pass(const uint64_t *d_src, size_t n_src, const std::vector<size_t> &blocks,
                          const std::vector<uint64_t *> &outs);
     void gcm_product_pass(const std::vector<const uint64_t *> &a, const std::vector<const uint64_t *> &b,

@@ -787,6 +787,15 @@ void Engine::init_common() {
             throw std::runtime_error(std::string("TAE_CTR_CHUNK_BLOCKS must be a positive integer, got '") + cc + "'");
         ctr_chunk_ = (size_t)v;
     }
+    // segmented GHASH (aes_gcm_long_transcipher): inner segments per batch, 1 .. 64
+    if (const char *sb = getenv("TAE_GCM_SEG_BATCH")) {
+        char *end = nullptr;
+        errno = 0;
+        const long long v = strtoll(sb, &end, 10);
+        if (errno != 0 || end == sb || *end != '\0' || v <= 0 || v > 64)
+            throw std::runtime_error(std::string("TAE_GCM_SEG_BATCH must be an integer in 1..=64, got '") + sb + "'");
+        gcm_seg_batch_ = (size_t)v;
+    }
     HIPC(hipDeviceGetAttribute(&num_cu_, hipDeviceAttributeMultiprocessorCount, device_));
     if (mask_cus) num_cu_ = mask_cus;
     // the lvl_64 PBS throughput kernel: br512p16 (sixteen points per lane, two ciphertexts per workgroup) or

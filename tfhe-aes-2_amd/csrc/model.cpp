@@ -1738,6 +1738,42 @@ void require_gcm_rounds(int rounds) {
 void require_powers(int n_powers) {
     if (n_powers < 1 || n_powers > kGcmMaxPowers) throw ModelError{TAE_E_PARAM, "n_powers must be in 1..=64"};
 }
+
+// one product on metadata: 7168 partial bits at 8 with fresh ids, chunk sums, a refresh, the reduction, a refresh
+std::vector<NoiseLevel> product_noise(const GcmProductPlan &pp, uint64_t max, uint64_t *top_chunk, uint64_t *top_reduced) {
+    std::vector<NoiseLevel> parts(kGcmParts);
+    for (auto &x : parts) x = NoiseLevel::with_noise_level(8, next_ct_id());
+    rowsum_noise(parts, pp.chunks, max, top_chunk);
+    rowsum_noise(fresh_levels(pp.chunks.n_rows()), pp.reduce, max, top_reduced);
+    return fresh_levels(128);
+}
+
+// the generations of gcm_power_schedule(n) on out.table [n * 128], whose entry 0 is the base
+void power_generations_noise(GhashKeyNoise &out, int n, uint64_t max) {
+    auto put = [&](int k, std::vector<NoiseLevel> v) {
+        for (int i = 0; i < 128; i++) out.table[(size_t)(k - 1) * 128 + i] = std::move(v[i]);
+    };
+    const GcmProductPlan pp = gcm_product_plan();
+    RowPlan sq = gcm_square_plan();
+    for (const GcmGeneration &gen : gcm_power_schedule(n)) {
+        for (int k : gen.squares) {
+            sq.base_of.assign(128, (k / 2 - 1) * 128);  // the operand: power k / 2
+            rowsum_noise(out.table, sq, max, &out.max_square);
+            put(k, fresh_levels(128));  // refreshed even at 5: table entries must not share ids with each other
+        }
+        for (int k : gen.products) put(k, product_noise(pp, max, &out.max_chunk, &out.max_reduced));
+    }
+}
+
+void throw_gcm_long(GcmLongStatus st) {
+    switch (st) {
+        case GCM_LONG_SEG: throw ModelError{TAE_E_PARAM, "seg must be in 1..=min(n_powers, 64)"};
+        case GCM_LONG_STRIDES:
+            throw ModelError{TAE_E_PARAM, "n_strides must be in 1..=64 and at least the frame's segments less one"};
+        case GCM_LONG_NOISE: throw ModelError{TAE_E_NOISE, "a row needs more than 64 refreshed chunks"};
+        default: break;
+    }
+}
 }  // namespace
 
 GhashKeyNoise aes_ghash_key_noise_schedule(const std::vector<NoiseLevel> &rk, int n_powers, int rounds, uint64_t max,
@@ -1747,29 +1783,24 @@ GhashKeyNoise aes_ghash_key_noise_schedule(const std::vector<NoiseLevel> &rk, in
     require_key_words(rk.size(), nr, "expanded key");
     GhashKeyNoise out;
     out.table.resize((size_t)n_powers * 128);
-    auto put = [&](int k, std::vector<NoiseLevel> v) {
-        for (int i = 0; i < 128; i++) out.table[(size_t)(k - 1) * 128 + i] = std::move(v[i]);
-    };
     // E_K(0) is validated by the cipher's schedule; the identity bootstrap gives noise^2 = 1 with fresh ids
     aes_noise_schedule(rk, std::vector<NoiseLevel>(128, NoiseLevel::trivial()), rounds, max, nr);
-    put(1, fresh_levels(128));
-    const GcmProductPlan pp = gcm_product_plan();
-    RowPlan sq = gcm_square_plan();
-    for (const GcmGeneration &gen : gcm_power_schedule(n_powers)) {
-        for (int k : gen.squares) {
-            sq.base_of.assign(128, (k / 2 - 1) * 128);  // the operand: H^(k/2)
-            rowsum_noise(out.table, sq, max, &out.max_square);
-            put(k, fresh_levels(128));  // refreshed even at 5: table entries must not share ids with each other
-        }
-        for (int k : gen.products) {
-            (void)k;
-            std::vector<NoiseLevel> parts(kGcmParts);
-            for (auto &x : parts) x = NoiseLevel::with_noise_level(8, next_ct_id());
-            rowsum_noise(parts, pp.chunks, max, &out.max_chunk);
-            rowsum_noise(fresh_levels(pp.chunks.n_rows()), pp.reduce, max, &out.max_reduced);
-            put(k, fresh_levels(128));
-        }
-    }
+    const std::vector<NoiseLevel> h1 = fresh_levels(128);
+    std::copy(h1.begin(), h1.end(), out.table.begin());
+    power_generations_noise(out, n_powers, max);
+    return out;
+}
+
+GhashKeyNoise aes_ghash_stride_key_noise_schedule(const std::vector<NoiseLevel> &hk, size_t seg, int n_strides,
+                                                  uint64_t max) {
+    if (hk.empty() || hk.size() % 128) throw ModelError{TAE_E_ARG, "the power table is n_powers * 128 bits"};
+    if (seg < 1 || seg > hk.size() / 128 || seg > (size_t)kGcmMaxPowers)
+        throw ModelError{TAE_E_PARAM, "seg must be in 1..=min(n_powers, 64)"};
+    if (n_strides < 1 || n_strides > kGcmMaxStrides) throw ModelError{TAE_E_PARAM, "n_strides must be in 1..=64"};
+    GhashKeyNoise out;
+    out.table.resize((size_t)n_strides * 128);
+    std::copy(hk.begin() + (std::ptrdiff_t)((seg - 1) * 128), hk.begin() + (std::ptrdiff_t)(seg * 128), out.table.begin());
+    power_generations_noise(out, n_strides, max);
     return out;
 }
 
@@ -1800,6 +1831,54 @@ GcmNoise aes_gcm_noise_schedule(const std::vector<NoiseLevel> &rk, const std::ve
     GcmCallPlan plan;
     const std::vector<uint8_t> no_tag((size_t)f.tag_len, 0);
     gcm_call_plan_add(plan, rows, f.m(), 0, no_tag.data());
+    rowsum_noise(src, plan.chunks, max, &out.max_chunk);
+    out.tag_diff = rowsum_noise(fresh_levels(plan.chunks.n_rows()), plan.diff, max, nullptr);
+    return out;
+}
+
+GcmLongNoise aes_gcm_long_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &hk,
+                                         const std::vector<NoiseLevel> &sk, size_t seg, const GcmFrame &f, int rounds,
+                                         uint64_t max, int nr) {
+    require_rounds(rounds, nr);
+    require_gcm_rounds(rounds);
+    require_key_words(rk.size(), nr, "expanded key");
+    if (!f.m() || f.n_pub() < 2 || hk.size() % 128 || sk.size() % 128)
+        throw ModelError{TAE_E_ARG, "empty GCM frame or a broken power table"};
+    throw_gcm_long(gcm_long_shape_check(f.m(), seg, hk.size() / 128, sk.size() / 128));
+    // every row before any level: the refusal does not depend on how far the replay got
+    const size_t C = gcm_long_segments(f.m(), seg), table_blocks = std::min(seg, f.m());
+    std::vector<std::vector<int32_t>> rows;
+    std::vector<GcmInnerPlan> inner(C - 1);
+    for (size_t c = 1; c < C; c++) {
+        gcm_segment_rows(f, seg, c, 128, rows);
+        if (!gcm_inner_rows_ok(rows)) throw_gcm_long(GCM_LONG_NOISE);
+        gcm_inner_plan_add(inner[c - 1], rows);
+    }
+    gcm_long_final_rows(f, seg, table_blocks + 1, rows);
+    if (!gcm_final_rows_ok(rows)) throw_gcm_long(GCM_LONG_NOISE);
+    const std::vector<NoiseLevel> triv(128, NoiseLevel::trivial());
+    GcmLongNoise out;
+    out.plain.resize(f.data_len * 8);
+    for (size_t b = 0; b * 16 < f.data_len; b++) {
+        const std::vector<NoiseLevel> ks = aes_noise_schedule(rk, triv, rounds, max, nr);
+        for (size_t i = 0; i < 128 && (b * 16 + i / 8) < f.data_len; i++) out.plain[b * 128 + i] = ks[i];
+    }
+    // the final source array of a one-frame call: the table's first blocks, E(J0), then the products
+    std::vector<NoiseLevel> src(hk.begin(), hk.begin() + (std::ptrdiff_t)(table_blocks * 128));
+    const std::vector<NoiseLevel> j0 = aes_noise_schedule(rk, triv, rounds, max, nr);
+    src.insert(src.end(), j0.begin(), j0.end());
+    const GcmProductPlan pp = gcm_product_plan();
+    for (size_t c = 1; c < C; c++) {
+        const GcmInnerPlan &ip = inner[c - 1];
+        rowsum_noise(src, ip.chunks, max, &out.max_inner_chunk);  // reads table bits only: indices below 128 seg
+        rowsum_noise(fresh_levels(ip.chunks.n_rows()), ip.rows, max, &out.max_inner_row);
+        // S_c is refreshed to noise^2 = 1 with fresh ids; the product's partial bits are fresh whatever its operands
+        const std::vector<NoiseLevel> prod = product_noise(pp, max, &out.max_part_chunk, &out.max_reduced);
+        src.insert(src.end(), prod.begin(), prod.end());
+    }
+    GcmCallPlan plan;
+    const std::vector<uint8_t> no_tag((size_t)f.tag_len, 0);
+    gcm_call_plan_add(plan, rows, table_blocks, 0, no_tag.data());
     rowsum_noise(src, plan.chunks, max, &out.max_chunk);
     out.tag_diff = rowsum_noise(fresh_levels(plan.chunks.n_rows()), plan.diff, max, nullptr);
     return out;
@@ -1902,6 +1981,108 @@ Context::GcmBits Context::aes_gcm(const std::vector<const BitCt *> &expanded_key
     const std::vector<uint64_t> rk = gather_bits(expanded_key, L), table = gather_bits(hk, L);
     std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
     gcm_call(rk.data(), table.data(), n_powers, frames, in, tag_len, rounds, nr, kw, plain.data(), tag.data(), false);
+    // xor with a public bit adds no noise
+    return {wrap_bits(plain, std::move(pn), L, params().max_noise_sq), wrap_bits(tag, std::move(tn), L, params().max_noise_sq)};
+}
+
+// ---- frames beyond one table: segmented GHASH ----
+void Context::aes_ghash_stride_key_raw(const uint64_t *hk, size_t n_powers, size_t seg, int n_strides, uint64_t *out,
+                                       bool device_mem) {
+    if (params().model != 1) throw ModelError{TAE_E_PARAM, "GCM runs on the 1-bit WoP-PBS parameter sets only"};
+    if (!n_powers) throw ModelError{TAE_E_PARAM, "the power table is empty"};
+    if (seg < 1 || seg > n_powers || seg > (size_t)kGcmMaxPowers)
+        throw ModelError{TAE_E_PARAM, "seg must be in 1..=min(n_powers, 64)"};
+    // the replay reads block seg - 1 alone: a fresh table of seg blocks stands for the caller's n_powers
+    aes_ghash_stride_key_noise_schedule(fresh_levels(seg * 128), seg, n_strides, params().max_noise_sq);
+    Staged st(*this, device_mem);
+    engine_->ghash_stride_key(st.in(hk, n_powers * 128 * bit_len()), n_powers, seg, n_strides,
+                              st.out(out, (size_t)n_strides * 128 * bit_len()));
+    st.finish();
+}
+
+std::vector<BitCt> Context::aes_ghash_stride_key(const std::vector<const BitCt *> &hk, size_t seg, int n_strides) {
+    if (params().model != 1) throw ModelError{TAE_E_PARAM, "GCM runs on the 1-bit WoP-PBS parameter sets only"};
+    if (hk.empty() || hk.size() % 128) throw ModelError{TAE_E_ARG, "the power table is n_powers * 128 bits"};
+    const size_t L = bit_len(), n_powers = hk.size() / 128;
+    std::vector<NoiseLevel> khk(hk.size());
+    for (size_t i = 0; i < hk.size(); i++) khk[i] = hk[i]->noise;
+    GhashKeyNoise kn = aes_ghash_stride_key_noise_schedule(khk, seg, n_strides, params().max_noise_sq);
+    const std::vector<uint64_t> table = gather_bits(hk, L);
+    std::vector<uint64_t> sk(kn.table.size() * L);
+    {
+        Staged st(*this, false);
+        engine_->ghash_stride_key(st.in(table.data(), table.size()), n_powers, seg, n_strides, st.out(sk.data(), sk.size()));
+        st.finish();
+    }
+    return wrap_bits(sk, std::move(kn.table), L, params().max_noise_sq);
+}
+
+void Context::gcm_long_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const uint64_t *sk, size_t n_strides,
+                            size_t seg, const std::vector<GcmFrame> &frames, const std::vector<GcmFrameIn> &in,
+                            int tag_len, int rounds, int nr, size_t key_cts, uint64_t *out_plain, uint64_t *out_tag_diff,
+                            bool device_mem) {
+    const size_t n = frames.size(), S = bit_len();
+    size_t total = 0;
+    for (const GcmFrame &f : frames) total += f.data_len;
+    std::vector<Engine::GcmFrameIn> ein(n);
+    for (size_t s = 0; s < n; s++) ein[s] = {&frames[s], in[s].data, in[s].data + frames[s].data_len};
+    Staged st(*this, device_mem);
+    const uint64_t *d_rk = st.in(rk, key_cts * S), *d_hk = st.in(hk, n_powers * 128 * S);
+    const uint64_t *d_sk = st.in(sk, n_strides * 128 * S);
+    uint64_t *d_plain = st.out(out_plain, total * 8 * S), *d_tag = st.out(out_tag_diff, n * 8 * (size_t)tag_len * S);
+    engine_->aes_gcm_long_transcipher(d_rk, d_hk, n_powers, d_sk, n_strides, seg, ein, rounds, nr, d_plain, d_tag);
+    st.finish();
+}
+
+void Context::aes_gcm_long_raw(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const uint64_t *sk,
+                               size_t n_strides, size_t seg, const std::vector<GcmFrameIn> &in, int tag_len, int rounds,
+                               uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem, int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    require_gcm_rounds(rounds);
+    if (!n_powers) throw ModelError{TAE_E_PARAM, "the power table is empty"};
+    // before tables of that length are made for the replay
+    throw_gcm_long(gcm_long_shape_check(1, seg, n_powers, n_strides));
+    const std::vector<GcmFrame> frames = gcm_frames(in, tag_len);
+    if (frames.empty()) return;
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    // seg <= 64 and n_strides <= 64 by the shape check above: the replay's tables are bounded whatever n_powers is
+    const std::vector<NoiseLevel> krk = fresh_levels(kw), khk = fresh_levels(seg * 128), ksk = fresh_levels(n_strides * 128);
+    // the replay reads the table's first seg blocks only: hk stands for a table of n_powers through the shape check
+    for (const GcmFrame &f : frames) {
+        throw_gcm_long(gcm_long_shape_check(f.m(), seg, n_powers, n_strides));
+        aes_gcm_long_noise_schedule(krk, khk, ksk, seg, f, rounds, params().max_noise_sq, nr);
+    }
+    gcm_long_call(rk, hk, n_powers, sk, n_strides, seg, frames, in, tag_len, rounds, nr, kw, out_plain, out_tag_diff,
+                  device_mem);
+}
+
+Context::GcmBits Context::aes_gcm_long(const std::vector<const BitCt *> &expanded_key, const std::vector<const BitCt *> &hk,
+                                       const std::vector<const BitCt *> &sk, size_t seg, const std::vector<GcmFrameIn> &in,
+                                       int tag_len, int rounds, int key_bits) {
+    const int nr = require_inverse(rounds, key_bits);
+    require_gcm_rounds(rounds);
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
+    require_key_words(expanded_key.size(), nr, "expanded key");
+    if (hk.empty() || hk.size() % 128 || sk.size() % 128)
+        throw ModelError{TAE_E_ARG, "the power table and the stride key are n * 128 bits"};
+    const size_t n_powers = hk.size() / 128, n_strides = sk.size() / 128;
+    throw_gcm_long(gcm_long_shape_check(1, seg, n_powers, n_strides));
+    const std::vector<GcmFrame> frames = gcm_frames(in, tag_len);
+    if (frames.empty()) return {};
+    // the stride key's levels are not consulted (model.hpp): its length alone goes into the replay
+    const std::vector<NoiseLevel> ksk(sk.size());
+    std::vector<NoiseLevel> krk(kw), khk(hk.size()), pn, tn;
+    for (size_t i = 0; i < kw; i++) krk[i] = expanded_key[i]->noise;
+    for (size_t i = 0; i < hk.size(); i++) khk[i] = hk[i]->noise;
+    for (const GcmFrame &f : frames) {
+        GcmLongNoise gn = aes_gcm_long_noise_schedule(krk, khk, ksk, seg, f, rounds, params().max_noise_sq, nr);
+        for (NoiseLevel &x : gn.plain) pn.push_back(std::move(x));
+        for (NoiseLevel &x : gn.tag_diff) tn.push_back(std::move(x));
+    }
+    const std::vector<uint64_t> rk = gather_bits(expanded_key, L), table = gather_bits(hk, L), strides = gather_bits(sk, L);
+    std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
+    gcm_long_call(rk.data(), table.data(), n_powers, strides.data(), n_strides, seg, frames, in, tag_len, rounds, nr, kw,
+                  plain.data(), tag.data(), false);
     // xor with a public bit adds no noise
     return {wrap_bits(plain, std::move(pn), L, params().max_noise_sq), wrap_bits(tag, std::move(tn), L, params().max_noise_sq)};
 }

@@ -251,6 +251,24 @@ class Context {  // FheContext
     // BitCt variant: the bits carry the levels and ids of aes_gcm_noise_schedule
     GcmBits aes_gcm(const std::vector<const BitCt *> &expanded_key, const std::vector<const BitCt *> &hk,
                     const std::vector<GcmFrameIn> &frames, int tag_len, int rounds, int key_bits);
+    // ---- frames beyond one table: segmented GHASH (aes_gcm.hpp).  The scope and the refusals of the
+    // calls above, and before any device work: seg outside 1 .. min(n_powers, 64), n_strides outside 1 .. 64, a frame of more
+    // than n_strides + 1 segments (TAE_E_PARAM); an inner or a final row beyond 64 chunks (TAE_E_NOISE; never for
+    // seg <= 31) ----
+    // the stride key H^seg .. H^(n_strides seg) [n_strides][128][bit_len] of the table hk [n_powers][128][bit_len];
+    // entry 0 is a copy of hk's block seg - 1
+    void aes_ghash_stride_key_raw(const uint64_t *hk, size_t n_powers, size_t seg, int n_strides, uint64_t *out,
+                                  bool device_mem);
+    // BitCt variant: entry 0 clones the table's bits (their ids), every later bit is noise^2 = 1 with a fresh id
+    std::vector<BitCt> aes_ghash_stride_key(const std::vector<const BitCt *> &hk, size_t seg, int n_strides);
+    // the outputs of aes_gcm_raw for frames of up to (n_strides + 1) seg hashed blocks
+    void aes_gcm_long_raw(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const uint64_t *sk, size_t n_strides,
+                          size_t seg, const std::vector<GcmFrameIn> &frames, int tag_len, int rounds, uint64_t *out_plain,
+                          uint64_t *out_tag_diff, bool device_mem, int key_bits);
+    // BitCt variant: the bits carry the levels and ids of aes_gcm_long_noise_schedule
+    GcmBits aes_gcm_long(const std::vector<const BitCt *> &expanded_key, const std::vector<const BitCt *> &hk,
+                         const std::vector<const BitCt *> &sk, size_t seg, const std::vector<GcmFrameIn> &frames,
+                         int tag_len, int rounds, int key_bits);
     // stage calls, no noise rule: squares / products of `count` field elements [count][128][bit_len]
     void gf128_square_raw(const uint64_t *in, size_t count, uint64_t *out, bool device_mem);
     void gf128_product_raw(const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out, bool device_mem);
@@ -306,6 +324,9 @@ class Context {  // FheContext
     void gcm_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrame> &frames,
                   const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int nr, size_t key_cts, uint64_t *out_plain,
                   uint64_t *out_tag_diff, bool device_mem);
+    void gcm_long_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const uint64_t *sk, size_t n_strides,
+                       size_t seg, const std::vector<GcmFrame> &frames, const std::vector<GcmFrameIn> &in, int tag_len,
+                       int rounds, int nr, size_t key_cts, uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem);
     void run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
                      const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem, int nr);
     void run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint64_t *d_in, size_t n_blocks, int rounds,
@@ -382,6 +403,24 @@ struct GcmNoise {
 };
 GcmNoise aes_gcm_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &hk, const GcmFrame &frame,
                                 int rounds, uint64_t max_noise_sq, int nr = 10);
+// Segmented GHASH.  The stride key of the table hk [n_powers * 128]: entry 0 keeps the levels and ids
+// of hk's block seg - 1 and enters no sum with a table bit; the rest is the schedule above on that base, every bit at
+// noise^2 = 1 with a fresh id.  seg outside 1 .. min(n_powers, 64) and n_strides outside 1 .. 64 are TAE_E_PARAM.
+GhashKeyNoise aes_ghash_stride_key_noise_schedule(const std::vector<NoiseLevel> &hk, size_t seg, int n_strides,
+                                                  uint64_t max_noise_sq);
+// ONE frame under rk, hk and the stride key sk [n_strides * 128].  An inner chunk is at most 64 table bits; an inner
+// row the sum of its refreshed chunks (at most 64), then 1 after its refresh; a product as the key schedule replays
+// it; the first final chunk the E(J0) bit (8 + 1) plus at most 55 level-1 bits (table bits and product bits), later
+// ones at most 64; a tag-difference bit its chunk count with fresh ids and no key bit; a payload bit 8 + 1.  Of sk
+// only the length is read: a stride power enters nothing but a product, whose 256 operand bits each go through the
+// circuit bootstrap, so its levels and ids reach no sum (the key schedules replay a product the same way).
+struct GcmLongNoise {
+    std::vector<NoiseLevel> plain, tag_diff;  // [data_len * 8], [8 tag_len]
+    uint64_t max_inner_chunk = 0, max_inner_row = 0, max_part_chunk = 0, max_reduced = 0, max_chunk = 0;
+};
+GcmLongNoise aes_gcm_long_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &hk,
+                                         const std::vector<NoiseLevel> &sk, size_t seg, const GcmFrame &frame, int rounds,
+                                         uint64_t max_noise_sq, int nr = 10);
 
 // Counter mode on the 1-bit model: output noise [n_blocks][128] of the gal-mul schedule for trivial counter
 // blocks.  rounds >= 2: aes_noise_schedule per block.  rounds == 1: the final SubBytes runs on the plan's

@@ -57,6 +57,8 @@ EXPORTED = [
     "tae_aesx_gcm_format", "tae_aesx_gcm_tag_rows", "tae_aesx_gcm_noise_schedule_check", "tae_aesx_ghash_key_raw",
     "tae_aesx_ghash_key", "tae_aesx_gcm_transcipher_raw", "tae_aesx_gcm_transcipher", "tae_stage_gf128_square",
     "tae_stage_gf128_product",
+    "tae_aesx_gcm_long_rows", "tae_aesx_gcm_long_noise_schedule_check", "tae_aesx_ghash_stride_key_raw",
+    "tae_aesx_ghash_stride_key", "tae_aesx_gcm_long_transcipher_raw", "tae_aesx_gcm_long_transcipher",
     "tae_last_pfks_kernel",
     "tae_packed_len", "tae_encrypt_packed_raw", "tae_decrypt_packed_raw", "tae_packed_narrow", "tae_packed_widen",
     "tae_unpack_bits_raw", "tae_pack_bits_raw", "tae_unpack_bits", "tae_pack_bits", "tae_last_pack_time",
@@ -226,6 +228,13 @@ def lib() -> C.CDLL:
         "tae_aesx_ghash_key": ([vp, C.c_int, vp, C.c_int, C.c_int, vp], C.c_int),
         "tae_aesx_gcm_transcipher_raw": ([vp, C.c_int, vp, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp, C.c_int], C.c_int),
         "tae_aesx_gcm_transcipher": ([vp, C.c_int, vp, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp], C.c_int),
+        "tae_aesx_gcm_long_rows": ([vp, sz, vp, sz, vp, sz, C.c_int, sz, sz, sz, vp, vp], C.c_int),
+        "tae_aesx_gcm_long_noise_schedule_check": ([C.c_int, C.c_int, C.c_int, C.c_int, sz, C.c_int, sz, sz], C.c_int),
+        "tae_aesx_ghash_stride_key_raw": ([vp, vp, sz, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesx_ghash_stride_key": ([vp, vp, sz, sz, C.c_int, vp], C.c_int),
+        "tae_aesx_gcm_long_transcipher_raw": ([vp, C.c_int, vp, vp, sz, vp, sz, sz, vp, sz, C.c_int, C.c_int, vp, vp,
+                                               C.c_int], C.c_int),
+        "tae_aesx_gcm_long_transcipher": ([vp, C.c_int, vp, vp, sz, vp, sz, sz, vp, sz, C.c_int, C.c_int, vp, vp], C.c_int),
         "tae_stage_gf128_square": ([vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_gf128_product": ([vp, vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_keyswitch": ([vp, vp, sz, vp, C.c_int], C.c_int),

@@ -424,6 +424,28 @@ def gcm_noise_schedule_check(param_set: int, key_bits: int, rounds: int, n_power
     check(lib().tae_aesx_gcm_noise_schedule_check(param_set, key_bits, rounds, n_powers, aad_len, data_len))
 
 
+def gcm_long_rows(iv: bytes, aad: bytes, data: bytes, tag_len: int, n_powers: int, seg: int, n_strides: int):
+    """(sources [C][128], chunks [C][128]) of the frame's segmented plan (tae_aesx_gcm_long_rows), C = ceil(m / seg):
+    segment 0 holds the final rows r < 8 tag_len (table bits and one bit per product), segment c >= 1 the inner rows of
+    S_c.  The refusals of gcm_long_transcipher: TAE_E_PARAM for the shape, TAE_E_NOISE for a row of more than 64 chunks."""
+    (ib, _), (ab, a_ptr), (db, d_ptr) = _bytes_ptr(iv), _bytes_ptr(aad), _bytes_ptr(data)
+    m = (len(ab) + 15) // 16 + (len(db) + 15) // 16 + 1
+    segs = max(-(-m // seg), 1) if seg >= 1 else 1
+    src = np.zeros((segs, 128), dtype=np.int32)
+    chunks = np.zeros((segs, 128), dtype=np.int32)
+    check(lib().tae_aesx_gcm_long_rows(_p(ib), len(ib), a_ptr, len(ab), d_ptr, len(db), tag_len, n_powers, seg,
+                                       n_strides, _p(src), _p(chunks)))
+    return src, chunks
+
+
+def gcm_long_noise_schedule_check(param_set: int, key_bits: int, rounds: int, n_powers: int, seg: int, n_strides: int,
+                                  aad_len: int = 8, data_len: int = 17) -> None:
+    """The noise bookkeeping of the power table, the stride key and one dense frame for a fresh key, without a context
+    or device."""
+    check(lib().tae_aesx_gcm_long_noise_schedule_check(param_set, key_bits, rounds, n_powers, seg, n_strides, aad_len,
+                                                       data_len))
+
+
 def gcm_tag_ok(client_key, tag_diff) -> bool:
     """The client's check, with the semantics of ccm_tag_ok: accepts iff every tag-difference bit decrypts to zero."""
     return ccm_tag_ok(client_key, tag_diff)
@@ -465,6 +487,14 @@ def _raw_key(key: np.ndarray, key_bits: Optional[int]):
         raise N.TaeError(N.TAE_E_ARG, f"the key has {key.shape[0] // 32} words, AES-{key_bits} needs "
                                       f"{expanded_words(key_bits)}")
     return key, kb
+
+
+def _raw_table(table: np.ndarray, what: str) -> np.ndarray:
+    """A table of field elements [n][128][L] as a contiguous array (TAE_E_ARG for another shape)."""
+    table = np.ascontiguousarray(table, dtype=np.uint64)
+    if table.ndim != 3 or table.shape[1] != 128:
+        raise N.TaeError(N.TAE_E_ARG, what)
+    return table
 
 
 def _bit_key(key, key_bits: Optional[int]):
@@ -891,6 +921,85 @@ class GalMulAes:
         check(lib().tae_aesx_gcm_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_rk), C.c_void_p(d_hk), n_powers, arr,
                                                  len(frames), tag_len, rounds, C.c_void_p(d_out),
                                                  C.c_void_p(d_tag_diff), N.TAE_MEM_DEVICE))
+
+    # ---- frames beyond one table: segmented GHASH ----
+    # ghash_stride_key makes H^seg, H^(2 seg) .. H^(n_strides seg) once per key and seg from a table of at least seg
+    # powers; gcm_long_transcipher then takes frames of up to (n_strides + 1) seg hashed blocks and returns what
+    # gcm_transcipher returns.  seg <= 31 is never refused for noise.
+    @staticmethod
+    def ghash_stride_key(ctx: FheContext, hk, seg: int, n_strides: int):
+        """hk BitCt (nested or flat) -> the stride key as a flat list of n_strides * 128 BitCt; entry 0 clones hk's
+        block seg - 1."""
+        table = _flat_bits(hk)
+        outs = (C.c_void_p * max(128 * n_strides, 1))()
+        check(lib().tae_aesx_ghash_stride_key(ctx._h, _handles(table), len(table) // 128, seg, n_strides, outs))
+        return [BitCt(outs[i], ctx) for i in range(128 * n_strides)]
+
+    @staticmethod
+    def ghash_stride_key_raw(ctx: FheContext, hk: np.ndarray, seg: int, n_strides: int) -> np.ndarray:
+        """Host arrays: hk [n_powers][128][L] -> sk [n_strides][128][L], sk[j - 1] = H^(seg j)."""
+        hk = _raw_table(hk, "a power table is an array [n_powers][128][L]")
+        sk = np.zeros((max(n_strides, 1), 128, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_ghash_stride_key_raw(ctx._h, _p(hk), hk.shape[0], seg, n_strides, _p(sk), N.TAE_MEM_HOST))
+        return sk[:max(n_strides, 0)]
+
+    @staticmethod
+    def ghash_stride_key_device(ctx: FheContext, d_hk: int, n_powers: int, seg: int, n_strides: int, d_sk: int):
+        check(lib().tae_aesx_ghash_stride_key_raw(ctx._h, C.c_void_p(d_hk), n_powers, seg, n_strides, C.c_void_p(d_sk),
+                                                  N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def gcm_long_transcipher(ctx: FheContext, ek, hk, sk, seg: int, frames, tag_len: int, rounds: Optional[int] = None,
+                             key_bits: Optional[int] = None):
+        """ek / hk / sk BitCt (nested or flat) -> [(bits [len - tag_len][8], tag_diff [tag_len][8]), ..] BitCt."""
+        key, kb = _bit_key(ek, key_bits)
+        table, strides = _flat_bits(hk), _flat_bits(sk)
+        arr, _keep, lens = _gcm_frames(frames, tag_len)
+        n, total = len(frames), sum(lens)
+        outs, tags = (C.c_void_p * max(8 * total, 1))(), (C.c_void_p * max(8 * tag_len * n, 1))()
+        check(lib().tae_aesx_gcm_long_transcipher(ctx._h, kb, _handles(key), _handles(table), len(table) // 128,
+                                                  _handles(strides), len(strides) // 128, seg, arr, n, tag_len,
+                                                  _nr(kb, rounds), outs, tags))
+        res, at = [], 0
+        for f in range(n):
+            bits = [BitCt(outs[8 * at + i], ctx) for i in range(8 * lens[f])]
+            diff = [BitCt(tags[8 * tag_len * f + i], ctx) for i in range(8 * tag_len)]
+            res.append(([bits[8 * i:8 * i + 8] for i in range(lens[f])], [diff[8 * i:8 * i + 8] for i in range(tag_len)]))
+            at += lens[f]
+        return res
+
+    @staticmethod
+    def gcm_long_transcipher_raw(ctx: FheContext, rk: np.ndarray, hk: np.ndarray, sk: np.ndarray, seg: int, frames,
+                                 tag_len: int, rounds: Optional[int] = None, key_bits: Optional[int] = None):
+        """Host arrays: rk [W*32][L], hk [n_powers][128][L], sk [n_strides][128][L] ->
+        [(bits [len - tag_len][8][L], tag_diff [tag_len][8][L]), ..]."""
+        rk, kb = _raw_key(rk, key_bits)
+        hk = _raw_table(hk, "a power table is an array [n_powers][128][L]")
+        sk = _raw_table(sk, "a stride key is an array [n_strides][128][L]")
+        arr, _keep, lens = _gcm_frames(frames, tag_len)
+        n, total = len(frames), sum(lens)
+        out = np.zeros((total, 8, ctx.lwe_size), dtype=np.uint64)
+        diff = np.zeros((n, max(tag_len, 0), 8, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesx_gcm_long_transcipher_raw(ctx._h, kb, _p(rk), _p(hk), hk.shape[0], _p(sk), sk.shape[0], seg,
+                                                      arr, n, tag_len, _nr(kb, rounds), _p(out), _p(diff),
+                                                      N.TAE_MEM_HOST))
+        res, at = [], 0
+        for f in range(n):
+            res.append((out[at:at + lens[f]], diff[f]))
+            at += lens[f]
+        return res
+
+    @staticmethod
+    def gcm_long_transcipher_device(ctx: FheContext, key_bits: int, d_rk: int, d_hk: int, n_powers: int, d_sk: int,
+                                    n_strides: int, seg: int, frames, tag_len: int, rounds: int, d_out: int,
+                                    d_tag_diff: int):
+        """Device pointers (ints) for rk, hk, sk, the payload bits [sum (len - tag_len)][8][L] and the tag differences
+        [n_frames][tag_len][8][L]; the frames are host bytes."""
+        arr, _keep, _ = _gcm_frames(frames, tag_len)
+        check(lib().tae_aesx_gcm_long_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_rk), C.c_void_p(d_hk), n_powers,
+                                                      C.c_void_p(d_sk), n_strides, seg, arr, len(frames), tag_len,
+                                                      rounds, C.c_void_p(d_out), C.c_void_p(d_tag_diff),
+                                                      N.TAE_MEM_DEVICE))
 
     @staticmethod
     def gf128_square_raw(ctx: FheContext, elems: np.ndarray) -> np.ndarray:
