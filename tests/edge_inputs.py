@@ -518,3 +518,131 @@ def tree_mixed_lut(n_out: int, N: int, tree: int, seed: int) -> np.ndarray:
             elif q % 3 == 2:
                 lut[j, i, (np.arange(N) // 8) % 2 == 0] = U64(1 << 62)
     return lut.reshape(-1)
+
+
+# ---- shortint_1bit: the noiseless set, the test-vector windows and the packing sum --------------------------------
+# Shared by test_gpu_s1_edges.py (GPU against the oracle and against these references) and test_edge_inputs.py (CPU
+# pins).  The blind rotation of the set is br512x4<7, true, 6>: 7 levels of 2^6, 22 discarded bits, a test vector per
+# ciphertext.
+
+def zero_key(length: int) -> np.ndarray:
+    """An all-zero key array: under it a (packing) keyswitch returns the trivial ciphertext of the input's body."""
+    return np.zeros(length, dtype=U64)
+
+
+def noiseless_test_vectors(params: dict, rng) -> dict:
+    """The three test vectors of the noiseless-key runs, {name: GLWE [(k+1)N]}: zero mask with the body constant
+    2^62 (every non-zero rotated difference is exactly 2^63: the top digit is the tie 2^(B-1)), zero mask with the
+    body constant 2^63 (every rotated difference is 2^64 = 0: exact zeros at every step) and random words."""
+    return {"const 2^62": const_lut_glwe(params, 1 << 62), "const 2^63": const_lut_glwe(params, 1 << 63),
+            "random": random_words(rng, (params["k"] + 1) * params["N"])}
+
+
+def monomial_mul_np(p, e: int) -> np.ndarray:
+    """X^e p mod X^N + 1 along the last axis (N its length, any integer e), wrapping u64."""
+    p = np.asarray(p, dtype=U64)
+    N = p.shape[-1]
+    e %= 2 * N
+    if e >= N:
+        p, e = U64(0) - p, e - N
+    return p.copy() if e == 0 else np.concatenate([U64(0) - p[..., N - e:], p[..., :N - e]], axis=-1)
+
+
+TV_WINDOW_POSITIONS = lambda N: (0, 1, N // 4 - 1, N // 4, 3 * N // 4 - 1, 3 * N // 4, N - 1)
+TV_WINDOW_VALUES = (1 << 63, MASK64)  # of P0 and of P1
+
+
+def tv_window_polys(N: int) -> list:
+    """Polynomial pairs [(name, P0 [N], P1 [N])] on the window edges of test_vector_from_ciphertexts: a single
+    non-zero coefficient at each of the positions 0, 1, N/4 - 1, N/4, 3N/4 - 1, 3N/4 and N - 1, 2^63 in P0 and
+    2^64 - 1 in P1 (single_coefficient_tv gives the closed form); all ones against all 2^63; one random pair."""
+    pairs = []
+    for pos in TV_WINDOW_POSITIONS(N):
+        p0, p1 = np.zeros(N, dtype=U64), np.zeros(N, dtype=U64)
+        p0[pos], p1[pos] = U64(TV_WINDOW_VALUES[0]), U64(TV_WINDOW_VALUES[1])
+        pairs.append((f"single {pos}", p0, p1))
+    pairs.append(("ones / 2^63", np.ones(N, dtype=U64), np.full(N, 1 << 63, dtype=U64)))
+    rng = np.random.default_rng(N + 4)
+    pairs.append(("random", random_words(rng, N), random_words(rng, N)))
+    return pairs
+
+
+def single_coefficient_tv(N: int, pos: int, v0: int, v1: int) -> np.ndarray:
+    """The test vector of P0 = v0 X^pos, P1 = v1 X^pos in closed form: shift i moves the coefficient to
+    t = pos + i mod N, negated when it wraps, and takes v1 for N/4 <= i < 3N/4 and v0 otherwise."""
+    tv = np.zeros(N, dtype=U64)
+    for t in range(N):
+        i = (t - pos) % N
+        v = v1 if N // 4 <= i < 3 * N // 4 else v0
+        tv[t] = U64(v if t >= pos else (-v) & MASK64)
+    return tv
+
+
+def tv_from_polys_np(P0, P1) -> np.ndarray:
+    """test_vector_from_ciphertexts on the packing keyswitches P0, P1 ([..., N], the last axis a polynomial):
+    sum_{i < N} X^i (P1 if N/4 <= i < 3N/4 else P0), negacyclic, wrapping u64, as N explicit rotations (the
+    device kernel takes windows of prefix sums instead)."""
+    P0, P1 = np.asarray(P0, dtype=U64), np.asarray(P1, dtype=U64)
+    assert P0.shape == P1.shape
+    N = P0.shape[-1]
+    acc = np.zeros_like(P0)
+    for i in range(N):
+        acc += monomial_mul_np(P1 if N // 4 <= i < 3 * N // 4 else P0, i)
+    return acc
+
+
+def pack_np(pks_rows) -> np.ndarray:
+    """The packing sum sum_j X^j P_j over the keyswitched GLWEs pks_rows [count][..., N], as explicit rotations."""
+    rows = np.asarray(pks_rows, dtype=U64)
+    assert 1 <= len(rows) <= rows.shape[-1]
+    acc = np.zeros_like(rows[0])
+    for j, p in enumerate(rows):
+        acc += monomial_mul_np(p, j)
+    return acc
+
+
+def asymmetric_table(nbits: int, seed: int = 0) -> list:
+    """A 0 / 1 function table of nbits inputs (index MSB first) that no permutation of the input bits combined
+    with complementing any of them leaves unchanged (is_asymmetric_table checks it): a selector tree that
+    gathers its bits in another order, or reads a selector inverted, computes another function."""
+    rng = np.random.default_rng([nbits, seed])
+    while True:
+        tab = rng.integers(0, 2, 1 << nbits).tolist()
+        if is_asymmetric_table(tab, nbits):
+            return tab
+
+
+def is_asymmetric_table(tab, nbits: int) -> bool:
+    """Up to four bits by trying every permutation and complement.  Above that by a sufficient condition: with
+    c_i(b) the number of ones of the table among the indices whose bit i is b, a symmetry that sends bit i to bit
+    j complemented by f needs c_j(b ^ f) = c_i(b); so if the unordered pairs {c_i(0), c_i(1)} all differ no bit
+    can move, and if c_i(0) != c_i(1) for every i none can be complemented."""
+    import itertools
+    idx = np.arange(1 << nbits)
+    bits = [(idx >> (nbits - 1 - i)) & 1 for i in range(nbits)]  # bit i, MSB first
+    t = np.asarray(tab)
+    if nbits > 4:
+        sig = [(int(t[b == 0].sum()), int(t[b == 1].sum())) for b in bits]
+        return all(c0 != c1 for c0, c1 in sig) and len({frozenset(s) for s in sig}) == nbits
+    for perm in itertools.permutations(range(nbits)):
+        for flip in range(1 << nbits):
+            if flip == 0 and perm == tuple(range(nbits)):
+                continue
+            j = sum((bits[perm[i]] ^ ((flip >> i) & 1)) << (nbits - 1 - i) for i in range(nbits))
+            if np.array_equal(t[j], t):
+                return False
+    return True
+
+
+# ---- extract_bits of the 8-bit model: trivial ints on the bit boundaries (test_gpu_extract8_edges.py) ------------
+EXTRACT_TIE_VALUES = (0x00, 0xFF, 0x80)
+
+
+def extract_tie_ints(K: int, v: int, delta_log: int = 56) -> np.ndarray:
+    """Four big-key LWEs [4][K+1] with a zero mask and the bodies v 2^56, v 2^56 + 2^55 - 1 (just below the
+    rounding boundary of bit 0), v 2^56 + 2^55 (on it) and v 2^56 - 1 (every bit below the message set)."""
+    half = 1 << (delta_log - 1)
+    rows = np.zeros((4, K + 1), dtype=U64)
+    for r, d in enumerate((0, half - 1, half, -1)):
+        rows[r, K] = U64(((v << delta_log) + d) & MASK64)
+    return rows

@@ -250,3 +250,161 @@ def test_tree_mixed_lut_polynomials_differ(N):
         if len(lut) > 2:  # depth 1 with one output has two polynomials only
             runs = lut[2]
             assert (runs[:8] == np.uint64(1 << 62)).all() and not (runs[8:16] == np.uint64(1 << 62)).any()
+
+
+# ---- shortint_1bit: the noiseless set, test-vector windows, packing sum (test_gpu_s1_edges.py) ----
+S1_SEED = bytes(range(32))
+
+
+@pytest.fixture(scope="module")
+def s1_real(oracle_mod):
+    """The real shortint_1bit keys: the oracle with its client key, and the raw server arrays."""
+    ok = oracle_mod.S1Keys(S1_SEED, threads=8)
+    return ok, ok.raw_server()
+
+
+@pytest.fixture(scope="module")
+def s1_noiseless(oracle_mod, s1_real):
+    """(oracle on (real ksk, noiseless bsk, real packing key), the twelve input rows, the key pattern)."""
+    ok, raw = s1_real
+    p = ok.p
+    s = E.key_pattern(p["n"])
+    nl = oracle_mod.S1Keys(None, raw=(raw[0], E.noiseless_bsk(p, s), raw[2]))
+    real = ok.s1_encrypt([0, 1, 1], S1_SEED, 150)
+    rows = np.concatenate([E.crafted_small(p["n"], p["N"], real, 0),
+                           E.random_words(np.random.default_rng(105), (2, p["n"] + 1))])
+    return nl, rows, s
+
+
+def test_monomial_mul_np_matches_the_exact_product(oracle_mod):
+    """monomial_mul_np (the rotation of tv_from_polys_np and pack_np) against the oracle's exact negacyclic
+    product with the monomial, for shifts on both sides of every wrap."""
+    N = 512
+    p = E.random_words(np.random.default_rng(12), N)
+    for e in (0, 1, N // 4, N - 1, N, N + 1, 2 * N - 1, 2 * N, -1, -N):
+        mono = np.zeros(N, dtype=np.int64)
+        mono[e % N] = 1 if (e % (2 * N)) < N else -1
+        assert np.array_equal(E.monomial_mul_np(p, e), oracle_mod.negacyclic_mul_exact(p, mono)), e
+
+
+def test_s1_noiseless_steps_reach_the_tie_at_base_2_6(oracle_mod, s1_noiseless):
+    """A CMux step on the accumulator the blind rotation starts from, computed exactly (an exact rotation of the
+    constant 2^62), for the first 22 rotating steps of every row: the rotated difference X^a acc - acc holds words of
+    exactly 2^63 and nothing else but zeros, the
+    decomposition of 2^63 at 7 levels of 2^6 is [32, 0, ...] (the tie 2^(B-1)), and over the rows those steps meet
+    key entries 1, -1 and 0; the 0 entry's GGSW is all zero, so that step adds exact zeros."""
+    nl, rows, s = s1_noiseless
+    p = nl.p
+    n, N, B, lv = p["n"], p["N"], p["pbs_b"], p["pbs_l"]
+    assert (lv, B) == (7, 6)
+    assert oracle_mod.decompose(1 << 63, B, lv) == [1 << (B - 1)] + [0] * (lv - 1) == [32, 0, 0, 0, 0, 0, 0]
+    ms = lambda x: int(oracle_mod.lib().or_pbs_modulus_switch(int(x) & MASK, N))
+    bsk = E.noiseless_bsk(p, s).reshape(n, -1)
+    assert not bsk[s == 0].any() and bsk[s != 0].any(axis=1).all()
+    met = set()
+    for r, row in enumerate(rows):
+        acc = E.monomial_mul_np(np.full(N, 1 << 62, dtype=np.uint64), -ms(row[n]))
+        steps = [i for i in range(n) if ms(row[i]) % (2 * N)]
+        if r in (0, 2):  # the all-zero mask and the mask that rounds to 2N rotate nowhere
+            assert not steps
+            continue
+        # every rotating step of the row on the accumulator it would meet first
+        for i in steps[:22]:
+            diff = E.monomial_mul_np(acc, ms(row[i])) - acc
+            assert np.isin(diff, [0, 1 << 63]).all() and (diff == np.uint64(1 << 63)).any(), (r, i)
+            met.add(int(s[i]))
+    assert met == {0, 1, MASK}
+
+
+def test_s1_noiseless_bootstrap_stays_on_the_boundary(s1_noiseless):
+    """S1Keys.bootstrap_big (the blind rotation alone) under the noiseless key: with the constant-2^62 vector the
+    mask stays exactly zero and the body ends within 2^32 of +-2^62 (every step's differences were 0 or +-2^63 up to
+    rounding); with the constant-2^63 vector every difference is 2^64 = 0, every step adds exact zeros and the
+    output is exactly 2^63.  The two outputs differ in the body alone: where the tie was taken."""
+    nl, rows, _ = s1_noiseless
+    tvs = E.noiseless_test_vectors(nl.p, np.random.default_rng(106))
+    for i in (1, 3, 6, 9, 10, 11):
+        out = nl.bootstrap_big(rows[i], tvs["const 2^62"])
+        assert not out[:-1].any(), i
+        body = int(out[-1])
+        assert min((body - (1 << 62)) & MASK, ((1 << 62) - body) & MASK,
+                   (body + (1 << 62)) & MASK, (-(1 << 62) - body) & MASK) < 1 << 32, (i, hex(body))
+        flat = nl.bootstrap_big(rows[i], tvs["const 2^63"])
+        assert not flat[:-1].any() and int(flat[-1]) == 1 << 63, i
+
+
+def test_tv_window_polys_closed_form():
+    """tv_from_polys_np on the window-edge pairs: a single coefficient gives single_coefficient_tv (each output
+    coefficient is +-2^63 or +-(2^64 - 1) by the window of its shift), all ones against all 2^63 gives
+    sum of signs times the window counts, and each of the seven positions puts another output coefficient on each
+    window edge."""
+    N = 512
+    pairs = E.tv_window_polys(N)
+    assert [name for name, _, _ in pairs] == [f"single {q}" for q in E.TV_WINDOW_POSITIONS(N)] + ["ones / 2^63", "random"]
+    v0, v1 = E.TV_WINDOW_VALUES
+    for pos, (_, p0, p1) in zip(E.TV_WINDOW_POSITIONS(N), pairs):
+        assert np.count_nonzero(p0) == np.count_nonzero(p1) == 1 and int(p0[pos]) == v0 and int(p1[pos]) == v1
+        tv = E.tv_from_polys_np(p0, p1)
+        assert np.array_equal(tv, E.single_coefficient_tv(N, pos, v0, v1)), pos
+        # the four window edges: shifts N/4 - 1 | N/4 and 3N/4 - 1 | 3N/4
+        for i, v in ((N // 4 - 1, v0), (N // 4, v1), (3 * N // 4 - 1, v1), (3 * N // 4, v0), (0, v0), (N - 1, v0)):
+            t = (pos + i) % N
+            assert int(tv[t]) == (v if pos + i < N else (-v) & MASK), (pos, i)
+    _, ones, halves = pairs[-2]
+    tv = E.tv_from_polys_np(ones, halves)
+    # coefficient t: shifts i <= t count +1, the others -1; N/2 shifts take 2^63 each (an even count: 0 mod 2^64)
+    for t in (0, 1, N // 4 - 1, N // 4, 3 * N // 4 - 1, 3 * N // 4, N - 1):
+        plus = sum(1 for i in range(N) if not (N // 4 <= i < 3 * N // 4) and i <= t)
+        assert int(tv[t]) == (2 * plus - N // 2) & MASK, t
+    _, r0, r1 = pairs[-1]
+    ref = np.zeros(N, dtype=np.uint64)
+    for t in range(0, N, 37):  # the definition, coefficient by coefficient, in Python integers
+        acc = 0
+        for i in range(N):
+            src = r1 if N // 4 <= i < 3 * N // 4 else r0
+            acc += int(src[t - i]) if t >= i else -int(src[t - i + N])
+        assert int(E.tv_from_polys_np(r0, r1)[t]) == acc & MASK, t
+
+
+def test_tv_and_pack_references_equal_the_oracle(s1_real):
+    """tv_from_polys_np and pack_np on the oracle's packing keyswitches of real ciphertexts equal S1Keys.tv_from_cts
+    and S1Keys.pack (the reference's add-then-rotate loops) under the real key."""
+    ok, _ = s1_real
+    N = ok.p["N"]
+    cts = ok.s1_encrypt([1, 0, 1, 1, 0], S1_SEED, 900)
+    P = np.stack([ok.pks(c) for c in cts]).reshape(len(cts), -1, N)
+    for a, b in ((0, 1), (2, 3), (4, 4)):
+        assert np.array_equal(E.tv_from_polys_np(P[a], P[b]).reshape(-1), ok.tv_from_cts(cts[a], cts[b])), (a, b)
+    for count in (1, 2, 5):
+        assert np.array_equal(E.pack_np(P[:count]).reshape(-1), ok.pack(cts[:count])), count
+
+
+def test_asymmetric_tables():
+    """The function tables of the selector-tree tests: no permutation or complement of the input bits fixes
+    them; parity (the table the existing tests use most) is fixed by every permutation."""
+    for nbits in (4, 8):
+        for seed in (0, 1):
+            tab = E.asymmetric_table(nbits, seed)
+            assert len(tab) == 1 << nbits and set(tab) == {0, 1} and E.is_asymmetric_table(tab, nbits)
+    assert E.asymmetric_table(8, 0) != E.asymmetric_table(8, 1)
+    assert not E.is_asymmetric_table([bin(v).count("1") % 2 for v in range(16)], 4)
+    assert not E.is_asymmetric_table([1, 0, 0, 1, 0, 1, 1, 0], 3)
+    assert not E.is_asymmetric_table([bin(v).count("1") % 2 for v in range(256)], 8)
+
+
+# ---- extract_bits of the 8-bit model (test_gpu_extract8_edges.py) ----
+def test_extract_bits_tie_rows_are_on_the_edge(oracle_keys8):
+    """Trivial ints (zero mask) with the body on either side of the rounding boundary of bit 0: the shift to the
+    MSB and the keyswitch of a zero mask give the trivial small LWE of body << 7, i.e. v 2^63 + 2^62 - 128 below the
+    boundary and v 2^63 + 2^62 on it, which decode to v & 1 and to its complement: the extracted bits differ."""
+    n = oracle_keys8.p["n"]
+    for v in (0x00, 0xFF, 0x80):
+        rows = E.extract_tie_ints(oracle_keys8.K, v)
+        below, tie = (oracle_keys8.extract_bits(rows[i]) for i in (1, 2))
+        for out, body in ((below, rows[1, -1]), (tie, rows[2, -1])):
+            assert not out[7, :n].any() and int(out[7, n]) == (int(body) << 7) & MASK
+        assert int(tie[7, n]) - int(below[7, n]) == 128
+        bit = lambda row: ((int(row[n]) + (1 << 62)) & MASK) >> 63
+        assert bit(below[7]) == v & 1 and bit(tie[7]) == 1 - (v & 1)
+        assert list(oracle_keys8.decrypt_small_bits(below[7:])) == [v & 1]
+        assert list(oracle_keys8.decrypt_small_bits(tie[7:])) == [1 - (v & 1)]
