@@ -31,13 +31,14 @@ def engine_members():
 
 
 def grown_members():
-    """The members the drivers pass to grow(, upload( or ensure_digits(: the buffers a call may free and reallocate."""
+    """The members the drivers call .grow( or .upload( on (rowsum_pass: through its up( helper) or pass to ensure_digits(:
+    the buffers a call may free and reallocate."""
     out = set()
     for name in sorted(os.listdir(CSRC)):
         if not name.endswith((".hip", ".hpp")):
             continue
-        for m in re.finditer(r"\b(?:grow|upload|up|ensure_digits)\(\s*(d_\w+_)\b", _code(_read(name))):
-            out.add(m.group(1))
+        for m in re.finditer(r"\b(d_\w+_)\.(?:grow|upload)\(|\b(?:up|ensure_digits)\(\s*(d_\w+_)\b", _code(_read(name))):
+            out.add(m.group(1) or m.group(2))
     return out
 
 

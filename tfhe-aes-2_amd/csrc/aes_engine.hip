@@ -164,7 +164,7 @@ void check_ctr_plan(size_t U, const std::vector<int32_t> &map, size_t nb) {
 // Byte::bootstrap_with_lut of the 8-bit model: the circuit bootstrap into one 8-bit int per byte, then its bits
 void Engine::bootstrap_bytes8(const uint64_t *d_bytes, size_t G, const uint64_t *d_lut, uint64_t *d_out) {
     if (!G) return;
-    grow(d_ints_, cap_ints_, G * p_.big_len());
+    d_ints_.grow(G * p_.big_len());
     cbs_vp(d_bytes, G, 8, d_lut, 1, d_ints_);
     timed(ST_EXTRACT, [&] { extract_bits(d_ints_, G, 56, 8, d_out); });
     collect_times();
@@ -216,8 +216,8 @@ void Engine::aes_forward(const AesRun &a) {
     // one round of a plan works on its U groups alone; the per-block state and the 24 SubBytes multiples of the
     // 1-bit model exist from round 2 on
     const bool groups_only = plan && a.rounds == 1;
-    grow(d_state_, cap_state_, groups_only ? G * byte_stride : state_len);
-    grow(d_muls_, cap_muls_, groups_only ? G * byte_stride : nb * 16 * (gal ? 24 : 8) * (size_t)L);
+    d_state_.grow(groups_only ? G * byte_stride : state_len);
+    d_muls_.grow(groups_only ? G * byte_stride : nb * 16 * (gal ? 24 : 8) * (size_t)L);
     MixTerms T;
     std::memcpy(T.idx, mix_idx_, sizeof(T.idx));
     auto linear = [&](auto launch) {
@@ -321,17 +321,10 @@ void Engine::s1_aes_encrypt_blocks(const uint64_t *d_rk, const uint64_t *d_block
 }
 
 // ---- multi-key batches: a key table [n_keys][4 (nr + 1) * 32][L], block i under slot key_of[i] ----
-// An asynchronous upload of a host array into a grown device buffer: the host array must live until the next call
-template <class T>
-const T *Engine::upload(T *&d_buf, size_t &cap, const T *host, size_t count) {
-    grow(d_buf, cap, count);
-    HIPC(hipMemcpyAsync(d_buf, host, count * sizeof(T), hipMemcpyHostToDevice, stream_));
-    return d_buf;
-}
-
+// The uploads into the engine's buffers are asynchronous: the host array must live until the next call
 const int32_t *Engine::upload_key_of(const int32_t *key_of, size_t nb) {
     key_of_host_.assign(key_of, key_of + nb);
-    return upload(d_key_of_, cap_key_of_, key_of_host_.data(), nb);
+    return d_key_of_.upload(key_of_host_.data(), nb, stream_);
 }
 
 void Engine::aes_encrypt_blocks_multi(const uint64_t *d_table, const int32_t *key_of, const uint64_t *d_blocks,
@@ -351,8 +344,8 @@ void Engine::aes_ctr_chunk(const uint64_t *d_rk, const CtrPlan &plan, size_t nb,
     require_rounds(rounds, nr);
     if (out_bytes > nb * 16) throw std::runtime_error("more output bytes than keystream");
     check_ctr_plan(plan.groups.size(), plan.map, nb);
-    upload(d_ctr_groups_, cap_ctr_groups_, plan.groups.data(), plan.groups.size());
-    upload(d_ctr_map_, cap_ctr_map_, plan.map.data(), plan.map.size());
+    d_ctr_groups_.upload(plan.groups.data(), plan.groups.size(), stream_);
+    d_ctr_map_.upload(plan.map.data(), plan.map.size(), stream_);
     AesRun a{p_.model == 8 ? AesRun::BYTES8 : AesRun::GAL_MUL, d_rk, nb, rounds, nr};
     a.U = plan.groups.size();
     a.data = d_data;
@@ -416,22 +409,22 @@ void Engine::aes_ctr_blocks_multi(const uint64_t *d_table, const CtrPlanMulti &p
         if (n < (k ? 0 : 1) || n > 16 || (k != 0 && k != 16))
             throw std::runtime_error("counter plan: block length out of range");
     }
-    upload(d_ctr_groups_, cap_ctr_groups_, plan.groups.data(), U);
-    upload(d_ctr_map_, cap_ctr_map_, plan.map.data(), nb * 16);
+    d_ctr_groups_.upload(plan.groups.data(), U, stream_);
+    d_ctr_map_.upload(plan.map.data(), nb * 16, stream_);
     AesRun a{AesRun::GAL_MUL, d_table, nb, rounds, nr};
     a.U = U;
-    a.group_key = upload(d_ctr_gslot_, cap_ctr_gslot_, plan.group_slot.data(), U);
-    a.key_of = upload(d_key_of_, cap_key_of_, plan.block_slot.data(), nb);
+    a.group_key = d_ctr_gslot_.upload(plan.group_slot.data(), U, stream_);
+    a.key_of = d_key_of_.upload(plan.block_slot.data(), nb, stream_);
     a.key_stride = (size_t)4 * (nr + 1) * 32 * p_.big_len();
     a.time_linear = true;
     a.data = d_data;
     a.out_bytes = nb * 16;
-    a.blk_out = upload(d_ctr_bout_, cap_ctr_bout_, plan.block_out.data(), nb);
-    a.blk_len = upload(d_ctr_blen_, cap_ctr_blen_, plan.block_len.data(), nb);
+    a.blk_out = d_ctr_bout_.upload(plan.block_out.data(), nb, stream_);
+    a.blk_len = d_ctr_blen_.upload(plan.block_len.data(), nb, stream_);
     a.out = d_out;
     if (d_keep) {
-        a.keep_out = upload(d_pub_kout_, cap_pub_kout_, keep_out->data(), nb);
-        a.keep_len = upload(d_pub_klen_, cap_pub_klen_, keep_len->data(), nb);
+        a.keep_out = d_pub_kout_.upload(keep_out->data(), nb, stream_);
+        a.keep_len = d_pub_klen_.upload(keep_len->data(), nb, stream_);
         a.keep = d_keep;
     }
     aes_forward(a);
@@ -531,10 +524,10 @@ void Engine::aes_ccm_transcipher(const uint64_t *d_table, const std::vector<CcmS
             std::memcpy(&ccm_bytes_[(size_t)off[(size_t)ccm_order_[j]]], st.data, st.frame->payload_len);
         std::memcpy(&ccm_bytes_[total + j * (size_t)M], st.tag, (size_t)M);
     }
-    const uint8_t *d_bytes = upload(d_ccm_bytes_, cap_ccm_bytes_, ccm_bytes_.data(), ccm_bytes_.size());
-    const int32_t *d_slot = upload(d_ccm_slot_, cap_ccm_slot_, ccm_slot_.data(), n);
-    const int32_t *d_order = upload(d_ccm_order_, cap_ccm_order_, ccm_order_.data(), n);
-    grow(d_ccm_keep_, cap_ccm_keep_, 2 * n * block_len);
+    const uint8_t *d_bytes = d_ccm_bytes_.upload(ccm_bytes_.data(), ccm_bytes_.size(), stream_);
+    const int32_t *d_slot = d_ccm_slot_.upload(ccm_slot_.data(), n, stream_);
+    const int32_t *d_order = d_ccm_order_.upload(ccm_order_.data(), n, stream_);
+    d_ccm_keep_.grow(2 * n * block_len);
     uint64_t *d_s0 = d_ccm_keep_, *d_x = d_ccm_keep_ + n * block_len;  // chain order, both
 
     // ---- pass 1: A_1 .. A_n into the result, A_0 and B_0 into the kept blocks ----
@@ -578,8 +571,8 @@ void Engine::aes_ccm_transcipher(const uint64_t *d_table, const std::vector<CcmS
             step_n[t] = j + 1;
         }
     }
-    const int64_t *d_src = ccm_src_.empty() ? nullptr : upload(d_ccm_src_, cap_ccm_src_, ccm_src_.data(), ccm_src_.size());
-    if (depth > 1) grow(d_state_, cap_state_, step_n[1] * block_len);  // the largest step: aes_forward keeps the buffer
+    const int64_t *d_src = ccm_src_.empty() ? nullptr : d_ccm_src_.upload(ccm_src_.data(), ccm_src_.size(), stream_);
+    if (depth > 1) d_state_.grow(step_n[1] * block_len);  // the largest step: aes_forward keeps the buffer
     for (size_t t = 1; t < depth; t++) {
         const size_t na = step_n[t];
         timed(ST_LINEAR, [&] {
@@ -619,12 +612,12 @@ void Engine::rowsum_pass(const uint64_t *d_sources, size_t n_src, RowPlan plan, 
     if (!plan.n_rows()) return;
     rowsum_plans_.push_back(std::move(plan));
     const RowPlan &p = rowsum_plans_.back();
-    auto up = [&](auto *&d_buf, size_t &cap, const auto &v) {  // an empty array is a null argument
-        return v.empty() ? nullptr : upload(d_buf, cap, v.data(), v.size());
+    auto up = [&](auto &d_buf, const auto &v) {  // an empty array is a null argument
+        return v.empty() ? nullptr : d_buf.upload(v.data(), v.size(), stream_);
     };
-    const int32_t *rs = up(d_rs_start_, cap_rs_start_, p.row_start), *ix = up(d_rs_src_, cap_rs_src_, p.src);
-    const int32_t *lo = up(d_rs_list_, cap_rs_list_, p.list_of), *bo = up(d_rs_base_, cap_rs_base_, p.base_of);
-    const uint8_t *pb = up(d_rs_pub_, cap_rs_pub_, p.pub_bit);
+    const int32_t *rs = up(d_rs_start_, p.row_start), *ix = up(d_rs_src_, p.src);
+    const int32_t *lo = up(d_rs_list_, p.list_of), *bo = up(d_rs_base_, p.base_of);
+    const uint8_t *pb = up(d_rs_pub_, p.pub_bit);
     const int L = (int)p_.big_len();
     const size_t n_rows = p.n_rows();
     timed(ST_LINEAR, [&] {
@@ -645,8 +638,8 @@ void Engine::gcm_square_pass(const uint64_t *d_src, size_t n_src, const std::vec
             plan.list_of.push_back(r);
             plan.base_of.push_back((int32_t)(blocks[s] * 128));
         }
-    grow(d_gcm_a_, cap_gcm_a_, n * block_len);
-    grow(d_gcm_b_, cap_gcm_b_, n * block_len);
+    d_gcm_a_.grow(n * block_len);
+    d_gcm_b_.grow(n * block_len);
     rowsum_pass(d_src, n_src, std::move(plan), d_gcm_a_);
     circuit_bootstrap(d_gcm_a_, n * 128, 1, d_lut_id1_, 1, d_gcm_b_);
     for (size_t s = 0; s < n; s++)
@@ -671,11 +664,11 @@ void Engine::gcm_product_pass(const std::vector<const uint64_t *> &a, const std:
         }
         return p;
     };
-    grow(d_gcm_ops_, cap_gcm_ops_, n * 2 * block_len);
-    grow(d_gcm_ks_, cap_gcm_ks_, n * 256 * S);
-    grow(d_gcm_parts_, cap_gcm_parts_, n * kGcmParts * L);
-    grow(d_gcm_a_, cap_gcm_a_, n * n_chunks * L);
-    grow(d_gcm_b_, cap_gcm_b_, n * n_chunks * L);
+    d_gcm_ops_.grow(n * 2 * block_len);
+    d_gcm_ks_.grow(n * 256 * S);
+    d_gcm_parts_.grow(n * kGcmParts * L);
+    d_gcm_a_.grow(n * n_chunks * L);
+    d_gcm_b_.grow(n * n_chunks * L);
     for (size_t c = 0; c < n; c++) {
         HIPC(hipMemcpyAsync(d_gcm_ops_ + 2 * c * block_len, a[c], block_len * 8, hipMemcpyDeviceToDevice, stream_));
         HIPC(hipMemcpyAsync(d_gcm_ops_ + (2 * c + 1) * block_len, b[c], block_len * 8, hipMemcpyDeviceToDevice, stream_));
@@ -738,7 +731,7 @@ void Engine::ghash_key(const uint64_t *d_rk, int n_powers, int rounds, int nr, u
     // H = E_K(0^128), then the identity bootstrap: H^1 at noise^2 = 1
     PubBlock zero{};
     zero.len = 16;
-    grow(d_gcm_a_, cap_gcm_a_, block_len);
+    d_gcm_a_.grow(block_len);
     aes_pub_blocks_multi(d_rk, std::vector<PubBlock>{zero}, rounds, d_gcm_a_, nr);  // resets the stage times
     circuit_bootstrap(d_gcm_a_, 128, 1, d_lut_id1_, 1, d_out);
     gcm_power_generations(d_out, n_powers);
@@ -799,7 +792,7 @@ void Engine::gcm_public_pass(const uint64_t *d_rk, const std::vector<GcmFrameIn>
     gcm_bytes_.assign(std::max<size_t>(total, 1), 0);
     for (size_t s = 0; s < n; s++)
         if (frames[s].frame->data_len) std::memcpy(&gcm_bytes_[(size_t)off[s]], frames[s].data, frames[s].frame->data_len);
-    const uint8_t *d_bytes = upload(d_gcm_bytes_, cap_gcm_bytes_, gcm_bytes_.data(), gcm_bytes_.size());
+    const uint8_t *d_bytes = d_gcm_bytes_.upload(gcm_bytes_.data(), gcm_bytes_.size(), stream_);
     // the counters into the result, J0 into the kept blocks
     std::vector<PubBlock> blocks;
     std::vector<int64_t> kout;
@@ -846,9 +839,9 @@ void Engine::aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, siz
     const size_t n_src = (table_blocks + n) * 128, n_chunks = plan.chunks.n_rows();
     times_ = StageTimes{};
     rowsum_plans_.clear();
-    grow(d_gcm_src_, cap_gcm_src_, n_src * L);
-    grow(d_gcm_a_, cap_gcm_a_, n_chunks * L);
-    grow(d_gcm_b_, cap_gcm_b_, n_chunks * L);
+    d_gcm_src_.grow(n_src * L);
+    d_gcm_a_.grow(n_chunks * L);
+    d_gcm_b_.grow(n_chunks * L);
     HIPC(hipMemcpyAsync(d_gcm_src_, d_hk, table_blocks * block_len * 8, hipMemcpyDeviceToDevice, stream_));
     gcm_public_pass(d_rk, frames, off, total, rounds, nr, d_out_plain, d_gcm_src_ + table_blocks * block_len);
 
@@ -907,9 +900,9 @@ void Engine::aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk
     for (const GcmInnerPlan &ip : inner) scratch = std::max(scratch, ip.chunks.n_rows());
     times_ = StageTimes{};
     rowsum_plans_.clear();
-    grow(d_gcm_src_, cap_gcm_src_, (s_block0 + batch) * block_len);
-    grow(d_gcm_a_, cap_gcm_a_, scratch * L);
-    grow(d_gcm_b_, cap_gcm_b_, scratch * L);
+    d_gcm_src_.grow((s_block0 + batch) * block_len);
+    d_gcm_a_.grow(scratch * L);
+    d_gcm_b_.grow(scratch * L);
     HIPC(hipMemcpyAsync(d_gcm_src_, d_hk, table_blocks * block_len * 8, hipMemcpyDeviceToDevice, stream_));
     gcm_public_pass(d_rk, frames, off, total, rounds, nr, d_out_plain, d_gcm_src_ + table_blocks * block_len);
 
@@ -955,8 +948,8 @@ void Engine::aes_decrypt_rounds(const uint64_t *d_dk, const uint64_t *d_blocks, 
     const int L = (int)p_.big_len();
     const size_t state_len = nb * 128 * (size_t)L, byte_stride = 8 * (size_t)L;
     if (!keep_times) times_ = StageTimes{};
-    grow(d_state_, cap_state_, state_len);
-    grow(d_muls_, cap_muls_, nb * 16 * (size_t)(rounds > 1 ? 32 : 8) * L);
+    d_state_.grow(state_len);
+    d_muls_.grow(nb * 16 * (size_t)(rounds > 1 ? 32 : 8) * L);
     timed(ST_LINEAR, [&] {
         aes_round0_kernel<<<grid_for(state_len), kThreads, 0, stream_>>>(d_dk + (size_t)16 * nr * byte_stride, d_blocks,
                                                                           d_cur, nullptr, d_state_, nb * 128, L, d_key_of,
@@ -1024,7 +1017,7 @@ void Engine::xts_tweak_pass(const uint64_t *d_rk2, const uint8_t *d_tweaks, size
     a.time_linear = true;
     a.out_bytes = n * 16;
     // the final kernel reads d_muls_ and the key alone, so the state buffer is free to take the cipher's output
-    a.out = grow(d_state_, cap_state_, n * 128 * p_.big_len());
+    a.out = d_state_.grow(n * 128 * p_.big_len());
     aes_forward(a);
     circuit_bootstrap(d_state_, n * 128, 1, d_lut_id1_, 1, d_out);
 }
@@ -1059,11 +1052,11 @@ void Engine::aes_xts_transcipher(const uint64_t *d_dk1, const uint64_t *d_rk2, c
     require_inverse(rounds, nr);
     const size_t block_len = 128 * p_.big_len();
     times_ = StageTimes{};
-    grow(d_xts_tweaks_, cap_xts_tweaks_, n_tweaks * block_len);
+    d_xts_tweaks_.grow(n_tweaks * block_len);
     xts_tweak_pass(d_rk2, d_tweaks, n_tweaks, rounds, d_xts_tweaks_, nr);
     // the tweaks stay resident across the chunks; every chunk's plan lives until the next call
     rowsum_plans_.clear();
-    grow(d_xts_masks_, cap_xts_masks_, std::min(ctr_chunk_, nb) * block_len);
+    d_xts_masks_.grow(std::min(ctr_chunk_, nb) * block_len);
     for (size_t b0 = 0; b0 < nb; b0 += ctr_chunk_) {
         const size_t cn = std::min(ctr_chunk_, nb - b0);
         uint64_t *out = d_out + b0 * block_len;
@@ -1112,8 +1105,8 @@ void Engine::aes_decrypt_key_multi(const uint64_t *d_table, size_t n_keys, uint6
     const size_t stride = last + 4 * word;
     const bool one = n_keys == 1;
     times_ = StageTimes{};
-    grow(d_state_, cap_state_, n_keys * mid);
-    grow(d_muls_, cap_muls_, n_keys * 16 * (size_t)(nr - 1) * 32 * L);
+    d_state_.grow(n_keys * mid);
+    d_muls_.grow(n_keys * 16 * (size_t)(nr - 1) * 32 * L);
     copy_key_words(d_table, stride, d_dtable, stride, n_keys, 4 * word);
     copy_key_words(d_table + last, stride, d_dtable + last, stride, n_keys, 4 * word);
     const uint64_t *middle = d_table + 4 * word;
@@ -1148,8 +1141,8 @@ void Engine::aes_key_expand_multi(const uint64_t *d_keys, int nk, size_t n_keys,
     const size_t word = 32 * (size_t)L, stride = (size_t)words * word, batch = n_keys * word;
     const bool one = n_keys == 1;
     times_ = StageTimes{};
-    grow(d_state_, cap_state_, batch);
-    grow(d_muls_, cap_muls_, batch);
+    d_state_.grow(batch);
+    d_muls_.grow(batch);
     copy_key_words(d_keys, (size_t)nk * word, d_table, stride, n_keys, (size_t)nk * word);
     for (int i = nk; i < words; i++) {
         const uint64_t *back = d_table + (size_t)(i - nk) * word, *other = d_table + (size_t)(i - 1) * word;

@@ -86,62 +86,6 @@ std::vector<const tae::BitCt *> unwrap(const tae_bit *const *bits, size_t n) {
     return v;
 }
 
-// run `fn(d_in, d_out, d_aux)` with host staging when mem == TAE_MEM_HOST.  `aux` (aux_bytes, may
-// be null) is a second input in the same memory kind, staged the same way (a LUT).
-template <class TI, class TO, class F>
-void staged(tae_context const *ctx, const TI *in, size_t in_bytes, TO *out, size_t out_bytes, int mem, F fn,
-            const uint64_t *aux = nullptr, size_t aux_bytes = 0) {
-    tae::Context &c = *ctx->ctx;
-    std::lock_guard<std::mutex> g(c.mutex());
-    tae::Engine &e = c.engine();
-    tae::hip_check(hipSetDevice(e.device()), "hipSetDevice");
-    struct Dev {
-        void *p = nullptr;
-        ~Dev() {
-            if (p) hipFree(p);
-        }
-    } daux;
-    if (aux && mem != TAE_MEM_DEVICE) {
-        tae::hip_check(hipMalloc(&daux.p, std::max<size_t>(aux_bytes, 16)), "hipMalloc");
-        tae::hip_check(hipMemcpyAsync(daux.p, aux, aux_bytes, hipMemcpyHostToDevice, e.stream()), "upload aux");
-        aux = static_cast<const uint64_t *>(daux.p);
-    }
-    // a stage call owns the stage times (Engine::begin_call): bootstrap() records the throughput kernel's span
-    auto call = [&](const TI *a, TO *b) {
-        e.begin_call();
-        fn(a, b, aux);
-        e.end_call();
-    };
-    if (mem == TAE_MEM_DEVICE) {
-        e.order_after_caller();
-        call(in, out);
-        e.synchronize();
-        return;
-    }
-    void *di = nullptr, *dout = nullptr;
-    tae::hip_check(hipMalloc(&di, std::max<size_t>(in_bytes, 16)), "hipMalloc");
-    if (hipMalloc(&dout, std::max<size_t>(out_bytes, 16)) != hipSuccess) {
-        hipFree(di);
-        throw tae::HipError{"hipMalloc"};
-    }
-    try {
-        // everything on the engine stream, in order.  The output is cleared first: not every stage
-        // writes every word (tae_stage_pfks_ggsw fills only the rows of the requested level), and the
-        // caller must get zeros there, not uninitialized device memory.
-        tae::hip_check(hipMemcpyAsync(di, in, in_bytes, hipMemcpyHostToDevice, e.stream()), "upload");
-        tae::hip_check(hipMemsetAsync(dout, 0, out_bytes, e.stream()), "clear output");
-        call(static_cast<const TI *>(di), static_cast<TO *>(dout));
-        tae::hip_check(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, e.stream()), "download");
-        e.synchronize();
-    } catch (...) {
-        hipFree(di);
-        hipFree(dout);
-        throw;
-    }
-    hipFree(di);
-    hipFree(dout);
-}
-
 void emit(const std::vector<tae::BitCt> &res, tae_bit **out) {
     for (size_t i = 0; i < res.size(); i++) out[i] = new tae_bit{res[i]};
 }
@@ -467,38 +411,7 @@ int tae_xor_batch(const tae_context *ctx, uint64_t *lhs, const uint64_t *rhs, si
                                                            std::to_string(i)};
             }
         }
-        const size_t words = count * ctx->ctx->bit_len();
-        if (count) {
-            tae::Context &c = *ctx->ctx;
-            std::lock_guard<std::mutex> g(c.mutex());
-            tae::Engine &e = c.engine();
-            tae::hip_check(hipSetDevice(e.device()), "hipSetDevice");
-            if (mem == TAE_MEM_DEVICE) {
-                e.order_after_caller();
-                e.lwe_add(lhs, rhs, words);
-                e.synchronize();
-            } else {
-                void *da = nullptr, *db = nullptr;
-                tae::hip_check(hipMalloc(&da, words * 8), "hipMalloc");
-                if (hipMalloc(&db, words * 8) != hipSuccess) {
-                    hipFree(da);
-                    throw tae::HipError{"hipMalloc"};
-                }
-                try {
-                    tae::hip_check(hipMemcpyAsync(da, lhs, words * 8, hipMemcpyHostToDevice, e.stream()), "upload");
-                    tae::hip_check(hipMemcpyAsync(db, rhs, words * 8, hipMemcpyHostToDevice, e.stream()), "upload");
-                    e.lwe_add(static_cast<uint64_t *>(da), static_cast<const uint64_t *>(db), words);
-                    tae::hip_check(hipMemcpyAsync(lhs, da, words * 8, hipMemcpyDeviceToHost, e.stream()), "download");
-                    e.synchronize();
-                } catch (...) {
-                    hipFree(da);
-                    hipFree(db);
-                    throw;
-                }
-                hipFree(da);
-                hipFree(db);
-            }
-        }
+        ctx->ctx->xor_raw(lhs, rhs, count, mem == TAE_MEM_DEVICE);
         if (out_noise_sq && lhs_noise_sq)
             for (size_t i = 0; i < count; i++) out_noise_sq[i] = lhs_noise_sq[i] + rhs_noise_sq[i];
     });
@@ -1656,9 +1569,7 @@ int tae_stage_pack_pfks(const tae_context *ctx, const uint64_t *bits, size_t cou
 int tae_stage_keyswitch(const tae_context *ctx, const uint64_t *in, size_t count, uint64_t *out, int mem) {
     return guarded([&] {
         require(ctx && in && out, "null");
-        const auto &p = ctx->ctx->params();
-        staged(ctx, in, count * p.big_len() * 8, out, count * p.small_len() * 8, mem,
-               [&](const uint64_t *a, uint64_t *b, const uint64_t *) { ctx->ctx->engine().keyswitch(a, b, count); });
+        ctx->ctx->keyswitch_raw(in, count, out, mem == TAE_MEM_DEVICE);
     });
 }
 
@@ -1666,10 +1577,8 @@ int tae_stage_pbs_shift_boolean(const tae_context *ctx, const uint64_t *small, s
                                 int mem) {
     return guarded([&] {
         require(ctx && small && big, "null");
-        const auto &p = ctx->ctx->params();
-        require(level >= 1 && level <= p.cbs_l, "level out of range");
-        staged(ctx, small, count * p.small_len() * 8, big, count * p.big_len() * 8, mem,
-               [&](const uint64_t *a, uint64_t *b, const uint64_t *) { ctx->ctx->engine().pbs_shift_boolean(a, b, count, level); });
+        require(level >= 1 && level <= ctx->ctx->params().cbs_l, "level out of range");
+        ctx->ctx->pbs_shift_boolean_raw(small, count, level, big, mem == TAE_MEM_DEVICE);
     });
 }
 
@@ -1677,32 +1586,22 @@ int tae_stage_bootstrap(const tae_context *ctx, const uint64_t *small, size_t co
                         uint64_t *big, int mem) {
     return guarded([&] {
         require(ctx && small && lut_glwe && big, "null");
-        const auto &p = ctx->ctx->params();
-        staged(
-            ctx, small, count * p.small_len() * 8, big, count * p.big_len() * 8, mem,
-            [&](const uint64_t *a, uint64_t *b, const uint64_t *lut) { ctx->ctx->engine().bootstrap(a, lut, b, count, 0, 0); },
-            lut_glwe, p.glwe_len() * 8);
+        ctx->ctx->bootstrap_raw(small, count, lut_glwe, big, mem == TAE_MEM_DEVICE);
     });
 }
 
 int tae_stage_pfks_ggsw(const tae_context *ctx, const uint64_t *big, size_t count, int level, uint64_t *ggsw, int mem) {
     return guarded([&] {
         require(ctx && big && ggsw, "null");
-        const auto &p = ctx->ctx->params();
-        require(level >= 1 && level <= p.cbs_l, "level out of range");
-        staged(ctx, big, count * p.big_len() * 8, ggsw, count * p.cbs_ggsw_len() * 8, mem,
-               [&](const uint64_t *a, uint64_t *b, const uint64_t *) { ctx->ctx->engine().pfks_into_ggsw(a, b, count, level); });
+        require(level >= 1 && level <= ctx->ctx->params().cbs_l, "level out of range");
+        ctx->ctx->pfks_ggsw_raw(big, count, level, ggsw, mem == TAE_MEM_DEVICE);
     });
 }
 
 int tae_stage_ggsw_fourier(const tae_context *ctx, const uint64_t *ggsw, size_t count, double *ggsw_f, int mem) {
     return guarded([&] {
         require(ctx && ggsw && ggsw_f, "null");
-        const auto &p = ctx->ctx->params();
-        staged(ctx, ggsw, count * p.cbs_ggsw_len() * 8, ggsw_f, count * p.cbs_ggsw_fourier_len() * 16, mem,
-               [&](const uint64_t *a, double *b, const uint64_t *) {
-                   ctx->ctx->engine().ggsw_to_fourier(a, reinterpret_cast<tae::cplx *>(b), count);
-               });
+        ctx->ctx->ggsw_fourier_raw(ggsw, count, reinterpret_cast<tae::cplx *>(ggsw_f), mem == TAE_MEM_DEVICE);
     });
 }
 
@@ -1710,19 +1609,9 @@ int tae_stage_vertical_packing(const tae_context *ctx, const double *ggsw_f, siz
                                const uint64_t *lut, int n_out, uint64_t *out, int mem) {
     return guarded([&] {
         require(ctx && ggsw_f && lut && out, "null");
-        const auto &p = ctx->ctx->params();
         require(n_in >= 1 && n_out >= 1, "n_in and n_out must be at least 1");
-        int log_n = 0;
-        while ((1 << log_n) < p.N) log_n++;
-        // n_in > log2 N: the LUT of every output holds 2^tree polynomials (the CMux tree's leaves)
-        const int tree = std::max(0, n_in - log_n);
-        require(tree <= 16, "n_in exceeds log2 N + 16");
-        staged(
-            ctx, ggsw_f, groups * n_in * p.cbs_ggsw_fourier_len() * 16, out, groups * n_out * p.big_len() * 8, mem,
-            [&](const double *a, uint64_t *b, const uint64_t *l) {
-                ctx->ctx->engine().vertical_packing(reinterpret_cast<const tae::cplx *>(a), groups, n_in, l, n_out, b);
-            },
-            lut, (size_t)n_out * ((size_t)p.N << tree) * 8);
+        ctx->ctx->vertical_packing_raw(reinterpret_cast<const tae::cplx *>(ggsw_f), groups, n_in, lut, n_out, out,
+                                       mem == TAE_MEM_DEVICE);
     });
 }
 

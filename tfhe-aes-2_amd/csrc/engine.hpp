@@ -20,17 +20,12 @@
 #include "aes_gcm.hpp"
 #include "aes_xts.hpp"
 #include "ctr_plan.hpp"
+#include "devbuf.hpp"
 #include "kslots.hpp"
 #include "params.hpp"
 #include "rowsum.hpp"
 
 namespace tae {
-
-struct HipError {
-    std::string msg;
-};
-
-void hip_check(hipError_t e, const char *what);
 
 // Timing of the most recent batched call, per stage (ms, HIP events on the engine stream).
 struct StageTimes {
@@ -317,23 +312,26 @@ class Engine {
   private:
     void init_common();
     void bsk_to_fourier(const uint64_t *d_bsk_std);
-    void *alloc(size_t bytes);
-    template <class T>
-    T *grow(T *&ptr, size_t &cap, size_t count);
 
     Params p_;
     int device_;
     hipStream_t stream_ = nullptr;
     hipStream_t caller_stream_ = nullptr;
     hipEvent_t caller_ev_ = nullptr;
-    bool owns_keys_ = false;
-    uint64_t *d_ksk_ = nullptr, *d_pfpksk_ = nullptr;
-    cplx *d_bsk_f_ = nullptr;
-    cplx *d_twist_ = nullptr, *d_untwist_ = nullptr, *d_w_ = nullptr;
-    uint64_t *d_lut_shift_ = nullptr;  // per cbs level: trivial GLWE with body = -alpha
-    uint64_t *d_lut24_ = nullptr, *d_lut8_ = nullptr;
+    std::vector<hipEvent_t> ev_pool_;
+    // Destroys the events, then the stream.  Declared before every buffer: members go in reverse order, so the
+    // buffers are freed first, after ~Engine or when a constructor throws
+    struct Teardown {
+        Engine &e;
+        ~Teardown();
+    } teardown_{*this};
+    DevBuf<uint64_t> d_ksk_, d_pfpksk_;  // borrowed by the device-key constructor
+    DevBuf<cplx> d_bsk_f_;
+    DevBuf<cplx> d_twist_, d_untwist_, d_w_;
+    DevBuf<uint64_t> d_lut_shift_;  // per cbs level: trivial GLWE with body = -alpha
+    DevBuf<uint64_t> d_lut24_, d_lut8_;
     // inverse cipher (1-bit model): InvSbox * {14,11,13,9}, InvSbox, the multiples alone, the 1 -> 1 identity
-    uint64_t *d_lut_inv32_ = nullptr, *d_lut_inv8_ = nullptr, *d_lut_mul32_ = nullptr, *d_lut_id1_ = nullptr;
+    DevBuf<uint64_t> d_lut_inv32_, d_lut_inv8_, d_lut_mul32_, d_lut_id1_;
     void require_inverse(int rounds, int nr) const;
     void aes_decrypt_rounds(const uint64_t *d_dk, const uint64_t *d_blocks, const uint8_t *d_cur, size_t nb, int rounds,
                             const uint8_t *d_xor, uint64_t *d_out, int nr, const int32_t *d_key_of, size_t key_stride,
@@ -341,28 +339,23 @@ class Engine {
     // the forward cipher's one round loop (aes_engine.hip): every forward entry point fills an AesRun
     struct AesRun;
     void aes_forward(const AesRun &run);
-    uint64_t *d_wlut_sbox_ = nullptr, *d_wlut_id_ = nullptr;  // 8-bit model
-    uint64_t *d_lut_x_ = nullptr;                             // extract_bits accumulators [nbits][glwe]
+    DevBuf<uint64_t> d_wlut_sbox_, d_wlut_id_;  // 8-bit model
+    DevBuf<uint64_t> d_lut_x_;                  // extract_bits accumulators [nbits][glwe]
     int lut_x_delta_ = -1, lut_x_bits_ = 0;
-    uint64_t *d_xbuf_ = nullptr, *d_xsh_ = nullptr, *d_xks_ = nullptr, *d_xpbs_ = nullptr, *d_ints_ = nullptr;
-    size_t cap_xbuf_ = 0, cap_xsh_ = 0, cap_xks_ = 0, cap_xpbs_ = 0, cap_ints_ = 0;
+    DevBuf<uint64_t> d_xbuf_, d_xsh_, d_xks_, d_xpbs_, d_ints_;
     int8_t mix_idx_[32][8] = {};
     // counter mode: blocks per device pass (TAE_CTR_CHUNK_BLOCKS; 1024 = the largest batch the tests pin),
     // the plan of the chunk in flight on the device, and the host plans the pending uploads read
     size_t ctr_chunk_ = 1024;
-    uint16_t *d_ctr_groups_ = nullptr;
-    int32_t *d_ctr_map_ = nullptr;
-    size_t cap_ctr_groups_ = 0, cap_ctr_map_ = 0;
+    DevBuf<uint16_t> d_ctr_groups_;
+    DevBuf<int32_t> d_ctr_map_;
     std::vector<CtrPlan> ctr_plans_;
     void aes_ctr_chunk(const uint64_t *d_rk, const CtrPlan &plan, size_t nb, int rounds, const uint8_t *d_data,
                        size_t out_bytes, uint64_t *d_out, int nr);
-    template <class T>
-    const T *upload(T *&d_buf, size_t &cap, const T *host, size_t count);
     // multi-key batches: the per-block slots on the device and the host copy its pending upload reads; the
     // parallel arrays of a CtrPlanMulti and the plans of the chunks in flight
-    int32_t *d_key_of_ = nullptr, *d_ctr_gslot_ = nullptr, *d_ctr_blen_ = nullptr;
-    int64_t *d_ctr_bout_ = nullptr;
-    size_t cap_key_of_ = 0, cap_ctr_gslot_ = 0, cap_ctr_blen_ = 0, cap_ctr_bout_ = 0;
+    DevBuf<int32_t> d_key_of_, d_ctr_gslot_, d_ctr_blen_;
+    DevBuf<int64_t> d_ctr_bout_;
     std::vector<int32_t> key_of_host_;
     std::vector<CtrPlanMulti> ctr_mplans_;
     const int32_t *upload_key_of(const int32_t *key_of, size_t nb);
@@ -376,38 +369,32 @@ class Engine {
     void pub_pass(const uint64_t *d_table, const std::vector<PubBlock> &blocks, int rounds, const uint8_t *d_data,
                   uint64_t *d_out, int nr, const std::vector<int64_t> *keep_out = nullptr,
                   const std::vector<int32_t> *keep_len = nullptr, uint64_t *d_keep = nullptr);
-    int64_t *d_pub_kout_ = nullptr;
-    int32_t *d_pub_klen_ = nullptr;
-    size_t cap_pub_kout_ = 0, cap_pub_klen_ = 0;
+    DevBuf<int64_t> d_pub_kout_;
+    DevBuf<int32_t> d_pub_klen_;
     std::vector<std::vector<int64_t>> pub_kout_;
     std::vector<std::vector<int32_t>> pub_klen_;
     // Row sums (rowsum.hpp): validates the plan against the n_src sources [n_src][K+1], keeps it alive until the next
     // call (the uploads are asynchronous) and launches once under ST_LINEAR: -> d_out [n_rows][K+1].  The plan's
     // arrays on the device and the host plans their pending uploads read
     void rowsum_pass(const uint64_t *d_sources, size_t n_src, RowPlan plan, uint64_t *d_out);
-    int32_t *d_rs_start_ = nullptr, *d_rs_src_ = nullptr, *d_rs_list_ = nullptr, *d_rs_base_ = nullptr;
-    uint8_t *d_rs_pub_ = nullptr;
-    size_t cap_rs_start_ = 0, cap_rs_src_ = 0, cap_rs_list_ = 0, cap_rs_base_ = 0, cap_rs_pub_ = 0;
+    DevBuf<int32_t> d_rs_start_, d_rs_src_, d_rs_list_, d_rs_base_;
+    DevBuf<uint8_t> d_rs_pub_;
     std::deque<RowPlan> rowsum_plans_;
     // CCM: S_0 and the chain value Xk of every stream [2 n][128][K+1], the arrays of the call on the device and
     // the host copies their pending uploads read
-    uint64_t *d_ccm_keep_ = nullptr;
-    uint8_t *d_ccm_bytes_ = nullptr;
-    int64_t *d_ccm_src_ = nullptr;
-    int32_t *d_ccm_slot_ = nullptr, *d_ccm_order_ = nullptr;
-    size_t cap_ccm_keep_ = 0, cap_ccm_bytes_ = 0, cap_ccm_src_ = 0, cap_ccm_slot_ = 0, cap_ccm_order_ = 0;
+    DevBuf<uint64_t> d_ccm_keep_;
+    DevBuf<uint8_t> d_ccm_bytes_;
+    DevBuf<int64_t> d_ccm_src_;
+    DevBuf<int32_t> d_ccm_slot_, d_ccm_order_;
     std::vector<uint8_t> ccm_bytes_;
     std::vector<int64_t> ccm_src_;
     std::vector<int32_t> ccm_slot_, ccm_order_;
     // GCM: the 8 -> 7 nibble-product table; the source array of a call's chunk sums (power table, then E(J0) of every
     // frame); two scratch arrays the row sums and the refreshes alternate between; the operand bits and the partial
     // bits of a product batch; the public bytes of a call and the host copy their pending upload reads
-    uint64_t *d_lut_gcm_ = nullptr;
-    uint64_t *d_gcm_src_ = nullptr, *d_gcm_a_ = nullptr, *d_gcm_b_ = nullptr, *d_gcm_ops_ = nullptr, *d_gcm_ks_ = nullptr,
-             *d_gcm_parts_ = nullptr;
-    uint8_t *d_gcm_bytes_ = nullptr;
-    size_t cap_gcm_src_ = 0, cap_gcm_a_ = 0, cap_gcm_b_ = 0, cap_gcm_ops_ = 0, cap_gcm_ks_ = 0, cap_gcm_parts_ = 0,
-           cap_gcm_bytes_ = 0;
+    DevBuf<uint64_t> d_lut_gcm_;
+    DevBuf<uint64_t> d_gcm_src_, d_gcm_a_, d_gcm_b_, d_gcm_ops_, d_gcm_ks_, d_gcm_parts_;
+    DevBuf<uint8_t> d_gcm_bytes_;
     std::vector<uint8_t> gcm_bytes_;
     // segmented GHASH: inner segments per batch (TAE_GCM_SEG_BATCH, 1 .. 64; 16 products are the largest cbs_vp launch
     // the tests pin)
@@ -426,31 +413,25 @@ class Engine {
     void gcm_product_pass(const std::vector<const uint64_t *> &a, const std::vector<const uint64_t *> &b,
                           const std::vector<uint64_t *> &outs);
     // XTS: the refreshed tweaks of the call and the masks of the chunk in flight
-    uint64_t *d_xts_tweaks_ = nullptr, *d_xts_masks_ = nullptr;
-    size_t cap_xts_tweaks_ = 0, cap_xts_masks_ = 0;
+    DevBuf<uint64_t> d_xts_tweaks_, d_xts_masks_;
     void xts_tweak_pass(const uint64_t *d_rk2, const uint8_t *d_tweaks, size_t n, int rounds, uint64_t *d_out, int nr);
     void copy_rows(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t rows,
                    size_t len);
     void copy_key_words(const uint64_t *d_src, size_t src_stride, uint64_t *d_dst, size_t dst_stride, size_t n_keys,
                         size_t len);
     // shortint_1bit: S-box / identity test vectors and tree-level scratch
-    uint64_t *d_s1_sbox_tv_ = nullptr, *d_s1_id_tv_ = nullptr, *d_s1_in_ = nullptr, *d_s1_out_ = nullptr,
-             *d_s1_pks_ = nullptr, *d_s1_tv_ = nullptr;
-    size_t cap_s1_in_ = 0, cap_s1_out_ = 0, cap_s1_pks_ = 0, cap_s1_tv_ = 0;
+    DevBuf<uint64_t> d_s1_sbox_tv_, d_s1_id_tv_, d_s1_in_, d_s1_out_, d_s1_pks_, d_s1_tv_;
     void require_s1() const;
     void cbs_vp_stages(const uint64_t *d_small_bits, size_t G, int n_in, const uint64_t *d_lut, int n_out,
                        uint64_t *d_out);
     // scratch
-    uint64_t *d_small_ = nullptr, *d_big_ = nullptr, *d_ggsw_ = nullptr, *d_state_ = nullptr,
-             *d_muls_ = nullptr;
-    cplx *d_ggsw_f_ = nullptr;
-    size_t cap_small_ = 0, cap_big_ = 0, cap_ggsw_ = 0, cap_ggsw_f_ = 0, cap_state_ = 0, cap_muls_ = 0;
+    DevBuf<uint64_t> d_small_, d_big_, d_ggsw_, d_state_, d_muls_;
+    DevBuf<cplx> d_ggsw_f_;
     // stage timing (HIP events around each stage call on the engine stream, summed in collect_times)
     struct Span {
         hipEvent_t a, b;
         int stage;
     };
-    std::vector<hipEvent_t> ev_pool_;
     size_t ev_used_ = 0;
     std::vector<Span> spans_;
     hipEvent_t next_event();
@@ -470,18 +451,15 @@ class Engine {
     // default "w16" (8 waves of 96 x 128, 16x16x64 MFMAs), the fastest by stage and by bench wall time
     int pf_gemm_ = 3;
     const char *last_pfks_kernel_ = "none";
-    int8_t *d_pf_bt_kl_ = nullptr;
-    uint64_t *d_pf_corr_ = nullptr;  // [ncols] digit-offset correction of the K layout
-    uint32_t *d_pf_flags_ = nullptr;  // [B][words] clamped-digit flags of the K layout (kslots_build)
-    size_t cap_pf_flags_ = 0;
-    int8_t *d_pf_bt_ = nullptr, *d_ks_bt_ = nullptr, *d_digits_ = nullptr;
-    size_t cap_digits_ = 0;
+    DevBuf<int8_t> d_pf_bt_kl_;
+    DevBuf<uint64_t> d_pf_corr_;   // [ncols] digit-offset correction of the K layout
+    DevBuf<uint32_t> d_pf_flags_;  // [B][words] clamped-digit flags of the K layout (kslots_build)
+    DevBuf<int8_t> d_pf_bt_, d_ks_bt_, d_digits_;
     int kp_pf_ = 0, kp_ks_ = 0;
     void prepare_mfma_keys();
     void pfks_keys(const uint64_t *d_big, size_t B, int q0, int nq, uint64_t *dst, long out_stride);
     void require_pack() const;
-    uint64_t *d_pack_ = nullptr;  // pack_bits: keyswitch outputs of one chunk [bits][(k+1)N]
-    size_t cap_pack_ = 0;
+    DevBuf<uint64_t> d_pack_;  // pack_bits: keyswitch outputs of one chunk [bits][(k+1)N]
     // batched N=1024, k=2 blind rotation (br1024.hpp) for this set's (levels, base_log), or nullptr
     void (*br1024_pbs_)(const uint64_t *, int, const uint64_t *, int, const cplx *, int, uint64_t *, long, uint64_t,
                         uint64_t, const cplx *, const cplx *, const cplx *, const double *, uint64_t *) = nullptr;
@@ -491,8 +469,7 @@ class Engine {
     int br1024_pbs1_lp_ = 1;                       // its levels per pass
     bool lf1k_ = false;                            // the 8-bit model's PBS: the N = 1024 fused transform (lf1k.hpp)
     bool b1kw_ = false;                            // ... on br1024w (four ciphertexts per workgroup, ACC stash)
-    uint64_t *d_acc_w_ = nullptr;                  // br1024w's ACC stash [B][k+1][N]
-    size_t cap_acc_w_ = 0;
+    DevBuf<uint64_t> d_acc_w_;                     // br1024w's ACC stash [B][k+1][N]
     // latency blind rotation, one ciphertext per 1024-thread workgroup (br1024lat.hpp), or nullptr
     void (*br1024lat_)(const uint64_t *, int, const uint64_t *, const cplx *, uint64_t *, long, uint64_t, uint64_t,
                        const cplx *, const double *) = nullptr;
@@ -505,10 +482,9 @@ class Engine {
     bool p16_ = false;        // lvl_64 PBS batches on br512p16 (two ciphertexts per workgroup) instead of br512x4
                               // (TAE_PBS_KERNEL = p16 / x4)
     int num_cu_ = 256;
-    double *d_lf_ = nullptr;  // the fused-twiddle transform's table (lf512.hpp: params_sqrd_lvl_64, lf1k.hpp: 8-bit)
+    DevBuf<double> d_lf_;     // the fused-twiddle transform's table (lf512.hpp: params_sqrd_lvl_64, lf1k.hpp: 8-bit)
     bool timing_ = false, clock_ = false;
-    uint64_t *d_clk_ = nullptr;
-    size_t cap_clk_ = 0;
+    DevBuf<uint64_t> d_clk_;
     uint64_t *clock_buffer(size_t wgs);                   // nullptr unless clock mode is on
     void record_clock(const uint64_t *clk, size_t wgs);  // median GHz of one stamped launch
     StageTimes times_;

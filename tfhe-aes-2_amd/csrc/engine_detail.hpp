@@ -26,18 +26,6 @@ static __global__ void copy_rows_strided_kernel(const uint64_t *__restrict__ src
     }
 }
 
-template <class T>
-T *Engine::grow(T *&ptr, size_t &cap, size_t count) {
-    if (count > cap) {
-        if (ptr) HIPC(hipFree(ptr));
-        ptr = nullptr;  // a failing alloc below must not leave a freed pointer for ~Engine
-        cap = 0;
-        ptr = static_cast<T *>(alloc(count * sizeof(T)));
-        cap = count;
-    }
-    return ptr;
-}
-
 template <class F>
 void Engine::timed(int stage, F fn) {
     if (!timing_) {

@@ -623,12 +623,6 @@ size_t br_lds_bytes(int k, int levels) {
 // Engine
 // =============================================================================================
 
-void *Engine::alloc(size_t bytes) {
-    void *p = nullptr;
-    HIPC(hipMalloc(&p, std::max<size_t>(bytes, 16)));
-    return p;
-}
-
 void Engine::init_common() {
     HIPC(hipSetDevice(device_));
     // TAE_CU_MASK (probe / A-B knob, scripts/probes/stage_overlap.py): "lo:N" or "hi:N" restricts the engine
@@ -660,9 +654,9 @@ void Engine::init_common() {
     if (p_.N != 512 && p_.N != 1024) throw std::runtime_error("unsupported polynomial size");
     const FftTables t = make_fft_tables(p_.N);
     const size_t tb = sizeof(double) * 2 * t.M;
-    d_twist_ = static_cast<cplx *>(alloc(tb));
-    d_untwist_ = static_cast<cplx *>(alloc(tb));
-    d_w_ = static_cast<cplx *>(alloc(tb));
+    d_twist_.alloc(t.M);
+    d_untwist_.alloc(t.M);
+    d_w_.alloc(t.M);
     HIPC(hipMemcpy(d_twist_, t.twist.data(), tb, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(d_untwist_, t.untwist.data(), tb, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(d_w_, t.w.data(), tb, hipMemcpyHostToDevice));
@@ -672,7 +666,7 @@ void Engine::init_common() {
         const uint64_t alpha = 1ull << (63 - p_.cbs_b * lev);
         for (int j = 0; j < p_.N; j++) luts[(size_t)(lev - 1) * p_.glwe_len() + (size_t)p_.k * p_.N + j] = 0 - alpha;
     }
-    d_lut_shift_ = static_cast<uint64_t *>(alloc(luts.size() * 8));
+    d_lut_shift_.alloc(luts.size());
     HIPC(hipMemcpy(d_lut_shift_, luts.data(), luts.size() * 8, hipMemcpyHostToDevice));
     // AES LUTs (fhe_impls/shortint_woppbs_1bit.rs:32-45, :94-128) -- built host-side once
     std::vector<uint64_t> f24(256), f8(256);
@@ -684,8 +678,8 @@ void Engine::init_common() {
     std::vector<uint64_t> l24(24 * lut_small_len(p_.N, 8)), l8(8 * lut_small_len(p_.N, 8));
     generate_lut(p_.N, 8, 24, f24.data(), l24.data());
     generate_lut(p_.N, 8, 8, f8.data(), l8.data());
-    d_lut24_ = static_cast<uint64_t *>(alloc(l24.size() * 8));
-    d_lut8_ = static_cast<uint64_t *>(alloc(l8.size() * 8));
+    d_lut24_.alloc(l24.size());
+    d_lut8_.alloc(l8.size());
     HIPC(hipMemcpy(d_lut24_, l24.data(), l24.size() * 8, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(d_lut8_, l8.data(), l8.size() * 8, hipMemcpyHostToDevice));
     if (p_.model == 1) {
@@ -697,21 +691,19 @@ void Engine::init_common() {
             fi8[x] = inv_sbox_lut((uint8_t)x);
             fm32[x] = inv_mul_lut((uint8_t)x);
         }
-        auto upload = [&](int n_in, int n_out, const std::vector<uint64_t> &f) {
+        auto upload = [&](DevBuf<uint64_t> &d, int n_in, int n_out, const std::vector<uint64_t> &f) {
             std::vector<uint64_t> l((size_t)n_out * lut_small_len(p_.N, n_in));
             generate_lut(p_.N, n_in, n_out, f.data(), l.data());
-            uint64_t *d = static_cast<uint64_t *>(alloc(l.size() * 8));
-            HIPC(hipMemcpy(d, l.data(), l.size() * 8, hipMemcpyHostToDevice));
-            return d;
+            HIPC(hipMemcpy(d.alloc(l.size()), l.data(), l.size() * 8, hipMemcpyHostToDevice));
         };
-        d_lut_inv32_ = upload(8, 32, fi32);
-        d_lut_inv8_ = upload(8, 8, fi8);
-        d_lut_mul32_ = upload(8, 32, fm32);
-        d_lut_id1_ = upload(1, 1, fid);
+        upload(d_lut_inv32_, 8, 32, fi32);
+        upload(d_lut_inv8_, 8, 8, fi8);
+        upload(d_lut_mul32_, 8, 32, fm32);
+        upload(d_lut_id1_, 1, 1, fid);
         // GCM (aes_gcm.hpp): the carry-less product of two nibbles, 8 -> 7
         std::vector<uint64_t> fg(256);
         for (unsigned x = 0; x < 256; x++) fg[x] = gcm_nibble_product(x);
-        d_lut_gcm_ = upload(8, 7, fg);
+        upload(d_lut_gcm_, 8, 7, fg);
     }
     if (p_.model == 2) {
         // shortint_1bit ByteT (fhe_impls/shortint_1bit.rs:17-50): bootstrap_assign's identity test vector
@@ -725,8 +717,8 @@ void Engine::init_common() {
                 s1_test_vector(p_, (s0 >> (7 - f)) & 1, (s1 >> (7 - f)) & 1, &tvs[(f * V + v) * glwe]);
             }
         s1_test_vector(p_, 0, 1, id.data());
-        d_s1_sbox_tv_ = static_cast<uint64_t *>(alloc(tvs.size() * 8));
-        d_s1_id_tv_ = static_cast<uint64_t *>(alloc(id.size() * 8));
+        d_s1_sbox_tv_.alloc(tvs.size());
+        d_s1_id_tv_.alloc(id.size());
         HIPC(hipMemcpy(d_s1_sbox_tv_, tvs.data(), tvs.size() * 8, hipMemcpyHostToDevice));
         HIPC(hipMemcpy(d_s1_id_tv_, id.data(), id.size() * 8, hipMemcpyHostToDevice));
     }
@@ -752,8 +744,8 @@ void Engine::init_common() {
         }
         generate_lut_without_padding(p_.N, fs.data(), ws.data());
         generate_lut_without_padding(p_.N, fi.data(), wi.data());
-        d_wlut_sbox_ = static_cast<uint64_t *>(alloc(ws.size() * 8));
-        d_wlut_id_ = static_cast<uint64_t *>(alloc(wi.size() * 8));
+        d_wlut_sbox_.alloc(ws.size());
+        d_wlut_id_.alloc(wi.size());
         HIPC(hipMemcpy(d_wlut_sbox_, ws.data(), ws.size() * 8, hipMemcpyHostToDevice));
         HIPC(hipMemcpy(d_wlut_id_, wi.data(), wi.size() * 8, hipMemcpyHostToDevice));
     }
@@ -773,7 +765,7 @@ void Engine::init_common() {
     lf1k_ = p_.N == 1024 && p_.k == 2 && p_.pbs_l == 6 && p_.pbs_b == 7;
     if (lf512_ || lf1k_) {  // the blind rotations' fused-twiddle transform (lf512.hpp / lf1k.hpp)
         const std::vector<double> lf = lf512_ ? make_lf512_table() : make_lf1k_table();
-        d_lf_ = static_cast<double *>(alloc(lf.size() * 8));
+        d_lf_.alloc(lf.size());
         HIPC(hipMemcpy(d_lf_, lf.data(), lf.size() * 8, hipMemcpyHostToDevice));
     }
     const char *blat = getenv("TAE_BR_LAT_MAX");
@@ -876,7 +868,7 @@ void Engine::init_common() {
 }
 
 void Engine::bsk_to_fourier(const uint64_t *d_bsk_std) {
-    d_bsk_f_ = static_cast<cplx *>(alloc(p_.bsk_fourier_len() * sizeof(cplx)));
+    d_bsk_f_.alloc(p_.bsk_fourier_len());
     const size_t polys = (size_t)p_.n * p_.pbs_l * (p_.k + 1) * (p_.k + 1);
     const int M = p_.M();
     if (p_.N == 512) {
@@ -899,15 +891,13 @@ void Engine::bsk_to_fourier(const uint64_t *d_bsk_std) {
 
 Engine::Engine(const ServerKeyRaw &keys, int device) : p_(keys.p), device_(device) {
     init_common();
-    owns_keys_ = true;
-    d_ksk_ = static_cast<uint64_t *>(alloc(keys.ksk.size() * 8));
-    d_pfpksk_ = static_cast<uint64_t *>(alloc(keys.pfpksk.size() * 8));
-    HIPC(hipMemcpy(d_ksk_, keys.ksk.data(), keys.ksk.size() * 8, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(d_pfpksk_, keys.pfpksk.data(), keys.pfpksk.size() * 8, hipMemcpyHostToDevice));
-    uint64_t *d_bsk = static_cast<uint64_t *>(alloc(keys.bsk.size() * 8));
-    HIPC(hipMemcpy(d_bsk, keys.bsk.data(), keys.bsk.size() * 8, hipMemcpyHostToDevice));
-    bsk_to_fourier(d_bsk);
-    HIPC(hipFree(d_bsk));
+    HIPC(hipMemcpy(d_ksk_.alloc(keys.ksk.size()), keys.ksk.data(), keys.ksk.size() * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_pfpksk_.alloc(keys.pfpksk.size()), keys.pfpksk.data(), keys.pfpksk.size() * 8, hipMemcpyHostToDevice));
+    {
+        DevBuf<uint64_t> d_bsk(keys.bsk.size());  // the standard-domain key, freed once it is converted
+        HIPC(hipMemcpy(d_bsk, keys.bsk.data(), keys.bsk.size() * 8, hipMemcpyHostToDevice));
+        bsk_to_fourier(d_bsk);
+    }
     prepare_mfma_keys();
 }
 
@@ -935,8 +925,8 @@ void Engine::prepare_mfma_keys() {
         if (p_.pfks_b > 7) throw std::runtime_error("packing keyswitch digits must fit one byte");
         kp_pf_ = (kd + ksgemm::TK - 1) / ksgemm::TK * ksgemm::TK;
         kp_ks_ = (kd_ks + ksgemm::TK - 1) / ksgemm::TK * ksgemm::TK;
-        d_pf_bt_ = static_cast<int8_t *>(alloc((size_t)nc * 8 * kp_pf_));
-        d_ks_bt_ = static_cast<int8_t *>(alloc((size_t)nc_ks * 8 * kp_ks_));
+        d_pf_bt_.alloc((size_t)nc * 8 * kp_pf_);
+        d_ks_bt_.alloc((size_t)nc_ks * 8 * kp_ks_);
         dim3 gp((kp_pf_ + 63) / 64, (nc + 63) / 64), gks((kp_ks_ + 63) / 64, (nc_ks + 63) / 64);
         ksgemm::prep_key<<<gp, kThreads, 0, stream_>>>(d_pfpksk_, d_pf_bt_, kd, kp_pf_, nc, nc, nc, 0);
         ksgemm::prep_key<<<gks, kThreads, 0, stream_>>>(d_ksk_, d_ks_bt_, kd_ks, kp_ks_, nc_ks, nc_ks, nc_ks, 0);
@@ -949,8 +939,8 @@ void Engine::prepare_mfma_keys() {
     kp_ks_ = (kd_ks + ksgemm::TK - 1) / ksgemm::TK * ksgemm::TK;
     const int nc_pf = (p_.k + 1) * glwe, nc_ks = p_.n + 1;
     const long pf_blk = (long)(p_.K() + 1) * p_.pfks_l * glwe;
-    d_pf_bt_ = static_cast<int8_t *>(alloc((size_t)nc_pf * 8 * kp_pf_));
-    d_ks_bt_ = static_cast<int8_t *>(alloc((size_t)nc_ks * 8 * kp_ks_));
+    d_pf_bt_.alloc((size_t)nc_pf * 8 * kp_pf_);
+    d_ks_bt_.alloc((size_t)nc_ks * 8 * kp_ks_);
     dim3 gpf((kp_pf_ + 63) / 64, (nc_pf + 63) / 64), gks((kp_ks_ + 63) / 64, (nc_ks + 63) / 64);
     // the LDS-DMA GEMM reads both operands row-pair interleaved (ksgemm::op_off; Kp % 128 == 0)
     ksgemm::prep_key<<<gpf, kThreads, 0, stream_>>>(d_pfpksk_, d_pf_bt_, kd_pf, kp_pf_, nc_pf, glwe, glwe, pf_blk, true);
@@ -980,11 +970,11 @@ void Engine::prepare_mfma_keys() {
     }
     if (pf_kl_) {  // K-layout key rows (limbs in K) and the per-column offset correction
         kp_pf_kl_ = ((p_.K() + 1) * pf_slots_.S + ksgemm::TK - 1) / ksgemm::TK * ksgemm::TK;
-        d_pf_bt_kl_ = static_cast<int8_t *>(alloc((size_t)nc_pf * 8 * kp_pf_kl_));
+        d_pf_bt_kl_.alloc((size_t)nc_pf * 8 * kp_pf_kl_);
         dim3 gkl((kp_pf_kl_ + 63) / 64, (nc_pf + 63) / 64);
         ksgemm::prep_key_kl<<<gkl, kThreads, 0, stream_>>>(d_pfpksk_, d_pf_bt_kl_, p_.K() + 1, p_.pfks_l, kp_pf_kl_,
                                                            nc_pf, glwe, glwe, pf_blk, pf_slots_);
-        d_pf_corr_ = static_cast<uint64_t *>(alloc((size_t)nc_pf * 8));
+        d_pf_corr_.alloc((size_t)nc_pf);
         ksgemm::key_offset_corr<<<(nc_pf + 255) / 256, 256, 0, stream_>>>(d_pfpksk_, d_pf_corr_, p_.K() + 1, p_.pfks_l,
                                                                           nc_pf, glwe, glwe, pf_blk, pf_slots_);
     }
@@ -994,13 +984,8 @@ void Engine::prepare_mfma_keys() {
 }
 
 // digit scratch for B ciphertexts x rows_per_ct rows of Kp bytes (padding columns zeroed)
-static void ensure_digits(int8_t *&buf, size_t &cap, size_t rows, int Kd, int Kp, hipStream_t s, bool il = false) {
-    const size_t need = rows * (size_t)Kp;
-    if (need > cap) {
-        if (buf) hip_check(hipFree(buf), "hipFree");
-        hip_check(hipMalloc(&buf, need), "hipMalloc digits");
-        cap = need;
-    }
+static void ensure_digits(DevBuf<int8_t> &buf, size_t rows, int Kd, int Kp, hipStream_t s, bool il = false) {
+    buf.grow(rows * (size_t)Kp);
     if (Kp > Kd) {
         const size_t total = rows * (size_t)(Kp - Kd);
         ksgemm::zero_pad<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(buf, (long)rows, Kd, Kp, il);
@@ -1012,10 +997,9 @@ Engine::Engine(const Params &p, int device, const uint64_t *d_ksk, const uint64_
                const uint64_t *d_pfpksk)
     : p_(p), device_(device) {
     init_common();
-    owns_keys_ = false;
     order_after_caller();  // the key buffers may still be in flight on the caller's stream (RCCL broadcast)
-    d_ksk_ = const_cast<uint64_t *>(d_ksk);
-    d_pfpksk_ = const_cast<uint64_t *>(d_pfpksk);
+    d_ksk_.borrow(const_cast<uint64_t *>(d_ksk));
+    d_pfpksk_.borrow(const_cast<uint64_t *>(d_pfpksk));
     bsk_to_fourier(d_bsk);
     prepare_mfma_keys();
 }
@@ -1023,29 +1007,12 @@ Engine::Engine(const Params &p, int device, const uint64_t *d_ksk, const uint64_
 Engine::~Engine() {
     hipSetDevice(device_);
     hipStreamSynchronize(stream_);
-    if (owns_keys_) {
-        hipFree(d_ksk_);
-        hipFree(d_pfpksk_);
-    }
-    for (void *q : {(void *)d_bsk_f_, (void *)d_twist_, (void *)d_untwist_, (void *)d_w_, (void *)d_lut_shift_,
-                    (void *)d_lut24_, (void *)d_lut8_, (void *)d_small_, (void *)d_big_, (void *)d_ggsw_,
-                    (void *)d_ggsw_f_, (void *)d_state_, (void *)d_muls_, (void *)d_pf_bt_, (void *)d_ks_bt_, (void *)d_pf_corr_, (void *)d_pf_bt_kl_,
-                    (void *)d_digits_, (void *)d_wlut_sbox_, (void *)d_wlut_id_, (void *)d_lut_x_, (void *)d_xbuf_,
-                    (void *)d_xsh_, (void *)d_xks_, (void *)d_xpbs_, (void *)d_ints_, (void *)d_s1_sbox_tv_,
-                    (void *)d_s1_id_tv_, (void *)d_s1_in_, (void *)d_s1_out_, (void *)d_s1_pks_, (void *)d_s1_tv_, (void *)d_pf_flags_, (void *)d_clk_, (void *)d_lf_, (void *)d_acc_w_,
-                    (void *)d_ctr_groups_, (void *)d_ctr_map_, (void *)d_key_of_, (void *)d_ctr_gslot_,
-                    (void *)d_ctr_blen_, (void *)d_ctr_bout_, (void *)d_pack_, (void *)d_xts_tweaks_, (void *)d_xts_masks_,
-                    (void *)d_ccm_keep_, (void *)d_ccm_bytes_, (void *)d_ccm_src_, (void *)d_pub_kout_, (void *)d_ccm_slot_,
-                    (void *)d_pub_klen_, (void *)d_ccm_order_,
-                    (void *)d_rs_start_, (void *)d_rs_src_, (void *)d_rs_list_, (void *)d_rs_base_, (void *)d_rs_pub_,
-                    (void *)d_lut_gcm_, (void *)d_gcm_src_, (void *)d_gcm_a_, (void *)d_gcm_b_, (void *)d_gcm_ops_,
-                    (void *)d_gcm_ks_, (void *)d_gcm_parts_,
-                    (void *)d_gcm_bytes_,
-                    (void *)d_lut_inv32_, (void *)d_lut_inv8_, (void *)d_lut_mul32_, (void *)d_lut_id1_})
-        if (q) hipFree(q);
-    for (auto &e : ev_pool_) hipEventDestroy(e);
-    if (caller_ev_) hipEventDestroy(caller_ev_);
-    hipStreamDestroy(stream_);
+}
+
+Engine::Teardown::~Teardown() {
+    for (auto &ev : e.ev_pool_) hipEventDestroy(ev);
+    if (e.caller_ev_) hipEventDestroy(e.caller_ev_);
+    if (e.stream_) hipStreamDestroy(e.stream_);
 }
 
 void Engine::synchronize() { HIPC(hipStreamSynchronize(stream_)); }
@@ -1062,10 +1029,10 @@ void Engine::order_after_caller() {
 }
 
 void Engine::reserve(size_t bits, size_t outputs) {
-    grow(d_small_, cap_small_, bits * p_.small_len());
-    grow(d_big_, cap_big_, bits * p_.big_len());
-    grow(d_ggsw_, cap_ggsw_, bits * p_.cbs_ggsw_len());
-    grow(d_ggsw_f_, cap_ggsw_f_, bits * p_.cbs_ggsw_fourier_len());
+    d_small_.grow(bits * p_.small_len());
+    d_big_.grow(bits * p_.big_len());
+    d_ggsw_.grow(bits * p_.cbs_ggsw_len());
+    d_ggsw_f_.grow(bits * p_.cbs_ggsw_fourier_len());
     (void)outputs;
 }
 
@@ -1073,7 +1040,7 @@ void Engine::keyswitch(const uint64_t *d_in, uint64_t *d_out, size_t B) {
     if (!B) return;
     if (mfma_ks_) {
         const int K = p_.K(), kd = K * p_.ks_l;
-        ensure_digits(d_digits_, cap_digits_, B, kd, kp_ks_, stream_);
+        ensure_digits(d_digits_, B, kd, kp_ks_, stream_);
         const size_t thr = B * (size_t)K;
         ksgemm::prep_digits<1, 8><<<(unsigned)((thr + 255) / 256), 256, 0, stream_>>>(
             d_in, K + 1, d_digits_, (long)B, K, kp_ks_, p_.ks_b, p_.ks_l);
@@ -1157,7 +1124,7 @@ void Engine::bootstrap(const uint64_t *d_small, const uint64_t *d_lut_glwe, uint
     if (b1kw_ && lut_mod == 1 && (long)B >= (long)br1024w::C * num_cu_) {
         // four ciphertexts per workgroup (every CU busy from 4 x CUs ciphertexts on)
         const size_t wgs = (B + br1024w::C - 1) / br1024w::C;
-        grow(d_acc_w_, cap_acc_w_, B * (size_t)(p_.k + 1) * p_.N);
+        d_acc_w_.grow(B * (size_t)(p_.k + 1) * p_.N);
         uint64_t *clk = clock_buffer(wgs);
         br1024w::br_kernel<6, 7><<<(unsigned)wgs, br1024w::THREADS, br1024w::lds_bytes(), stream_>>>(
             d_small, p_.n, d_lut_glwe, d_bsk_f_, d_big, (long)B, body_add, out_add, d_w_, d_lf_, d_acc_w_, clk);
@@ -1217,14 +1184,14 @@ void Engine::pfks_keys(const uint64_t *d_big, size_t B, int q0, int nq, uint64_t
         const int K = p_.K(), kd = (K + 1) * pf_slots_.S;
         constexpr long TMR = 96 * kG6WM;  // ciphertexts per tile (384)
         const long mt = (long)((B + TMR - 1) / TMR);
-        ensure_digits(d_digits_, cap_digits_, (size_t)mt * TMR, kd, kp_pf_kl_, stream_, true);
+        ensure_digits(d_digits_, (size_t)mt * TMR, kd, kp_pf_kl_, stream_, true);
         const size_t thr = B * (size_t)(K + 1);
         bool clamp = false;
         for (int l = 0; l < p_.pfks_l; l++) clamp = clamp || pf_slots_.clamp[l];
         const int fw = (int)(((size_t)(K + 1) * p_.pfks_l + 31) / 32);  // flag words per ciphertext
         if (clamp) {
             const size_t need = B * (size_t)fw;
-            grow(d_pf_flags_, cap_pf_flags_, need);
+            d_pf_flags_.grow(need);
             HIPC(hipMemsetAsync(d_pf_flags_, 0, need * 4, stream_));
         }
         ksgemm::prep_digits_kl<<<(unsigned)((thr + 255) / 256), 256, 0, stream_>>>(
@@ -1263,7 +1230,7 @@ void Engine::pfks_keys(const uint64_t *d_big, size_t B, int q0, int nq, uint64_t
         // digits as 3 balanced 6-bit limbs, limb index in the MFMA row tile (ksgemm.hpp gemm_g6)
         const int K = p_.K(), kd = (K + 1) * p_.pfks_l;
         const long mt4 = (long)((B + 127) / 128);  // 384-row tiles (128 ciphertexts x 3 limbs)
-        ensure_digits(d_digits_, cap_digits_, (size_t)mt4 * 384, kd, kp_pf_, stream_, true);
+        ensure_digits(d_digits_, (size_t)mt4 * 384, kd, kp_pf_, stream_, true);
         const size_t thr = B * (size_t)(K + 1);
         ksgemm::prep_digits3<6><<<(unsigned)((thr + 255) / 256), 256, 0, stream_>>>(
             d_big, K + 1, d_digits_, (long)B, K + 1, kp_pf_, p_.pfks_b, p_.pfks_l, true);
@@ -1306,7 +1273,7 @@ void Engine::pack_bits(const uint64_t *d_bits, size_t count, uint64_t *d_glwes) 
     if (!count) return;
     const size_t glwe = p_.glwe_len(), N = (size_t)p_.N;
     static_assert(glwe_pack::kChunkBits % 512 == 0, "chunks are whole GLWEs");
-    grow(d_pack_, cap_pack_, std::min(count, glwe_pack::kChunkBits) * glwe);
+    d_pack_.grow(std::min(count, glwe_pack::kChunkBits) * glwe);
     timed(ST_PACK, [&] {
         for (size_t b0 = 0; b0 < count; b0 += glwe_pack::kChunkBits) {
             const size_t n = std::min(glwe_pack::kChunkBits, count - b0);
@@ -1427,7 +1394,7 @@ hipEvent_t Engine::next_event() {
 
 uint64_t *Engine::clock_buffer(size_t wgs) {
     if (!clock_) return nullptr;
-    grow(d_clk_, cap_clk_, 2 * wgs);
+    d_clk_.grow(2 * wgs);
     HIPC(hipMemsetAsync(d_clk_, 0, 2 * wgs * 8, stream_));
     return d_clk_;
 }
@@ -1501,16 +1468,15 @@ void Engine::extract_bits(const uint64_t *d_in, size_t B, int delta_log, int nbi
             const uint64_t alpha = 1ull << (delta_log - 1 + b);
             for (int j = 0; j < p_.N; j++) luts[(size_t)b * glwe + (size_t)p_.k * p_.N + j] = 0 - alpha;
         }
-        if (d_lut_x_) HIPC(hipFree(d_lut_x_));
-        d_lut_x_ = static_cast<uint64_t *>(alloc(luts.size() * 8));
+        d_lut_x_.alloc(luts.size());
         HIPC(hipMemcpy(d_lut_x_, luts.data(), luts.size() * 8, hipMemcpyHostToDevice));
         lut_x_delta_ = delta_log;
         lut_x_bits_ = nbits;
     }
-    grow(d_xbuf_, cap_xbuf_, B * L);
-    grow(d_xsh_, cap_xsh_, B * L);
-    grow(d_xks_, cap_xks_, B * S);
-    grow(d_xpbs_, cap_xpbs_, B * L);
+    d_xbuf_.grow(B * L);
+    d_xsh_.grow(B * L);
+    d_xks_.grow(B * S);
+    d_xpbs_.grow(B * L);
     HIPC(hipMemcpyAsync(d_xbuf_, d_in, B * L * 8, hipMemcpyDeviceToDevice, stream_));
     for (int bit_idx = 0; bit_idx < nbits; bit_idx++) {
         // shift the extracted bit to the MSB, keyswitch: that is the output bit (LSB first, stored
@@ -1539,7 +1505,7 @@ void Engine::require_s1() const {
 void Engine::s1_bootstrap(const uint64_t *d_in, const uint64_t *d_tvs, size_t lut_mod, uint64_t *d_out, size_t B) {
     require_s1();
     if (!B) return;
-    grow(d_big_, cap_big_, B * p_.big_len());
+    d_big_.grow(B * p_.big_len());
     timed(ST_PBS, [&] { bootstrap(d_in, d_tvs, d_big_, B, 0, 0, lut_mod); });
     timed(ST_KS, [&] { keyswitch(d_big_, d_out, B); });
 }
@@ -1548,7 +1514,7 @@ void Engine::s1_pks(const uint64_t *d_in, size_t B, uint64_t *d_out) {
     require_s1();
     if (!B) return;
     const int L = p_.n + 1, kd = p_.n * p_.pfks_l, nc = (p_.k + 1) * p_.N;
-    ensure_digits(d_digits_, cap_digits_, B, kd, kp_pf_, stream_);
+    ensure_digits(d_digits_, B, kd, kp_pf_, stream_);
     const size_t thr = B * (size_t)p_.n;
     ksgemm::prep_digits<1, 8><<<(unsigned)((thr + 255) / 256), 256, 0, stream_>>>(d_in, L, d_digits_, (long)B, p_.n,
                                                                                   kp_pf_, p_.pfks_b, p_.pfks_l);
@@ -1569,7 +1535,7 @@ void Engine::s1_tv_from_pks(const uint64_t *d_pks, size_t P, uint64_t *d_tv) {
 void Engine::s1_pack(const uint64_t *d_in, int count, uint64_t *d_out) {
     require_s1();
     if (count < 1 || count > p_.N) throw std::runtime_error("packing keyswitch: 1..N ciphertexts");
-    grow(d_s1_pks_, cap_s1_pks_, (size_t)count * p_.glwe_len());
+    d_s1_pks_.grow((size_t)count * p_.glwe_len());
     s1_pks(d_in, (size_t)count, d_s1_pks_);
     s1_pack_kernel<512><<<(unsigned)(p_.k + 1), kThreads, 0, stream_>>>(d_s1_pks_, count, d_out, p_.k);
     HIPC(hipGetLastError());
@@ -1620,10 +1586,10 @@ void Engine::s1_multivariate_chunk(const uint64_t *d_bits, size_t G, int nbits, 
     const int L = p_.n + 1;
     const size_t glwe = p_.glwe_len();
     size_t V = (size_t)1 << (nbits - 1), B = G * n_fn * V;
-    grow(d_s1_in_, cap_s1_in_, B * L);
-    grow(d_s1_out_, cap_s1_out_, B * L);
-    grow(d_s1_pks_, cap_s1_pks_, B * glwe);
-    grow(d_s1_tv_, cap_s1_tv_, std::max<size_t>(B / 2, 1) * glwe);
+    d_s1_in_.grow(B * L);
+    d_s1_out_.grow(B * L);
+    d_s1_pks_.grow(B * glwe);
+    d_s1_tv_.grow(std::max<size_t>(B / 2, 1) * glwe);
     const uint64_t *tvs = d_tvs;
     size_t lut_mod = (size_t)n_fn * V;  // level 0: the cleartext test vectors, shared by every group
     for (int sel = nbits - 1;; sel--) {

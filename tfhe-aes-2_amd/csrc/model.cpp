@@ -131,20 +131,6 @@ Lut Context::generate_lookup_table(int input_bits, int output_bits, const uint64
     return l;
 }
 
-namespace {
-struct DevBuf {
-    void *p = nullptr;
-    explicit DevBuf(size_t bytes) { hip_check(hipMalloc(&p, std::max<size_t>(bytes, 16)), "hipMalloc"); }
-    ~DevBuf() {
-        if (p) hipFree(p);
-    }
-    template <class T>
-    T *as() const {
-        return static_cast<T *>(p);
-    }
-};
-}  // namespace
-
 // The staging scope of one entry point: it holds the context's lock, sets its device and hands the engine the arrays
 // of the call.  Device memory (TAE_MEM_DEVICE) passes through, ordered after the caller's work; host memory is
 // uploaded into buffers the scope owns (one hipMalloc per array) and the outputs are downloaded by finish().  The
@@ -173,6 +159,27 @@ class Context::Staged {
         downloads_.push_back({p, d, n * sizeof(T)});
         return d;
     }
+    // ... for a stage that does not write every word: the host caller reads zeros there (a device array is the
+    // caller's to clear)
+    template <class T>
+    T *out_zeroed(T *p, size_t n) {
+        T *d = out(p, n);
+        if (!dev_ && n) hip_check(hipMemsetAsync(d, 0, n * sizeof(T), e_.stream()), "clear output");
+        return d;
+    }
+    // n elements the engine updates in place: the caller's array, or its upload, downloaded by finish()
+    template <class T>
+    T *inout(T *p, size_t n) {
+        if (dev_) return p;
+        T *d = const_cast<T *>(upload(p, n));
+        downloads_.push_back({p, d, n * sizeof(T)});
+        return d;
+    }
+    // a lookup table or test vector in the memory kind of the call
+    template <class T>
+    const T *lut(const T *p, size_t n) {
+        return dev_ ? p : pub(p, n);
+    }
     // a key table [..][stride]: the caller's, or a compact upload of only the slots that `slots` refers to, which is
     // rewritten to index it, so a slot that nothing refers to is not read in either case
     const uint64_t *table(const uint64_t *table, std::vector<int32_t> &slots, size_t stride);
@@ -199,7 +206,7 @@ class Context::Staged {
     template <class T>
     T *alloc(size_t n) {
         bufs_.emplace_back(n * sizeof(T));
-        return bufs_.back().as<T>();
+        return reinterpret_cast<T *>(bufs_.back().get());
     }
     template <class T>
     const T *upload(const T *p, size_t n) {
@@ -211,7 +218,7 @@ class Context::Staged {
     Engine &e_;
     const bool dev_;
     bool own_times_ = false;
-    std::deque<DevBuf> bufs_;  // freed before the lock is released
+    std::deque<DevBuf<uint8_t>> bufs_;  // freed before the lock is released
     std::vector<Download> downloads_;
 };
 
@@ -931,12 +938,11 @@ void Context::aes_xts_tweaks_raw(const uint64_t *rk2, const uint8_t *tweaks, siz
     for (size_t i = 0; i < n; i++) slot[i] = xts_tweak_slot(distinct, tweaks + 16 * i);
     const size_t nd = distinct.size() / 16;
     Staged st(*this, device_mem);
-    DevBuf d_T(nd * block_len * 8);  // the distinct tweaks, each copied to its places in the result
+    DevBuf<uint64_t> d_T(nd * block_len);  // the distinct tweaks, each copied to its places in the result
     uint64_t *dst = st.out(out, n * block_len);
-    engine_->aes_xts_tweaks(st.in(rk2, kw * S), st.pub(distinct.data(), distinct.size()), nd, rounds, d_T.as<uint64_t>(),
-                            nr);
+    engine_->aes_xts_tweaks(st.in(rk2, kw * S), st.pub(distinct.data(), distinct.size()), nd, rounds, d_T, nr);
     for (size_t i = 0; i < n; i++)
-        hip_check(hipMemcpyAsync(dst + i * block_len, d_T.as<uint64_t>() + (size_t)slot[i] * block_len, block_len * 8,
+        hip_check(hipMemcpyAsync(dst + i * block_len, d_T + (size_t)slot[i] * block_len, block_len * 8,
                                  hipMemcpyDeviceToDevice, engine_->stream()),
                   "place tweak");
     st.finish();
@@ -2177,6 +2183,72 @@ void Context::pack_pfks_raw(const uint64_t *bits, size_t count, uint64_t *glwes,
     st.finish();
 }
 
+// ---- the engine's stages one at a time (tae_stage_*; no noise rule).  Host outputs are cleared first, as not every
+// stage writes every word: pfks_into_ggsw fills only the rows of its level ----
+void Context::keyswitch_raw(const uint64_t *in, size_t count, uint64_t *out, bool device_mem) {
+    Staged st(*this, device_mem);
+    st.own_times();
+    engine_->keyswitch(st.in(in, count * params().big_len()), st.out_zeroed(out, count * params().small_len()), count);
+    st.finish();
+}
+
+void Context::pbs_shift_boolean_raw(const uint64_t *small, size_t count, int level, uint64_t *big, bool device_mem) {
+    Staged st(*this, device_mem);
+    st.own_times();
+    engine_->pbs_shift_boolean(st.in(small, count * params().small_len()), st.out_zeroed(big, count * params().big_len()),
+                               count, level);
+    st.finish();
+}
+
+void Context::bootstrap_raw(const uint64_t *small, size_t count, const uint64_t *lut_glwe, uint64_t *big,
+                            bool device_mem) {
+    Staged st(*this, device_mem);
+    st.own_times();
+    engine_->bootstrap(st.in(small, count * params().small_len()), st.lut(lut_glwe, params().glwe_len()),
+                       st.out_zeroed(big, count * params().big_len()), count, 0, 0);
+    st.finish();
+}
+
+void Context::pfks_ggsw_raw(const uint64_t *big, size_t count, int level, uint64_t *ggsw, bool device_mem) {
+    Staged st(*this, device_mem);
+    st.own_times();
+    engine_->pfks_into_ggsw(st.in(big, count * params().big_len()), st.out_zeroed(ggsw, count * params().cbs_ggsw_len()),
+                            count, level);
+    st.finish();
+}
+
+void Context::ggsw_fourier_raw(const uint64_t *ggsw, size_t count, cplx *ggsw_f, bool device_mem) {
+    Staged st(*this, device_mem);
+    st.own_times();
+    engine_->ggsw_to_fourier(st.in(ggsw, count * params().cbs_ggsw_len()),
+                             st.out_zeroed(ggsw_f, count * params().cbs_ggsw_fourier_len()), count);
+    st.finish();
+}
+
+void Context::vertical_packing_raw(const cplx *ggsw_f, size_t groups, int n_in, const uint64_t *lut, int n_out,
+                                   uint64_t *out, bool device_mem) {
+    int log_n = 0;
+    while ((1 << log_n) < params().N) log_n++;
+    // n_in > log2 N: the LUT of every output holds 2^tree polynomials (the CMux tree's leaves)
+    const int tree = std::max(0, n_in - log_n);
+    if (tree > 16) throw ModelError{TAE_E_ARG, "n_in exceeds log2 N + 16"};
+    Staged st(*this, device_mem);
+    st.own_times();
+    engine_->vertical_packing(st.in(ggsw_f, groups * n_in * params().cbs_ggsw_fourier_len()), groups, n_in,
+                              st.lut(lut, (size_t)n_out * ((size_t)params().N << tree)), n_out,
+                              st.out_zeroed(out, groups * n_out * params().big_len()));
+    st.finish();
+}
+
+// lhs += rhs over count ciphertexts (tae_xor_batch, after its noise rule)
+void Context::xor_raw(uint64_t *lhs, const uint64_t *rhs, size_t count, bool device_mem) {
+    if (!count) return;
+    const size_t words = count * bit_len();
+    Staged st(*this, device_mem);
+    engine_->lwe_add(st.inout(lhs, words), st.in(rhs, words), words);
+    st.finish();
+}
+
 void Context::s1_packing_keyswitch_raw(const uint64_t *cts, size_t count, uint64_t *glwe, bool device_mem) {
     require_s1();
     if (count < 1 || count > (size_t)params().N) throw ModelError{TAE_E_ARG, "packing keyswitch takes 1..N ciphertexts"};
@@ -2193,20 +2265,20 @@ void Context::s1_test_vectors_from_ciphertexts_raw(const uint64_t *ct0, const ui
     std::lock_guard<std::mutex> g(mu_);
     hip_check(hipSetDevice(engine_->device()), "hipSetDevice");
     // interleave the pairs (2b, 2b+1) = (ct0[b], ct1[b]) on the device, as the tree levels hold them
-    DevBuf d_pairs(2 * B * L * 8), d_pks(2 * B * G * 8);
+    DevBuf<uint64_t> d_pairs(2 * B * L), d_pks(2 * B * G);
     const auto kind = device_mem ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (device_mem) engine_->order_after_caller();
-    hip_check(hipMemcpy2DAsync(d_pairs.p, 2 * L * 8, ct0, L * 8, L * 8, B, kind, engine_->stream()), "pairs");
-    hip_check(hipMemcpy2DAsync(d_pairs.as<uint64_t>() + L, 2 * L * 8, ct1, L * 8, L * 8, B, kind, engine_->stream()),
+    hip_check(hipMemcpy2DAsync(d_pairs, 2 * L * 8, ct0, L * 8, L * 8, B, kind, engine_->stream()), "pairs");
+    hip_check(hipMemcpy2DAsync(d_pairs + L, 2 * L * 8, ct1, L * 8, L * 8, B, kind, engine_->stream()),
               "pairs");
     engine_->begin_call();
-    engine_->s1_pks(d_pairs.as<uint64_t>(), 2 * B, d_pks.as<uint64_t>());
+    engine_->s1_pks(d_pairs, 2 * B, d_pks);
     if (device_mem) {
-        engine_->s1_tv_from_pks(d_pks.as<uint64_t>(), B, tvs);
+        engine_->s1_tv_from_pks(d_pks, B, tvs);
     } else {
-        DevBuf d_tv(B * G * 8);
-        engine_->s1_tv_from_pks(d_pks.as<uint64_t>(), B, d_tv.as<uint64_t>());
-        hip_check(hipMemcpyAsync(tvs, d_tv.p, B * G * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
+        DevBuf<uint64_t> d_tv(B * G);
+        engine_->s1_tv_from_pks(d_pks, B, d_tv);
+        hip_check(hipMemcpyAsync(tvs, d_tv, B * G * 8, hipMemcpyDeviceToHost, engine_->stream()), "download");
         engine_->synchronize();
         return;
     }

@@ -306,6 +306,18 @@ class Context {  // FheContext
     void pack_pfks_raw(const uint64_t *bits, size_t count, uint64_t *glwes, bool device_mem);
     void require_pack(size_t count) const;
 
+    // ---- the engine's stages one at a time (tae_stage_*): no noise rule.  Shapes as in engine.hpp; a LUT is in the
+    // memory kind of the call; a host output is zero where the stage writes nothing ----
+    void keyswitch_raw(const uint64_t *in, size_t count, uint64_t *out, bool device_mem);
+    void pbs_shift_boolean_raw(const uint64_t *small, size_t count, int level, uint64_t *big, bool device_mem);
+    void bootstrap_raw(const uint64_t *small, size_t count, const uint64_t *lut_glwe, uint64_t *big, bool device_mem);
+    void pfks_ggsw_raw(const uint64_t *big, size_t count, int level, uint64_t *ggsw, bool device_mem);
+    void ggsw_fourier_raw(const uint64_t *ggsw, size_t count, cplx *ggsw_f, bool device_mem);
+    void vertical_packing_raw(const cplx *ggsw_f, size_t groups, int n_in, const uint64_t *lut, int n_out, uint64_t *out,
+                              bool device_mem);
+    // lhs += rhs over count ciphertexts [count][bit_len]: tae_xor_batch after its noise rule
+    void xor_raw(uint64_t *lhs, const uint64_t *rhs, size_t count, bool device_mem);
+
   private:
     void require_s1() const;
     class Staged;  // the staging scope of an entry point (model.cpp)
