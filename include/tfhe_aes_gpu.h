@@ -638,6 +638,34 @@ int tae_stage_gf128_square(const tae_context *ctx, const uint64_t *in, size_t co
 int tae_stage_gf128_product(const tae_context *ctx, const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out,
                             int mem);
 
+/* ---- AEAD open: a tag verdict bit and the verdict-gated payload (no counterpart in the reference) ----
+ * The CCM and GCM calls above return the payload bits [sum payload_lens][8][L], frames in order, and the
+ * tag-difference bits [n_frames][8 tag_len][L], and leave the verdict to the client.  These calls join the two on the
+ * server: ok [n_frames][L] encrypts 1 iff every difference bit of the frame is 0 (levels of "OR of 8" circuit
+ * bootstraps, the last one "NOR of 8": 128 -> 16 -> 2 -> 1), and out_plain is the payload where ok = 1 and all zeros
+ * where ok = 0 (one 9 -> 8 circuit bootstrap per byte: its 8 bits and the frame's verdict).  One tag_len per call, any
+ * length CCM or GCM accepts (4 .. 16 even, 13, 15); a frame of length 0 still gets its verdict.
+ * 1-bit WoP-PBS parameter sets only: the 8-bit model and shortint_1bit are TAE_E_PARAM, as is another tag_len; both
+ * come before any device work and leave the stage times untouched.  n_frames == 0 is a no-op.
+ * Noise: every input of a bootstrap must be at or below the cap of the parameter set (TAE_E_NOISE); verdict bits come
+ * out at noise^2 = 8 and gated payload bits at 9, with fresh ids and no key bit.  The raw forms replay this for inputs
+ * at the cap; the handle form for its inputs' levels. */
+/* The plan alone, no GPU: *levels (2 or 3), verdict_groups [*levels] (room for 3: the groups per frame of every
+ * level) and *gate_groups = sum payload_lens */
+int tae_aead_open_plan(int tag_len, const size_t *payload_lens, size_t n_frames, int *levels, size_t *verdict_groups,
+                       size_t *gate_groups);
+/* the schedule of one frame of one byte with payload bits at plain_level and difference bits at diff_level */
+int tae_aead_open_noise_schedule_check(int param_set, int tag_len, uint64_t plain_level, uint64_t diff_level);
+int tae_aead_verdict_raw(const tae_context *ctx, const uint64_t *tag_diff, size_t n_frames, int tag_len, uint64_t *ok,
+                         int mem);
+/* payload_lens is a host array in either memory kind; out_plain is not plain */
+int tae_aead_open_raw(const tae_context *ctx, const uint64_t *plain, const size_t *payload_lens, const uint64_t *tag_diff,
+                      size_t n_frames, int tag_len, uint64_t *out_plain, uint64_t *out_ok, int mem);
+/* plain [sum payload_lens * 8] and tag_diff [n_frames * 8 tag_len] handles -> out_plain [sum payload_lens * 8],
+ * out_ok [n_frames] */
+int tae_aead_open(const tae_context *ctx, const tae_bit *const *plain, const size_t *payload_lens,
+                  const tae_bit *const *tag_diff, size_t n_frames, int tag_len, tae_bit **out_plain, tae_bit **out_ok);
+
 /* ---- Aes128Encrypt for the fhe_sbox_pbs driver (src/aes_128/fhe/fhe_sbox_pbs.rs:22-171) ------------
  * ShortintWoppbs1BitSboxPbsAesEncrypt on the 1-bit model (fhe_impls/shortint_woppbs_1bit.rs:47-81:
  * SubBytes = one 8 -> 8 circuit bootstrap per byte, MixColumns = gf_256_mul by BitCt XORs) and

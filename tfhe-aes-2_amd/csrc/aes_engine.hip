@@ -124,6 +124,19 @@ __global__ void gcm_pairs_kernel(const uint64_t *__restrict__ small, uint64_t *_
     }
 }
 
+// ---- AEAD open (aead_open.hpp): the groups of a verdict level or of a gate pass from small ciphertexts that were
+// keyswitched once: out [n][S] = small [idx[t]][S], or the zero ciphertext where idx[t] < 0.  Consecutive lanes take
+// consecutive coefficients of one output ciphertext; the host checks every index against the source count ----
+__global__ void gather_small_kernel(const uint64_t *__restrict__ small, const int32_t *__restrict__ idx,
+                                    uint64_t *__restrict__ out, size_t n, int S) {
+    const size_t total = n * (size_t)S;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t ct = t / S, coef = t - ct * S;
+        const int32_t s = idx[ct];
+        out[t] = s < 0 ? 0 : small[(size_t)s * S + coef];
+    }
+}
+
 // ---- key expansion (FIPS-197 5.2, figure 11): one word before its identity bootstrap ----
 // t = back + other (+ Rcon), whole ciphertexts: back = rk[i-Nk], other = rk[i-1] or SubWord(rk[i-1]), both
 // [4 bytes][8 bits][L].  SubWord works byte by byte, so RotWord is applied here, on the read of its output:
@@ -928,6 +941,83 @@ void Engine::aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk
     rowsum_pass(d_gcm_src_, n_src, std::move(plan.chunks), d_gcm_a_);
     circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
     rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
+    collect_times();
+}
+
+// ---------------------------------------------------------------------------------------------
+// AEAD open: the verdict bit and the gated payload (aead_open.hpp).  Both keep their keyswitched
+// ciphertexts in d_gcm_ks_ and the verdict its level outputs in d_gcm_a_; the groups are gathered into d_small_, where
+// cbs_vp's own reserve leaves its scratch (reserved first, as gcm_product_pass does).  The keyswitch is per ciphertext,
+// so a gathered small ciphertext has the words the keyswitch of the gathered big one would have, and the all-zero big
+// ciphertext keyswitches to the all-zero small one: body 0, and every digit of a zero mask is 0.
+// ---------------------------------------------------------------------------------------------
+namespace {
+void require_open(const Params &p) {
+    if (p.model != 1) throw std::runtime_error("the AEAD open runs on the 1-bit model parameters");
+}
+
+// every entry of an index table is -1 or below n_src
+void check_gather(const std::vector<int32_t> &idx, size_t n_src) {
+    for (int32_t s : idx)
+        if (s < -1 || (s >= 0 && (size_t)s >= n_src)) throw std::runtime_error("AEAD open: gather index out of range");
+}
+}  // namespace
+
+void Engine::aead_verdict(const uint64_t *d_tag_diff, const VerdictPlan &plan, const std::vector<const int32_t *> &d_idx,
+                          const uint64_t *d_lut_or8, const uint64_t *d_lut_nor8, uint64_t *d_ok) {
+    require_open(p_);
+    const size_t n = plan.n_frames, L = p_.big_len(), S = p_.small_len();
+    const int levels = plan.levels();
+    if (!n) return;
+    if (levels < 1 || d_idx.size() != (size_t)levels) throw std::runtime_error("AEAD open: the plan has no levels");
+    for (int l = 0; l < levels; l++) {
+        if (plan.idx[l].size() != n * plan.groups[l] * kOpenOrBits || (l && plan.bits[l] != plan.groups[l - 1]))
+            throw std::runtime_error("AEAD open: the verdict plan does not match its frames");
+        check_gather(plan.idx[l], n * plan.bits[l]);
+    }
+    if (plan.groups[levels - 1] != 1) throw std::runtime_error("AEAD open: the last verdict level has one group");
+    d_gcm_ks_.grow(n * plan.bits[0] * S);
+    d_gcm_a_.grow(n * plan.groups[0] * L);
+    reserve(n * plan.groups[0] * kOpenOrBits, n * plan.groups[0]);
+    timed(ST_KS, [&] { keyswitch(d_tag_diff, d_gcm_ks_, n * plan.bits[0]); });
+    for (int l = 0; l < levels; l++) {
+        const bool last = l + 1 == levels;
+        const size_t G = n * plan.groups[l];
+        timed(ST_LINEAR, [&] {
+            gather_small_kernel<<<grid_for(G * kOpenOrBits * S), kThreads, 0, stream_>>>(d_gcm_ks_, d_idx[l], d_small_,
+                                                                                         G * kOpenOrBits, (int)S);
+            HIPC(hipGetLastError());
+        });
+        cbs_vp(d_small_, G, kOpenOrBits, last ? d_lut_nor8 : d_lut_or8, 1, last ? d_ok : d_gcm_a_.get());
+        if (!last) timed(ST_KS, [&] { keyswitch(d_gcm_a_, d_gcm_ks_, G); });
+    }
+    collect_times();
+}
+
+void Engine::aead_gate(const uint64_t *d_plain, const GatePlan &plan, const std::vector<const int32_t *> &d_idx,
+                       const uint64_t *d_ok, const uint64_t *d_lut_gate, uint64_t *d_out) {
+    require_open(p_);
+    const size_t n_bytes = plan.n_bytes(), n = plan.n_frames, L = p_.big_len(), S = p_.small_len();
+    const size_t pass = aead_gate_pass();
+    if (!n_bytes) return;
+    if (d_idx.size() != (n_bytes + pass - 1) / pass) throw std::runtime_error("AEAD open: one index table per gate pass");
+    for (int32_t f : plan.frame_of_byte)
+        if (f < 0 || (size_t)f >= n) throw std::runtime_error("AEAD open: frame index out of range");
+    const size_t widest = std::min(pass, n_bytes);
+    d_gcm_ks_.grow((n + widest * 8) * S);
+    reserve(widest * kOpenGateBits, widest * 8);
+    // the verdicts go through the keyswitch once and are copied into the byte groups as small ciphertexts
+    timed(ST_KS, [&] { keyswitch(d_ok, d_gcm_ks_, n); });
+    for (size_t g0 = 0, i = 0; g0 < n_bytes; g0 += pass, i++) {
+        const size_t m = std::min(pass, n_bytes - g0);
+        timed(ST_KS, [&] { keyswitch(d_plain + g0 * 8 * L, d_gcm_ks_ + n * S, m * 8); });
+        timed(ST_LINEAR, [&] {
+            gather_small_kernel<<<grid_for(m * kOpenGateBits * S), kThreads, 0, stream_>>>(d_gcm_ks_, d_idx[i], d_small_,
+                                                                                           m * kOpenGateBits, (int)S);
+            HIPC(hipGetLastError());
+        });
+        cbs_vp(d_small_, m, kOpenGateBits, d_lut_gate, 8, d_out + g0 * 8 * L);
+    }
     collect_times();
 }
 

@@ -1361,6 +1361,87 @@ int tae_stage_gf128_product(const tae_context *ctx, const uint64_t *a, const uin
     });
 }
 
+/* ---- AEAD open: the verdict bit and the verdict-gated payload (no counterpart in the reference) ---- */
+extern "C++" {
+namespace {
+void require_tag_len(int tag_len) {
+    if (!tae::aead_tag_len_ok(tag_len)) throw tae::ModelError{TAE_E_PARAM, "a tag is 4 .. 16 bytes, and even or 13 or 15"};
+}
+
+size_t payload_bytes(const size_t *payload_lens, size_t n_frames) {
+    size_t total = 0;
+    for (size_t f = 0; f < n_frames; f++) total += payload_lens[f];
+    return total;
+}
+}  // namespace
+}  // extern "C++"
+
+int tae_aead_open_plan(int tag_len, const size_t *payload_lens, size_t n_frames, int *levels, size_t *verdict_groups,
+                       size_t *gate_groups) {
+    return guarded([&] {
+        require(levels && verdict_groups && gate_groups && (payload_lens || !n_frames), "null");
+        require_tag_len(tag_len);
+        const tae::VerdictPlan v = tae::aead_verdict_plan(tag_len, 1);
+        *levels = v.levels();
+        for (int l = 0; l < v.levels(); l++) verdict_groups[l] = v.groups[l];
+        *gate_groups = payload_bytes(payload_lens, n_frames);
+    });
+}
+
+int tae_aead_open_noise_schedule_check(int param_set, int tag_len, uint64_t plain_level, uint64_t diff_level) {
+    return guarded([&] {
+        const tae::Params p = params_of(param_set);
+        if (p.model != 1)
+            throw tae::ModelError{TAE_E_PARAM, "the AEAD open runs on the 1-bit WoP-PBS parameter sets only"};
+        require_tag_len(tag_len);
+        // one frame of one payload byte
+        const size_t one = 1;
+        const tae::VerdictPlan v = tae::aead_verdict_plan(tag_len, 1);
+        const tae::GatePlan g = tae::aead_gate_plan(&one, 1);
+        std::vector<tae::NoiseLevel> plain(8), diff(v.bits[0]);
+        for (auto &x : plain) x = tae::NoiseLevel::with_noise_level(plain_level, tae::next_ct_id());
+        for (auto &x : diff) x = tae::NoiseLevel::with_noise_level(diff_level, tae::next_ct_id());
+        tae::aead_open_noise_schedule(plain, diff, v, g, p.max_noise_sq);
+    });
+}
+
+int tae_aead_verdict_raw(const tae_context *ctx, const uint64_t *tag_diff, size_t n_frames, int tag_len, uint64_t *ok,
+                         int mem) {
+    return guarded([&] {
+        require((tag_diff && ok) || !n_frames, "null");
+        require_tag_len(tag_len);
+        require_xts_server(ctx);
+        ctx->ctx->aead_verdict_raw(tag_diff, n_frames, tag_len, ok, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_aead_open_raw(const tae_context *ctx, const uint64_t *plain, const size_t *payload_lens, const uint64_t *tag_diff,
+                      size_t n_frames, int tag_len, uint64_t *out_plain, uint64_t *out_ok, int mem) {
+    return guarded([&] {
+        require((payload_lens && tag_diff && out_ok) || !n_frames, "null");
+        require((plain && out_plain) || !payload_bytes(payload_lens, n_frames), "null");
+        require_tag_len(tag_len);
+        require_xts_server(ctx);
+        ctx->ctx->aead_open_raw(plain, payload_lens, tag_diff, n_frames, tag_len, out_plain, out_ok, mem == TAE_MEM_DEVICE);
+    });
+}
+
+int tae_aead_open(const tae_context *ctx, const tae_bit *const *plain, const size_t *payload_lens,
+                  const tae_bit *const *tag_diff, size_t n_frames, int tag_len, tae_bit **out_plain, tae_bit **out_ok) {
+    return guarded([&] {
+        require((payload_lens && tag_diff && out_ok) || !n_frames, "null");
+        const size_t n_bytes = payload_bytes(payload_lens, n_frames);
+        require((plain && out_plain) || !n_bytes, "null");
+        require_tag_len(tag_len);
+        require_xts_server(ctx);
+        if (!n_frames) return;
+        const tae::Context::OpenBits res = ctx->ctx->aead_open(
+            unwrap(plain, n_bytes * 8), payload_lens, unwrap(tag_diff, n_frames * 8 * (size_t)tag_len), n_frames, tag_len);
+        emit(res.plain, out_plain);
+        emit(res.ok, out_ok);
+    });
+}
+
 int tae_aes_sbox_pbs_encrypt_blocks(const tae_context *ctx, const tae_bit *const *expanded_key,
                                     const tae_bit *const *blocks, size_t n_blocks, int rounds, tae_bit **out) {
     return guarded([&] {

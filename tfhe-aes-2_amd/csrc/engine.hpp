@@ -16,6 +16,7 @@
 
 #include "client.hpp"
 #include "cplx.hpp"
+#include "aead_open.hpp"
 #include "aes_ccm.hpp"
 #include "aes_gcm.hpp"
 #include "aes_xts.hpp"
@@ -227,6 +228,21 @@ class Engine {
     void aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers, const uint64_t *d_sk,
                                   size_t n_strides, size_t seg, const std::vector<GcmFrameIn> &frames, int rounds, int nr,
                                   uint64_t *d_out_plain, uint64_t *d_out_tagdiff);
+
+    // ---- AEAD open on the 1-bit model (aead_open.hpp; the reference has no AEAD).  The lookup tables
+    // and the index tables are the call's: device arrays of its staging scope ----
+    // d_tag_diff [n_frames][tag_bits][K+1] -> d_ok [n_frames][K+1], 1 iff every difference bit of the frame is 0: one
+    // keyswitch of all difference bits, then per level of the plan (d_idx[l] its index table) a gather of small
+    // ciphertexts and one 8 -> 1 cbs_vp over all frames, "OR of 8" below the last level and "NOR of 8" at it; a level's
+    // outputs are keyswitched for the next
+    void aead_verdict(const uint64_t *d_tag_diff, const VerdictPlan &plan, const std::vector<const int32_t *> &d_idx,
+                      const uint64_t *d_lut_or8, const uint64_t *d_lut_nor8, uint64_t *d_ok);
+    // d_plain [n_bytes][8][K+1], d_ok [n_frames][K+1] -> d_out [n_bytes][8][K+1] (not d_plain), byte g and-ed with the
+    // verdict of its frame: the verdicts are keyswitched once, then passes of at most aead_gate_pass() bytes, each a
+    // keyswitch, a gather (d_idx[pass]: aead_gate_pass_index) and one 9 -> 8 cbs_vp
+    void aead_gate(const uint64_t *d_plain, const GatePlan &plan, const std::vector<const int32_t *> &d_idx,
+                   const uint64_t *d_ok, const uint64_t *d_lut_gate, uint64_t *d_out);
+    size_t aead_gate_pass() const { return (size_t)kOpenGateBlockBytes * ctr_chunk_; }
 
     // ---- multi-key batches on the 1-bit model (the reference has one key).  A key table is
     // [n_keys][4 (nr + 1) * 32][K+1], slot s an expanded (or decryption) key in the layout above.  The bootstraps

@@ -2112,6 +2112,132 @@ void Context::gf128_product_raw(const uint64_t *a, const uint64_t *b, size_t cou
 }
 
 // ---------------------------------------------------------------------------------------------
+// AEAD open: the verdict bit and the verdict-gated payload (aead_open.hpp).  The reference has no AEAD.
+// ---------------------------------------------------------------------------------------------
+AeadOpenNoise aead_open_noise_schedule(const std::vector<NoiseLevel> &plain, const std::vector<NoiseLevel> &diff,
+                                       const VerdictPlan &verdict, const GatePlan &gate, uint64_t max) {
+    const size_t n = verdict.n_frames;
+    if (verdict.levels() < 1 || diff.size() != n * verdict.bits[0] || gate.n_frames != n ||
+        (!plain.empty() && plain.size() != gate.n_bytes() * 8))
+        throw ModelError{TAE_E_ARG, "the bits do not match the plans"};
+    // MaxNoiseLevel::validate on an input of a bootstrap
+    auto input = [max](const NoiseLevel &x) {
+        if (x.noise_level_squared > max)
+            throw ModelError{TAE_E_NOISE, "NoiseTooBig { noise_level: " + std::to_string(x.noise_level_squared) +
+                                              ", max_noise_level: " + std::to_string(max) + " }"};
+    };
+    auto outputs = [](size_t count, uint64_t level) {
+        std::vector<NoiseLevel> o(count);
+        for (auto &x : o) x = NoiseLevel::with_noise_level(level, next_ct_id());
+        return o;
+    };
+    std::vector<NoiseLevel> cur = diff;
+    for (int l = 0; l < verdict.levels(); l++) {
+        for (int32_t s : verdict.idx[l])
+            if (s >= 0) input(cur[(size_t)s]);  // the padding is the trivial zero
+        cur = outputs(n * verdict.groups[l], kOpenOrBits);
+    }
+    AeadOpenNoise out;
+    out.ok = std::move(cur);
+    if (plain.empty()) return out;
+    for (size_t g = 0; g < gate.n_bytes(); g++) {
+        for (int b = 0; b < 8; b++) input(plain[g * 8 + b]);
+        input(out.ok[(size_t)gate.frame_of_byte[g]]);
+    }
+    out.plain = outputs(plain.size(), kOpenGateBits);
+    return out;
+}
+
+const Context::OpenLuts &Context::open_luts() {
+    std::call_once(open_once_, [this] {
+        const AeadOpenTables t = aead_open_tables();
+        open_luts_.or8 = generate_lookup_table(kOpenOrBits, 1, t.or8.data());
+        open_luts_.nor8 = generate_lookup_table(kOpenOrBits, 1, t.nor8.data());
+        open_luts_.gate = generate_lookup_table(kOpenGateBits, 8, t.gate.data());
+    });
+    return open_luts_;
+}
+
+namespace {
+void require_open(const Params &p, int tag_len) {
+    if (p.model != 1) throw ModelError{TAE_E_PARAM, "the AEAD open runs on the 1-bit WoP-PBS parameter sets only"};
+    if (!aead_tag_len_ok(tag_len)) throw ModelError{TAE_E_PARAM, "a tag is 4 .. 16 bytes, and even or 13 or 15"};
+}
+}  // namespace
+
+// the verdicts, and with `gate` the gated payload, in one staging scope; the tables go up with the call
+void Context::open_call(const uint64_t *plain, const GatePlan *gate, const uint64_t *tag_diff, const VerdictPlan &verdict,
+                        uint64_t *out_plain, uint64_t *out_ok, bool device_mem) {
+    const OpenLuts &luts = open_luts();
+    const size_t n = verdict.n_frames, L = bit_len();
+    std::vector<std::vector<int32_t>> gate_idx;
+    if (gate)
+        for (size_t g0 = 0, pass = engine_->aead_gate_pass(); g0 < gate->n_bytes(); g0 += pass)
+            gate_idx.push_back(aead_gate_pass_index(*gate, g0, std::min(pass, gate->n_bytes() - g0)));
+    Staged st(*this, device_mem);
+    st.own_times();
+    const uint64_t *d_diff = st.in(tag_diff, n * verdict.bits[0] * L);
+    uint64_t *d_ok = st.out(out_ok, n * L);
+    std::vector<const int32_t *> d_idx;
+    for (const std::vector<int32_t> &ix : verdict.idx) d_idx.push_back(st.pub(ix.data(), ix.size()));
+    engine_->aead_verdict(d_diff, verdict, d_idx, st.pub(luts.or8.data.data(), luts.or8.data.size()),
+                          st.pub(luts.nor8.data.data(), luts.nor8.data.size()), d_ok);
+    if (gate && gate->n_bytes()) {
+        const size_t len = gate->n_bytes() * 8 * L;
+        std::vector<const int32_t *> d_gidx;
+        for (const std::vector<int32_t> &ix : gate_idx) d_gidx.push_back(st.pub(ix.data(), ix.size()));
+        engine_->aead_gate(st.in(plain, len), *gate, d_gidx, d_ok, st.pub(luts.gate.data.data(), luts.gate.data.size()),
+                           st.out(out_plain, len));
+    }
+    st.finish();
+}
+
+void Context::aead_verdict_raw(const uint64_t *tag_diff, size_t n_frames, int tag_len, uint64_t *ok, bool device_mem) {
+    require_open(params(), tag_len);
+    if (!n_frames) return;
+    const VerdictPlan verdict = aead_verdict_plan(tag_len, n_frames);
+    GatePlan none;
+    none.n_frames = n_frames;
+    const std::vector<NoiseLevel> at_cap(n_frames * verdict.bits[0], NoiseLevel{params().max_noise_sq, {}});
+    aead_open_noise_schedule({}, at_cap, verdict, none, params().max_noise_sq);
+    open_call(nullptr, nullptr, tag_diff, verdict, nullptr, ok, device_mem);
+}
+
+void Context::aead_open_raw(const uint64_t *plain, const size_t *payload_lens, const uint64_t *tag_diff, size_t n_frames,
+                            int tag_len, uint64_t *out_plain, uint64_t *out_ok, bool device_mem) {
+    require_open(params(), tag_len);
+    if (!n_frames) return;
+    const VerdictPlan verdict = aead_verdict_plan(tag_len, n_frames);
+    const GatePlan gate = aead_gate_plan(payload_lens, n_frames);
+    if (gate.n_bytes() && (!plain || !out_plain)) throw ModelError{TAE_E_ARG, "null"};
+    const NoiseLevel cap{params().max_noise_sq, {}};
+    aead_open_noise_schedule(std::vector<NoiseLevel>(gate.n_bytes() * 8, cap),
+                             std::vector<NoiseLevel>(n_frames * verdict.bits[0], cap), verdict, gate, params().max_noise_sq);
+    open_call(plain, &gate, tag_diff, verdict, out_plain, out_ok, device_mem);
+}
+
+Context::OpenBits Context::aead_open(const std::vector<const BitCt *> &plain, const size_t *payload_lens,
+                                     const std::vector<const BitCt *> &tag_diff, size_t n_frames, int tag_len) {
+    require_open(params(), tag_len);
+    if (!n_frames) return {};
+    const size_t L = bit_len();
+    const VerdictPlan verdict = aead_verdict_plan(tag_len, n_frames);
+    const GatePlan gate = aead_gate_plan(payload_lens, n_frames);
+    if (plain.size() != gate.n_bytes() * 8 || tag_diff.size() != n_frames * verdict.bits[0])
+        throw ModelError{TAE_E_ARG, "the bits do not match the payload lengths and the tag length"};
+    std::vector<NoiseLevel> pn(plain.size()), dn(tag_diff.size());
+    for (size_t i = 0; i < plain.size(); i++) pn[i] = plain[i]->noise;
+    for (size_t i = 0; i < tag_diff.size(); i++) dn[i] = tag_diff[i]->noise;
+    // a frame of no payload has no group, and a call of no payload no gate: the schedule then walks the verdict alone
+    AeadOpenNoise on = aead_open_noise_schedule(pn, dn, verdict, gate, params().max_noise_sq);
+    const std::vector<uint64_t> in = gather_bits(plain, L), diff = gather_bits(tag_diff, L);
+    std::vector<uint64_t> out(in.size()), ok(n_frames * L);
+    open_call(in.data(), &gate, diff.data(), verdict, out.data(), ok.data(), false);
+    return {wrap_bits(out, std::move(on.plain), L, params().max_noise_sq),
+            wrap_bits(ok, std::move(on.ok), L, params().max_noise_sq)};
+}
+
+// ---------------------------------------------------------------------------------------------
 // shortint_1bit model (src/tfhe/shortint_1bit.rs)
 // ---------------------------------------------------------------------------------------------
 void Context::require_s1() const {

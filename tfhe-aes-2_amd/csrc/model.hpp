@@ -273,6 +273,24 @@ class Context {  // FheContext
     void gf128_square_raw(const uint64_t *in, size_t count, uint64_t *out, bool device_mem);
     void gf128_product_raw(const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out, bool device_mem);
 
+    // ---- AEAD open: the verdict bit and the verdict-gated payload (aead_open.hpp; the reference has
+    // no AEAD).  Works on what the CCM and GCM calls return: plain [sum payload_lens][8][bit_len], frames in order, and
+    // tag_diff [n_frames][8 tag_len][bit_len].  1-bit WoP-PBS sets only and a tag_len CCM or GCM accepts (TAE_E_PARAM
+    // otherwise); n_frames == 0 is a no-op.  Refusals come before any device work and leave the stage times alone ----
+    struct OpenBits {
+        std::vector<BitCt> plain, ok;  // [sum payload_lens * 8] at level 9, [n_frames] at level 8, fresh ids
+    };
+    // ok [n_frames][bit_len]: 1 iff every difference bit of the frame is 0.  The raw forms replay the schedule for
+    // inputs at the parameter set's cap
+    void aead_verdict_raw(const uint64_t *tag_diff, size_t n_frames, int tag_len, uint64_t *ok, bool device_mem);
+    // out_plain [sum payload_lens][8][bit_len] (not plain): the payload where ok = 1, zeros where ok = 0; payload_lens
+    // is a host array
+    void aead_open_raw(const uint64_t *plain, const size_t *payload_lens, const uint64_t *tag_diff, size_t n_frames,
+                       int tag_len, uint64_t *out_plain, uint64_t *out_ok, bool device_mem);
+    // BitCt variant: replays aead_open_noise_schedule on the inputs' levels (TAE_E_NOISE above the cap)
+    OpenBits aead_open(const std::vector<const BitCt *> &plain, const size_t *payload_lens,
+                       const std::vector<const BitCt *> &tag_diff, size_t n_frames, int tag_len);
+
     // ---- 8-bit model (src/tfhe/shortint_woppbs_8bit.rs, fhe_impls/shortint_woppbs_8bit.rs) ----
     size_t bit_len() const { return params().bit_len(); }
     // FheContext::bootstrap_from_bits over G bytes: bits [G][8][n+1] -> int ciphertexts [G][K+1]
@@ -339,6 +357,15 @@ class Context {  // FheContext
     void gcm_long_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const uint64_t *sk, size_t n_strides,
                        size_t seg, const std::vector<GcmFrame> &frames, const std::vector<GcmFrameIn> &in, int tag_len,
                        int rounds, int nr, size_t key_cts, uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem);
+    // the AEAD open's three tables (or8, nor8, gate), built once per context and kept on the host
+    struct OpenLuts {
+        Lut or8, nor8, gate;
+    };
+    const OpenLuts &open_luts();
+    std::once_flag open_once_;
+    OpenLuts open_luts_;
+    void open_call(const uint64_t *plain, const GatePlan *gate, const uint64_t *tag_diff, const VerdictPlan &verdict,
+                   uint64_t *out_plain, uint64_t *out_ok, bool device_mem);
     void run_aes_ctr(const uint64_t *rk, const uint8_t iv[8], uint64_t first_counter, size_t n_blocks, int rounds,
                      const uint8_t *data, size_t out_bytes, uint64_t *out, bool device_mem, int nr);
     void run_aes_blocks(AesDriver driver, const uint64_t *d_rk, const uint64_t *d_in, size_t n_blocks, int rounds,
@@ -433,6 +460,16 @@ struct GcmLongNoise {
 GcmLongNoise aes_gcm_long_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &hk,
                                          const std::vector<NoiseLevel> &sk, size_t seg, const GcmFrame &frame, int rounds,
                                          uint64_t max_noise_sq, int nr = 10);
+
+// The AEAD open (aead_open.hpp) on metadata: plain [n_bytes * 8] (empty: the verdict alone), diff [n_frames * 8 tag_len].
+// A circuit bootstrap's outputs are at its input bit count with fresh ids (Lemma 3.2), whatever its inputs hold: a
+// verdict-level output is at 8, the padding is trivial, a gated payload bit is at 9 and no output holds a key bit.  Every
+// input of every bootstrap must be at or below the cap: TAE_E_NOISE otherwise.
+struct AeadOpenNoise {
+    std::vector<NoiseLevel> plain, ok;  // [n_bytes * 8], [n_frames]
+};
+AeadOpenNoise aead_open_noise_schedule(const std::vector<NoiseLevel> &plain, const std::vector<NoiseLevel> &diff,
+                                       const VerdictPlan &verdict, const GatePlan &gate, uint64_t max_noise_sq);
 
 // Counter mode on the 1-bit model: output noise [n_blocks][128] of the gal-mul schedule for trivial counter
 // blocks.  rounds >= 2: aes_noise_schedule per block.  rounds == 1: the final SubBytes runs on the plan's

@@ -59,6 +59,8 @@ EXPORTED = [
     "tae_stage_gf128_product",
     "tae_aesx_gcm_long_rows", "tae_aesx_gcm_long_noise_schedule_check", "tae_aesx_ghash_stride_key_raw",
     "tae_aesx_ghash_stride_key", "tae_aesx_gcm_long_transcipher_raw", "tae_aesx_gcm_long_transcipher",
+    "tae_aead_open_plan", "tae_aead_open_noise_schedule_check", "tae_aead_verdict_raw", "tae_aead_open_raw",
+    "tae_aead_open",
     "tae_last_pfks_kernel",
     "tae_packed_len", "tae_encrypt_packed_raw", "tae_decrypt_packed_raw", "tae_packed_narrow", "tae_packed_widen",
     "tae_unpack_bits_raw", "tae_pack_bits_raw", "tae_unpack_bits", "tae_pack_bits", "tae_last_pack_time",
@@ -237,6 +239,11 @@ def lib() -> C.CDLL:
         "tae_aesx_gcm_long_transcipher": ([vp, C.c_int, vp, vp, sz, vp, sz, sz, vp, sz, C.c_int, C.c_int, vp, vp], C.c_int),
         "tae_stage_gf128_square": ([vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_gf128_product": ([vp, vp, vp, sz, vp, C.c_int], C.c_int),
+        "tae_aead_open_plan": ([C.c_int, vp, sz, C.POINTER(C.c_int), vp, C.POINTER(sz)], C.c_int),
+        "tae_aead_open_noise_schedule_check": ([C.c_int, C.c_int, u64, u64], C.c_int),
+        "tae_aead_verdict_raw": ([vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aead_open_raw": ([vp, vp, vp, vp, sz, C.c_int, vp, vp, C.c_int], C.c_int),
+        "tae_aead_open": ([vp, vp, vp, vp, sz, C.c_int, vp, vp], C.c_int),
         "tae_stage_keyswitch": ([vp, vp, sz, vp, C.c_int], C.c_int),
         "tae_stage_pbs_shift_boolean": ([vp, vp, sz, C.c_int, vp, C.c_int], C.c_int),
         "tae_stage_bootstrap": ([vp, vp, sz, vp, vp, C.c_int], C.c_int),

@@ -19,7 +19,7 @@ import numpy as np
 from . import _native as N
 from ._native import check, lib
 from .aes_128 import _flat_bits, _iv8, _iv16
-from .aes_var import KEY_BITS, _bytes_ptr, _key_bits_of_words, _nr, _p, _words, expanded_words
+from .aes_var import KEY_BITS, _bytes_ptr, _key_bits_of_words, _nr, _open_frames, _p, _words, expanded_words
 from .tfhe import BitCt, FheContext, _handles
 
 
@@ -331,3 +331,9 @@ class GalMulAesMulti:
         per = 8 * tag_len
         return [(plain[s], [diff[s * per + 8 * i:s * per + 8 * i + 8] for i in range(tag_len)])
                 for s in range(len(streams))]
+
+    @classmethod
+    def ccm_open(cls, ctx: FheContext, table, streams, tag_len: int, rounds: Optional[int] = None):
+        """ccm_transcipher, then aes_var.aead_open on what it returned -> (per frame the gated bits
+        [len - tag_len][8], per frame ok) BitCt."""
+        return _open_frames(ctx, cls.ccm_transcipher(ctx, table, streams, tag_len, rounds), tag_len)

@@ -516,6 +516,107 @@ def _words(bits: List[BitCt]):
     return [[bits[w * 32 + 8 * b:w * 32 + 8 * b + 8] for b in range(4)] for w in range(len(bits) // 32)]
 
 
+# ---- AEAD open: a tag verdict bit and the verdict-gated payload ----
+# The CCM and GCM calls return payload bits and tag-difference bits and leave the verdict to the client.  The open joins
+# them on the server: per frame one bit ok = 1 iff every difference bit is 0, and a payload that is the plaintext where
+# ok = 1 and all zeros where it is not, so nothing downstream computes on a forged frame's bytes.  One tag_len per call.
+AEAD_TAG_LENGTHS = (4, 6, 8, 10, 12, 13, 14, 15, 16)
+
+
+def aead_open_plan(tag_len: int, payload_lens):
+    """(groups per frame of every verdict level, gate groups) of a call (tae_aead_open_plan), without a device:
+    tag_len 16 -> ((16, 2, 1), sum payload_lens)."""
+    lens = np.ascontiguousarray(payload_lens, dtype=np.uintp).reshape(-1)
+    levels, gate = C.c_int(0), C.c_size_t(0)
+    groups = np.zeros(3, dtype=np.uintp)
+    check(lib().tae_aead_open_plan(tag_len, _p(lens) if len(lens) else None, len(lens), C.byref(levels), _p(groups),
+                                   C.byref(gate)))
+    return tuple(int(g) for g in groups[:levels.value]), gate.value
+
+
+def aead_open_noise_schedule_check(param_set: int, tag_len: int, plain_level: int = 9, diff_level: int = 16) -> None:
+    """The noise bookkeeping of the open for payload bits at plain_level and difference bits at diff_level, without a
+    context or device."""
+    check(lib().tae_aead_open_noise_schedule_check(param_set, tag_len, plain_level, diff_level))
+
+
+def _open_raw_args(ctx: FheContext, plain, tag_diff, tag_len: int):
+    """Per-frame raw arrays -> (payload [sum len][8][L], lens, differences [n][8 tag_len][L])."""
+    L = ctx.lwe_size
+    frames = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 8, L) for p in plain]
+    diff = [np.ascontiguousarray(d, dtype=np.uint64).reshape(-1, L) for d in tag_diff]
+    if len(frames) != len(diff) or any(d.shape[0] != 8 * tag_len for d in diff):
+        raise N.TaeError(N.TAE_E_ARG, "one payload and 8 * tag_len difference bits per frame")
+    lens = np.array([f.shape[0] for f in frames], dtype=np.uintp)
+    flat = np.concatenate(frames) if frames else np.zeros((0, 8, L), dtype=np.uint64)
+    return np.ascontiguousarray(flat), lens, np.ascontiguousarray(np.stack(diff)) if diff else np.zeros((0, 0, L), np.uint64)
+
+
+def aead_verdict_raw(ctx: FheContext, tag_diff, tag_len: int) -> np.ndarray:
+    """Host arrays: per frame [tag_len][8][L] (or one array [n][tag_len][8][L]) -> ok [n][L]."""
+    n = len(tag_diff)
+    diff = np.ascontiguousarray(tag_diff, dtype=np.uint64)
+    if n and diff.size != n * 8 * tag_len * ctx.lwe_size:
+        raise N.TaeError(N.TAE_E_ARG, "8 * tag_len difference bits per frame")
+    ok = np.zeros((n, ctx.lwe_size), dtype=np.uint64)
+    check(lib().tae_aead_verdict_raw(ctx._h, _p(diff), n, tag_len, _p(ok), N.TAE_MEM_HOST))
+    return ok
+
+
+def aead_open_raw(ctx: FheContext, plain, tag_diff, tag_len: int):
+    """Host arrays: per frame the payload [len][8][L] and the differences [tag_len][8][L], as the transcipher calls
+    return them -> (per frame the gated payload [len][8][L], ok [n][L])."""
+    flat, lens, diff = _open_raw_args(ctx, plain, tag_diff, tag_len)
+    out, ok = np.zeros_like(flat), np.zeros((len(lens), ctx.lwe_size), dtype=np.uint64)
+    check(lib().tae_aead_open_raw(ctx._h, _p(flat), _p(lens), _p(diff), len(lens), tag_len, _p(out), _p(ok),
+                                  N.TAE_MEM_HOST))
+    res, at = [], 0
+    for n in lens:
+        res.append(out[at:at + int(n)])
+        at += int(n)
+    return res, ok
+
+
+def aead_open_device(ctx: FheContext, d_plain: int, payload_lens, d_tag_diff: int, tag_len: int, d_out: int, d_ok: int):
+    """Device pointers (ints) for the payload [sum len][8][L], the differences [n][tag_len][8][L], the gated payload
+    and ok [n][L]: what a `*_transcipher_device` call wrote is opened without leaving the card.  payload_lens is host
+    data; d_out is not d_plain."""
+    lens = np.ascontiguousarray(payload_lens, dtype=np.uintp).reshape(-1)
+    check(lib().tae_aead_open_raw(ctx._h, C.c_void_p(d_plain), _p(lens), C.c_void_p(d_tag_diff), len(lens), tag_len,
+                                  C.c_void_p(d_out), C.c_void_p(d_ok), N.TAE_MEM_DEVICE))
+
+
+def aead_open(ctx: FheContext, plain, tag_diff, payload_lens, tag_len: int):
+    """BitCt: per frame the payload [len][8] and the differences [tag_len][8] (nested or flat) -> (per frame the gated
+    payload [len][8] at level 9, per frame ok at level 8).  An input above the cap is NoiseTooBig."""
+    lens = np.ascontiguousarray(payload_lens, dtype=np.uintp).reshape(-1)
+    bits, diff = _flat_bits(plain), _flat_bits(tag_diff)
+    n, total = len(lens), int(lens.sum()) if len(lens) else 0
+    if len(bits) != 8 * total or len(diff) != 8 * tag_len * n:
+        raise N.TaeError(N.TAE_E_ARG, "8 bits per payload byte and 8 * tag_len difference bits per frame")
+    outs, oks = (C.c_void_p * max(8 * total, 1))(), (C.c_void_p * max(n, 1))()
+    check(lib().tae_aead_open(ctx._h, _handles(bits) if bits else None, _p(lens) if n else None,
+                              _handles(diff) if diff else None, n, tag_len, outs, oks))
+    res, at = [], 0
+    for f in range(n):
+        ln = int(lens[f])
+        res.append([[BitCt(outs[8 * (at + i) + j], ctx) for j in range(8)] for i in range(ln)])
+        at += ln
+    return res, [BitCt(oks[f], ctx) for f in range(n)]
+
+
+def open_ok(client_key, ok) -> bool:
+    """The client's reading of one verdict: a BitCt or a raw ciphertext [L] -> True iff it decrypts to 1."""
+    if isinstance(ok, np.ndarray):
+        return bool(int(client_key.decrypt_bits_raw(ok.reshape(1, -1))[0]))
+    return bool(int(client_key.decrypt(ok).value))
+
+
+def _open_frames(ctx: FheContext, res, tag_len: int):
+    """What a BitCt transcipher call returns, [(bits, tag_diff), ..] -> aead_open of it."""
+    return aead_open(ctx, [p for p, _ in res], [d for _, d in res], [len(p) for p, _ in res], tag_len)
+
+
 class GalMulAes:
     """The method set of aes_128.ShortintWoppbs1BitSboxGalMulPbsAesEncrypt for 128-, 192- and 256-bit keys.
     The key size is read from what is passed: `key_schedule*` from the key (16 / 24 / 32 encrypted bytes), every
@@ -1018,3 +1119,25 @@ class GalMulAes:
         out = np.zeros_like(a)
         check(lib().tae_stage_gf128_product(ctx._h, _p(a), _p(b), a.shape[0], _p(out), N.TAE_MEM_HOST))
         return out
+
+    # ---- AEAD open: the transcipher call, then aead_open on what it returned ----
+    @classmethod
+    def ccm_open(cls, ctx: FheContext, ek, nonce: bytes, aad: bytes, data: bytes, tag_len: int,
+                 rounds: Optional[int] = None, key_bits: Optional[int] = None):
+        """ccm_transcipher, then the open -> (gated bits [len - tag_len][8], ok) BitCt."""
+        res = cls.ccm_transcipher(ctx, ek, nonce, aad, data, tag_len, rounds, key_bits)
+        plain, ok = _open_frames(ctx, [res], tag_len)
+        return plain[0], ok[0]
+
+    @classmethod
+    def gcm_open(cls, ctx: FheContext, ek, hk, frames, tag_len: int, rounds: Optional[int] = None,
+                 key_bits: Optional[int] = None):
+        """gcm_transcipher, then the open -> (per frame the gated bits [len - tag_len][8], per frame ok) BitCt."""
+        return _open_frames(ctx, cls.gcm_transcipher(ctx, ek, hk, frames, tag_len, rounds, key_bits), tag_len)
+
+    @classmethod
+    def gcm_long_open(cls, ctx: FheContext, ek, hk, sk, seg: int, frames, tag_len: int, rounds: Optional[int] = None,
+                      key_bits: Optional[int] = None):
+        """gcm_long_transcipher, then the open -> (per frame the gated bits, per frame ok) BitCt."""
+        return _open_frames(ctx, cls.gcm_long_transcipher(ctx, ek, hk, sk, seg, frames, tag_len, rounds, key_bits),
+                            tag_len)
