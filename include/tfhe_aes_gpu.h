@@ -591,6 +591,42 @@ int tae_aesx_gcm_transcipher_raw(const tae_context *ctx, int key_bits, const uin
 int tae_aesx_gcm_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *expanded_key,
                              const tae_bit *const *hk, size_t n_powers, const tae_gcm_frame *frames, size_t n_frames,
                              int tag_len, int rounds, tae_bit **out_plain, tae_bit **out_tag_diff);
+/* ---- GCM over key tables ---------------------------------------------------------------
+ * The two calls above for many AES keys under one FHE key: `table` is a key table [n_keys][W*32][L] as in the
+ * multi-key batches, `htable` the power tables of its slots [n_keys][n_powers][128][L], and every frame names its slot.
+ * tae_aesm_ghash_key* makes all power tables in the launch sequence of one (a generation's squares and products of all
+ * keys share their launches, the products in batches of TAE_GCM_SEG_BATCH); tae_aesm_gcm_transcipher* runs the frames of
+ * all slots through one public pass, one chunk-sum launch that reads `htable` in place, one refresh and one difference
+ * launch.  Slot s of the result, and every frame's words, levels and ids, equal the single-key call on table[s] /
+ * htable[s].  Scope and refusals of the single-key calls; one key size and one tag_len per call.  A slot outside
+ * 0..n_keys-1 and null arrays are TAE_E_ARG.  The frames are validated before the context is looked at.  A slot no
+ * frame names is not read, in either table; with TAE_MEM_HOST only the named slots are uploaded. */
+/* one frame under slot `key` of both tables */
+typedef struct {
+    int32_t key;
+    const uint8_t *iv;
+    size_t iv_len;      /* 12 */
+    const uint8_t *aad; /* may be NULL when aad_len == 0 */
+    size_t aad_len;
+    const uint8_t *data; /* ciphertext || received tag */
+    size_t len;          /* >= tag_len */
+} tae_gcm_stream;
+/* table [n_keys][W*32][L] -> htable [n_keys][n_powers][128][L] */
+int tae_aesm_ghash_key_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys, int n_powers,
+                           int rounds, uint64_t *htable, int mem);
+/* the same on handles: table[n_keys * W*32] -> htable[n_keys * n_powers * 128], every bit at noise^2 = 1 with a
+ * fresh id */
+int tae_aesm_ghash_key(const tae_context *ctx, int key_bits, const tae_bit *const *table, size_t n_keys, int n_powers,
+                       int rounds, tae_bit **htable);
+/* out_plain [sum (len - tag_len)][8][L], frames in order (may be NULL when no frame has a payload); out_tag_diff
+ * [n_streams][8 tag_len][L] */
+int tae_aesm_gcm_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys,
+                                 const uint64_t *htable, size_t n_powers, const tae_gcm_stream *streams, size_t n_streams,
+                                 int tag_len, int rounds, uint64_t *out_plain, uint64_t *out_tag_diff, int mem);
+/* the same on handles; the entries of slots no frame names may be NULL in both tables */
+int tae_aesm_gcm_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *table, size_t n_keys,
+                             const tae_bit *const *htable, size_t n_powers, const tae_gcm_stream *streams,
+                             size_t n_streams, int tag_len, int rounds, tae_bit **out_plain, tae_bit **out_tag_diff);
 /* ---- frames beyond one table: segmented GHASH ------------------------------------------
  * tae_aesx_gcm_transcipher* stops at about 55 hashed blocks.  These calls split GHASH into C = ceil(m / seg) segments
  * of seg hashed blocks.  With e = m + 1 - i the exponent of X_i, c = (e - 1) / seg and k = (e - 1) % seg + 1:

@@ -92,6 +92,17 @@ __global__ void rowsum_kernel(const uint64_t *__restrict__ sources, const int32_
         out[t] = rowsum_word(sources, row_start, src, list_of, base_of, pub_bit, t, L);
 }
 
+// the same over two source arrays (rowsum2_word): consecutive lanes on consecutive coefficients of one output
+// ciphertext, and the array a source lies in is uniform over a row, so every read stays a contiguous run
+__global__ void rowsum2_kernel(const uint64_t *__restrict__ A, size_t n_a, const uint64_t *__restrict__ B,
+                               const int32_t *__restrict__ row_start, const int32_t *__restrict__ src,
+                               const int32_t *__restrict__ list_of, const int32_t *__restrict__ base_of,
+                               const uint8_t *__restrict__ pub_bit, uint64_t *__restrict__ out, size_t n_rows, int L) {
+    const size_t total = n_rows * (size_t)L;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x)
+        out[t] = rowsum2_word(A, n_a, B, row_start, src, list_of, base_of, pub_bit, t, L);
+}
+
 // ---- CCM (aes_ccm.hpp): the round-0 state [n][128][L] of a chain step from the previous cipher output x, the
 // payload ciphertexts in the result buffer and the public bytes; the tag differences after the last step ----
 __global__ void aes_ccm_absorb_kernel(const uint64_t *__restrict__ x, const uint64_t *__restrict__ plain,
@@ -639,6 +650,28 @@ void Engine::rowsum_pass(const uint64_t *d_sources, size_t n_src, RowPlan plan, 
     });
 }
 
+// The same over two source arrays: one launch of rowsum2_kernel, the plan kept alive like rowsum_pass's
+void Engine::rowsum2_pass(const uint64_t *d_a, size_t n_a, const uint64_t *d_b, size_t n_b, RowPlan plan,
+                          uint64_t *d_out) {
+    if (!rowplan2_ok(plan, n_a, n_b)) throw std::runtime_error("row-sum plan: index out of range");
+    if (!plan.n_rows()) return;
+    rowsum_plans_.push_back(std::move(plan));
+    const RowPlan &p = rowsum_plans_.back();
+    auto up = [&](auto &d_buf, const auto &v) {  // an empty array is a null argument
+        return v.empty() ? nullptr : d_buf.upload(v.data(), v.size(), stream_);
+    };
+    const int32_t *rs = up(d_rs_start_, p.row_start), *ix = up(d_rs_src_, p.src);
+    const int32_t *lo = up(d_rs_list_, p.list_of), *bo = up(d_rs_base_, p.base_of);
+    const uint8_t *pb = up(d_rs_pub_, p.pub_bit);
+    const int L = (int)p_.big_len();
+    const size_t n_rows = p.n_rows();
+    timed(ST_LINEAR, [&] {
+        rowsum2_kernel<<<grid_for(n_rows * (size_t)L), kThreads, 0, stream_>>>(d_a, n_a, d_b, rs, ix, lo, bo, pb, d_out,
+                                                                                n_rows, L);
+        HIPC(hipGetLastError());
+    });
+}
+
 // Squares of blocks `blocks` of the source array [n_src / 128][128][L], square s written to outs[s]: one row-sum
 // launch and one identity bootstrap for all of them
 void Engine::gcm_square_pass(const uint64_t *d_src, size_t n_src, const std::vector<size_t> &blocks,
@@ -747,29 +780,68 @@ void Engine::ghash_key(const uint64_t *d_rk, int n_powers, int rounds, int nr, u
     d_gcm_a_.grow(block_len);
     aes_pub_blocks_multi(d_rk, std::vector<PubBlock>{zero}, rounds, d_gcm_a_, nr);  // resets the stage times
     circuit_bootstrap(d_gcm_a_, 128, 1, d_lut_id1_, 1, d_out);
-    gcm_power_generations(d_out, n_powers);
+    gcm_power_generations(d_out, (size_t)n_powers, {0}, n_powers);
     collect_times();
 }
 
-// Power k of the base at entry k - 1: a generation's squares in one launch sequence, its products in another
-void Engine::gcm_power_generations(uint64_t *d_tab, int n) {
+// Power k of a table's base at its entry k - 1: a generation's squares of all tables in one launch sequence, its
+// products in another.  The product scratch grows with the batch, so several tables split a generation's products at
+// gcm_seg_batch_; the bootstraps are per ciphertext, so where a batch ends changes no word.
+void Engine::gcm_power_generations(uint64_t *d_base, size_t n_blocks, const std::vector<size_t> &tabs, int n) {
     const size_t block_len = 128 * p_.big_len();
     for (const GcmGeneration &gen : gcm_power_schedule(n)) {
         std::vector<size_t> blocks;
         std::vector<const uint64_t *> a, b;
         std::vector<uint64_t *> sq_out, pr_out;
-        for (int k : gen.squares) {
-            blocks.push_back((size_t)(k / 2 - 1));
-            sq_out.push_back(d_tab + (size_t)(k - 1) * block_len);
+        for (size_t t0 : tabs) {
+            uint64_t *d_tab = d_base + t0 * block_len;
+            for (int k : gen.squares) {
+                blocks.push_back(t0 + (size_t)(k / 2 - 1));
+                sq_out.push_back(d_tab + (size_t)(k - 1) * block_len);
+            }
+            for (int k : gen.products) {
+                a.push_back(d_tab + (size_t)(k - 2) * block_len);
+                b.push_back(d_tab);
+                pr_out.push_back(d_tab + (size_t)(k - 1) * block_len);
+            }
         }
-        for (int k : gen.products) {
-            a.push_back(d_tab + (size_t)(k - 2) * block_len);
-            b.push_back(d_tab);
-            pr_out.push_back(d_tab + (size_t)(k - 1) * block_len);
+        gcm_square_pass(d_base, n_blocks * 128, blocks, sq_out);
+        const size_t batch = tabs.size() > 1 ? gcm_seg_batch_ : std::max<size_t>(a.size(), 1);
+        for (size_t at = 0; at < a.size(); at += batch) {
+            const size_t end = std::min(a.size(), at + batch);
+            gcm_product_pass({a.begin() + (std::ptrdiff_t)at, a.begin() + (std::ptrdiff_t)end},
+                             {b.begin() + (std::ptrdiff_t)at, b.begin() + (std::ptrdiff_t)end},
+                             {pr_out.begin() + (std::ptrdiff_t)at, pr_out.begin() + (std::ptrdiff_t)end});
         }
-        gcm_square_pass(d_tab, (size_t)n * 128, blocks, sq_out);
-        gcm_product_pass(a, b, pr_out);
     }
+}
+
+// The power tables of a key table.  H of every slot comes out of one public-block batch and one identity bootstrap
+// in slot order; a row copy puts it at entry 0 of the slot's table, and the generations run over all tables.
+void Engine::ghash_key_multi(const uint64_t *d_table, size_t n_keys, int n_powers, int rounds, int nr, uint64_t *d_out) {
+    require_gcm();
+    require_rounds(rounds, nr);
+    if (n_powers < 1 || n_powers > kGcmMaxPowers) throw std::runtime_error("GCM: n_powers must be in 1..=64");
+    if (!gcm_multi_shape_ok(n_keys, (size_t)n_powers, 0)) throw std::runtime_error("GCM: too many keys for one call");
+    if (!n_keys) return;
+    const size_t block_len = 128 * p_.big_len();
+    rowsum_plans_.clear();
+    std::vector<PubBlock> zeros(n_keys);
+    std::vector<size_t> tabs(n_keys);
+    for (size_t s = 0; s < n_keys; s++) {
+        zeros[s] = PubBlock{};
+        zeros[s].slot = (int32_t)s;
+        zeros[s].out_byte = (int64_t)(16 * s);
+        zeros[s].len = 16;
+        tabs[s] = s * (size_t)n_powers;
+    }
+    d_gcm_a_.grow(n_keys * block_len);
+    d_gcm_b_.grow(n_keys * block_len);
+    aes_pub_blocks_multi(d_table, zeros, rounds, d_gcm_a_, nr);  // resets the stage times
+    circuit_bootstrap(d_gcm_a_, n_keys * 128, 1, d_lut_id1_, 1, d_gcm_b_);
+    copy_rows(d_gcm_b_, block_len, d_out, (size_t)n_powers * block_len, n_keys, block_len);
+    gcm_power_generations(d_out, n_keys * (size_t)n_powers, tabs, n_powers);
+    collect_times();
 }
 
 void Engine::ghash_stride_key(const uint64_t *d_hk, size_t n_powers, size_t seg, int n_strides, uint64_t *d_out) {
@@ -781,7 +853,7 @@ void Engine::ghash_stride_key(const uint64_t *d_hk, size_t n_powers, size_t seg,
     times_ = StageTimes{};
     rowsum_plans_.clear();
     HIPC(hipMemcpyAsync(d_out, d_hk + (seg - 1) * block_len, block_len * 8, hipMemcpyDeviceToDevice, stream_));
-    gcm_power_generations(d_out, n_strides);
+    gcm_power_generations(d_out, (size_t)n_strides, {0}, n_strides);
     collect_times();
 }
 
@@ -800,7 +872,8 @@ size_t Engine::gcm_frame_offsets(const std::vector<GcmFrameIn> &frames, std::vec
 }
 
 void Engine::gcm_public_pass(const uint64_t *d_rk, const std::vector<GcmFrameIn> &frames, const std::vector<int64_t> &off,
-                             size_t total, int rounds, int nr, uint64_t *d_out_plain, uint64_t *d_j0) {
+                             size_t total, int rounds, int nr, uint64_t *d_out_plain, uint64_t *d_j0,
+                             const std::vector<int32_t> *slots) {
     const size_t n = frames.size();
     gcm_bytes_.assign(std::max<size_t>(total, 1), 0);
     for (size_t s = 0; s < n; s++)
@@ -814,6 +887,7 @@ void Engine::gcm_public_pass(const uint64_t *d_rk, const std::vector<GcmFrameIn>
         const GcmFrame &f = *frames[s].frame;
         for (size_t i = 1; i < f.n_pub(); i++) {
             PubBlock b{};
+            if (slots) b.slot = (*slots)[s];
             std::memcpy(b.bytes, &f.pub[16 * i], 16);
             const bool j0 = i == 1;
             b.out_byte = j0 ? 0 : off[s] + (int64_t)(16 * (i - 2));
@@ -860,6 +934,55 @@ void Engine::aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, siz
 
     // ---- GHASH + E(J0) + the received tag: chunk sums, one refresh, the differences ----
     rowsum_pass(d_gcm_src_, n_src, std::move(plan.chunks), d_gcm_a_);
+    circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
+    rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
+    collect_times();
+}
+
+// GCM over key tables.  The launches of aes_gcm_transcipher, with the chunk sums on rowsum2_kernel:
+// A is the caller's power tables where they lie, B the kept E(J0) blocks in d_gcm_src_.  Nothing of a table is copied.
+void Engine::aes_gcm_transcipher_multi(const uint64_t *d_table, size_t n_keys, const uint64_t *d_htable, size_t n_powers,
+                                       const std::vector<GcmStreamIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
+                                       uint64_t *d_out_tagdiff) {
+    const size_t n = frames.size();
+    if (!n) return;
+    require_gcm();
+    require_rounds(rounds, nr);
+    if (rounds < 2) throw std::runtime_error("GCM needs rounds >= 2");
+    if (!gcm_multi_shape_ok(n_keys, n_powers, n)) throw std::runtime_error("GCM: n_powers must be in 1..=64");
+    const size_t L = p_.big_len(), block_len = 128 * L;
+    // ---- the plans, before any device work ----
+    std::vector<GcmFrameIn> fin(n);
+    std::vector<int32_t> slots(n);
+    for (size_t s = 0; s < n; s++) {
+        fin[s] = {frames[s].frame, frames[s].data, frames[s].tag};
+        slots[s] = frames[s].slot;
+    }
+    std::vector<int64_t> off;
+    const size_t total = gcm_frame_offsets(fin, off);  // one tag length, whole layouts
+    GcmCallPlan plan;
+    std::vector<std::vector<int32_t>> rows;
+    for (size_t s = 0; s < n; s++) {
+        const GcmFrame &f = *frames[s].frame;
+        gcm_frame_rows(f, rows);
+        switch (gcm_multi_frame_check(f, slots[s], n_keys, n_powers, fin[0].frame->tag_len, rows)) {
+            case GCM_MULTI_OK: break;
+            case GCM_MULTI_SLOT: throw std::runtime_error("GCM frame: key slot outside 0..n_keys-1");
+            default: throw std::runtime_error("GCM frame: more hashed blocks than the power table or the chunk sum takes");
+        }
+        gcm_multi_plan_add(plan, rows, n_keys, n_powers, (size_t)slots[s], s, frames[s].tag);
+    }
+    const size_t n_a = n_keys * n_powers * 128, n_b = n * 128, n_chunks = plan.chunks.n_rows();
+    if (!rowplan2_ok(plan.chunks, n_a, n_b)) throw std::runtime_error("row-sum plan: index out of range");
+    times_ = StageTimes{};
+    rowsum_plans_.clear();
+    d_gcm_src_.grow(n * block_len);
+    d_gcm_a_.grow(n_chunks * L);
+    d_gcm_b_.grow(n_chunks * L);
+    gcm_public_pass(d_table, fin, off, total, rounds, nr, d_out_plain, d_gcm_src_, &slots);
+
+    // ---- GHASH + E(J0) + the received tag: chunk sums over the two arrays, one refresh, the differences ----
+    rowsum2_pass(d_htable, n_a, d_gcm_src_, n_b, std::move(plan.chunks), d_gcm_a_);
     circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
     rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
     collect_times();

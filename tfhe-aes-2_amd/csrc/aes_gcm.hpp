@@ -381,4 +381,37 @@ inline GcmLongStatus gcm_long_frame_check(const GcmFrame &f, size_t seg, size_t 
     return gcm_final_rows_ok(rows) ? GCM_LONG_OK : GCM_LONG_NOISE;
 }
 
+// ---- frames over key tables ----
+// The chunk sums of a call read two source arrays (rowsum2_word): A, the power tables [n_keys][n_powers][128] where
+// the caller keeps them, and B, E(J0) of every frame [n_frames][128].  A frame under slot s has the rows of the
+// single-key call under the base 128 s n_powers, which selects the slot's table; its E(J0) entry is written relative
+// to that base, so base + entry = |A| + 128 frame + r whatever the slot.  The sets summed are the single-key call's.
+enum GcmMultiStatus { GCM_MULTI_OK = 0, GCM_MULTI_SLOT, GCM_MULTI_TAG, GCM_MULTI_POWERS, GCM_MULTI_NOISE, GCM_MULTI_SIZE };
+
+// every index of a call's plans fits an int32_t
+inline bool gcm_multi_shape_ok(size_t n_keys, size_t n_powers, size_t n_frames) {
+    return n_powers >= 1 && n_powers <= (size_t)kGcmMaxPowers && n_keys <= ((size_t)1 << 16) &&
+           n_frames <= ((size_t)1 << 20);  // (2^16 * 64 + 2^20) * 128 < 2^31
+}
+
+// One frame of a call, before any device work: its slot, the call's tag length, then gcm_frame_check on its rows
+inline GcmMultiStatus gcm_multi_frame_check(const GcmFrame &f, int64_t slot, size_t n_keys, size_t n_powers, int tag_len,
+                                            const std::vector<std::vector<int32_t>> &rows) {
+    if (slot < 0 || (uint64_t)slot >= n_keys) return GCM_MULTI_SLOT;
+    if (f.tag_len != tag_len) return GCM_MULTI_TAG;
+    switch (gcm_frame_check(f, n_powers, rows)) {
+        case GCM_PLAN_POWERS: return GCM_MULTI_POWERS;
+        case GCM_PLAN_NOISE: return GCM_MULTI_NOISE;
+        default: return GCM_MULTI_OK;
+    }
+}
+
+// gcm_call_plan_add for frame `frame` under slot `slot`: the same lists, E(J0) at |A| - base + 128 frame + r, and the
+// slot's base on every chunk row the frame adds
+inline void gcm_multi_plan_add(GcmCallPlan &P, const std::vector<std::vector<int32_t>> &rows, size_t n_keys,
+                               size_t n_powers, size_t slot, size_t frame, const uint8_t *tag) {
+    gcm_call_plan_add(P, rows, (n_keys - slot) * n_powers, frame, tag);
+    P.chunks.base_of.resize(P.chunks.n_lists(), (int32_t)(slot * n_powers * 128));
+}
+
 }  // namespace tae

@@ -1238,6 +1238,76 @@ int tae_aesx_gcm_transcipher(const tae_context *ctx, int key_bits, const tae_bit
     });
 }
 
+/* ---- GCM over key tables.  The frames are validated on the host before the context is looked at,
+ * so their refusals need no device ---- */
+extern "C++" {
+namespace {
+std::vector<tae::Context::GcmStreamIn> gcm_streams_in(const tae_gcm_stream *streams, size_t n_streams) {
+    require(streams || !n_streams, "null");
+    std::vector<tae::Context::GcmStreamIn> v(n_streams);
+    for (size_t i = 0; i < n_streams; i++)
+        v[i] = {streams[i].key,
+                {streams[i].iv, streams[i].iv_len, streams[i].aad, streams[i].aad_len, streams[i].data, streams[i].len}};
+    return v;
+}
+}  // namespace
+}  // extern "C++"
+
+int tae_aesm_ghash_key_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys, int n_powers,
+                           int rounds, uint64_t *htable, int mem) {
+    return guarded([&] {
+        require((table && htable) || !n_keys, "null");
+        key_cts(key_bits);
+        require_xts_server(ctx);
+        ctx->ctx->aes_ghash_key_multi_raw(table, n_keys, n_powers, rounds, htable, mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesm_ghash_key(const tae_context *ctx, int key_bits, const tae_bit *const *table, size_t n_keys, int n_powers,
+                       int rounds, tae_bit **htable) {
+    return guarded([&] {
+        require((table && htable) || !n_keys, "null");
+        const size_t kw = key_cts(key_bits);
+        require_xts_server(ctx);
+        if (!n_keys) return;
+        emit(ctx->ctx->aes_ghash_key_multi(unwrap(table, n_keys * kw), n_keys, n_powers, rounds, key_bits), htable);
+    });
+}
+
+int tae_aesm_gcm_transcipher_raw(const tae_context *ctx, int key_bits, const uint64_t *table, size_t n_keys,
+                                 const uint64_t *htable, size_t n_powers, const tae_gcm_stream *streams, size_t n_streams,
+                                 int tag_len, int rounds, uint64_t *out_plain, uint64_t *out_tag_diff, int mem) {
+    return guarded([&] {
+        require((table && htable && out_tag_diff) || !n_streams, "null");
+        key_cts(key_bits);
+        const std::vector<tae::Context::GcmStreamIn> in = gcm_streams_in(streams, n_streams);
+        std::vector<int32_t> slots;
+        tae::gcm_multi_frames(in, n_keys, n_powers, tag_len, slots);
+        require_xts_server(ctx);
+        ctx->ctx->aes_gcm_multi_raw(table, n_keys, htable, n_powers, in, tag_len, rounds, out_plain, out_tag_diff,
+                                    mem == TAE_MEM_DEVICE, key_bits);
+    });
+}
+
+int tae_aesm_gcm_transcipher(const tae_context *ctx, int key_bits, const tae_bit *const *table, size_t n_keys,
+                             const tae_bit *const *htable, size_t n_powers, const tae_gcm_stream *streams,
+                             size_t n_streams, int tag_len, int rounds, tae_bit **out_plain, tae_bit **out_tag_diff) {
+    return guarded([&] {
+        require((table && htable && out_tag_diff) || !n_streams, "null");
+        key_cts(key_bits);
+        const std::vector<tae::Context::GcmStreamIn> in = gcm_streams_in(streams, n_streams);
+        std::vector<int32_t> slots;
+        tae::gcm_multi_frames(in, n_keys, n_powers, tag_len, slots);
+        require_xts_server(ctx);
+        if (!n_streams) return;
+        const tae::Context::GcmBits res = ctx->ctx->aes_gcm_multi(bit_at(table), n_keys, bit_at(htable), n_powers, in,
+                                                                  tag_len, rounds, key_bits);
+        require(out_plain || res.plain.empty(), "null");
+        emit(res.plain, out_plain);
+        emit(res.tag_diff, out_tag_diff);
+    });
+}
+
 /* ---- frames beyond one table: segmented GHASH ---- */
 int tae_aesx_gcm_long_rows(const uint8_t *iv, size_t iv_len, const uint8_t *aad, size_t aad_len, const uint8_t *data,
                            size_t data_len, int tag_len, size_t n_powers, size_t seg, size_t n_strides,

@@ -195,7 +195,7 @@ class Engine {
                              uint64_t *d_out_plain, uint64_t *d_out_tagdiff);
 
     // ---- AES-GCM decryption of public frames on the 1-bit model (aes_gcm.hpp; the reference has no
-    // GCM).  One key per call ----
+    // GCM).  One key per call; key tables further down ----
     // squares of `count` field elements [count][128][K+1]: row sums, then one identity bootstrap (noise^2 = 1)
     void gf128_square(const uint64_t *d_in, size_t count, uint64_t *d_out);
     // products a_c b_c of `count` pairs, a / b / out [count][128][K+1]: the 256 operand bits of a pair are keyswitched
@@ -228,6 +228,27 @@ class Engine {
     void aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers, const uint64_t *d_sk,
                                   size_t n_strides, size_t seg, const std::vector<GcmFrameIn> &frames, int rounds, int nr,
                                   uint64_t *d_out_plain, uint64_t *d_out_tagdiff);
+
+    // ---- GCM over key tables: d_table [n_keys][4 (nr + 1) * 32][K+1] as in the multi-key batches
+    // below, power tables [n_keys][n_powers][128][K+1].  Every output word equals the single-key call's on that slot ----
+    // the power tables of all slots: E_K(0) of every slot in one public-block batch, one identity bootstrap over
+    // n_keys * 128 bits, then every generation of gcm_power_schedule once: its squares of all keys in one
+    // gcm_square_pass, its products of all keys in gcm_product_pass calls of at most gcm_seg_batch_ products
+    void ghash_key_multi(const uint64_t *d_table, size_t n_keys, int n_powers, int rounds, int nr, uint64_t *d_out);
+    // One frame under slot `slot` of both tables
+    struct GcmStreamIn {
+        int32_t slot;
+        const GcmFrame *frame;
+        const uint8_t *data, *tag;
+    };
+    // aes_gcm_transcipher's launches over frames of several slots: one public pass (every block under its frame's slot),
+    // one two-source row-sum launch for all chunks (A = d_htable in place, B = the kept E(J0) blocks; the row base selects
+    // the slot's table), one identity bootstrap, one row-sum launch for the differences.  Refused before any device work,
+    // the stage times untouched: a slot outside 0 .. n_keys - 1, m > n_powers, a row of more than 64 chunks, rounds < 2,
+    // mixed tag lengths.  A slot that no frame names is not read, neither its expanded key nor its power table
+    void aes_gcm_transcipher_multi(const uint64_t *d_table, size_t n_keys, const uint64_t *d_htable, size_t n_powers,
+                                   const std::vector<GcmStreamIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
+                                   uint64_t *d_out_tagdiff);
 
     // ---- AEAD open on the 1-bit model (aead_open.hpp; the reference has no AEAD).  The lookup tables
     // and the index tables are the call's: device arrays of its staging scope ----
@@ -393,6 +414,9 @@ class Engine {
     // call (the uploads are asynchronous) and launches once under ST_LINEAR: -> d_out [n_rows][K+1].  The plan's
     // arrays on the device and the host plans their pending uploads read
     void rowsum_pass(const uint64_t *d_sources, size_t n_src, RowPlan plan, uint64_t *d_out);
+    // the same over two source arrays A [n_a][K+1] and B [n_b][K+1] (rowsum2_word): the plan is validated against
+    // n_a + n_b and kept alive in the same way
+    void rowsum2_pass(const uint64_t *d_a, size_t n_a, const uint64_t *d_b, size_t n_b, RowPlan plan, uint64_t *d_out);
     DevBuf<int32_t> d_rs_start_, d_rs_src_, d_rs_list_, d_rs_base_;
     DevBuf<uint8_t> d_rs_pub_;
     std::deque<RowPlan> rowsum_plans_;
@@ -412,18 +436,22 @@ class Engine {
     DevBuf<uint64_t> d_gcm_src_, d_gcm_a_, d_gcm_b_, d_gcm_ops_, d_gcm_ks_, d_gcm_parts_;
     DevBuf<uint8_t> d_gcm_bytes_;
     std::vector<uint8_t> gcm_bytes_;
-    // segmented GHASH: inner segments per batch (TAE_GCM_SEG_BATCH, 1 .. 64; 16 products are the largest cbs_vp launch
-    // the tests pin)
+    // products per gcm_product_pass (TAE_GCM_SEG_BATCH, 1 .. 64; 16 products are the largest cbs_vp launch the tests
+    // pin).  It bounds the product scratch of both the segmented GHASH (inner segments per batch) and ghash_key_multi
+    // (a generation's products of all keys), at about 0.21 GB a product
     size_t gcm_seg_batch_ = 16;
     void require_gcm() const;
-    // the generations of gcm_power_schedule(n) on the table d_tab [n][128][K+1], whose entry 0 is the base
-    void gcm_power_generations(uint64_t *d_tab, int n);
+    // the generations of gcm_power_schedule(n) on the tables [n][128][K+1] that start at the blocks `tabs` of d_base
+    // [n_blocks][128][K+1], entry 0 of each the base: one square pass and the product passes per generation for all
+    // tables.  Several tables split a generation's products at gcm_seg_batch_; one table runs them in one pass
+    void gcm_power_generations(uint64_t *d_base, size_t n_blocks, const std::vector<size_t> &tabs, int n);
     // the layout checks and payload offsets of a call's frames; returns the payload bytes
     size_t gcm_frame_offsets(const std::vector<GcmFrameIn> &frames, std::vector<int64_t> &off) const;
     // the public blocks of a call: the ciphertext bytes up, the counters into d_out_plain, E(J0) of frame s into block
-    // s of d_j0
+    // s of d_j0.  slots != nullptr: d_rk is a key table and the blocks of frame s run under slot (*slots)[s]
     void gcm_public_pass(const uint64_t *d_rk, const std::vector<GcmFrameIn> &frames, const std::vector<int64_t> &off,
-                         size_t total, int rounds, int nr, uint64_t *d_out_plain, uint64_t *d_j0);
+                         size_t total, int rounds, int nr, uint64_t *d_out_plain, uint64_t *d_j0,
+                         const std::vector<int32_t> *slots = nullptr);
     void gcm_square_pass(const uint64_t *d_src, size_t n_src, const std::vector<size_t> &blocks,
                          const std::vector<uint64_t *> &outs);
     void gcm_product_pass(const std::vector<const uint64_t *> &a, const std::vector<const uint64_t *> &b,

@@ -1991,6 +1991,136 @@ Context::GcmBits Context::aes_gcm(const std::vector<const BitCt *> &expanded_key
     return {wrap_bits(plain, std::move(pn), L, params().max_noise_sq), wrap_bits(tag, std::move(tn), L, params().max_noise_sq)};
 }
 
+// ---- GCM over key tables ----
+std::vector<GcmFrame> gcm_multi_frames(const std::vector<Context::GcmStreamIn> &in, size_t n_keys, size_t n_powers,
+                                       int tag_len, std::vector<int32_t> &slots) {
+    std::vector<Context::GcmFrameIn> fin(in.size());
+    for (size_t s = 0; s < in.size(); s++) fin[s] = in[s].f;
+    std::vector<GcmFrame> frames = gcm_frames(fin, tag_len);
+    slots.resize(in.size());
+    if (in.empty()) return frames;
+    if (!gcm_multi_shape_ok(n_keys, n_powers, in.size()))
+        throw ModelError{TAE_E_PARAM, "n_powers must be in 1..=64, and at most 65536 keys and 1048576 frames a call"};
+    std::vector<std::vector<int32_t>> rows;
+    for (size_t s = 0; s < in.size(); s++) {
+        gcm_frame_rows(frames[s], rows);
+        switch (gcm_multi_frame_check(frames[s], in[s].slot, n_keys, n_powers, tag_len, rows)) {
+            case GCM_MULTI_SLOT: throw ModelError{TAE_E_ARG, "a frame's key slot is outside 0..n_keys-1"};
+            case GCM_MULTI_POWERS:
+                throw ModelError{TAE_E_PARAM, "the frame has more hashed blocks than the power table has powers"};
+            case GCM_MULTI_NOISE: throw ModelError{TAE_E_NOISE, "a tag row needs more than 64 refreshed chunks"};
+            case GCM_MULTI_TAG: throw ModelError{TAE_E_PARAM, "the frames of a call have one tag length"};
+            default: break;
+        }
+        slots[s] = in[s].slot;
+    }
+    return frames;
+}
+
+void Context::aes_ghash_key_multi_raw(const uint64_t *table, size_t n_keys, int n_powers, int rounds, uint64_t *out,
+                                      bool device_mem, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    require_powers(n_powers);
+    if (!n_keys) return;
+    if (!gcm_multi_shape_ok(n_keys, (size_t)n_powers, 0)) throw ModelError{TAE_E_PARAM, "at most 65536 keys a call"};
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    // the single-key schedule: batching keys mixes no ciphertexts of different keys
+    aes_ghash_key_noise_schedule(fresh_levels(kw), n_powers, rounds, params().max_noise_sq, nr);
+    Staged st(*this, device_mem);
+    engine_->ghash_key_multi(st.in(table, n_keys * kw * bit_len()), n_keys, n_powers, rounds, nr,
+                             st.out(out, n_keys * (size_t)n_powers * 128 * bit_len()));
+    st.finish();
+}
+
+std::vector<BitCt> Context::aes_ghash_key_multi(const std::vector<const BitCt *> &table, size_t n_keys, int n_powers,
+                                                int rounds, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    require_powers(n_powers);
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
+    if (table.size() != n_keys * kw) throw ModelError{TAE_E_ARG, "the key table is n_keys expanded keys"};
+    if (!n_keys) return {};
+    if (!gcm_multi_shape_ok(n_keys, (size_t)n_powers, 0)) throw ModelError{TAE_E_PARAM, "at most 65536 keys a call"};
+    const std::vector<uint64_t> tab = gather_bits(table, L);
+    std::vector<NoiseLevel> noise;  // the single-key bookkeeping, slot by slot
+    noise.reserve(n_keys * (size_t)n_powers * 128);
+    for (size_t s = 0; s < n_keys; s++) {
+        std::vector<NoiseLevel> krk(kw);
+        for (size_t i = 0; i < kw; i++) krk[i] = table[s * kw + i]->noise;
+        GhashKeyNoise kn = aes_ghash_key_noise_schedule(krk, n_powers, rounds, params().max_noise_sq, nr);
+        for (NoiseLevel &x : kn.table) noise.push_back(std::move(x));
+    }
+    std::vector<uint64_t> hk(noise.size() * L);
+    {
+        Staged st(*this, false);
+        engine_->ghash_key_multi(st.in(tab.data(), tab.size()), n_keys, n_powers, rounds, nr, st.out(hk.data(), hk.size()));
+        st.finish();
+    }
+    return wrap_bits(hk, std::move(noise), L, params().max_noise_sq);
+}
+
+// the frames of a call over key tables through the engine; host memory uploads the named slots of both tables alone,
+// renumbered alike
+void Context::gcm_multi_call(const uint64_t *table, size_t n_keys, const uint64_t *htable, size_t n_powers,
+                             std::vector<int32_t> slots, const std::vector<GcmFrame> &frames,
+                             const std::vector<GcmStreamIn> &in, int tag_len, int rounds, int nr, size_t key_cts,
+                             uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem) {
+    const size_t n = frames.size(), S = bit_len();
+    size_t total = 0;
+    for (const GcmFrame &f : frames) total += f.data_len;
+    Staged st(*this, device_mem);
+    std::vector<int32_t> hslots = slots;
+    const uint64_t *d_tab = st.table(table, slots, key_cts * S), *d_htab = st.table(htable, hslots, n_powers * 128 * S);
+    if (!device_mem) n_keys = (size_t)*std::max_element(slots.begin(), slots.end()) + 1;
+    std::vector<Engine::GcmStreamIn> ein(n);
+    for (size_t s = 0; s < n; s++) ein[s] = {slots[s], &frames[s], in[s].f.data, in[s].f.data + frames[s].data_len};
+    uint64_t *d_plain = st.out(out_plain, total * 8 * S), *d_tag = st.out(out_tag_diff, n * 8 * (size_t)tag_len * S);
+    engine_->aes_gcm_transcipher_multi(d_tab, n_keys, d_htab, n_powers, ein, rounds, nr, d_plain, d_tag);
+    st.finish();
+}
+
+void Context::aes_gcm_multi_raw(const uint64_t *table, size_t n_keys, const uint64_t *htable, size_t n_powers,
+                                const std::vector<GcmStreamIn> &in, int tag_len, int rounds, uint64_t *out_plain,
+                                uint64_t *out_tag_diff, bool device_mem, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    require_gcm_rounds(rounds);
+    if (!n_powers) throw ModelError{TAE_E_PARAM, "the power table is empty"};
+    std::vector<int32_t> slots;
+    const std::vector<GcmFrame> frames = gcm_multi_frames(in, n_keys, n_powers, tag_len, slots);
+    if (frames.empty()) return;
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    const std::vector<NoiseLevel> krk = fresh_levels(kw), khk = fresh_levels(n_powers * 128);
+    for (const GcmFrame &f : frames) aes_gcm_noise_schedule(krk, khk, f, rounds, params().max_noise_sq, nr);
+    gcm_multi_call(table, n_keys, htable, n_powers, slots, frames, in, tag_len, rounds, nr, kw, out_plain, out_tag_diff,
+                   device_mem);
+}
+
+Context::GcmBits Context::aes_gcm_multi(const BitAt &table, size_t n_keys, const BitAt &htable, size_t n_powers,
+                                        const std::vector<GcmStreamIn> &in, int tag_len, int rounds, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    require_gcm_rounds(rounds);
+    if (!n_powers) throw ModelError{TAE_E_PARAM, "the power table is empty"};
+    std::vector<int32_t> slots;
+    const std::vector<GcmFrame> frames = gcm_multi_frames(in, n_keys, n_powers, tag_len, slots);
+    if (frames.empty()) return {};
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len(), n = frames.size();
+    std::vector<std::vector<NoiseLevel>> knoise, hnoise;
+    std::vector<int32_t> hslots = slots;
+    const std::vector<uint64_t> tab = gather_slots(table, slots, kw, L, knoise);
+    const std::vector<uint64_t> htab = gather_slots(htable, hslots, n_powers * 128, L, hnoise);
+    std::vector<NoiseLevel> pn, tn;
+    for (size_t s = 0; s < n; s++) {
+        GcmNoise gn = aes_gcm_noise_schedule(knoise[(size_t)slots[s]], hnoise[(size_t)slots[s]], frames[s], rounds,
+                                             params().max_noise_sq, nr);
+        for (NoiseLevel &x : gn.plain) pn.push_back(std::move(x));
+        for (NoiseLevel &x : gn.tag_diff) tn.push_back(std::move(x));
+    }
+    std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
+    gcm_multi_call(tab.data(), knoise.size(), htab.data(), n_powers, slots, frames, in, tag_len, rounds, nr, kw,
+                   plain.data(), tag.data(), false);
+    // xor with a public bit adds no noise
+    return {wrap_bits(plain, std::move(pn), L, params().max_noise_sq), wrap_bits(tag, std::move(tn), L, params().max_noise_sq)};
+}
+
 // ---- frames beyond one table: segmented GHASH ----
 void Context::aes_ghash_stride_key_raw(const uint64_t *hk, size_t n_powers, size_t seg, int n_strides, uint64_t *out,
                                        bool device_mem) {

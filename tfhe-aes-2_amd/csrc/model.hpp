@@ -269,6 +269,25 @@ class Context {  // FheContext
     GcmBits aes_gcm_long(const std::vector<const BitCt *> &expanded_key, const std::vector<const BitCt *> &hk,
                          const std::vector<const BitCt *> &sk, size_t seg, const std::vector<GcmFrameIn> &frames,
                          int tag_len, int rounds, int key_bits);
+    // ---- GCM over key tables: the calls above with a key table [n_keys][W*32][bit_len] and the power
+    // tables [n_keys][n_powers][128][bit_len] of its slots.  The scope and the refusals of the single-key calls; a slot
+    // outside 0..n_keys-1 is TAE_E_ARG, a slot no frame names is not read (neither table), and host memory uploads the
+    // named slots alone.  Every output word, level and id is the single-key call's on that slot ----
+    struct GcmStreamIn {
+        int32_t slot;
+        GcmFrameIn f;
+    };
+    void aes_ghash_key_multi_raw(const uint64_t *table, size_t n_keys, int n_powers, int rounds, uint64_t *out,
+                                 bool device_mem, int key_bits);
+    // BitCt variant: aes_ghash_key_noise_schedule per slot; table [n_keys * W*32]
+    std::vector<BitCt> aes_ghash_key_multi(const std::vector<const BitCt *> &table, size_t n_keys, int n_powers, int rounds,
+                                           int key_bits);
+    void aes_gcm_multi_raw(const uint64_t *table, size_t n_keys, const uint64_t *htable, size_t n_powers,
+                           const std::vector<GcmStreamIn> &frames, int tag_len, int rounds, uint64_t *out_plain,
+                           uint64_t *out_tag_diff, bool device_mem, int key_bits);
+    // BitCt variant: aes_gcm_noise_schedule per frame on its slot's key and table
+    GcmBits aes_gcm_multi(const BitAt &table, size_t n_keys, const BitAt &htable, size_t n_powers,
+                          const std::vector<GcmStreamIn> &frames, int tag_len, int rounds, int key_bits);
     // stage calls, no noise rule: squares / products of `count` field elements [count][128][bit_len]
     void gf128_square_raw(const uint64_t *in, size_t count, uint64_t *out, bool device_mem);
     void gf128_product_raw(const uint64_t *a, const uint64_t *b, size_t count, uint64_t *out, bool device_mem);
@@ -354,6 +373,10 @@ class Context {  // FheContext
     void gcm_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrame> &frames,
                   const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int nr, size_t key_cts, uint64_t *out_plain,
                   uint64_t *out_tag_diff, bool device_mem);
+    void gcm_multi_call(const uint64_t *table, size_t n_keys, const uint64_t *htable, size_t n_powers,
+                        std::vector<int32_t> slots, const std::vector<GcmFrame> &frames, const std::vector<GcmStreamIn> &in,
+                        int tag_len, int rounds, int nr, size_t key_cts, uint64_t *out_plain, uint64_t *out_tag_diff,
+                        bool device_mem);
     void gcm_long_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const uint64_t *sk, size_t n_strides,
                        size_t seg, const std::vector<GcmFrame> &frames, const std::vector<GcmFrameIn> &in, int tag_len,
                        int rounds, int nr, size_t key_cts, uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem);
@@ -440,6 +463,11 @@ struct GcmNoise {
     std::vector<NoiseLevel> plain, tag_diff;  // [data_len * 8], [8 tag_len]
     uint64_t max_chunk = 0;
 };
+// The frames of a call over key tables, host only and before any device work: the format refusals of the single-key
+// call (TAE_E_PARAM), a slot outside 0..n_keys-1 (TAE_E_ARG), more hashed blocks than n_powers (TAE_E_PARAM), a row
+// beyond 64 chunks (TAE_E_NOISE).  Returns the frames and writes their slots
+std::vector<GcmFrame> gcm_multi_frames(const std::vector<Context::GcmStreamIn> &in, size_t n_keys, size_t n_powers,
+                                       int tag_len, std::vector<int32_t> &slots);
 GcmNoise aes_gcm_noise_schedule(const std::vector<NoiseLevel> &rk, const std::vector<NoiseLevel> &hk, const GcmFrame &frame,
                                 int rounds, uint64_t max_noise_sq, int nr = 10);
 // Segmented GHASH.  The stride key of the table hk [n_powers * 128]: entry 0 keeps the levels and ids

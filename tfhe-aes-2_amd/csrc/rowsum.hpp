@@ -1,7 +1,8 @@
 // LWE row sums: output ciphertext r = the u64 sum of listed source ciphertexts (+ a public bit).  The one linear
 // layer XTS's tweak masks (aes_xts.hpp) and GCM's squares, products and tag rows (aes_gcm.hpp) share (DESIGN.md
 // 5.15).  Host/device in the style of aes_linear.hpp: the device kernel (rowsum_kernel in aes_engine.hip) is a
-// grid-stride loop around rowsum_word, so a host program runs the same arithmetic (tests/native/rowsum_test.cpp).
+// grid-stride loop around rowsum_word, so a host program runs the same arithmetic (tests/native/rowsum_test.cpp);
+// rowsum2_word / rowsum2_kernel are the same over two source arrays (tests/native/rowsum2_test.cpp).
 //
 // The lists are CSR: list l is src[row_start[l] .. row_start[l + 1]) into one source array [n_src][L]; their widths
 // range from 0 to 64, so no table padded to the largest.  Nullable per-output-row arrays, as aes_linear.hpp's:
@@ -87,6 +88,33 @@ TAE_ROWSUM_HD uint64_t rowsum_word(const uint64_t *sources, const int32_t *row_s
 inline uint64_t rowsum_word(const uint64_t *sources, const RowPlan &p, size_t t, int L) {
     return rowsum_word(sources, p.row_start.data(), rowplan_ptr(p.src), rowplan_ptr(p.list_of), rowplan_ptr(p.base_of),
                        rowplan_ptr(p.pub_bit), t, L);
+}
+
+// ---- two source arrays: A [n_a][L] and B [n_b][L] read as one array of n_a + n_b sources without
+// being one allocation.  The effective index base_of[row] + src[q] reads A below n_a and B at index - n_a from there
+// on.  GCM over key tables sums bits of a caller's power tables (A, read in place) and bits of the call's kept E(J0)
+// blocks (B): no table block is staged next to them. ----
+inline bool rowplan2_ok(const RowPlan &p, size_t n_a, size_t n_b) { return rowplan_ok(p, n_a + n_b); }
+
+// Word t of the row sums over the two arrays.  Which array a source lies in depends on the row and the list entry
+// alone, so the choice is uniform over the L words of a row and every read is a contiguous run of L words.
+TAE_ROWSUM_HD uint64_t rowsum2_word(const uint64_t *A, size_t n_a, const uint64_t *B, const int32_t *row_start,
+                                    const int32_t *src, const int32_t *list_of, const int32_t *base_of,
+                                    const uint8_t *pub_bit, size_t t, int L) {
+    const size_t coef = t % L, row = t / L, list = list_of ? (size_t)list_of[row] : row;
+    const size_t base = base_of ? (size_t)base_of[row] : 0;
+    uint64_t acc = 0;
+    for (int32_t q = row_start[list]; q < row_start[list + 1]; q++) {
+        const size_t s = base + (size_t)src[q];
+        acc += s < n_a ? A[s * L + coef] : B[(s - n_a) * L + coef];
+    }
+    if (pub_bit && coef == (size_t)L - 1) acc += (uint64_t)pub_bit[row] << 63;
+    return acc;
+}
+
+inline uint64_t rowsum2_word(const uint64_t *A, size_t n_a, const uint64_t *B, const RowPlan &p, size_t t, int L) {
+    return rowsum2_word(A, n_a, B, p.row_start.data(), rowplan_ptr(p.src), rowplan_ptr(p.list_of),
+                        rowplan_ptr(p.base_of), rowplan_ptr(p.pub_bit), t, L);
 }
 
 }  // namespace tae

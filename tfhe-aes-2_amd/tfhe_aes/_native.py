@@ -59,6 +59,7 @@ EXPORTED = [
     "tae_stage_gf128_product",
     "tae_aesx_gcm_long_rows", "tae_aesx_gcm_long_noise_schedule_check", "tae_aesx_ghash_stride_key_raw",
     "tae_aesx_ghash_stride_key", "tae_aesx_gcm_long_transcipher_raw", "tae_aesx_gcm_long_transcipher",
+    "tae_aesm_ghash_key_raw", "tae_aesm_ghash_key", "tae_aesm_gcm_transcipher_raw", "tae_aesm_gcm_transcipher",
     "tae_aead_open_plan", "tae_aead_open_noise_schedule_check", "tae_aead_verdict_raw", "tae_aead_open_raw",
     "tae_aead_open",
     "tae_last_pfks_kernel",
@@ -106,6 +107,12 @@ class TaeGcmFrame(C.Structure):
     """tae_gcm_frame: one GCM frame of a call."""
     _fields_ = [("iv", C.c_void_p), ("iv_len", C.c_size_t), ("aad", C.c_void_p), ("aad_len", C.c_size_t),
                 ("data", C.c_void_p), ("len", C.c_size_t)]
+
+
+class TaeGcmStream(C.Structure):
+    """tae_gcm_stream: one GCM frame of a call over key tables."""
+    _fields_ = [("key", C.c_int32), ("iv", C.c_void_p), ("iv_len", C.c_size_t), ("aad", C.c_void_p),
+                ("aad_len", C.c_size_t), ("data", C.c_void_p), ("len", C.c_size_t)]
 
 
 class TaeError(RuntimeError):
@@ -230,6 +237,10 @@ def lib() -> C.CDLL:
         "tae_aesx_ghash_key": ([vp, C.c_int, vp, C.c_int, C.c_int, vp], C.c_int),
         "tae_aesx_gcm_transcipher_raw": ([vp, C.c_int, vp, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp, C.c_int], C.c_int),
         "tae_aesx_gcm_transcipher": ([vp, C.c_int, vp, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp], C.c_int),
+        "tae_aesm_ghash_key_raw": ([vp, C.c_int, vp, sz, C.c_int, C.c_int, vp, C.c_int], C.c_int),
+        "tae_aesm_ghash_key": ([vp, C.c_int, vp, sz, C.c_int, C.c_int, vp], C.c_int),
+        "tae_aesm_gcm_transcipher_raw": ([vp, C.c_int, vp, sz, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp, C.c_int], C.c_int),
+        "tae_aesm_gcm_transcipher": ([vp, C.c_int, vp, sz, vp, sz, vp, sz, C.c_int, C.c_int, vp, vp], C.c_int),
         "tae_aesx_gcm_long_rows": ([vp, sz, vp, sz, vp, sz, C.c_int, sz, sz, sz, vp, vp], C.c_int),
         "tae_aesx_gcm_long_noise_schedule_check": ([C.c_int, C.c_int, C.c_int, C.c_int, sz, C.c_int, sz, sz], C.c_int),
         "tae_aesx_ghash_stride_key_raw": ([vp, vp, sz, sz, C.c_int, vp, C.c_int], C.c_int),

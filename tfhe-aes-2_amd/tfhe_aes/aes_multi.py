@@ -1,4 +1,4 @@
-"""Multi-key batches: key expansion, cipher, counter mode and CBC across many AES keys under one FHE key.
+"""Multi-key batches: key expansion, cipher, counter mode, CBC, CCM and GCM across many AES keys under one FHE key.
 
 A key table is `n_keys` expanded keys (or decryption keys) of one key size, `[n_keys][W*32][L]` with W = 44 / 52 /
 60.  Slot `s` is an expanded key in the layout of `aes_var`, so `table[s]` can be passed to any `GalMulAes` method
@@ -112,6 +112,44 @@ def _ccm_streams(streams, tag_len: int):
     return arr, keep, lens
 
 
+def _gcm_streams(streams, tag_len: int):
+    """(slot, iv12, aad, data) -> tae_gcm_stream array, the buffers it points into, and the payload lengths."""
+    arr = (N.TaeGcmStream * max(len(streams), 1))()
+    keep, lens = [], []
+    for i, (slot, iv, aad, data) in enumerate(streams):
+        (ib, i_ptr), (ab, a_ptr), (db, d_ptr) = _bytes_ptr(iv), _bytes_ptr(aad), _bytes_ptr(data)
+        keep += [ib, ab, db]
+        arr[i].key = slot
+        arr[i].iv, arr[i].iv_len = (i_ptr.value if i_ptr else None), len(ib)
+        arr[i].aad, arr[i].aad_len = (a_ptr.value if a_ptr else None), len(ab)
+        arr[i].data, arr[i].len = (d_ptr.value if d_ptr else None), len(db)
+        lens.append(max(len(db) - tag_len, 0))
+    return arr, keep, lens
+
+
+def _raw_htable(htable: np.ndarray, n_keys: int) -> np.ndarray:
+    htable = np.ascontiguousarray(htable, dtype=np.uint64)
+    if htable.ndim != 4 or htable.shape[0] != n_keys or htable.shape[2] != 128:
+        raise N.TaeError(N.TAE_E_ARG, "the power tables are an array [n_keys][n_powers][128][L]")
+    return htable
+
+
+def _bit_htable(htable, n_keys: int):
+    """Per-slot power tables of handles ([n_powers * 128] BitCt, nested or flat; None for a slot that is not used)
+    -> the flat handle array and n_powers."""
+    slots = [None if t is None else _flat_bits(t) for t in htable]
+    sizes = {len(t) for t in slots if t is not None}
+    if len(slots) != n_keys or len(sizes) != 1 or next(iter(sizes)) % 128:
+        raise N.TaeError(N.TAE_E_ARG, "one power table per slot of the key table, all of one size")
+    n = next(iter(sizes))
+    arr = (C.c_void_p * (n * len(slots)))()
+    for s, t in enumerate(slots):
+        if t is not None:
+            for i, b in enumerate(t):
+                arr[s * n + i] = b._h.value
+    return arr, n // 128
+
+
 def _split(out, lens):
     res, at = [], 0
     for n in lens:
@@ -124,7 +162,8 @@ class GalMulAesMulti:
     """aes_var.GalMulAes over a key table.  The key size is read from the table (or, for `key_schedule*`, from the
     keys); the `_device` variants take pointers and therefore `key_bits` and `n_keys`.  `rounds` defaults to Nr.
     Counter-mode streams are `(slot, iv, first_counter, data)` tuples, or `(slot, iv, first_counter, None, length)`
-    for the keystream; CBC streams are `(slot, iv16, data)`.  The stream methods return one result per stream."""
+    for the keystream; CBC streams are `(slot, iv16, data)`, CCM frames `(slot, nonce, aad, data)` and GCM frames
+    `(slot, iv12, aad, data)`.  The stream methods return one result per stream."""
 
     # ---- key expansion (FIPS-197 5.2), all keys in one pass ----
     @staticmethod
@@ -337,3 +376,80 @@ class GalMulAesMulti:
         """ccm_transcipher, then aes_var.aead_open on what it returned -> (per frame the gated bits
         [len - tag_len][8], per frame ok) BitCt."""
         return _open_frames(ctx, cls.ccm_transcipher(ctx, table, streams, tag_len, rounds), tag_len)
+
+    # ---- AES-GCM decryption of public frames over key tables (SP 800-38D; DESIGN.md 5.19) ----
+    # Frames are (slot, iv12, aad, data) with data = ciphertext || received tag, one tag_len for the call.  The power
+    # tables are [n_keys][n_powers][128][L]: slot s is what aes_var.GalMulAes.ghash_key* gives on table[s].
+    @staticmethod
+    def ghash_key_raw(ctx: FheContext, table: np.ndarray, n_powers: int, rounds: Optional[int] = None) -> np.ndarray:
+        """Host arrays: table [n_keys][W*32][L] -> htable [n_keys][n_powers][128][L]."""
+        table, kb = _raw_table(table)
+        out = np.zeros((table.shape[0], max(n_powers, 1), 128, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesm_ghash_key_raw(ctx._h, kb, _p(table), table.shape[0], n_powers, _nr(kb, rounds), _p(out),
+                                           N.TAE_MEM_HOST))
+        return out[:, :max(n_powers, 0)]
+
+    @staticmethod
+    def ghash_key_device(ctx: FheContext, key_bits: int, d_table: int, n_keys: int, n_powers: int, rounds: int,
+                         d_htable: int):
+        check(lib().tae_aesm_ghash_key_raw(ctx._h, key_bits, C.c_void_p(d_table), n_keys, n_powers, rounds,
+                                           C.c_void_p(d_htable), N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def ghash_key(ctx: FheContext, table, n_powers: int, rounds: Optional[int] = None) -> list:
+        """table: a list of expanded keys ([W][4][8] BitCt, every slot present) -> per slot [n_powers * 128] BitCt."""
+        arr_t, n_keys, kb = _bit_table(table)
+        if any(k is None for k in table):
+            raise N.TaeError(N.TAE_E_ARG, "ghash_key reads every slot of the key table")
+        per = 128 * max(n_powers, 0)
+        outs = (C.c_void_p * max(per * n_keys, 1))()
+        check(lib().tae_aesm_ghash_key(ctx._h, kb, arr_t, n_keys, n_powers, _nr(kb, rounds), outs))
+        return [[BitCt(outs[s * per + i], ctx) for i in range(per)] for s in range(n_keys)]
+
+    @staticmethod
+    def gcm_transcipher_raw(ctx: FheContext, table: np.ndarray, htable: np.ndarray, streams, tag_len: int,
+                            rounds: Optional[int] = None) -> list:
+        """Host arrays: per frame (bits [len - tag_len][8][L], tag_diff [tag_len][8][L]), in the caller's order."""
+        table, kb = _raw_table(table)
+        htable = _raw_htable(htable, table.shape[0])
+        arr, _keep, lens = _gcm_streams(streams, tag_len)
+        out = np.zeros((sum(lens), 8, ctx.lwe_size), dtype=np.uint64)
+        diff = np.zeros((len(streams), max(tag_len, 0), 8, ctx.lwe_size), dtype=np.uint64)
+        check(lib().tae_aesm_gcm_transcipher_raw(ctx._h, kb, _p(table), table.shape[0], _p(htable), htable.shape[1], arr,
+                                                 len(streams), tag_len, _nr(kb, rounds), _p(out), _p(diff),
+                                                 N.TAE_MEM_HOST))
+        return list(zip(_split(out, lens), diff))
+
+    @staticmethod
+    def gcm_transcipher_device(ctx: FheContext, key_bits: int, d_table: int, n_keys: int, d_htable: int, n_powers: int,
+                               streams, tag_len: int, rounds: int, d_out: int, d_tag_diff: int):
+        """Device pointers (ints) for both tables, the payload bits [sum (len - tag_len)][8][L] and the tag differences
+        [n_streams][tag_len][8][L]; the frames are host data.  The power tables are read where they lie."""
+        arr, _keep, _ = _gcm_streams(streams, tag_len)
+        check(lib().tae_aesm_gcm_transcipher_raw(ctx._h, key_bits, C.c_void_p(d_table), n_keys, C.c_void_p(d_htable),
+                                                 n_powers, arr, len(streams), tag_len, rounds, C.c_void_p(d_out),
+                                                 C.c_void_p(d_tag_diff), N.TAE_MEM_DEVICE))
+
+    @staticmethod
+    def gcm_transcipher(ctx: FheContext, table, htable, streams, tag_len: int, rounds: Optional[int] = None) -> list:
+        """table / htable: lists of expanded keys and of power tables (ghash_key), None for a slot no frame uses ->
+        per frame (bits [len - tag_len][8], tag_diff [tag_len][8]) BitCt."""
+        arr_t, n_keys, kb = _bit_table(table)
+        arr_h, n_powers = _bit_htable(htable, n_keys)
+        arr, _keep, lens = _gcm_streams(streams, tag_len)
+        outs = (C.c_void_p * max(8 * sum(lens), 1))()
+        tags = (C.c_void_p * max(8 * tag_len * len(streams), 1))()
+        check(lib().tae_aesm_gcm_transcipher(ctx._h, kb, arr_t, n_keys, arr_h, n_powers, arr, len(streams), tag_len,
+                                             _nr(kb, rounds), outs, tags))
+        bits = [BitCt(outs[i], ctx) for i in range(8 * sum(lens))]
+        diff = [BitCt(tags[i], ctx) for i in range(8 * tag_len * len(streams))]
+        plain = _split([bits[8 * i:8 * i + 8] for i in range(sum(lens))], lens)
+        per = 8 * tag_len
+        return [(plain[s], [diff[s * per + 8 * i:s * per + 8 * i + 8] for i in range(tag_len)])
+                for s in range(len(streams))]
+
+    @classmethod
+    def gcm_open(cls, ctx: FheContext, table, htable, streams, tag_len: int, rounds: Optional[int] = None):
+        """gcm_transcipher, then aes_var.aead_open on what it returned -> (per frame the gated bits
+        [len - tag_len][8], per frame ok) BitCt."""
+        return _open_frames(ctx, cls.gcm_transcipher(ctx, table, htable, streams, tag_len, rounds), tag_len)
