@@ -3,11 +3,13 @@
 // additions rowsum_word does and a refresh is the identity on the bit.  The whole plan (inner chunk sums, refresh, row
 // sums, refresh, the product by gcm_mul, the final chunk sums, refresh, the differences) must give
 // E(J0) ^ GHASH ^ tag with GHASH by Horner's rule; the stride schedule must give H^(seg j); at C = 1 the plan is the
-// single-table plan, array for array; and the refusals.  Built and run by tests/test_aes_gcm_long.py, also under
+// single-table plan, array for array; the plans of m = 5 at seg = 2 over the table and the E(J0) / product blocks in
+// separate exact allocations; and the refusals.  Built and run by tests/test_aes_gcm_long.py, also under
 // -fsanitize=address,undefined.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <set>
 #include <vector>
 
@@ -140,6 +142,43 @@ static void whole_plan(size_t seg, size_t m, const GcmElem &H, const GcmElem &EJ
     }
 }
 
+// The plans of one frame as the engine reads them: A is the table's first table_blocks blocks where the
+// caller keeps them, B is E(J0) followed by the products, each a heap allocation of exactly its size, so the sanitized
+// build reports an index past either end.  The inner chunk sums read A alone, the final ones A and B (rowsum2_word).
+static void split_plan(size_t seg, size_t m, const GcmElem &H, const GcmElem &EJ0) {
+    const GcmFrame f = frame_of(m, 0x00, true);
+    const size_t C = gcm_long_segments(m, seg), tb = seg < m ? seg : m, n_a = tb * 128, n_b = C * 128;
+    std::unique_ptr<uint64_t[]> A(new uint64_t[n_a * L]), B(new uint64_t[n_b * L]);
+    for (size_t k = 1; k <= tb; k++) {
+        const Cts e = refresh(encode(pow_of(H, k)));
+        std::memcpy(&A[(k - 1) * 128 * L], e.data(), e.size() * 8);
+    }
+    const Cts ej = encode(EJ0);
+    std::memcpy(B.get(), ej.data(), ej.size() * 8);
+    std::vector<std::vector<int32_t>> rows;
+    GcmInnerPlan ip;
+    for (size_t c = 1; c < C; c++) {
+        gcm_segment_rows(f, seg, c, 128, rows);
+        gcm_inner_plan_add(ip, rows);
+    }
+    CHECK(rowplan_ok(ip.chunks, n_a));
+    Cts chunks(ip.chunks.n_rows() * L);
+    for (size_t t = 0; t < chunks.size(); t++) chunks[t] = rowsum_word(A.get(), ip.chunks, t, L);
+    const Cts S = refresh(rowsum(refresh(chunks), ip.rows));
+    for (size_t c = 1; c < C; c++) {
+        const Cts prod = refresh(encode(gcm_mul(decode(&S[(c - 1) * 128 * L]), pow_of(H, seg * c))));
+        std::memcpy(&B[c * 128 * L], prod.data(), prod.size() * 8);
+    }
+    gcm_long_final_rows(f, seg, tb + 1, rows);  // one frame: its products follow its E(J0) block
+    GcmCallPlan plan;
+    gcm_call_plan_add(plan, rows, tb, 0, kTag);
+    CHECK(rowplan2_ok(plan.chunks, n_a, n_b) && !rowplan2_ok(plan.chunks, n_a, n_b - 1));
+    Cts fin(plan.chunks.n_rows() * L);
+    for (size_t t = 0; t < fin.size(); t++) fin[t] = rowsum2_word(A.get(), n_a, B.get(), plan.chunks, t, L);
+    const Cts diff = rowsum(refresh(fin), plan.diff);
+    CHECK(eq(decode(diff.data()), add(add(EJ0, ghash_plain(f, H)), gcm_from_bytes(kTag))));
+}
+
 // one product through the product plan, as aes_gcm_test.cpp
 static GcmElem product(const GcmElem &a, const GcmElem &b, const GcmProductPlan &P) {
     Cts parts((size_t)kGcmParts * L, 0);
@@ -167,6 +206,7 @@ int main() {
         for (size_t m : ms) whole_plan(seg, m, H, EJ0, true);
     }
     whole_plan(1, 3, H, EJ0, false);  // all-zero blocks: every inner row is one empty chunk
+    split_plan(2, 5, H, EJ0);         // three segments over a table read in place
     {
         const GcmFrame z = frame_of(3, 0x00, false);
         std::vector<std::vector<int32_t>> rows;

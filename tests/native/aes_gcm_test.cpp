@@ -2,11 +2,13 @@
 // whose body word holds the bit at 1 << 63, sums are the u64 additions rowsum_word does, a refresh is the identity
 // on the bit (the body's top bit) and the 8 -> 7 table is evaluated directly.  Checked against the bitwise product of
 // SP 800-38D algorithm 1: the power schedule H^1 .. H^5 of test case 2's H, products with 0, 1, x^127 and all-ones,
-// the tag difference of test case 4 and of a one-bit-flipped tag.  Built and run by tests/test_aes_gcm.py, also under
-// -fsanitize=address,undefined.
+// the tag difference of test case 4 and of a one-bit-flipped tag, and the one-slot plan of a two-frame call over a
+// table and E(J0) blocks in separate exact allocations (rowsum2_word).  Built and run by tests/test_aes_gcm.py, also
+// under -fsanitize=address,undefined.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "../../tfhe-aes-2_amd/csrc/aes_gcm.hpp"
@@ -192,6 +194,56 @@ int main() {
     for (const auto &r : rows) CHECK(r.empty());
     CHECK(gcm_format(iv.data(), 16, nullptr, 0, nullptr, 0, 16, e) == GCM_FMT_IV);
     CHECK(gcm_format(iv.data(), 12, nullptr, 0, nullptr, 0, 5, e) == GCM_FMT_TAG);
+    // ---- the one-slot plan of a call: a table of 4 powers, frames of m = 1 and m = 2.  A is the table
+    // and B the E(J0) blocks, each a heap allocation of exactly its size, so the sanitized build reports an index past
+    // either end.  E(J0) of frame f is source (n_powers + f) 128 + r whatever the frames' m is ----
+    {
+        const size_t n_powers = 4, n_a = n_powers * 128, n_b = 2 * 128;
+        const int tl = 8;
+        std::unique_ptr<uint64_t[]> A(new uint64_t[n_a * L]), B(new uint64_t[n_b * L]);
+        GcmElem pw = H4;
+        for (size_t k = 0; k < n_powers; k++, pw = gcm_mul(pw, H4)) {
+            const Cts c = refresh(encode(pw));
+            std::memcpy(&A[k * 128 * L], c.data(), c.size() * 8);
+        }
+        const GcmElem j0[2] = {EJ0, gcm_mul(EJ0, H)};
+        for (size_t fi = 0; fi < 2; fi++) {
+            const Cts c = encode(j0[fi]);
+            std::memcpy(&B[fi * 128 * L], c.data(), c.size() * 8);
+        }
+        GcmFrame fr[2];
+        CHECK(gcm_format(iv.data(), 12, nullptr, 0, nullptr, 0, tl, fr[0]) == GCM_FMT_OK && fr[0].m() == 1);
+        CHECK(gcm_format(iv.data(), 12, nullptr, 0, ct.data(), 9, tl, fr[1]) == GCM_FMT_OK && fr[1].m() == 2);
+        const uint8_t tags[2][8] = {{0x5b, 0xc9, 0x4f, 0xbc, 0x32, 0x21, 0xa5, 0xdb}, {0x94, 0xfa, 0xe9, 0x5a, 0xe7, 0x12, 0x1a, 0x47}};
+        CHECK(gcm_plan_index_ok(1, n_powers, 2) && gcm_plan_index_ok(1, 128, 1) && !gcm_plan_index_ok(1, (size_t)1 << 24, 1) &&
+              !gcm_plan_index_ok((size_t)1 << 12, (size_t)1 << 12, 1));
+        GcmCallPlan plan;
+        for (size_t fi = 0; fi < 2; fi++) {
+            gcm_frame_rows(fr[fi], rows);
+            CHECK(gcm_multi_frame_check(fr[fi], 0, 1, n_powers, tl, rows) == GCM_MULTI_OK);
+            gcm_multi_plan_add(plan, rows, 1, n_powers, 0, fi, tags[fi]);
+        }
+        // the largest index is bit 8 tl - 1 of the last frame's E(J0); row 0 of frame 1 starts with its E(J0) bit 0
+        CHECK(rowplan2_ok(plan.chunks, n_a, n_b) && rowplan2_ok(plan.chunks, n_a, 128 + 64) && !rowplan2_ok(plan.chunks, n_a, 128 + 63));
+        CHECK(plan.chunks.src[(size_t)plan.chunks.row_start[(size_t)8 * tl]] == (int32_t)((n_powers + 1) * 128));
+        Cts chunks(plan.chunks.n_rows() * L);
+        for (size_t t = 0; t < chunks.size(); t++) chunks[t] = rowsum2_word(A.get(), n_a, B.get(), plan.chunks, t, L);
+        const Cts diff = rowsum(refresh(chunks), plan.diff);
+        CHECK(diff.size() == (size_t)2 * 8 * tl * L);
+        for (size_t fi = 0; fi < 2; fi++) {
+            GcmElem y{{0, 0}};  // GHASH by Horner's rule, then E(J0) and the received tag
+            for (size_t i = 0; i < fr[fi].m(); i++) {
+                const GcmElem x = gcm_from_bytes(&fr[fi].hashed[16 * i]);
+                y = gcm_mul(GcmElem{{y.w[0] ^ x.w[0], y.w[1] ^ x.w[1]}}, H4);
+            }
+            uint8_t tb[16] = {0};
+            std::memcpy(tb, tags[fi], 8);
+            const GcmElem t = gcm_from_bytes(tb);
+            const GcmElem wantd{{y.w[0] ^ j0[fi].w[0] ^ t.w[0], y.w[1] ^ j0[fi].w[1] ^ t.w[1]}};
+            for (int r = 0; r < 8 * tl; r++)
+                CHECK((int)(diff[(fi * 8 * tl + (size_t)r) * L + L - 1] >> 63) == gcm_coef(wantd, r));
+        }
+    }
     // a broken plan is refused before a launch
     RowPlan bad = P.reduce;
     bad.src[3] = 1135;

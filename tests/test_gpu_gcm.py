@@ -177,6 +177,58 @@ def test_single_frame_equals_composition(gpu_context, client, lut_id, rk2, hk2):
     assert np.array_equal(d_diff.cpu().numpy().view(np.uint64), diff)
 
 
+@pytest.fixture(scope="module")
+def ragged(gpu_context, rk2, hk2):
+    """One call of two frames under the 4-power table at tag_len = 8: m = 1 (nothing hashed but the length block) and
+    m = 2 (9 ciphertext bytes and the tag: 17 data bytes, a ragged block).  E(J0) of frame f is source
+    (n_powers + f) * 128 + r of the call's plan, behind the whole table and not behind max m = 2 blocks of it."""
+    shapes = [(R.IV3, b"", b""), (R.IV3[::-1], b"", bytes((7 * i + 3) & 255 for i in range(9)))]
+    frames = [(iv, aad, aes_var.gcm_encrypt_plain(R.KEY3, iv, aad, pt, 8, rounds=2)) for iv, aad, pt in shapes]
+    assert [len(R.hashed_blocks(aad, d[:-8])) for _, aad, d in frames] == [1, 2] and len(frames[1][2]) == 17
+    return frames, V.gcm_transcipher_raw(gpu_context, rk2, hk2, frames, 8, rounds=2)
+
+
+def _device_call(torch, ctx, rk, hk, frames, tag_len, n_bytes):
+    """gcm_transcipher_device on uploads of rk and hk: the payload bits, the differences and hk read back."""
+    d_rk = torch.from_numpy(rk.view(np.int64)).to("cuda:0")
+    d_hk = torch.from_numpy(np.ascontiguousarray(hk).view(np.int64)).to("cuda:0")
+    d_out = torch.full((n_bytes, 8, BIG), -1, dtype=torch.int64, device="cuda:0")
+    d_diff = torch.full((len(frames), tag_len, 8, BIG), -1, dtype=torch.int64, device="cuda:0")
+    V.gcm_transcipher_device(ctx, 128, d_rk.data_ptr(), d_hk.data_ptr(), hk.shape[0], frames, tag_len, 2,
+                             d_out.data_ptr(), d_diff.data_ptr())
+    return [d.cpu().numpy().view(np.uint64) for d in (d_out, d_diff, d_hk)]
+
+
+def test_ragged_batch_equals_composition(gpu_context, client, lut_id, rk2, hk2, ragged):
+    torch = pytest.importorskip("torch")
+    frames, got = ragged
+    assert [g[0].shape[0] for g in got] == [0, 9]
+    for (iv, aad, data), (plain, diff) in zip(frames, got):
+        want_plain, want_diff = _frame_np(gpu_context, lut_id, rk2, hk2, iv, aad, data, 8, 2)
+        assert np.array_equal(plain, want_plain)
+        assert np.array_equal(diff, want_diff)
+        assert aes_var.gcm_tag_ok(client, diff)
+    d_plain, d_diff, _ = _device_call(torch, gpu_context, rk2, hk2, frames, 8, 9)
+    assert np.array_equal(d_plain, np.concatenate([g[0] for g in got]))
+    assert np.array_equal(d_diff, np.stack([g[1] for g in got]))
+
+
+def test_table_is_read_in_place(gpu_context, rk2, hk2, ragged):
+    """Blocks 2..3 of the table lie beyond max m = 2: nothing the result depends on reads them.  The caller's device
+    table is a source where it lies and is never written."""
+    torch = pytest.importorskip("torch")
+    frames, got = ragged
+    scribbled = hk2.copy()
+    scribbled[2:] = (np.arange(scribbled[2:].size, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)).reshape(scribbled[2:].shape)
+    again = V.gcm_transcipher_raw(gpu_context, rk2, scribbled, frames, 8, rounds=2)
+    for (plain, diff), (want_plain, want_diff) in zip(again, got):
+        assert np.array_equal(plain, want_plain) and np.array_equal(diff, want_diff)
+    d_plain, d_diff, hk_after = _device_call(torch, gpu_context, rk2, scribbled, frames, 8, 9)
+    assert np.array_equal(d_plain, np.concatenate([g[0] for g in got]))
+    assert np.array_equal(d_diff, np.stack([g[1] for g in got]))
+    assert np.array_equal(hk_after, scribbled)
+
+
 def test_chunked_pass_gives_the_same_words(gpu_context, product_raw, rk2, hk2, monkeypatch):
     """The frame of test_single_frame_equals_composition with its three public blocks in chunks of 2: J0 and the first
     counter fall in one chunk, the last counter in the next.  The chunk size is read when the context is created."""

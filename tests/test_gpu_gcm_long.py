@@ -198,6 +198,28 @@ def test_three_segments_equal_the_composition(gpu_context, client, lut_id, two):
     assert any(want) and _bytes_of(client, bad_diff) == want and not aes_var.gcm_tag_ok(client, bad_diff)
 
 
+def test_table_and_stride_key_are_read_in_place(gpu_context, two):
+    """seg = 2 and m = 5: the inner and the final chunk sums read the table's first two blocks where the caller keeps
+    them.  Blocks 2..3 enter no output word, and neither the table nor the stride key is written."""
+    torch = pytest.importorskip("torch")
+    rk, hk, sk = two
+    frames = [(R.IV3, COMP_AAD, aes_var.gcm_encrypt_plain(R.KEY3, R.IV3, COMP_AAD, COMP_MSG, 12, rounds=2))]
+    (plain, diff), = V.gcm_long_transcipher_raw(gpu_context, rk, hk, sk, 2, frames, 12, rounds=2)
+    scribbled = hk.copy()
+    scribbled[2:] = (np.arange(scribbled[2:].size, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)).reshape(scribbled[2:].shape)
+    (plain2, diff2), = V.gcm_long_transcipher_raw(gpu_context, rk, scribbled, sk, 2, frames, 12, rounds=2)
+    assert np.array_equal(plain2, plain) and np.array_equal(diff2, diff)
+    d_rk, d_hk, d_sk = _dev(torch, rk), _dev(torch, scribbled), _dev(torch, sk)
+    d_out = torch.full((40, 8, BIG), -1, dtype=torch.int64, device="cuda:0")
+    d_diff = torch.full((12, 8, BIG), -1, dtype=torch.int64, device="cuda:0")
+    V.gcm_long_transcipher_device(gpu_context, 128, d_rk.data_ptr(), d_hk.data_ptr(), 4, d_sk.data_ptr(), 3, 2, frames, 12,
+                                  2, d_out.data_ptr(), d_diff.data_ptr())
+    assert np.array_equal(d_out.cpu().numpy().view(np.uint64), plain)
+    assert np.array_equal(d_diff.cpu().numpy().view(np.uint64), diff)
+    assert np.array_equal(d_hk.cpu().numpy().view(np.uint64), scribbled)
+    assert np.array_equal(d_sk.cpu().numpy().view(np.uint64), sk)
+
+
 def test_rows_without_a_source(gpu_context, client, lut_id, two):
     """seg = 1 and an all-zero ciphertext block: every inner row of that segment is one empty chunk, the zero
     ciphertext through rowsum_kernel and the identity bootstrap.  At seg = 1 the stride key is the table."""

@@ -628,31 +628,11 @@ void Engine::require_gcm() const {
     if (p_.model != 1 || !d_lut_gcm_ || !d_lut_id1_) throw std::runtime_error("GCM runs on the 1-bit model parameters");
 }
 
-// Row sums (rowsum.hpp) for GCM and XTS: one launch.  The plan's arrays are uploaded asynchronously into buffers the
-// stream's earlier launches may still read, which the stream order allows; the host copy lives until the next call
-// clears rowsum_plans_.
-void Engine::rowsum_pass(const uint64_t *d_sources, size_t n_src, RowPlan plan, uint64_t *d_out) {
-    if (!rowplan_ok(plan, n_src)) throw std::runtime_error("row-sum plan: index out of range");
-    if (!plan.n_rows()) return;
-    rowsum_plans_.push_back(std::move(plan));
-    const RowPlan &p = rowsum_plans_.back();
-    auto up = [&](auto &d_buf, const auto &v) {  // an empty array is a null argument
-        return v.empty() ? nullptr : d_buf.upload(v.data(), v.size(), stream_);
-    };
-    const int32_t *rs = up(d_rs_start_, p.row_start), *ix = up(d_rs_src_, p.src);
-    const int32_t *lo = up(d_rs_list_, p.list_of), *bo = up(d_rs_base_, p.base_of);
-    const uint8_t *pb = up(d_rs_pub_, p.pub_bit);
-    const int L = (int)p_.big_len();
-    const size_t n_rows = p.n_rows();
-    timed(ST_LINEAR, [&] {
-        rowsum_kernel<<<grid_for(n_rows * (size_t)L), kThreads, 0, stream_>>>(d_sources, rs, ix, lo, bo, pb, d_out, n_rows, L);
-        HIPC(hipGetLastError());
-    });
-}
-
-// The same over two source arrays: one launch of rowsum2_kernel, the plan kept alive like rowsum_pass's
-void Engine::rowsum2_pass(const uint64_t *d_a, size_t n_a, const uint64_t *d_b, size_t n_b, RowPlan plan,
-                          uint64_t *d_out) {
+// Row sums (rowsum.hpp) for GCM and XTS: one launch, rowsum_kernel over A alone or rowsum2_kernel over A and B.  The
+// plan's arrays are uploaded asynchronously into buffers the stream's earlier launches may still read, which the stream
+// order allows; the host copy lives until the next call clears rowsum_plans_.
+void Engine::rowsum_pass(const uint64_t *d_a, size_t n_a, const uint64_t *d_b, size_t n_b, RowPlan plan,
+                         uint64_t *d_out) {
     if (!rowplan2_ok(plan, n_a, n_b)) throw std::runtime_error("row-sum plan: index out of range");
     if (!plan.n_rows()) return;
     rowsum_plans_.push_back(std::move(plan));
@@ -665,9 +645,12 @@ void Engine::rowsum2_pass(const uint64_t *d_a, size_t n_a, const uint64_t *d_b, 
     const uint8_t *pb = up(d_rs_pub_, p.pub_bit);
     const int L = (int)p_.big_len();
     const size_t n_rows = p.n_rows();
+    const unsigned grid = grid_for(n_rows * (size_t)L);
     timed(ST_LINEAR, [&] {
-        rowsum2_kernel<<<grid_for(n_rows * (size_t)L), kThreads, 0, stream_>>>(d_a, n_a, d_b, rs, ix, lo, bo, pb, d_out,
-                                                                                n_rows, L);
+        if (n_b)
+            rowsum2_kernel<<<grid, kThreads, 0, stream_>>>(d_a, n_a, d_b, rs, ix, lo, bo, pb, d_out, n_rows, L);
+        else
+            rowsum_kernel<<<grid, kThreads, 0, stream_>>>(d_a, rs, ix, lo, bo, pb, d_out, n_rows, L);
         HIPC(hipGetLastError());
     });
 }
@@ -768,22 +751,6 @@ void Engine::gf128_product(const uint64_t *d_a, const uint64_t *d_b, size_t coun
     collect_times();
 }
 
-void Engine::ghash_key(const uint64_t *d_rk, int n_powers, int rounds, int nr, uint64_t *d_out) {
-    require_gcm();
-    require_rounds(rounds, nr);
-    if (n_powers < 1 || n_powers > kGcmMaxPowers) throw std::runtime_error("GCM: n_powers must be in 1..=64");
-    const size_t block_len = 128 * p_.big_len();
-    rowsum_plans_.clear();
-    // H = E_K(0^128), then the identity bootstrap: H^1 at noise^2 = 1
-    PubBlock zero{};
-    zero.len = 16;
-    d_gcm_a_.grow(block_len);
-    aes_pub_blocks_multi(d_rk, std::vector<PubBlock>{zero}, rounds, d_gcm_a_, nr);  // resets the stage times
-    circuit_bootstrap(d_gcm_a_, 128, 1, d_lut_id1_, 1, d_out);
-    gcm_power_generations(d_out, (size_t)n_powers, {0}, n_powers);
-    collect_times();
-}
-
 // Power k of a table's base at its entry k - 1: a generation's squares of all tables in one launch sequence, its
 // products in another.  The product scratch grows with the batch, so several tables split a generation's products at
 // gcm_seg_batch_; the bootstraps are per ciphertext, so where a batch ends changes no word.
@@ -816,8 +783,9 @@ void Engine::gcm_power_generations(uint64_t *d_base, size_t n_blocks, const std:
     }
 }
 
-// The power tables of a key table.  H of every slot comes out of one public-block batch and one identity bootstrap
-// in slot order; a row copy puts it at entry 0 of the slot's table, and the generations run over all tables.
+// The power tables of a key table; a single key is a table of one slot.  H = E_K(0^128) of every slot comes out of one
+// public-block batch and one identity bootstrap (H^1 at noise^2 = 1) in slot order; a row copy puts it at entry 0 of the
+// slot's table, and the generations run over all tables.
 void Engine::ghash_key_multi(const uint64_t *d_table, size_t n_keys, int n_powers, int rounds, int nr, uint64_t *d_out) {
     require_gcm();
     require_rounds(rounds, nr);
@@ -871,9 +839,9 @@ size_t Engine::gcm_frame_offsets(const std::vector<GcmFrameIn> &frames, std::vec
     return total;
 }
 
-void Engine::gcm_public_pass(const uint64_t *d_rk, const std::vector<GcmFrameIn> &frames, const std::vector<int64_t> &off,
-                             size_t total, int rounds, int nr, uint64_t *d_out_plain, uint64_t *d_j0,
-                             const std::vector<int32_t> *slots) {
+void Engine::gcm_public_pass(const uint64_t *d_table, const std::vector<GcmFrameIn> &frames,
+                             const std::vector<int64_t> &off, size_t total, int rounds, int nr, uint64_t *d_out_plain,
+                             uint64_t *d_j0) {
     const size_t n = frames.size();
     gcm_bytes_.assign(std::max<size_t>(total, 1), 0);
     for (size_t s = 0; s < n; s++)
@@ -887,7 +855,7 @@ void Engine::gcm_public_pass(const uint64_t *d_rk, const std::vector<GcmFrameIn>
         const GcmFrame &f = *frames[s].frame;
         for (size_t i = 1; i < f.n_pub(); i++) {
             PubBlock b{};
-            if (slots) b.slot = (*slots)[s];
+            b.slot = frames[s].slot;
             std::memcpy(b.bytes, &f.pub[16 * i], 16);
             const bool j0 = i == 1;
             b.out_byte = j0 ? 0 : off[s] + (int64_t)(16 * (i - 2));
@@ -897,80 +865,46 @@ void Engine::gcm_public_pass(const uint64_t *d_rk, const std::vector<GcmFrameIn>
             klen.push_back(j0 ? 16 : 0);
         }
     }
-    pub_pass(d_rk, blocks, rounds, d_bytes, d_out_plain, nr, &kout, &klen, d_j0);
+    pub_pass(d_table, blocks, rounds, d_bytes, d_out_plain, nr, &kout, &klen, d_j0);
 }
 
-void Engine::aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers,
-                                 const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
-                                 uint64_t *d_out_tagdiff) {
+// GHASH + E(J0) + the received tag: chunk sums over A and B, one refresh, the differences
+void Engine::gcm_tag_tail(const uint64_t *d_a, size_t n_a, const uint64_t *d_b, size_t n_b, GcmCallPlan plan,
+                          uint64_t *d_out_tagdiff) {
+    const size_t n_chunks = plan.chunks.n_rows();
+    rowsum_pass(d_a, n_a, d_b, n_b, std::move(plan.chunks), d_gcm_a_);
+    circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
+    rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
+}
+
+// The short-frame call.  A is the caller's power tables where they lie, B the kept E(J0)
+// blocks in d_gcm_src_: nothing of a table is copied.  Frame s under slot t reads its table at base 128 t n_powers and
+// bit r of its E(J0) at source (n_keys n_powers + s) 128 + r.
+void Engine::gcm_frames_pass(const uint64_t *d_table, size_t n_keys, const uint64_t *d_htable, size_t n_powers,
+                             const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
+                             uint64_t *d_out_tagdiff) {
     const size_t n = frames.size();
     if (!n) return;
     require_gcm();
     require_rounds(rounds, nr);
     // at one round J0 and the counter blocks share their de-duplicated SubBytes outputs at the IV positions
     if (rounds < 2) throw std::runtime_error("GCM needs rounds >= 2");
+    if (!gcm_plan_index_ok(n_keys, n_powers, n)) throw std::runtime_error("GCM: more sources than a row-sum index takes");
     const size_t L = p_.big_len(), block_len = 128 * L;
     // ---- the plans, before any device work ----
-    size_t table_blocks = 0;
     std::vector<int64_t> off;
-    const size_t total = gcm_frame_offsets(frames, off);
-    for (size_t s = 0; s < n; s++) table_blocks = std::max(table_blocks, frames[s].frame->m());
-    GcmCallPlan plan;
-    std::vector<std::vector<int32_t>> rows;
-    for (size_t s = 0; s < n; s++) {
-        gcm_frame_rows(*frames[s].frame, rows);
-        if (gcm_frame_check(*frames[s].frame, n_powers, rows) != GCM_PLAN_OK)
-            throw std::runtime_error("GCM frame: more hashed blocks than the power table or the chunk sum takes");
-        gcm_call_plan_add(plan, rows, table_blocks, s, frames[s].tag);
-    }
-    const size_t n_src = (table_blocks + n) * 128, n_chunks = plan.chunks.n_rows();
-    times_ = StageTimes{};
-    rowsum_plans_.clear();
-    d_gcm_src_.grow(n_src * L);
-    d_gcm_a_.grow(n_chunks * L);
-    d_gcm_b_.grow(n_chunks * L);
-    HIPC(hipMemcpyAsync(d_gcm_src_, d_hk, table_blocks * block_len * 8, hipMemcpyDeviceToDevice, stream_));
-    gcm_public_pass(d_rk, frames, off, total, rounds, nr, d_out_plain, d_gcm_src_ + table_blocks * block_len);
-
-    // ---- GHASH + E(J0) + the received tag: chunk sums, one refresh, the differences ----
-    rowsum_pass(d_gcm_src_, n_src, std::move(plan.chunks), d_gcm_a_);
-    circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
-    rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
-    collect_times();
-}
-
-// GCM over key tables.  The launches of aes_gcm_transcipher, with the chunk sums on rowsum2_kernel:
-// A is the caller's power tables where they lie, B the kept E(J0) blocks in d_gcm_src_.  Nothing of a table is copied.
-void Engine::aes_gcm_transcipher_multi(const uint64_t *d_table, size_t n_keys, const uint64_t *d_htable, size_t n_powers,
-                                       const std::vector<GcmStreamIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
-                                       uint64_t *d_out_tagdiff) {
-    const size_t n = frames.size();
-    if (!n) return;
-    require_gcm();
-    require_rounds(rounds, nr);
-    if (rounds < 2) throw std::runtime_error("GCM needs rounds >= 2");
-    if (!gcm_multi_shape_ok(n_keys, n_powers, n)) throw std::runtime_error("GCM: n_powers must be in 1..=64");
-    const size_t L = p_.big_len(), block_len = 128 * L;
-    // ---- the plans, before any device work ----
-    std::vector<GcmFrameIn> fin(n);
-    std::vector<int32_t> slots(n);
-    for (size_t s = 0; s < n; s++) {
-        fin[s] = {frames[s].frame, frames[s].data, frames[s].tag};
-        slots[s] = frames[s].slot;
-    }
-    std::vector<int64_t> off;
-    const size_t total = gcm_frame_offsets(fin, off);  // one tag length, whole layouts
+    const size_t total = gcm_frame_offsets(frames, off);  // one tag length, whole layouts
     GcmCallPlan plan;
     std::vector<std::vector<int32_t>> rows;
     for (size_t s = 0; s < n; s++) {
         const GcmFrame &f = *frames[s].frame;
         gcm_frame_rows(f, rows);
-        switch (gcm_multi_frame_check(f, slots[s], n_keys, n_powers, fin[0].frame->tag_len, rows)) {
+        switch (gcm_multi_frame_check(f, frames[s].slot, n_keys, n_powers, frames[0].frame->tag_len, rows)) {
             case GCM_MULTI_OK: break;
             case GCM_MULTI_SLOT: throw std::runtime_error("GCM frame: key slot outside 0..n_keys-1");
             default: throw std::runtime_error("GCM frame: more hashed blocks than the power table or the chunk sum takes");
         }
-        gcm_multi_plan_add(plan, rows, n_keys, n_powers, (size_t)slots[s], s, frames[s].tag);
+        gcm_multi_plan_add(plan, rows, n_keys, n_powers, (size_t)frames[s].slot, s, frames[s].tag);
     }
     const size_t n_a = n_keys * n_powers * 128, n_b = n * 128, n_chunks = plan.chunks.n_rows();
     if (!rowplan2_ok(plan.chunks, n_a, n_b)) throw std::runtime_error("row-sum plan: index out of range");
@@ -979,17 +913,30 @@ void Engine::aes_gcm_transcipher_multi(const uint64_t *d_table, size_t n_keys, c
     d_gcm_src_.grow(n * block_len);
     d_gcm_a_.grow(n_chunks * L);
     d_gcm_b_.grow(n_chunks * L);
-    gcm_public_pass(d_table, fin, off, total, rounds, nr, d_out_plain, d_gcm_src_, &slots);
-
-    // ---- GHASH + E(J0) + the received tag: chunk sums over the two arrays, one refresh, the differences ----
-    rowsum2_pass(d_htable, n_a, d_gcm_src_, n_b, std::move(plan.chunks), d_gcm_a_);
-    circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
-    rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
+    gcm_public_pass(d_table, frames, off, total, rounds, nr, d_out_plain, d_gcm_src_);
+    gcm_tag_tail(d_htable, n_a, d_gcm_src_, n_b, std::move(plan), d_out_tagdiff);
     collect_times();
 }
 
-// Segmented GHASH (aes_gcm.hpp).  d_gcm_src_ is sized once and holds, in blocks of [128][K+1]: the
-// table's first table_blocks powers, E(J0) of every frame, every product S_c G_c, and one batch of S_c operands.
+void Engine::aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers,
+                                 const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
+                                 uint64_t *d_out_tagdiff) {
+    gcm_frames_pass(d_rk, 1, d_hk, n_powers, frames, rounds, nr, d_out_plain, d_out_tagdiff);
+}
+
+// The key-table door's own bound comes before the shared checks (the model, where the status codes are made, refuses
+// all of them first; only this backstop's message for a call with two reasons to refuse depends on the order)
+void Engine::aes_gcm_transcipher_multi(const uint64_t *d_table, size_t n_keys, const uint64_t *d_htable, size_t n_powers,
+                                       const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
+                                       uint64_t *d_out_tagdiff) {
+    if (!frames.empty() && !gcm_multi_shape_ok(n_keys, n_powers, frames.size()))
+        throw std::runtime_error("GCM: n_powers must be in 1..=64");
+    gcm_frames_pass(d_table, n_keys, d_htable, n_powers, frames, rounds, nr, d_out_plain, d_out_tagdiff);
+}
+
+// Segmented GHASH (aes_gcm.hpp).  The plans index the table's first table_blocks powers, E(J0) of
+// every frame, then every product S_c G_c; the table is read where d_hk keeps it, and d_gcm_src_ is sized once and
+// holds, in blocks of [128][K+1], the rest and one batch of S_c operands.
 // gcm_product_pass grows d_gcm_a_ / d_gcm_b_ / d_gcm_ops_ before it copies its operands, so no operand lives in those:
 // S_c is written into d_gcm_src_ and the stride operands are read from the caller's d_sk.
 void Engine::aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers, const uint64_t *d_sk,
@@ -1014,7 +961,7 @@ void Engine::aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk
         first_product[s] = n_products;
         n_products += gcm_long_segments(m, seg) - 1;
     }
-    const size_t prod_block0 = table_blocks + n, s_block0 = prod_block0 + n_products;
+    const size_t prod_block0 = table_blocks + n;  // in the plans' index space: table blocks, E(J0), products
     std::vector<GcmInnerPlan> inner((n_products + B - 1) / B);
     std::vector<size_t> stride_of;  // [n_products]: the stride power (c - 1) of every inner segment, in call order
     GcmCallPlan plan;
@@ -1031,22 +978,23 @@ void Engine::aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk
         if (!gcm_final_rows_ok(rows)) throw std::runtime_error("GCM frame: a tag row needs more than 64 chunks");
         gcm_call_plan_add(plan, rows, table_blocks, s, frames[s].tag);
     }
-    const size_t n_src = s_block0 * 128, n_chunks = plan.chunks.n_rows(), batch = std::min(B, n_products);
+    // A = the table's first table_blocks blocks where the caller keeps them (seg <= n_powers backs them); B = d_gcm_src_
+    const size_t n_a = table_blocks * 128, n_b = (n + n_products) * 128;
+    const size_t n_chunks = plan.chunks.n_rows(), batch = std::min(B, n_products);
     size_t scratch = std::max(n_chunks, batch * gcm_product_plan().chunks.n_rows());
     for (const GcmInnerPlan &ip : inner) scratch = std::max(scratch, ip.chunks.n_rows());
     times_ = StageTimes{};
     rowsum_plans_.clear();
-    d_gcm_src_.grow((s_block0 + batch) * block_len);
+    d_gcm_src_.grow((n + n_products + batch) * block_len);
     d_gcm_a_.grow(scratch * L);
     d_gcm_b_.grow(scratch * L);
-    HIPC(hipMemcpyAsync(d_gcm_src_, d_hk, table_blocks * block_len * 8, hipMemcpyDeviceToDevice, stream_));
-    gcm_public_pass(d_rk, frames, off, total, rounds, nr, d_out_plain, d_gcm_src_ + table_blocks * block_len);
+    gcm_public_pass(d_rk, frames, off, total, rounds, nr, d_out_plain, d_gcm_src_);
 
-    // ---- the inner segments: S_c at level 1 with fresh ids, then S_c G_c into the final source array ----
-    uint64_t *d_prod = d_gcm_src_ + prod_block0 * block_len, *d_s = d_gcm_src_ + s_block0 * block_len;
+    // ---- the inner segments: S_c at level 1 with fresh ids, then S_c G_c behind the E(J0) blocks ----
+    uint64_t *d_prod = d_gcm_src_ + n * block_len, *d_s = d_prod + n_products * block_len;
     for (size_t bi = 0; bi < inner.size(); bi++) {
         const size_t at = bi * B, nb = std::min(B, n_products - at), nck = inner[bi].chunks.n_rows();
-        rowsum_pass(d_gcm_src_, table_blocks * 128, std::move(inner[bi].chunks), d_gcm_a_);
+        rowsum_pass(d_hk, n_a, std::move(inner[bi].chunks), d_gcm_a_);
         circuit_bootstrap(d_gcm_a_, nck, 1, d_lut_id1_, 1, d_gcm_b_);
         rowsum_pass(d_gcm_b_, nck, std::move(inner[bi].rows), d_gcm_a_);
         circuit_bootstrap(d_gcm_a_, nb * 128, 1, d_lut_id1_, 1, d_s);
@@ -1060,10 +1008,8 @@ void Engine::aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk
         gcm_product_pass(a, b, outs);
     }
 
-    // ---- GHASH + E(J0) + the received tag, as aes_gcm_transcipher: the products are sources like the table's ----
-    rowsum_pass(d_gcm_src_, n_src, std::move(plan.chunks), d_gcm_a_);
-    circuit_bootstrap(d_gcm_a_, n_chunks, 1, d_lut_id1_, 1, d_gcm_b_);
-    rowsum_pass(d_gcm_b_, n_chunks, std::move(plan.diff), d_out_tagdiff);
+    // ---- GHASH + E(J0) + the received tag, as the short-frame call: the products are sources like the table's ----
+    gcm_tag_tail(d_hk, n_a, d_gcm_src_, n_b, std::move(plan), d_out_tagdiff);
     collect_times();
 }
 

@@ -386,9 +386,17 @@ inline GcmLongStatus gcm_long_frame_check(const GcmFrame &f, size_t seg, size_t 
 // the caller keeps them, and B, E(J0) of every frame [n_frames][128].  A frame under slot s has the rows of the
 // single-key call under the base 128 s n_powers, which selects the slot's table; its E(J0) entry is written relative
 // to that base, so base + entry = |A| + 128 frame + r whatever the slot.  The sets summed are the single-key call's.
+// A single key is the table of one slot: E(J0) of frame f at (n_powers + f) 128 + r.
 enum GcmMultiStatus { GCM_MULTI_OK = 0, GCM_MULTI_SLOT, GCM_MULTI_TAG, GCM_MULTI_POWERS, GCM_MULTI_NOISE, GCM_MULTI_SIZE };
 
-// every index of a call's plans fits an int32_t
+// what the plans of a call need, whatever its door: n_keys n_powers table blocks and a block per frame of 128 sources
+// each, every index an int32_t
+inline bool gcm_plan_index_ok(size_t n_keys, size_t n_powers, size_t n_frames) {
+    const size_t cap = (size_t)1 << 24;
+    return n_keys < cap && n_powers < cap && n_frames < cap && n_keys * n_powers + n_frames < cap;
+}
+
+// the key-table entry points and the key schedules refuse more: tables of at most 64 powers
 inline bool gcm_multi_shape_ok(size_t n_keys, size_t n_powers, size_t n_frames) {
     return n_powers >= 1 && n_powers <= (size_t)kGcmMaxPowers && n_keys <= ((size_t)1 << 16) &&
            n_frames <= ((size_t)1 << 20);  // (2^16 * 64 + 2^20) * 128 < 2^31

@@ -195,25 +195,22 @@ class Engine {
                              uint64_t *d_out_plain, uint64_t *d_out_tagdiff);
 
     // ---- AES-GCM decryption of public frames on the 1-bit model (aes_gcm.hpp; the reference has no
-    // GCM).  One key per call; key tables further down ----
+    // GCM).  A single key is a key table of one slot ----
     // squares of `count` field elements [count][128][K+1]: row sums, then one identity bootstrap (noise^2 = 1)
     void gf128_square(const uint64_t *d_in, size_t count, uint64_t *d_out);
     // products a_c b_c of `count` pairs, a / b / out [count][128][K+1]: the 256 operand bits of a pair are keyswitched
     // once and gathered as small ciphertexts into the 1024 groups of one 8 -> 7 cbs_vp call over all pairs; chunk
     // sums, identity bootstrap, reduction, identity bootstrap
     void gf128_product(const uint64_t *d_a, const uint64_t *d_b, size_t count, uint64_t *d_out);
-    // the power table H^1 .. H^n_powers [n_powers][128][K+1] of the expanded key rk, every bit at noise^2 = 1:
-    // E_K(0) through aes_pub_blocks_multi, one identity bootstrap, then the generations of gcm_power_schedule
-    void ghash_key(const uint64_t *d_rk, int n_powers, int rounds, int nr, uint64_t *d_out);
-    // One frame: `data` its data_len ciphertext bytes, `tag` its tag_len received-tag bytes (HOST, read during the call)
+    // One frame under slot `slot` of the key table and of the power tables (0 where the call has one key): `data` its
+    // data_len ciphertext bytes, `tag` its tag_len received-tag bytes (HOST, read during the call)
     struct GcmFrameIn {
+        int32_t slot;
         const GcmFrame *frame;
         const uint8_t *data, *tag;
     };
-    // One public-block batch over all frames' J0 and counter blocks: the payload bits E(ctr) + C go to d_out_plain
-    // [sum data_len][8][K+1], frames in order, and E(J0) is kept by the second placement.  Then one row-sum launch over
-    // all frames' chunks, one identity bootstrap of the chunk bits and one row-sum launch for the tag differences
-    // d_out_tagdiff [n_frames][8 tag_len][K+1].  d_hk [n_powers][128][K+1] (ghash_key); `rounds` >= 2
+    // aes_gcm_transcipher_multi on a table of one slot: d_rk the expanded key, d_hk [n_powers][128][K+1] its power
+    // table (ghash_key_multi of one slot), read in place.  A single key's n_powers is not bounded by 64
     void aes_gcm_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers,
                              const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
                              uint64_t *d_out_tagdiff);
@@ -224,7 +221,8 @@ class Engine {
     // aes_gcm_transcipher's public pass, then the inner segments of all frames in batches of gcm_seg_batch_ (chunk
     // sums over the table's first seg powers, identity bootstrap, row sums, identity bootstrap, one product with the
     // segment's stride power from d_sk), then the final chunk sums over the table, E(J0) and the products, one
-    // identity bootstrap and the differences.  A frame of at most seg hashed blocks runs aes_gcm_transcipher's launches
+    // identity bootstrap and the differences.  The table's first min(seg, m) blocks are read where d_hk keeps them.
+    // One key: every frame's slot is 0.  A frame of at most seg hashed blocks runs aes_gcm_transcipher's launches
     void aes_gcm_long_transcipher(const uint64_t *d_rk, const uint64_t *d_hk, size_t n_powers, const uint64_t *d_sk,
                                   size_t n_strides, size_t seg, const std::vector<GcmFrameIn> &frames, int rounds, int nr,
                                   uint64_t *d_out_plain, uint64_t *d_out_tagdiff);
@@ -234,20 +232,17 @@ class Engine {
     // the power tables of all slots: E_K(0) of every slot in one public-block batch, one identity bootstrap over
     // n_keys * 128 bits, then every generation of gcm_power_schedule once: its squares of all keys in one
     // gcm_square_pass, its products of all keys in gcm_product_pass calls of at most gcm_seg_batch_ products
+    // One table runs a generation's products in one pass: the power table of a single key is this call with n_keys = 1
     void ghash_key_multi(const uint64_t *d_table, size_t n_keys, int n_powers, int rounds, int nr, uint64_t *d_out);
-    // One frame under slot `slot` of both tables
-    struct GcmStreamIn {
-        int32_t slot;
-        const GcmFrame *frame;
-        const uint8_t *data, *tag;
-    };
-    // aes_gcm_transcipher's launches over frames of several slots: one public pass (every block under its frame's slot),
-    // one two-source row-sum launch for all chunks (A = d_htable in place, B = the kept E(J0) blocks; the row base selects
-    // the slot's table), one identity bootstrap, one row-sum launch for the differences.  Refused before any device work,
-    // the stage times untouched: a slot outside 0 .. n_keys - 1, m > n_powers, a row of more than 64 chunks, rounds < 2,
-    // mixed tag lengths.  A slot that no frame names is not read, neither its expanded key nor its power table
+    // One public-block batch over all frames' J0 and counter blocks, every block under its frame's slot: the payload
+    // bits E(ctr) + C go to d_out_plain [sum data_len][8][K+1], frames in order, and E(J0) is kept by the second
+    // placement.  Then one two-source row-sum launch for all chunks (A = d_htable in place, B = the kept E(J0) blocks;
+    // the row base selects the slot's table), one identity bootstrap of the chunk bits and one row-sum launch for the
+    // tag differences d_out_tagdiff [n_frames][8 tag_len][K+1].  Refused before any device work, the stage times
+    // untouched: a slot outside 0 .. n_keys - 1, m > n_powers, a row of more than 64 chunks, rounds < 2, mixed tag
+    // lengths, n_powers > 64.  A slot that no frame names is not read, neither its expanded key nor its power table
     void aes_gcm_transcipher_multi(const uint64_t *d_table, size_t n_keys, const uint64_t *d_htable, size_t n_powers,
-                                   const std::vector<GcmStreamIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
+                                   const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
                                    uint64_t *d_out_tagdiff);
 
     // ---- AEAD open on the 1-bit model (aead_open.hpp; the reference has no AEAD).  The lookup tables
@@ -410,13 +405,14 @@ class Engine {
     DevBuf<int32_t> d_pub_klen_;
     std::vector<std::vector<int64_t>> pub_kout_;
     std::vector<std::vector<int32_t>> pub_klen_;
-    // Row sums (rowsum.hpp): validates the plan against the n_src sources [n_src][K+1], keeps it alive until the next
-    // call (the uploads are asynchronous) and launches once under ST_LINEAR: -> d_out [n_rows][K+1].  The plan's
-    // arrays on the device and the host plans their pending uploads read
-    void rowsum_pass(const uint64_t *d_sources, size_t n_src, RowPlan plan, uint64_t *d_out);
-    // the same over two source arrays A [n_a][K+1] and B [n_b][K+1] (rowsum2_word): the plan is validated against
-    // n_a + n_b and kept alive in the same way
-    void rowsum2_pass(const uint64_t *d_a, size_t n_a, const uint64_t *d_b, size_t n_b, RowPlan plan, uint64_t *d_out);
+    // Row sums (rowsum.hpp) over the sources A [n_a][K+1] and B [n_b][K+1]: validates the plan against n_a + n_b,
+    // keeps it alive until the next call (the uploads are asynchronous) and launches once under ST_LINEAR: -> d_out
+    // [n_rows][K+1].  n_b = 0 is rowsum_kernel over A, anything else rowsum2_kernel.  The plan's arrays on the device
+    // and the host plans their pending uploads read
+    void rowsum_pass(const uint64_t *d_a, size_t n_a, const uint64_t *d_b, size_t n_b, RowPlan plan, uint64_t *d_out);
+    void rowsum_pass(const uint64_t *d_sources, size_t n_src, RowPlan plan, uint64_t *d_out) {
+        rowsum_pass(d_sources, n_src, nullptr, 0, std::move(plan), d_out);
+    }
     DevBuf<int32_t> d_rs_start_, d_rs_src_, d_rs_list_, d_rs_base_;
     DevBuf<uint8_t> d_rs_pub_;
     std::deque<RowPlan> rowsum_plans_;
@@ -429,9 +425,10 @@ class Engine {
     std::vector<uint8_t> ccm_bytes_;
     std::vector<int64_t> ccm_src_;
     std::vector<int32_t> ccm_slot_, ccm_order_;
-    // GCM: the 8 -> 7 nibble-product table; the source array of a call's chunk sums (power table, then E(J0) of every
-    // frame); two scratch arrays the row sums and the refreshes alternate between; the operand bits and the partial
-    // bits of a product batch; the public bytes of a call and the host copy their pending upload reads
+    // GCM: the 8 -> 7 nibble-product table; what a call's chunk sums read next to the caller's power table (E(J0) of
+    // every frame, then the segmented call's products and operand batch); two scratch arrays the row sums and the
+    // refreshes alternate between; the operand bits and the partial bits of a product batch; the public bytes of a call
+    // and the host copy their pending upload reads
     DevBuf<uint64_t> d_lut_gcm_;
     DevBuf<uint64_t> d_gcm_src_, d_gcm_a_, d_gcm_b_, d_gcm_ops_, d_gcm_ks_, d_gcm_parts_;
     DevBuf<uint8_t> d_gcm_bytes_;
@@ -448,10 +445,17 @@ class Engine {
     // the layout checks and payload offsets of a call's frames; returns the payload bytes
     size_t gcm_frame_offsets(const std::vector<GcmFrameIn> &frames, std::vector<int64_t> &off) const;
     // the public blocks of a call: the ciphertext bytes up, the counters into d_out_plain, E(J0) of frame s into block
-    // s of d_j0.  slots != nullptr: d_rk is a key table and the blocks of frame s run under slot (*slots)[s]
-    void gcm_public_pass(const uint64_t *d_rk, const std::vector<GcmFrameIn> &frames, const std::vector<int64_t> &off,
-                         size_t total, int rounds, int nr, uint64_t *d_out_plain, uint64_t *d_j0,
-                         const std::vector<int32_t> *slots = nullptr);
+    // s of d_j0; the blocks of a frame run under its slot of the key table
+    void gcm_public_pass(const uint64_t *d_table, const std::vector<GcmFrameIn> &frames, const std::vector<int64_t> &off,
+                         size_t total, int rounds, int nr, uint64_t *d_out_plain, uint64_t *d_j0);
+    // the short-frame call behind both of its doors: the plans (every index within int32_t), the public pass, the tail
+    void gcm_frames_pass(const uint64_t *d_table, size_t n_keys, const uint64_t *d_htable, size_t n_powers,
+                         const std::vector<GcmFrameIn> &frames, int rounds, int nr, uint64_t *d_out_plain,
+                         uint64_t *d_out_tagdiff);
+    // GHASH + E(J0) + the received tag: the plan's chunk sums over A and B, one identity bootstrap, the differences.
+    // d_gcm_a_ / d_gcm_b_ hold the chunk rows
+    void gcm_tag_tail(const uint64_t *d_a, size_t n_a, const uint64_t *d_b, size_t n_b, GcmCallPlan plan,
+                      uint64_t *d_out_tagdiff);
     void gcm_square_pass(const uint64_t *d_src, size_t n_src, const std::vector<size_t> &blocks,
                          const std::vector<uint64_t *> &outs);
     void gcm_product_pass(const std::vector<const uint64_t *> &a, const std::vector<const uint64_t *> &b,

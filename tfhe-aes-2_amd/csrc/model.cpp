@@ -1908,46 +1908,123 @@ std::vector<GcmFrame> gcm_frames(const std::vector<Context::GcmFrameIn> &in, int
 }
 }  // namespace
 
+// ---- the power tables: a single key is a table of one slot.  The forms keep their own argument
+// checks; what follows them is shared ----
+void Context::ghash_key_raw_call(const uint64_t *table, size_t n_keys, int n_powers, int rounds, int nr, size_t key_cts,
+                                 uint64_t *out, bool device_mem) {
+    // the single-key schedule: batching keys mixes no ciphertexts of different keys
+    aes_ghash_key_noise_schedule(fresh_levels(key_cts), n_powers, rounds, params().max_noise_sq, nr);
+    Staged st(*this, device_mem);
+    engine_->ghash_key_multi(st.in(table, n_keys * key_cts * bit_len()), n_keys, n_powers, rounds, nr,
+                             st.out(out, n_keys * (size_t)n_powers * 128 * bit_len()));
+    st.finish();
+}
+
+std::vector<BitCt> Context::ghash_key_bits(const std::vector<const BitCt *> &table, size_t n_keys, int n_powers,
+                                           int rounds, int nr, size_t kw) {
+    const size_t L = bit_len();
+    const std::vector<uint64_t> tab = gather_bits(table, L);
+    std::vector<NoiseLevel> noise;  // the single-key bookkeeping, slot by slot
+    for (size_t s = 0; s < n_keys; s++) {
+        std::vector<NoiseLevel> krk(kw);
+        for (size_t i = 0; i < kw; i++) krk[i] = table[s * kw + i]->noise;
+        GhashKeyNoise kn = aes_ghash_key_noise_schedule(krk, n_powers, rounds, params().max_noise_sq, nr);
+        for (NoiseLevel &x : kn.table) noise.push_back(std::move(x));
+    }
+    std::vector<uint64_t> hk(noise.size() * L);
+    {
+        Staged st(*this, false);
+        engine_->ghash_key_multi(st.in(tab.data(), tab.size()), n_keys, n_powers, rounds, nr, st.out(hk.data(), hk.size()));
+        st.finish();
+    }
+    return wrap_bits(hk, std::move(noise), L, params().max_noise_sq);
+}
+
 void Context::aes_ghash_key_raw(const uint64_t *rk, int n_powers, int rounds, uint64_t *out, bool device_mem, int key_bits) {
     const int nr = require_inverse(rounds, key_bits);
-    const size_t kw = (size_t)aes_words(key_bits) * 32;
-    aes_ghash_key_noise_schedule(fresh_levels(kw), n_powers, rounds, params().max_noise_sq, nr);
-    Staged st(*this, device_mem);
-    engine_->ghash_key(st.in(rk, kw * bit_len()), n_powers, rounds, nr, st.out(out, (size_t)n_powers * 128 * bit_len()));
-    st.finish();
+    ghash_key_raw_call(rk, 1, n_powers, rounds, nr, (size_t)aes_words(key_bits) * 32, out, device_mem);
 }
 
 std::vector<BitCt> Context::aes_ghash_key(const std::vector<const BitCt *> &expanded_key, int n_powers, int rounds,
                                           int key_bits) {
     const int nr = require_inverse(rounds, key_bits);
-    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
     require_key_words(expanded_key.size(), nr, "expanded key");
-    const std::vector<uint64_t> rk = gather_bits(expanded_key, L);
-    std::vector<NoiseLevel> krk(kw);
-    for (size_t i = 0; i < kw; i++) krk[i] = expanded_key[i]->noise;
-    GhashKeyNoise kn = aes_ghash_key_noise_schedule(krk, n_powers, rounds, params().max_noise_sq, nr);
-    std::vector<uint64_t> hk(kn.table.size() * L);
-    {
-        Staged st(*this, false);
-        engine_->ghash_key(st.in(rk.data(), rk.size()), n_powers, rounds, nr, st.out(hk.data(), hk.size()));
-        st.finish();
-    }
-    return wrap_bits(hk, std::move(kn.table), L, params().max_noise_sq);
+    return ghash_key_bits(expanded_key, 1, n_powers, rounds, nr, (size_t)aes_words(key_bits) * 32);
 }
 
-// the frames of a GCM call through the engine
-void Context::gcm_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrame> &frames,
-                       const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int nr, size_t key_cts,
-                       uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem) {
-    const size_t n = frames.size(), S = bit_len();
-    size_t total = 0;
-    for (const GcmFrame &f : frames) total += f.data_len;
-    std::vector<Engine::GcmFrameIn> ein(n);
-    for (size_t s = 0; s < n; s++) ein[s] = {&frames[s], in[s].data, in[s].data + frames[s].data_len};
+void Context::aes_ghash_key_multi_raw(const uint64_t *table, size_t n_keys, int n_powers, int rounds, uint64_t *out,
+                                      bool device_mem, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    require_powers(n_powers);
+    if (!n_keys) return;
+    if (!gcm_multi_shape_ok(n_keys, (size_t)n_powers, 0)) throw ModelError{TAE_E_PARAM, "at most 65536 keys a call"};
+    ghash_key_raw_call(table, n_keys, n_powers, rounds, nr, (size_t)aes_words(key_bits) * 32, out, device_mem);
+}
+
+std::vector<BitCt> Context::aes_ghash_key_multi(const std::vector<const BitCt *> &table, size_t n_keys, int n_powers,
+                                                int rounds, int key_bits) {
+    const int nr = require_multi(key_bits, rounds);
+    require_powers(n_powers);
+    const size_t kw = (size_t)aes_words(key_bits) * 32;
+    if (table.size() != n_keys * kw) throw ModelError{TAE_E_ARG, "the key table is n_keys expanded keys"};
+    if (!n_keys) return {};
+    if (!gcm_multi_shape_ok(n_keys, (size_t)n_powers, 0)) throw ModelError{TAE_E_PARAM, "at most 65536 keys a call"};
+    return ghash_key_bits(table, n_keys, n_powers, rounds, nr, kw);
+}
+
+// ---- frames of at most n_powers hashed blocks ----
+namespace {
+const uint8_t *data_of(const Context::GcmFrameIn &f) { return f.data; }
+const uint8_t *data_of(const Context::GcmStreamIn &s) { return s.f.data; }
+
+// The handle forms' assembly: replay(s) is the schedule of frame s, whose plain and tag_diff levels are appended in
+// frame order; call(plain, tag_diff) fills the words; both results are wrapped
+template <class Replay, class Call>
+Context::GcmBits gcm_bits(size_t n_frames, size_t L, uint64_t max, Replay replay, Call call) {
+    std::vector<NoiseLevel> pn, tn;
+    for (size_t s = 0; s < n_frames; s++) {
+        auto gn = replay(s);
+        for (NoiseLevel &x : gn.plain) pn.push_back(std::move(x));
+        for (NoiseLevel &x : gn.tag_diff) tn.push_back(std::move(x));
+    }
+    std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
+    call(plain.data(), tag.data());
+    // xor with a public bit adds no noise
+    return {wrap_bits(plain, std::move(pn), L, max), wrap_bits(tag, std::move(tn), L, max)};
+}
+}  // namespace
+
+// what the engine's frame calls take: every frame with its ciphertext and its received tag, under slot 0 until
+// gcm_call writes the staged slots; the u64 words of both outputs
+template <class In>
+Context::GcmStaging Context::gcm_staging(const std::vector<GcmFrame> &frames, const std::vector<In> &in,
+                                         int tag_len) const {
+    GcmStaging g;
+    g.ein.resize(frames.size());
+    for (size_t s = 0; s < frames.size(); s++) {
+        g.ein[s] = {0, &frames[s], data_of(in[s]), data_of(in[s]) + frames[s].data_len};
+        g.plain_words += frames[s].data_len * 8 * bit_len();
+    }
+    g.tag_words = frames.size() * 8 * (size_t)tag_len * bit_len();
+    return g;
+}
+
+// The frames of a call through the engine; host memory uploads the named slots of both tables alone, renumbered alike.
+// A single key is a table of one slot whose power table is not bounded by 64 (key_table = false)
+void Context::gcm_call(const uint64_t *table, size_t n_keys, bool key_table, const uint64_t *htable, size_t n_powers,
+                       std::vector<int32_t> slots, GcmStaging g, int rounds, int nr, size_t key_cts, uint64_t *out_plain,
+                       uint64_t *out_tag_diff, bool device_mem) {
+    const size_t S = bit_len();
     Staged st(*this, device_mem);
-    const uint64_t *d_rk = st.in(rk, key_cts * S), *d_hk = st.in(hk, n_powers * 128 * S);
-    uint64_t *d_plain = st.out(out_plain, total * 8 * S), *d_tag = st.out(out_tag_diff, n * 8 * (size_t)tag_len * S);
-    engine_->aes_gcm_transcipher(d_rk, d_hk, n_powers, ein, rounds, nr, d_plain, d_tag);
+    std::vector<int32_t> hslots = slots;
+    const uint64_t *d_tab = st.table(table, slots, key_cts * S), *d_htab = st.table(htable, hslots, n_powers * 128 * S);
+    if (!device_mem) n_keys = (size_t)*std::max_element(slots.begin(), slots.end()) + 1;
+    for (size_t s = 0; s < g.ein.size(); s++) g.ein[s].slot = slots[s];
+    uint64_t *d_plain = st.out(out_plain, g.plain_words), *d_tag = st.out(out_tag_diff, g.tag_words);
+    if (key_table)
+        engine_->aes_gcm_transcipher_multi(d_tab, n_keys, d_htab, n_powers, g.ein, rounds, nr, d_plain, d_tag);
+    else
+        engine_->aes_gcm_transcipher(d_tab, d_htab, n_powers, g.ein, rounds, nr, d_plain, d_tag);
     st.finish();
 }
 
@@ -1962,7 +2039,8 @@ void Context::aes_gcm_raw(const uint64_t *rk, const uint64_t *hk, size_t n_power
     const size_t kw = (size_t)aes_words(key_bits) * 32;
     const std::vector<NoiseLevel> krk = fresh_levels(kw), khk = fresh_levels(n_powers * 128);
     for (const GcmFrame &f : frames) aes_gcm_noise_schedule(krk, khk, f, rounds, params().max_noise_sq, nr);
-    gcm_call(rk, hk, n_powers, frames, in, tag_len, rounds, nr, kw, out_plain, out_tag_diff, device_mem);
+    gcm_call(rk, 1, false, hk, n_powers, std::vector<int32_t>(frames.size(), 0), gcm_staging(frames, in, tag_len), rounds,
+             nr, kw, out_plain, out_tag_diff, device_mem);
 }
 
 Context::GcmBits Context::aes_gcm(const std::vector<const BitCt *> &expanded_key, const std::vector<const BitCt *> &hk,
@@ -1976,19 +2054,17 @@ Context::GcmBits Context::aes_gcm(const std::vector<const BitCt *> &expanded_key
     if (!n_powers) throw ModelError{TAE_E_PARAM, "the power table is empty"};
     const std::vector<GcmFrame> frames = gcm_frames(in, tag_len);
     if (frames.empty()) return {};
-    std::vector<NoiseLevel> krk(kw), khk(hk.size()), pn, tn;
+    std::vector<NoiseLevel> krk(kw), khk(hk.size());
     for (size_t i = 0; i < kw; i++) krk[i] = expanded_key[i]->noise;
     for (size_t i = 0; i < hk.size(); i++) khk[i] = hk[i]->noise;
-    for (const GcmFrame &f : frames) {
-        GcmNoise gn = aes_gcm_noise_schedule(krk, khk, f, rounds, params().max_noise_sq, nr);
-        for (NoiseLevel &x : gn.plain) pn.push_back(std::move(x));
-        for (NoiseLevel &x : gn.tag_diff) tn.push_back(std::move(x));
-    }
-    const std::vector<uint64_t> rk = gather_bits(expanded_key, L), table = gather_bits(hk, L);
-    std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
-    gcm_call(rk.data(), table.data(), n_powers, frames, in, tag_len, rounds, nr, kw, plain.data(), tag.data(), false);
-    // xor with a public bit adds no noise
-    return {wrap_bits(plain, std::move(pn), L, params().max_noise_sq), wrap_bits(tag, std::move(tn), L, params().max_noise_sq)};
+    return gcm_bits(
+        frames.size(), L, params().max_noise_sq,
+        [&](size_t s) { return aes_gcm_noise_schedule(krk, khk, frames[s], rounds, params().max_noise_sq, nr); },
+        [&](uint64_t *plain, uint64_t *tag) {
+            const std::vector<uint64_t> rk = gather_bits(expanded_key, L), table = gather_bits(hk, L);
+            gcm_call(rk.data(), 1, false, table.data(), n_powers, std::vector<int32_t>(frames.size(), 0),
+                     gcm_staging(frames, in, tag_len), rounds, nr, kw, plain, tag, false);
+        });
 }
 
 // ---- GCM over key tables ----
@@ -2017,67 +2093,6 @@ std::vector<GcmFrame> gcm_multi_frames(const std::vector<Context::GcmStreamIn> &
     return frames;
 }
 
-void Context::aes_ghash_key_multi_raw(const uint64_t *table, size_t n_keys, int n_powers, int rounds, uint64_t *out,
-                                      bool device_mem, int key_bits) {
-    const int nr = require_multi(key_bits, rounds);
-    require_powers(n_powers);
-    if (!n_keys) return;
-    if (!gcm_multi_shape_ok(n_keys, (size_t)n_powers, 0)) throw ModelError{TAE_E_PARAM, "at most 65536 keys a call"};
-    const size_t kw = (size_t)aes_words(key_bits) * 32;
-    // the single-key schedule: batching keys mixes no ciphertexts of different keys
-    aes_ghash_key_noise_schedule(fresh_levels(kw), n_powers, rounds, params().max_noise_sq, nr);
-    Staged st(*this, device_mem);
-    engine_->ghash_key_multi(st.in(table, n_keys * kw * bit_len()), n_keys, n_powers, rounds, nr,
-                             st.out(out, n_keys * (size_t)n_powers * 128 * bit_len()));
-    st.finish();
-}
-
-std::vector<BitCt> Context::aes_ghash_key_multi(const std::vector<const BitCt *> &table, size_t n_keys, int n_powers,
-                                                int rounds, int key_bits) {
-    const int nr = require_multi(key_bits, rounds);
-    require_powers(n_powers);
-    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
-    if (table.size() != n_keys * kw) throw ModelError{TAE_E_ARG, "the key table is n_keys expanded keys"};
-    if (!n_keys) return {};
-    if (!gcm_multi_shape_ok(n_keys, (size_t)n_powers, 0)) throw ModelError{TAE_E_PARAM, "at most 65536 keys a call"};
-    const std::vector<uint64_t> tab = gather_bits(table, L);
-    std::vector<NoiseLevel> noise;  // the single-key bookkeeping, slot by slot
-    noise.reserve(n_keys * (size_t)n_powers * 128);
-    for (size_t s = 0; s < n_keys; s++) {
-        std::vector<NoiseLevel> krk(kw);
-        for (size_t i = 0; i < kw; i++) krk[i] = table[s * kw + i]->noise;
-        GhashKeyNoise kn = aes_ghash_key_noise_schedule(krk, n_powers, rounds, params().max_noise_sq, nr);
-        for (NoiseLevel &x : kn.table) noise.push_back(std::move(x));
-    }
-    std::vector<uint64_t> hk(noise.size() * L);
-    {
-        Staged st(*this, false);
-        engine_->ghash_key_multi(st.in(tab.data(), tab.size()), n_keys, n_powers, rounds, nr, st.out(hk.data(), hk.size()));
-        st.finish();
-    }
-    return wrap_bits(hk, std::move(noise), L, params().max_noise_sq);
-}
-
-// the frames of a call over key tables through the engine; host memory uploads the named slots of both tables alone,
-// renumbered alike
-void Context::gcm_multi_call(const uint64_t *table, size_t n_keys, const uint64_t *htable, size_t n_powers,
-                             std::vector<int32_t> slots, const std::vector<GcmFrame> &frames,
-                             const std::vector<GcmStreamIn> &in, int tag_len, int rounds, int nr, size_t key_cts,
-                             uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem) {
-    const size_t n = frames.size(), S = bit_len();
-    size_t total = 0;
-    for (const GcmFrame &f : frames) total += f.data_len;
-    Staged st(*this, device_mem);
-    std::vector<int32_t> hslots = slots;
-    const uint64_t *d_tab = st.table(table, slots, key_cts * S), *d_htab = st.table(htable, hslots, n_powers * 128 * S);
-    if (!device_mem) n_keys = (size_t)*std::max_element(slots.begin(), slots.end()) + 1;
-    std::vector<Engine::GcmStreamIn> ein(n);
-    for (size_t s = 0; s < n; s++) ein[s] = {slots[s], &frames[s], in[s].f.data, in[s].f.data + frames[s].data_len};
-    uint64_t *d_plain = st.out(out_plain, total * 8 * S), *d_tag = st.out(out_tag_diff, n * 8 * (size_t)tag_len * S);
-    engine_->aes_gcm_transcipher_multi(d_tab, n_keys, d_htab, n_powers, ein, rounds, nr, d_plain, d_tag);
-    st.finish();
-}
-
 void Context::aes_gcm_multi_raw(const uint64_t *table, size_t n_keys, const uint64_t *htable, size_t n_powers,
                                 const std::vector<GcmStreamIn> &in, int tag_len, int rounds, uint64_t *out_plain,
                                 uint64_t *out_tag_diff, bool device_mem, int key_bits) {
@@ -2090,8 +2105,8 @@ void Context::aes_gcm_multi_raw(const uint64_t *table, size_t n_keys, const uint
     const size_t kw = (size_t)aes_words(key_bits) * 32;
     const std::vector<NoiseLevel> krk = fresh_levels(kw), khk = fresh_levels(n_powers * 128);
     for (const GcmFrame &f : frames) aes_gcm_noise_schedule(krk, khk, f, rounds, params().max_noise_sq, nr);
-    gcm_multi_call(table, n_keys, htable, n_powers, slots, frames, in, tag_len, rounds, nr, kw, out_plain, out_tag_diff,
-                   device_mem);
+    gcm_call(table, n_keys, true, htable, n_powers, slots, gcm_staging(frames, in, tag_len), rounds, nr, kw, out_plain,
+             out_tag_diff, device_mem);
 }
 
 Context::GcmBits Context::aes_gcm_multi(const BitAt &table, size_t n_keys, const BitAt &htable, size_t n_powers,
@@ -2102,23 +2117,21 @@ Context::GcmBits Context::aes_gcm_multi(const BitAt &table, size_t n_keys, const
     std::vector<int32_t> slots;
     const std::vector<GcmFrame> frames = gcm_multi_frames(in, n_keys, n_powers, tag_len, slots);
     if (frames.empty()) return {};
-    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len(), n = frames.size();
+    const size_t kw = (size_t)aes_words(key_bits) * 32, L = bit_len();
     std::vector<std::vector<NoiseLevel>> knoise, hnoise;
     std::vector<int32_t> hslots = slots;
     const std::vector<uint64_t> tab = gather_slots(table, slots, kw, L, knoise);
     const std::vector<uint64_t> htab = gather_slots(htable, hslots, n_powers * 128, L, hnoise);
-    std::vector<NoiseLevel> pn, tn;
-    for (size_t s = 0; s < n; s++) {
-        GcmNoise gn = aes_gcm_noise_schedule(knoise[(size_t)slots[s]], hnoise[(size_t)slots[s]], frames[s], rounds,
-                                             params().max_noise_sq, nr);
-        for (NoiseLevel &x : gn.plain) pn.push_back(std::move(x));
-        for (NoiseLevel &x : gn.tag_diff) tn.push_back(std::move(x));
-    }
-    std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
-    gcm_multi_call(tab.data(), knoise.size(), htab.data(), n_powers, slots, frames, in, tag_len, rounds, nr, kw,
-                   plain.data(), tag.data(), false);
-    // xor with a public bit adds no noise
-    return {wrap_bits(plain, std::move(pn), L, params().max_noise_sq), wrap_bits(tag, std::move(tn), L, params().max_noise_sq)};
+    return gcm_bits(
+        frames.size(), L, params().max_noise_sq,
+        [&](size_t s) {
+            return aes_gcm_noise_schedule(knoise[(size_t)slots[s]], hnoise[(size_t)slots[s]], frames[s], rounds,
+                                          params().max_noise_sq, nr);
+        },
+        [&](uint64_t *plain, uint64_t *tag) {
+            gcm_call(tab.data(), knoise.size(), true, htab.data(), n_powers, slots, gcm_staging(frames, in, tag_len),
+                     rounds, nr, kw, plain, tag, false);
+        });
 }
 
 // ---- frames beyond one table: segmented GHASH ----
@@ -2157,16 +2170,13 @@ void Context::gcm_long_call(const uint64_t *rk, const uint64_t *hk, size_t n_pow
                             size_t seg, const std::vector<GcmFrame> &frames, const std::vector<GcmFrameIn> &in,
                             int tag_len, int rounds, int nr, size_t key_cts, uint64_t *out_plain, uint64_t *out_tag_diff,
                             bool device_mem) {
-    const size_t n = frames.size(), S = bit_len();
-    size_t total = 0;
-    for (const GcmFrame &f : frames) total += f.data_len;
-    std::vector<Engine::GcmFrameIn> ein(n);
-    for (size_t s = 0; s < n; s++) ein[s] = {&frames[s], in[s].data, in[s].data + frames[s].data_len};
+    const size_t S = bit_len();
+    const GcmStaging g = gcm_staging(frames, in, tag_len);
     Staged st(*this, device_mem);
     const uint64_t *d_rk = st.in(rk, key_cts * S), *d_hk = st.in(hk, n_powers * 128 * S);
     const uint64_t *d_sk = st.in(sk, n_strides * 128 * S);
-    uint64_t *d_plain = st.out(out_plain, total * 8 * S), *d_tag = st.out(out_tag_diff, n * 8 * (size_t)tag_len * S);
-    engine_->aes_gcm_long_transcipher(d_rk, d_hk, n_powers, d_sk, n_strides, seg, ein, rounds, nr, d_plain, d_tag);
+    uint64_t *d_plain = st.out(out_plain, g.plain_words), *d_tag = st.out(out_tag_diff, g.tag_words);
+    engine_->aes_gcm_long_transcipher(d_rk, d_hk, n_powers, d_sk, n_strides, seg, g.ein, rounds, nr, d_plain, d_tag);
     st.finish();
 }
 
@@ -2207,20 +2217,20 @@ Context::GcmBits Context::aes_gcm_long(const std::vector<const BitCt *> &expande
     if (frames.empty()) return {};
     // the stride key's levels are not consulted (model.hpp): its length alone goes into the replay
     const std::vector<NoiseLevel> ksk(sk.size());
-    std::vector<NoiseLevel> krk(kw), khk(hk.size()), pn, tn;
+    std::vector<NoiseLevel> krk(kw), khk(hk.size());
     for (size_t i = 0; i < kw; i++) krk[i] = expanded_key[i]->noise;
     for (size_t i = 0; i < hk.size(); i++) khk[i] = hk[i]->noise;
-    for (const GcmFrame &f : frames) {
-        GcmLongNoise gn = aes_gcm_long_noise_schedule(krk, khk, ksk, seg, f, rounds, params().max_noise_sq, nr);
-        for (NoiseLevel &x : gn.plain) pn.push_back(std::move(x));
-        for (NoiseLevel &x : gn.tag_diff) tn.push_back(std::move(x));
-    }
-    const std::vector<uint64_t> rk = gather_bits(expanded_key, L), table = gather_bits(hk, L), strides = gather_bits(sk, L);
-    std::vector<uint64_t> plain(pn.size() * L), tag(tn.size() * L);
-    gcm_long_call(rk.data(), table.data(), n_powers, strides.data(), n_strides, seg, frames, in, tag_len, rounds, nr, kw,
-                  plain.data(), tag.data(), false);
-    // xor with a public bit adds no noise
-    return {wrap_bits(plain, std::move(pn), L, params().max_noise_sq), wrap_bits(tag, std::move(tn), L, params().max_noise_sq)};
+    return gcm_bits(
+        frames.size(), L, params().max_noise_sq,
+        [&](size_t s) {
+            return aes_gcm_long_noise_schedule(krk, khk, ksk, seg, frames[s], rounds, params().max_noise_sq, nr);
+        },
+        [&](uint64_t *plain, uint64_t *tag) {
+            const std::vector<uint64_t> rk = gather_bits(expanded_key, L), table = gather_bits(hk, L),
+                                        strides = gather_bits(sk, L);
+            gcm_long_call(rk.data(), table.data(), n_powers, strides.data(), n_strides, seg, frames, in, tag_len, rounds,
+                          nr, kw, plain, tag, false);
+        });
 }
 
 void Context::gf128_square_raw(const uint64_t *in, size_t count, uint64_t *out, bool device_mem) {

@@ -228,7 +228,9 @@ class Context {  // FheContext
     // ---- AES-GCM decryption of public frames under one key (SP 800-38D; aes_gcm.hpp; the reference
     // has no GCM).  1-bit WoP-PBS sets, gal-mul driver, 96-bit IVs, decryption (TAE_E_PARAM elsewhere).  Refusals
     // before any device work: an IV that is not 12 bytes, a tag_len outside 4, 8, 12 .. 16, rounds < 2, more hashed
-    // blocks than n_powers (all TAE_E_PARAM); a row beyond the two-level chunk sum (TAE_E_NOISE). ----
+    // blocks than n_powers (all TAE_E_PARAM); a row beyond the two-level chunk sum (TAE_E_NOISE).  A single key is a
+    // table of one slot: these forms keep their argument checks and share the rest with the
+    // key-table forms below, except that n_powers of the frame call is not bounded by 64 here. ----
     struct GcmFrameIn {
         const uint8_t *iv;
         size_t iv_len;
@@ -370,13 +372,24 @@ class Context {  // FheContext
     void ccm_call(const uint64_t *table, std::vector<int32_t> slots, const std::vector<CcmFrame> &frames,
                   const std::vector<CcmStreamIn> &streams, int tag_len, int rounds, int nr, size_t key_cts,
                   uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem);
-    void gcm_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const std::vector<GcmFrame> &frames,
-                  const std::vector<GcmFrameIn> &in, int tag_len, int rounds, int nr, size_t key_cts, uint64_t *out_plain,
+    // the frame list of the engine's GCM calls and the u64 words of both outputs; In is GcmFrameIn or GcmStreamIn.
+    // gcm_staging leaves every slot 0 (one key); gcm_call writes the staged slot of every frame
+    struct GcmStaging {
+        std::vector<Engine::GcmFrameIn> ein;
+        size_t plain_words = 0, tag_words = 0;
+    };
+    template <class In>
+    GcmStaging gcm_staging(const std::vector<GcmFrame> &frames, const std::vector<In> &in, int tag_len) const;
+    // A single key is a table of one slot (n_keys = 1, every slot 0) and, with key_table = false, keeps its own bound:
+    // its power table may hold more than 64 powers
+    void gcm_call(const uint64_t *table, size_t n_keys, bool key_table, const uint64_t *htable, size_t n_powers,
+                  std::vector<int32_t> slots, GcmStaging g, int rounds, int nr, size_t key_cts, uint64_t *out_plain,
                   uint64_t *out_tag_diff, bool device_mem);
-    void gcm_multi_call(const uint64_t *table, size_t n_keys, const uint64_t *htable, size_t n_powers,
-                        std::vector<int32_t> slots, const std::vector<GcmFrame> &frames, const std::vector<GcmStreamIn> &in,
-                        int tag_len, int rounds, int nr, size_t key_cts, uint64_t *out_plain, uint64_t *out_tag_diff,
-                        bool device_mem);
+    // the power tables of n_keys slots after a form's own argument checks: raw arrays, and handles
+    void ghash_key_raw_call(const uint64_t *table, size_t n_keys, int n_powers, int rounds, int nr, size_t key_cts,
+                            uint64_t *out, bool device_mem);
+    std::vector<BitCt> ghash_key_bits(const std::vector<const BitCt *> &table, size_t n_keys, int n_powers, int rounds,
+                                      int nr, size_t key_cts);
     void gcm_long_call(const uint64_t *rk, const uint64_t *hk, size_t n_powers, const uint64_t *sk, size_t n_strides,
                        size_t seg, const std::vector<GcmFrame> &frames, const std::vector<GcmFrameIn> &in, int tag_len,
                        int rounds, int nr, size_t key_cts, uint64_t *out_plain, uint64_t *out_tag_diff, bool device_mem);
